@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s of the ray-casting hot path on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
 
 One "step" renders one full frame of the workload: every rank casts the primary
 and ambient-occlusion rays of its image bands (HIP kernel), box-filters them to
@@ -15,17 +15,21 @@ set) any-hit rays per hit sub-pixel.
 `python -m torch.distributed.run`, before this process touches torch or the GPU);
 under an external torchrun (RANK / WORLD_SIZE in the environment) it is a rank.
 
-The frames go through the library's frame ring (include/rt_hip_ring.h, rt_ring_*): several
-render hosts per GPU take them in turn, each replaying its captured hipGraph, and the
-ring itself runs the RCCL gather behind the next frames -- a timed block is ONE call
-into the library (rt_ring_run), Python is not on the per-frame path.  In the same run
-the frame is also timed ONE AT A TIME (a ring of one host = the reference's blocking
-OpenCLHost::operator()(), src/opencl_host.cc:137-149): `blocking` in the line.  Every
-block of K steps is bracketed by barrier + synchronize and repeated until half a second
-of GPU time is covered; the line reports the median block, with min / max beside it.
+The frames go through the library's frame ring (include/rt_hip_ring.h, rt_ring_*), and
+the ring itself runs the RCCL gather behind the next frames -- a timed block is ONE call
+into the library (rt_ring_run), Python is not on the per-frame path.  The headline times
+the frame ONE AT A TIME (a ring of one host = the reference's blocking
+OpenCLHost::operator()(), src/opencl_host.cc:137-149, replaying its captured hipGraph):
+W warm-up steps (more until --warmup-seconds are covered), then ONE block of exactly K
+steps, bracketed by barrier + synchronize;
+`ms_per_step` is that block's time over K.  `--dump-outputs DIR` then writes the last
+timed frame as the caller receives it (the 8-bit image) to DIR/image_u8.npy, as float32.
 
-Rank 0 prints ONE JSON line (contract in the task description) carrying
-`roofline` -- the bound the dominant kernel is actually under (vector-instruction
+A plain run does only that.  `--full` adds everything else: the headline block repeated
+until --min-seconds of GPU time are covered (`blocks`: median / min / max), and, timed
+before it, the same frames as a steady stream through a ring of several render hosts per
+GPU that take them in turn (`pipelined`).  Rank 0 prints ONE JSON line; with `--full` it
+also carries `roofline` -- the bound the dominant kernel is actually under (vector-instruction
 issue; the 12 MB scene is cache-resident): that kernel's instructions per launch over
 its launch duration, HIP events around the launch with ONE frame at a time; the
 pipelined frame rate in the same units under `roofline.frame_pipelined`; the
@@ -295,13 +299,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)  # (a quarter of a second of frames per block)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--warmup-seconds", type=float, default=0.5,
+                    help="after the --warmup steps, more warm-up steps until this much time is covered (not with --warmup 0)")
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed frame (the 8-bit image a caller of the ring receives) "
+                         "to DIR/image_u8.npy as float32 (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: repeated blocks, the pipelined stream, the dominant "
+                         "kernel alone and the roofline, the CPU baseline and the render CLI end to end")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baseline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="(--full) leave out the render CLI run")
     ap.add_argument("--in-flight", type=int, default=0, choices=list(range(17)),
-                    help="render hosts per GPU taking the frames in turn (1: one frame at a time; 0 = by the number of "
+                    help="(--full) render hosts per GPU of the pipelined ring (1: one frame at a time; 0 = by the number of "
                          "ranks: 3 on one GPU, 6 on two to seven, 8 from eight on)")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="repeat each block of --steps steps until this much time is covered")
+    ap.add_argument("--min-seconds", type=float, default=0.5, help="(--full) repeat each block of --steps steps until this much time is covered")
     ap.add_argument("--plain-launches", action="store_true", help="launch the kernels one by one instead of replaying the captured graph")
     ap.add_argument("--pacing", type=float, default=-1.0, help="the ring's pacing factor (rt_ring_set_pacing); default: the library's")
     args = ap.parse_args()
@@ -359,7 +371,7 @@ def main():
         golden_md5, counters = g["pgm_md5"], g["counters"]
 
     e2e = None
-    if world == 1 and not args.no_end_to_end and ":" not in w["mesh"]:  # (generated meshes are not files: no CLI run)
+    if args.full and world == 1 and not args.no_end_to_end and ":" not in w["mesh"]:  # (generated meshes are not files: no CLI run)
         e2e = end_to_end(w, golden_md5)  # (a child process, before this one opens the GPU)
 
     import numpy as np
@@ -418,9 +430,14 @@ def main():
     # with 16 queues the eighth reads 0.161 / 0.154 / 0.151 for 8 / 12 / 16.  The 4K and 64-samples frames do not care:
     # 0.460 / 0.462 / 0.463 and 4.78 / 4.80 / 4.69 ms for an eighth with 3 / 6 / 12.)
     in_flight = args.in_flight if args.in_flight > 0 else 3 if world == 1 else 6 if world < 8 else 8
+    # the headline needs the blocking ring only; the pipelined one (--full) also describes the scene in the line's config
+    lead = "pipelined" if args.full else "blocking"
+
     def make_rings():
-        made = {"pipelined": rt.FrameRing(opt, scene, device_index, rank, world, hosts=in_flight),
-                "blocking": rt.FrameRing(opt, scene, device_index, rank, world, hosts=1)}
+        made = {}
+        if args.full:
+            made["pipelined"] = rt.FrameRing(opt, scene, device_index, rank, world, hosts=in_flight)
+        made["blocking"] = rt.FrameRing(opt, scene, device_index, rank, world, hosts=1)
         for ring in made.values():
             ring.set_graph_mode(not args.plain_launches)
             if args.pacing >= 0.0:
@@ -440,7 +457,7 @@ def main():
     from opencl_raytracer_amd.multi_gpu import BandGatherer, BandLayout
 
     layout = BandLayout(opt, world)
-    assert layout.local_rows(rank) == rings["pipelined"].local_rows
+    assert layout.local_rows(rank) == rings[lead].local_rows
     rccl = launched and backend == "nccl"
     rccl_failure = None
 
@@ -568,10 +585,23 @@ def main():
 
     def timed_blocks(name):
         """Warm-up, then blocks of exactly --steps steps, each bracketed by barrier + synchronize, the MAX over ranks
-        of each block's time; repeated until --min-seconds are covered (the count is agreed on across the ranks)."""
+        of each block's time: one block, or with --full repeated until --min-seconds are covered (the count is agreed
+        on across the ranks)."""
         ring = rings[name]
+        t0 = time.perf_counter()
         run_steps(name, args.warmup)
         fence(name)
+        dt = time.perf_counter() - t0
+        if launched:
+            t = torch.tensor([dt], dtype=torch.float64, device=reduce_device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t[0])
+        if 0 < args.warmup and dt < args.warmup_seconds:
+            # more warm-up frames until --warmup-seconds have run: the clocks settle only after a fraction of a second of
+            # frames, and a plain run has no pipelined ring ahead of its blocking one to do that (the count is agreed on
+            # across the ranks)
+            run_steps(name, min(100000, math.ceil((args.warmup_seconds - dt) / (dt / args.warmup))))
+            fence(name)
         ring.reset_timers()
         ring.reset_clock()
         seconds, planned = [], 1
@@ -585,57 +615,63 @@ def main():
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 dt = float(t[0])
             seconds.append(dt)
-            if len(seconds) == 1:
+            if len(seconds) == 1 and args.full:
                 planned = max(1, min(50, math.ceil(args.min_seconds / max(dt, 1e-6))))
         return seconds
 
-    results = {}
-    for name in ("pipelined", "blocking"):
+    results, images = {}, {}
+    for name in rings:
         enter(f"timed blocks, {name}", 900.0)
         seconds = timed_blocks(name)
+        images[name] = final_image(name)  # (the last timed step's frame, outside the timed blocks)
         ring = rings[name]
         timers, cpu = ring.timers(), ring.cpu_times()
         results[name] = {"seconds": seconds, "kernel_ms": timers["kernel_ms"] / max(1, timers["frames"]),
                          "cpu_us": {k: round(cpu[k + "_s"] / max(1, cpu["frames"]) * 1e6, 1) for k in ("submit", "collect", "wait")}}
-    # The dominant kernel ALONE, by HIP events right around its launch on the launch stream (plain launches: the events
-    # of a replayed graph cannot be timed), one frame at a time -- the duration the roofline is quoted for.
-    enter("the dominant kernel alone (plain launches, HIP events)", 600.0)
-    ring = rings["blocking"]
-    ring.set_graph_mode(False)
-    run_steps("blocking", args.warmup)
-    fence("blocking")
-    ring.reset_timers()
-    run_steps("blocking", max(args.steps, 20))
-    fence("blocking")
-    timers = ring.timers()
-    alone_ao_ms = timers["ao_ms"] / max(1, timers["ao_frames"])
-    alone_kernel_ms = timers["kernel_ms"] / max(1, timers["frames"])
-    ring.set_graph_mode(not args.plain_launches)
+    if args.dump_outputs and rank == 0:
+        # what the timed path hands its caller: the last timed frame's 8-bit image (the blocking ring's), as float32
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "image_u8.npy"), images["blocking"].astype(np.float32))
+    if args.full:
+        # The dominant kernel ALONE, by HIP events right around its launch on the launch stream (plain launches: the events
+        # of a replayed graph cannot be timed), one frame at a time -- the duration the roofline is quoted for.
+        enter("the dominant kernel alone (plain launches, HIP events)", 600.0)
+        ring = rings["blocking"]
+        ring.set_graph_mode(False)
+        run_steps("blocking", args.warmup)
+        fence("blocking")
+        ring.reset_timers()
+        run_steps("blocking", max(args.steps, 20))
+        fence("blocking")
+        timers = ring.timers()
+        alone_ao_ms = timers["ao_ms"] / max(1, timers["ao_frames"])
+        alone_kernel_ms = timers["kernel_ms"] / max(1, timers["frames"])
+        ring.set_graph_mode(not args.plain_launches)
 
     # whole-job numbers: max time over ranks (above), sum of rays over ranks
-    st = rings["pipelined"].host(0).stats()
+    st = rings[lead].host(0).stats()
     my_rays = st["primary_rays"] + st["ao_rays"]
     if launched:
-        t = torch.tensor([alone_ao_ms, alone_kernel_ms, results["pipelined"]["kernel_ms"]], dtype=torch.float64, device=reduce_device)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        alone_ao_ms, alone_kernel_ms, results["pipelined"]["kernel_ms"] = (float(x) for x in t)
+        if args.full:
+            t = torch.tensor([alone_ao_ms, alone_kernel_ms, results["pipelined"]["kernel_ms"]], dtype=torch.float64, device=reduce_device)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            alone_ao_ms, alone_kernel_ms, results["pipelined"]["kernel_ms"] = (float(x) for x in t)
         r = torch.tensor([my_rays, st["primary_hits"], st["ao_occluded"]], dtype=torch.int64, device=reduce_device)
         dist.all_reduce(r, op=dist.ReduceOp.SUM)
         total_rays, total_hits, total_occluded = (int(x) for x in r)
     else:
         total_rays, total_hits, total_occluded = my_rays, st["primary_hits"], st["ao_occluded"]
-    enter("statistics, images, the line", 900.0)
-    images = {name: final_image(name) for name in rings}
+    enter("statistics, the line", 900.0)
     rccl_described = {"failed": rccl_failure, "world_size": world} if rccl_failure else None
     if rccl:
-        comm_ranks, version = rings["pipelined"].rccl_info()
+        comm_ranks, version = rings[lead].rccl_info()
         rccl_described = {"comm_ranks": comm_ranks, "version_code": version, "world_size": world}
         if comm_ranks not in (-1, world):
             sys.exit(f"bench.py: the RCCL communicator has {comm_ranks} ranks, the job {world}")
-    scene_bytes, scene_copies, _ = rings["pipelined"].device_bytes()
-    calibration = rings["pipelined"].calibration()
+    scene_bytes, scene_copies, _ = rings[lead].device_bytes()
+    calibration = rings[lead].calibration()
     # how far the walk intervals found at upload confine the any-hit packets (rt_walk_entries; this rank's bands)
-    intervals = rings["pipelined"].host(0).walk_entries()
+    intervals = rings[lead].host(0).walk_entries()
 
     if rank == 0:
         md5 = {name: hashlib.md5(rt.pgm_bytes(img)).hexdigest() for name, img in images.items()}
@@ -646,7 +682,7 @@ def main():
             if total_hits != counters["primary_hits"] or total_occluded != counters["ao_occluded"]:
                 sys.exit(f"bench.py: ray statistics differ from the reference traversal: {total_hits} hit sub-pixels, "
                          f"{total_occluded} occluded rays against {counters['primary_hits']}, {counters['ao_occluded']}")
-        elif md5["pipelined"] != md5["blocking"]:
+        elif "pipelined" in md5 and md5["pipelined"] != md5["blocking"]:
             sys.exit("bench.py: the pipelined and the blocking frame differ")
 
         def per_step_ms(name):
@@ -654,10 +690,10 @@ def main():
 
         # `value` is SURVEY 8d's metric: rays over the time from launch to completion of a frame, one frame at a time -- a
         # ring of ONE host, i.e. the reference's blocking OpenCLHost::operator()() (src/opencl_host.cc:137-149).  What the
-        # device sustains with several frames in flight is a machine-throughput figure and goes under its own key.
-        pipe_ms, block_ms = per_step_ms("pipelined"), per_step_ms("blocking")
-        ms_per_step = statistics.median(block_ms)
-        pipe_ms_per_step = statistics.median(pipe_ms)
+        # device sustains with several frames in flight is a machine-throughput figure and goes under its own key (--full).
+        # The headline is the first block: exactly --steps timed steps after --warmup.
+        block_ms = per_step_ms("blocking")
+        ms_per_step = block_ms[0]
         value = total_rays / (ms_per_step * 1e-3) / 1e6
         gather = ("the ring's RCCL gather to rank 0" if rccl else
                   f"torch.distributed ({backend}) gather to rank 0 on the device -- the library's RCCL gather could not be set up: {rccl_failure}"
@@ -693,87 +729,93 @@ def main():
                                           "share_of_node_records_per_tile": round(intervals["mean_share"], 4),
                                           "share_of_node_records_per_packet": round(intervals["mean_packet_share"], 4)},
                        "device": torch.cuda.get_device_name(device)},
-            # every block is exactly `steps` frames, one at a time, between barrier + synchronize; `value` / `ms_per_step` are the median block
-            "blocks": dict(summary(block_ms), unit="ms per step", seconds_covered=round(sum(results["blocking"]["seconds"]), 3),
-                           mrays_per_s_min=round(total_rays / (max(block_ms) * 1e-3) / 1e6, 1),
-                           mrays_per_s_max=round(total_rays / (min(block_ms) * 1e-3) / 1e6, 1)),
             "cpu_us_per_step": results["blocking"]["cpu_us"],
-            "kernels_ms_per_frame": round(alone_kernel_ms, 4),
-            # NOT the metric: the same frames as a steady stream through a ring of `frames_in_flight` hosts (the next
-            # frames' passes fill what a finishing pass frees) -- what the device sustains, measured the same way
-            "pipelined": dict(value=round(total_rays / (pipe_ms_per_step * 1e-3) / 1e6, 2), unit="Mrays/s",
-                              ms_per_frame=summary(pipe_ms), frames_in_flight=in_flight, n_hosts_per_gpu=in_flight,
-                              pgm_md5=md5["pipelined"], cpu_us_per_step=results["pipelined"]["cpu_us"],
-                              seconds_covered=round(sum(results["pipelined"]["seconds"]), 3)),
         }
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu, _ = cpu_baseline(opt, scene, images["blocking"], w)
-        has_ao = bool(opt.enable_ao)
-        dominant = "ao_kernel" if has_ao else "primary_kernel"
-        dominant_ms = alone_ao_ms if has_ao else alone_kernel_ms
-        seconds = dominant_ms * 1e-3
-        pmc = pmc_for(args.workload) if world == 1 else None  # counters are per launch of the WHOLE frame on one GPU
-        # The contractual HBM line: algorithmic bytes of the reference traversal over the measured
-        # launch time, beside the HBM bytes the counters really saw.  The scene is cache-resident, so this is NOT
-        # the bound the kernel is under; `x_peak` may exceed 1 and is therefore not called a fraction.
-        hbm = {"peak": HBM_PEAK_GBS, "unit": "GB/s"}
-        if counters is not None:
-            sub = opt.total_width * opt.total_height
-            parts = algorithmic_bytes(counters, sub)
-            bytes_per_launch = (parts["ao"] if has_ao else parts["frame"]) / world  # bands are interleaved over ranks
-            hbm.update(algorithmic_bytes_per_launch=int(bytes_per_launch),
-                       algorithmic_GBps=round(bytes_per_launch / seconds / 1e9, 1),
-                       algorithmic_x_peak=round(bytes_per_launch / seconds / 1e9 / HBM_PEAK_GBS, 3),
-                       frame_algorithmic_GBps=round(parts["frame"] / world / (alone_kernel_ms * 1e-3) / 1e9, 1))
-        traffic = None
-        if pmc is not None:
-            traffic = int(pmc["hbm_bytes"])
-            hbm.update(measured_bytes_per_launch=traffic, measured_GBps=round(traffic / seconds / 1e9, 1),
-                       measured_frac=round(traffic / seconds / 1e9 / HBM_PEAK_GBS, 4))
-        hbm["note"] = ("algorithmic bytes = REFERENCE traversal (36 B/node visit + 60 B/triangle test [+ 48 B/hit + 4 B/"
-                       "sub-pixel for the primary pass]); they are served by the scalar cache and L2, not by HBM")
-        # The binding roofline: vector-instruction issue.  ONE scope for achieved / frac: the dominant kernel's
-        # instructions per launch (PMC pass of the same kernel sources, the grid a host alone launches; null if the
-        # sources changed since) over its launch duration with one frame at a time, HIP events, measured live.
-        roof = {"bound": "valu", "achieved": None, "peak": VALU_PEAK_PER_CLK_SIMD,
-                "unit": "wave64 VALU instr/clk/SIMD (1024 SIMDs, 2.4 GHz)", "frac": None, "traffic": traffic,
-                "scope": "dominant kernel alone: its instructions per launch over its launch duration, one frame at a time",
-                "kernel": dominant, "kernel_ms": round(dominant_ms, 4), "frame_kernels_ms": round(alone_kernel_ms, 4)}
-        if pmc is not None:
-            rate = pmc["valu_insts"] / (seconds * CLOCK_HZ * SIMDS)
-            roof.update(achieved=round(rate, 4), frac=round(rate / VALU_PEAK_PER_CLK_SIMD, 4),
-                        insts_per_launch=int(pmc["valu_insts"]), ceiling_measured=pmc.get("valu_ceiling_measured"),
-                        levels=pmc.get("levels"), counters_from=pmc.get("source"))
-            if pmc.get("valu_ceiling_measured"):
-                roof["frac_of_measured_ceiling"] = round(rate / pmc["valu_ceiling_measured"], 4)
-            # the hardware's own view, from the counter pass: cycles the SIMDs spent issuing vector instructions
-            # (SQ_ACTIVE_INST_VALU, quad-cycles summed over the SIMDs) over the cycles the launch took
-            # (GRBM_GUI_ACTIVE, summed over the 8 XCDs).  The counter books 4 cycles per instruction; v_fma / v_mul /
-            # v_add on registers issue in 2.3 (tools/microbench/valu_rate_probe.hip), so a saturated SIMD can read > 1.
-            if pmc.get("active_inst_valu_quad_cycles") and pmc.get("gui_active_cycles"):
-                roof["valu_nominal_issue_share"] = round(pmc["active_inst_valu_quad_cycles"] * 4.0 / SIMDS /
-                                                   (pmc["gui_active_cycles"] / 8.0), 4)
-            # The other scope, under its own key: what the device does per unit of time with frames in flight -- the
-            # vector instructions of a whole frame, every kernel, counted for the grid a host launches when it shares
-            # its GPU, over the measured time per frame of the pipelined blocks.
-            frame_insts = pmc.get("shared_frame_valu_insts") or pmc.get("frame_valu_insts")
-            if frame_insts:
-                frame_rate = frame_insts / (pipe_ms_per_step * 1e-3 * CLOCK_HZ * SIMDS)
-                roof["frame_pipelined"] = {
-                    "valu_insts_per_frame": int(frame_insts), "grid": "shared" if pmc.get("shared_frame_valu_insts") else "alone",
-                    "ms_per_frame": round(pipe_ms_per_step, 4), "achieved": round(frame_rate, 4),
-                    "frac": round(frame_rate / VALU_PEAK_PER_CLK_SIMD, 4),
-                    "frac_of_measured_ceiling": round(frame_rate / pmc["valu_ceiling_measured"], 4) if pmc.get("valu_ceiling_measured") else None,
-                    "frames_in_flight": in_flight}
-        else:
-            roof["counters_from"] = None if world > 1 else "profiles/pmc.json is missing or was collected for other kernel sources"
-        roof["hbm"] = hbm
-        out["roofline"] = roof
+        if args.full:
+            pipe_ms = per_step_ms("pipelined")
+            pipe_ms_per_step = statistics.median(pipe_ms)
+            out.update({
+                # every block is exactly `steps` frames, one at a time, between barrier + synchronize; the first is `value` /
+                # `ms_per_step`, the rest repeat it until --min-seconds are covered
+                "blocks": dict(summary(block_ms), unit="ms per step", seconds_covered=round(sum(results["blocking"]["seconds"]), 3),
+                               mrays_per_s_min=round(total_rays / (max(block_ms) * 1e-3) / 1e6, 1),
+                               mrays_per_s_max=round(total_rays / (min(block_ms) * 1e-3) / 1e6, 1)),
+                "kernels_ms_per_frame": round(alone_kernel_ms, 4),
+                # NOT the metric: the same frames as a steady stream through a ring of `frames_in_flight` hosts (the next
+                # frames' passes fill what a finishing pass frees) -- what the device sustains, measured the same way
+                "pipelined": dict(value=round(total_rays / (pipe_ms_per_step * 1e-3) / 1e6, 2), unit="Mrays/s",
+                                  ms_per_frame=summary(pipe_ms), frames_in_flight=in_flight, n_hosts_per_gpu=in_flight,
+                                  pgm_md5=md5["pipelined"], cpu_us_per_step=results["pipelined"]["cpu_us"],
+                                  seconds_covered=round(sum(results["pipelined"]["seconds"]), 3)),
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                cpu, _ = cpu_baseline(opt, scene, images["blocking"], w)
+            has_ao = bool(opt.enable_ao)
+            dominant = "ao_kernel" if has_ao else "primary_kernel"
+            dominant_ms = alone_ao_ms if has_ao else alone_kernel_ms
+            seconds = dominant_ms * 1e-3
+            pmc = pmc_for(args.workload) if world == 1 else None  # counters are per launch of the WHOLE frame on one GPU
+            # The contractual HBM line: algorithmic bytes of the reference traversal over the measured
+            # launch time, beside the HBM bytes the counters really saw.  The scene is cache-resident, so this is NOT
+            # the bound the kernel is under; `x_peak` may exceed 1 and is therefore not called a fraction.
+            hbm = {"peak": HBM_PEAK_GBS, "unit": "GB/s"}
+            if counters is not None:
+                sub = opt.total_width * opt.total_height
+                parts = algorithmic_bytes(counters, sub)
+                bytes_per_launch = (parts["ao"] if has_ao else parts["frame"]) / world  # bands are interleaved over ranks
+                hbm.update(algorithmic_bytes_per_launch=int(bytes_per_launch),
+                           algorithmic_GBps=round(bytes_per_launch / seconds / 1e9, 1),
+                           algorithmic_x_peak=round(bytes_per_launch / seconds / 1e9 / HBM_PEAK_GBS, 3),
+                           frame_algorithmic_GBps=round(parts["frame"] / world / (alone_kernel_ms * 1e-3) / 1e9, 1))
+            traffic = None
+            if pmc is not None:
+                traffic = int(pmc["hbm_bytes"])
+                hbm.update(measured_bytes_per_launch=traffic, measured_GBps=round(traffic / seconds / 1e9, 1),
+                           measured_frac=round(traffic / seconds / 1e9 / HBM_PEAK_GBS, 4))
+            hbm["note"] = ("algorithmic bytes = REFERENCE traversal (36 B/node visit + 60 B/triangle test [+ 48 B/hit + 4 B/"
+                           "sub-pixel for the primary pass]); they are served by the scalar cache and L2, not by HBM")
+            # The binding roofline: vector-instruction issue.  ONE scope for achieved / frac: the dominant kernel's
+            # instructions per launch (PMC pass of the same kernel sources, the grid a host alone launches; null if the
+            # sources changed since) over its launch duration with one frame at a time, HIP events, measured live.
+            roof = {"bound": "valu", "achieved": None, "peak": VALU_PEAK_PER_CLK_SIMD,
+                    "unit": "wave64 VALU instr/clk/SIMD (1024 SIMDs, 2.4 GHz)", "frac": None, "traffic": traffic,
+                    "scope": "dominant kernel alone: its instructions per launch over its launch duration, one frame at a time",
+                    "kernel": dominant, "kernel_ms": round(dominant_ms, 4), "frame_kernels_ms": round(alone_kernel_ms, 4)}
+            if pmc is not None:
+                rate = pmc["valu_insts"] / (seconds * CLOCK_HZ * SIMDS)
+                roof.update(achieved=round(rate, 4), frac=round(rate / VALU_PEAK_PER_CLK_SIMD, 4),
+                            insts_per_launch=int(pmc["valu_insts"]), ceiling_measured=pmc.get("valu_ceiling_measured"),
+                            levels=pmc.get("levels"), counters_from=pmc.get("source"))
+                if pmc.get("valu_ceiling_measured"):
+                    roof["frac_of_measured_ceiling"] = round(rate / pmc["valu_ceiling_measured"], 4)
+                # the hardware's own view, from the counter pass: cycles the SIMDs spent issuing vector instructions
+                # (SQ_ACTIVE_INST_VALU, quad-cycles summed over the SIMDs) over the cycles the launch took
+                # (GRBM_GUI_ACTIVE, summed over the 8 XCDs).  The counter books 4 cycles per instruction; v_fma / v_mul /
+                # v_add on registers issue in 2.3 (tools/microbench/valu_rate_probe.hip), so a saturated SIMD can read > 1.
+                if pmc.get("active_inst_valu_quad_cycles") and pmc.get("gui_active_cycles"):
+                    roof["valu_nominal_issue_share"] = round(pmc["active_inst_valu_quad_cycles"] * 4.0 / SIMDS /
+                                                       (pmc["gui_active_cycles"] / 8.0), 4)
+                # The other scope, under its own key: what the device does per unit of time with frames in flight -- the
+                # vector instructions of a whole frame, every kernel, counted for the grid a host launches when it shares
+                # its GPU, over the measured time per frame of the pipelined blocks.
+                frame_insts = pmc.get("shared_frame_valu_insts") or pmc.get("frame_valu_insts")
+                if frame_insts:
+                    frame_rate = frame_insts / (pipe_ms_per_step * 1e-3 * CLOCK_HZ * SIMDS)
+                    roof["frame_pipelined"] = {
+                        "valu_insts_per_frame": int(frame_insts), "grid": "shared" if pmc.get("shared_frame_valu_insts") else "alone",
+                        "ms_per_frame": round(pipe_ms_per_step, 4), "achieved": round(frame_rate, 4),
+                        "frac": round(frame_rate / VALU_PEAK_PER_CLK_SIMD, 4),
+                        "frac_of_measured_ceiling": round(frame_rate / pmc["valu_ceiling_measured"], 4) if pmc.get("valu_ceiling_measured") else None,
+                        "frames_in_flight": in_flight}
+            else:
+                roof["counters_from"] = None if world > 1 else "profiles/pmc.json is missing or was collected for other kernel sources"
+            roof["hbm"] = hbm
+            out["roofline"] = roof
         if cpu is not None:
             out["cpu_baseline"] = cpu
         if golden_md5 is None and cpu is None:
-            # a generated scene without a committed golden, and the CPU check of this run switched off: nothing in THIS run
+            # a generated scene without a committed golden, and no CPU check in this run (a plain run, or --no-cpu-baseline): nothing in THIS run
             # has compared the frame with the CPU's (tests/test_big_scenes.py does, at small sizes) -- the metric says so
             out["metric"] = out["metric"].replace("PGM bit-exact vs CPU", "PGM not compared with the CPU in this run")
         elif golden_md5 is None:

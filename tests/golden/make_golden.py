@@ -76,6 +76,8 @@ CASES = [
     case("ties_64_s4_a3", "ties", width=64, height=64, ss=4, ao=3, aod=1.0),
     case("ties_5x3_s1_a1", "ties", width=5, height=3, ao=1, aod=2.0, dump=True),
     case("single_32_s1_a3", "single", width=32, height=32, ao=3, dump=True),
+    # the reference kernel on one more macro set, kept whole (tests/test_oracle_golden.py: test_reference_kernel_agrees_here)
+    case("blob_40x24_s4_a2_d03_f08", "blob", width=40, height=24, ss=4, ao=2, aod=0.3, focal=0.8, dump=True),
     # BASELINE.json configs 3-5 at full size (digests only): interior stand-in 1080p and 4K, bunny with 64 samples
     # per pixel (regular 8x8 grid: 15360x8640 sub-pixels, 2.2 G rays)
     case("interior_1080p_s1_a3", "interior", width=1920, height=1080, ao=3),

@@ -32,8 +32,8 @@ def _run_bench(nproc, extra_env=None, bare=False, extra_args=()):
     env.update(extra_env or {})
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    args = ["--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--workload", "bunny_600_defaults", "--no-cpu-baseline",
-            "--no-end-to-end", "--min-seconds", "0.05"] + list(extra_args)
+    args = ["--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--workload", "bunny_600_defaults", "--full",
+            "--no-cpu-baseline", "--no-end-to-end", "--min-seconds", "0.05"] + list(extra_args)
     if bare:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + args
     else:

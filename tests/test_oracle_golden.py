@@ -99,19 +99,19 @@ def test_band_rendering_matches_full(rt, oracle, golden, scene_for):
     assert np.array_equal(bits(full), bits(parts))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference tree only exists in the build container")
-def test_reference_kernel_agrees_here(rt, oracle, golden, scene_for):
-    """Where the reference tree is mounted: compile its kernel for one more macro
-    set that is NOT in golden.json and compare floats with the oracle."""
+def test_reference_kernel_agrees_here(rt, oracle, scene_for):
+    """The reference's own kernel on one more macro set (other focal length, AO distance and sample count): its float
+    image and its RayTracer::resize bytes, stored whole by tests/golden/make_golden.py, against the oracle's."""
     import orc
 
+    name = "blob_40x24_s4_a2_d03_f08"
     opt = rt.Options.defaults(width=40, height=24, n_super_samples=4, ao_num_samples=2, ao_max_distance=0.3,
                               focal_length=0.8)
     _, arrays = scene_for("blob", "longest")
     p = orc.params_from_options(opt)
-    lib = orc.ref_kernel(p, opt.n_super_samples)
-    ref_img, _ = orc.ref_render(lib, p, arrays)
     img, _, _ = oracle.render(p, arrays)
+    with np.load(os.path.join(GOLDEN_DIR, f"render_{name}.npz")) as z:
+        ref_img, ref_u8 = z["image"], z["u8"]
+    assert ref_img.shape == (p.height, p.width)
     assert np.array_equal(bits(ref_img), bits(img))
-    assert np.array_equal(orc.RefHost().resize(ref_img, opt.width, opt.height, opt.n_super_samples),
-                          oracle.resize(img, opt.width, opt.height, opt.n_super_samples))
+    assert np.array_equal(ref_u8, oracle.resize(img, opt.width, opt.height, opt.n_super_samples))

@@ -17,15 +17,15 @@ if [ $STAGE = pmc ] || [ $STAGE = all ]; then
 fi
 if [ $STAGE = stats ] || [ $STAGE = all ]; then
   cd /tmp && export TMPDIR=/tmp
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end > $R/$OUT/stats_bench.log 2>&1
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats_one -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end --in-flight 1 > $R/$OUT/stats_one_bench.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end > $R/$OUT/stats_bench.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats_one -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end --in-flight 1 > $R/$OUT/stats_one_bench.log 2>&1
   cd $R
   echo "stats stage done"
 fi
 if [ $STAGE = bench ] || [ $STAGE = all ]; then
   cd $R
   for W in $WORKLOADS; do
-    python3 bench.py --steps 20 --warmup 5 --workload $W $( [ $W = bunny_1080p_ao ] || echo --no-cpu-baseline ) 2>/dev/null | tail -1 > $OUT/bench_$W.json
+    python3 bench.py --full --steps 20 --warmup 5 --workload $W $( [ $W = bunny_1080p_ao ] || echo --no-cpu-baseline ) 2>/dev/null | tail -1 > $OUT/bench_$W.json
     echo "$W: $(cut -c1-160 $OUT/bench_$W.json)"
   done
 fi
