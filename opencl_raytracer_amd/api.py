@@ -1,4 +1,4 @@
-"""ctypes binding of include/rt_hip.h, rt_hip_ring.h and rt_hip_debug.h (see those headers for the contract)."""
+"""ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h and rt_hip_query.h (see those headers for the contract)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -184,7 +184,56 @@ _SIGNATURES = {
     "rt_debug_set_frame_form": (C.c_int, [C.c_void_p, C.c_int]),
     "rt_debug_frame_is_fused": (C.c_int, [C.c_void_p]),
     "rt_debug_poison_hit_list": (C.c_int, [C.c_void_p]),
+    # include/rt_hip_query.h
+    "rt_trace_closest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
+    "rt_trace_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
+    "rt_trace_closest_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
+                                          C.c_void_p]),
+    "rt_trace_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
+                                           C.c_void_p]),
+    "rt_last_query_ms": (C.c_float, [C.c_void_p]),
 }
+
+
+class _HitArrays(C.Structure):
+    """rt_hit_arrays (include/rt_hip_query.h)."""
+    _fields_ = [("hit", C.c_void_p), ("distance", C.c_void_p), ("leaf", C.c_void_p), ("barycentric", C.c_void_p),
+                ("position", C.c_void_p), ("normal", C.c_void_p)]
+
+
+RT_QUERY_NO_SORT = 1
+QUERY_OUTPUTS = ("hit", "distance", "leaf", "barycentric", "position", "normal")
+# per output: numpy dtype, values per ray
+_QUERY_LAYOUT = {"hit": (np.uint8, 1), "distance": (np.float32, 1), "leaf": (np.uint32, 1), "barycentric": (np.float32, 3),
+                 "position": (np.float32, 3), "normal": (np.float32, 3)}
+
+
+def _is_torch(x) -> bool:
+    return type(x).__module__.startswith("torch")
+
+
+def _rays4_numpy(a, what: str) -> np.ndarray:
+    if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 2 or a.shape[1] not in (3, 4):
+        raise ValueError(f"{what}: expected a float32 array of shape (N, 3) or (N, 4)")
+    if a.shape[1] == 4:
+        return np.ascontiguousarray(a)
+    out = np.zeros((a.shape[0], 4), dtype=np.float32)
+    out[:, :3] = a
+    return out
+
+
+def _rays4_torch(t, what: str):
+    import torch
+
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] not in (3, 4):
+        raise ValueError(f"{what}: expected a float32 tensor of shape (N, 3) or (N, 4)")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: the tensor must be contiguous")
+    if t.device.type != "cuda":
+        raise ValueError(f"{what}: the tensor must be on the host's GPU")
+    if t.shape[1] == 4:
+        return t
+    return torch.nn.functional.pad(t, (0, 1))  # (N, 4), on the device, stream-ordered
 
 
 def load_library() -> C.CDLL:
@@ -322,6 +371,16 @@ class Scene:
     @property
     def sorted_faces(self) -> np.ndarray:
         return self._arr("rt_scene_sorted_faces", 3 * self.num_faces if self.num_nodes else 0, np.uint32)
+
+    def face_of_leaf(self, leaf=None) -> np.ndarray:
+        """The file-order face a query's `leaf` index stands for (rt_scene_triangles, include/rt_hip_query.h); without an
+        argument the whole map.  Leaves of 0xFFFFFFFF (no hit) map to 0xFFFFFFFF."""
+        faces = self.triangles
+        if leaf is None:
+            return faces
+        leaf = np.asarray(leaf, dtype=np.uint32)
+        miss = leaf == 0xFFFFFFFF
+        return np.where(miss, np.uint32(0xFFFFFFFF), faces[np.where(miss, 0, leaf)]).astype(np.uint32)
 
 
 class Host:
@@ -502,6 +561,71 @@ class Host:
 
     def reset_timers(self) -> None:
         load_library().rt_reset_timers(self._h)
+
+    # ---- ray queries (include/rt_hip_query.h) ----
+    def trace_closest(self, origins, directions, max_distance: float = 100000.0, outputs=QUERY_OUTPUTS, sort: bool = True) -> dict:
+        """Closest hit of every ray: {output name: array}.  numpy (N, 3) / (N, 4) float32 in, numpy out (blocking); torch
+        tensors on the host's GPU in, torch tensors out, enqueued on torch.cuda.current_stream() without waiting."""
+        return self._trace(True, origins, directions, max_distance, tuple(outputs), sort)
+
+    def trace_occluded(self, origins, directions, max_distance: float = 100000.0, sort: bool = True):
+        """Occlusion of every ray (the `hit` of trace_closest for the same rays and max_distance): uint8 (N,)."""
+        return self._trace(False, origins, directions, max_distance, ("hit",), sort)["hit"]
+
+    def _trace(self, closest: bool, origins, directions, max_distance: float, outputs: tuple, sort: bool) -> dict:
+        unknown = [o for o in outputs if o not in QUERY_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {QUERY_OUTPUTS}")
+        flags = 0 if sort else RT_QUERY_NO_SORT
+        lib = load_library()
+        if _is_torch(origins) or _is_torch(directions):
+            if not (_is_torch(origins) and _is_torch(directions)):
+                raise ValueError("origins and directions must both be torch tensors or both numpy arrays")
+            import torch
+
+            o4, d4 = _rays4_torch(origins, "origins"), _rays4_torch(directions, "directions")
+            if o4.shape[0] != d4.shape[0] or o4.device != d4.device:
+                raise ValueError("origins and directions must hold the same number of rays on the same device")
+            n = int(o4.shape[0])
+            tdtype = {np.uint8: torch.uint8, np.float32: torch.float32, np.uint32: torch.uint32}
+            out = {}
+            for name in outputs:
+                dt, per = _QUERY_LAYOUT[name]
+                out[name] = torch.empty((n, per) if per > 1 else (n,), dtype=tdtype[dt], device=o4.device)
+            stream = torch.cuda.current_stream(o4.device).cuda_stream
+            if closest:
+                arrays = _HitArrays(*[out[name].data_ptr() if name in out and n else None for name in QUERY_OUTPUTS])
+                _check(lib.rt_trace_closest_device(self._h, o4.data_ptr(), d4.data_ptr(), n, float(max_distance), flags,
+                                                   C.byref(arrays), stream))
+            else:
+                _check(lib.rt_trace_occluded_device(self._h, o4.data_ptr(), d4.data_ptr(), n, float(max_distance), flags,
+                                                    out["hit"].data_ptr() if n else None, stream))
+            # (the padded copies must live until the kernels have read them)
+            if o4 is not origins:
+                o4.record_stream(torch.cuda.current_stream(o4.device))
+            if d4 is not directions:
+                d4.record_stream(torch.cuda.current_stream(d4.device))
+            return out
+        o4, d4 = _rays4_numpy(origins, "origins"), _rays4_numpy(directions, "directions")
+        if o4.shape[0] != d4.shape[0]:
+            raise ValueError("origins and directions must hold the same number of rays")
+        n = int(o4.shape[0])
+        out = {}
+        for name in outputs:
+            dt, per = _QUERY_LAYOUT[name]
+            out[name] = np.empty((n, per) if per > 1 else (n,), dtype=dt)
+        if closest:
+            arrays = _HitArrays(*[out[name].ctypes.data if name in out and n else None for name in QUERY_OUTPUTS])
+            _check(lib.rt_trace_closest(self._h, o4.ctypes.data, d4.ctypes.data, n, float(max_distance), flags, C.byref(arrays)))
+        else:
+            _check(lib.rt_trace_occluded(self._h, o4.ctypes.data, d4.ctypes.data, n, float(max_distance), flags,
+                                         out["hit"].ctypes.data if n else None))
+        return out
+
+    @property
+    def last_query_ms(self) -> float:
+        """HIP-event time of the last query's kernels (sort + walk), ms."""
+        return float(load_library().rt_last_query_ms(self._h))
 
 
 class FrameRing:

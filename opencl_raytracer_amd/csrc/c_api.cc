@@ -1,6 +1,7 @@
 // c_api.cc -- the extern "C" boundary declared in include/rt_hip.h (the seam), rt_hip_ring.h (streams of frames, several GPUs) and rt_hip_debug.h.
 #include "../../include/rt_hip.h"
 #include "../../include/rt_hip_debug.h"
+#include "../../include/rt_hip_query.h"
 
 #include <algorithm>
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 #include "frame_ring.h"
 #include "hip_host.h"
 #include "mesh.h"
+#include "ray_query.h"
 #include "ray_tracer.h"
 #include "scene_pack.h"
 
@@ -29,6 +31,7 @@ struct rt_scene {
 struct rt_host {
 	std::unique_ptr<ocrt::DeviceRenderer> owned;  // empty for a view of a ring's renderer (rt_ring_host)
 	ocrt::DeviceRenderer *dev = nullptr;
+	std::unique_ptr<ocrt::RayQueries> queries;  // rt_hip_query.h: made at the first query (destroyed before `owned`)
 };
 
 struct rt_ring {
@@ -45,6 +48,29 @@ int fail(int code, const std::string &message) {
 	g_error = message;
 	g_error_code = code;
 	return code;
+}
+
+// What every query entry point checks before it touches the device (include/rt_hip_query.h, "Errors").
+int query_precheck(rt_host *h, const float *origins4, const float *directions4, uint32_t n, bool device) {
+	if (!h)
+		return fail(RT_E_INVALID, "null host");
+	if (!h->owned)
+		return fail(RT_E_STATE, "ray queries are not available on the hosts of a frame ring");
+	if (!h->dev->sceneReady())
+		return fail(RT_E_STATE, "ray query before a scene was uploaded");
+	if (n > RT_QUERY_MAX_RAYS)
+		return fail(RT_E_INVALID, "more rays than RT_QUERY_MAX_RAYS in one call");
+	if (n > 0 && (!origins4 || !directions4))
+		return fail(RT_E_INVALID, "null ray arrays");
+	if (device && n > 0 && (((uintptr_t) origins4 | (uintptr_t) directions4) & 15u))
+		return fail(RT_E_INVALID, "device ray arrays must be 16-byte aligned");
+	return RT_OK;
+}
+
+ocrt::RayQueries &queries_of(rt_host *h) {
+	if (!h->queries)
+		h->queries.reset(new ocrt::RayQueries(*h->dev));
+	return *h->queries;
 }
 
 // Maps the exception in flight to an RT_E_* code.
@@ -769,6 +795,72 @@ int rt_ring_rccl_self_test(rt_ring *r) {
 }
 
 void rt_print_info(void) { HipHost::printInfo(); }
+// ---- rt_hip_query.h ----
+int rt_trace_closest(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
+                     const rt_hit_arrays *out) {
+	const int rc = query_precheck(h, origins4, directions4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	const rt_hit_arrays none{};
+	const rt_hit_arrays &o = out ? *out : none;
+	return guarded([&] {
+		queries_of(h).traceHost(true, origins4, directions4, n, max_distance, flags, o.hit, o.distance, o.leaf, o.barycentric,
+		                        o.position, o.normal);
+	});
+}
+
+int rt_trace_occluded(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
+                      uint8_t *occluded) {
+	const int rc = query_precheck(h, origins4, directions4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	return guarded([&] {
+		queries_of(h).traceHost(false, origins4, directions4, n, max_distance, flags, occluded, nullptr, nullptr, nullptr, nullptr,
+		                        nullptr);
+	});
+}
+
+int rt_trace_closest_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
+                            uint32_t flags, const rt_hit_arrays *out, void *hip_stream) {
+	const int rc = query_precheck(h, origins4, directions4, n, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	ocrt::QueryOutputs q;
+	if (out) {
+		if ((((uintptr_t) out->distance | (uintptr_t) out->leaf | (uintptr_t) out->barycentric | (uintptr_t) out->position |
+		      (uintptr_t) out->normal) & 3u) != 0)
+			return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+		q.hit = out->hit;
+		q.distance = out->distance;
+		q.leaf = out->leaf;
+		q.barycentric = out->barycentric;
+		q.position = out->position;
+		q.normal = out->normal;
+	}
+	return guarded([&] { queries_of(h).traceDevice(true, origins4, directions4, n, max_distance, flags, q, hip_stream); });
+}
+
+int rt_trace_occluded_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
+                             uint32_t flags, uint8_t *occluded, void *hip_stream) {
+	const int rc = query_precheck(h, origins4, directions4, n, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	ocrt::QueryOutputs q;
+	q.hit = occluded;
+	return guarded([&] { queries_of(h).traceDevice(false, origins4, directions4, n, max_distance, flags, q, hip_stream); });
+}
+
+float rt_last_query_ms(const rt_host *h) {
+	if (!h || !h->queries)
+		return 0.0f;
+	try {
+		return h->queries->lastMs();
+	} catch (...) {
+		fail_from_exception();
+		return 0.0f;
+	}
+}
+
 int rt_device_count(void) { return ocrt::visible_device_count(); }
 
 }  // extern "C"

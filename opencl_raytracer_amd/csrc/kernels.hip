@@ -28,6 +28,8 @@
 //   finish_kernel / finish_wide_kernel
 //                   value * (1 - occluded / n) into the tagged sub-pixels and the supersample box filter +
 //                   quantisation of the same sweep (n = 1: a thread per pixel; n >= 2: along the sub-pixel rows).
+//   (queries)       query_key_kernel / query_scan_kernel / query_scatter_kernel order caller-supplied rays by a coherence
+//                   key, query_kernel<CLOSEST> casts them (kernels/query.hip.h, include/rt_hip_query.h): not part of a frame.
 //   (on demand)     entry_kernel: the walk intervals, once per upload; occluded_sum_kernel: the frame's occlusion
 //                   total when the statistics are asked for; resize_kernel: a box filter on its own.
 // Why not one fused launch (it was, see profiles/r01_notes.md): cost per tile
@@ -64,6 +66,7 @@
 #include "kernels/frame.hip.h"
 #include "kernels/entry.hip.h"
 #include "kernels/finish.hip.h"
+#include "kernels/query.hip.h"
 
 
 namespace ocrt {
@@ -347,6 +350,58 @@ void launch_resize(const float *tmp, unsigned char *out, const KernelParams &P, 
 	}
 	hipLaunchKernelGGL(resize_kernel, dim3((out_width + 255) / 256, local_out_rows), dim3(256), 0,
 	                   (hipStream_t) stream, tmp, out, out_width, P.height / n, P.width, n, P.part, rows_per_band);
+}
+
+// Ray queries (kernels/query.hip.h).  `count`: QUERY_BUCKETS words of scratch, `order`: n words; both on the device.
+void launch_query_sort(const void *origins, const void *directions, uint32_t n, const float lo[3], const float scale[3], void *count,
+                       void *order, void *stream) {
+	if (n == 0)
+		return;
+	hipStream_t s = (hipStream_t) stream;
+	QueryKeyArgs a{};
+	a.origins = (const float4 *) origins;
+	a.directions = (const float4 *) directions;
+	a.count = (uint32_t *) count;
+	a.order = (uint32_t *) order;
+	a.n = n;
+	for (int k = 0; k < 3; ++k) {
+		a.lo[k] = lo[k];
+		a.scale[k] = scale[k];
+	}
+	(void) hipMemsetAsync(count, 0, QUERY_BUCKETS * sizeof(uint32_t), s);
+	const uint32_t blocks = (n + 255u) / 256u;
+	hipLaunchKernelGGL(query_key_kernel, dim3(blocks), dim3(256), 0, s, a);
+	hipLaunchKernelGGL(query_scan_kernel, dim3(1), dim3(QUERY_SCAN_THREADS), 0, s, (uint32_t *) count);
+	hipLaunchKernelGGL(query_scatter_kernel, dim3(blocks), dim3(256), 0, s, a);
+}
+
+void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *origins, const void *directions,
+                  const void *order, uint32_t n, float max_distance, unsigned char *hit, float *distance, uint32_t *leaf,
+                  float *barycentric, float *position, float *normal, void *stream) {
+	if (n == 0)
+		return;
+	QueryArgs a{};
+	a.nodes_ptr = (const float4 *) scene.nodes;
+	a.tris_ptr = (const float4 *) scene.tris;
+	a.shade = (const float4 *) scene.shade;
+	a.origins = (const float4 *) origins;
+	a.directions = (const float4 *) directions;
+	a.order = (const uint32_t *) order;
+	a.n = n;
+	a.node_count = node_count;
+	a.max_distance = max_distance;
+	a.hit = hit;
+	const uint32_t blocks = (n + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
+	if (closest) {
+		a.distance = distance;
+		a.leaf = leaf;
+		a.barycentric = barycentric;
+		a.position = position;
+		a.normal = normal;
+		hipLaunchKernelGGL(query_kernel<true>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
+	} else {
+		hipLaunchKernelGGL(query_kernel<false>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
+	}
 }
 
 }  // namespace ocrt

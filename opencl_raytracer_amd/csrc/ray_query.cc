@@ -1,0 +1,161 @@
+// ray_query.cc -- ray queries on a render host's uploaded scene (ray_query.h).
+#include "ray_query.h"
+
+#include <cmath>
+#include <stdexcept>
+
+#include "device_internal.h"
+
+namespace ocrt {
+
+namespace {
+constexpr size_t QUERY_COUNT_BYTES = (size_t) 1 << 18;  // kernels/query.hip.h: QUERY_BUCKETS words
+constexpr uint32_t QUERY_NO_SORT = 1u, QUERY_SORT_MIN = 16384u;  // include/rt_hip_query.h
+size_t round16(size_t bytes) { return (bytes + 15u) & ~(size_t) 15u; }
+}  // namespace
+
+RayQueries::RayQueries(DeviceRenderer &renderer) : dev(renderer) {
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	OCRT_HIP(hipEventCreate((hipEvent_t *) &ev_start));
+	OCRT_HIP(hipEventCreate((hipEvent_t *) &ev_stop));
+}
+
+RayQueries::~RayQueries() {
+	if (hipSetDevice(dev.deviceIndex()) != hipSuccess)
+		return;
+	if (timed)
+		(void) hipEventSynchronize((hipEvent_t) ev_stop);
+	device_free(d_count);
+	device_free(d_order);
+	device_free(d_stage);
+	(void) hipEventDestroy((hipEvent_t) ev_start);
+	(void) hipEventDestroy((hipEvent_t) ev_stop);
+}
+
+// (hipFree waits for the device: a query still running on the old buffer finishes first)
+void RayQueries::grow(void *&buffer, size_t &capacity, size_t bytes) {
+	if (bytes <= capacity && buffer)
+		return;
+	device_free(buffer);
+	capacity = 0;
+	buffer = device_alloc(bytes);
+	capacity = bytes;
+}
+
+// The sort key's origin cells: 8 per axis over the root's box (exact records, read once per uploaded scene).  A box that
+// is no box (damaged arrays) gives [-1, 1]: the key then sorts worse, the results are the same.
+void RayQueries::sceneBox(const DeviceScene &scene, float lo[3], float scale[3]) {
+	const std::shared_ptr<const DeviceScene> current = dev.deviceScene();
+	if (boxed.lock() != current) {
+		NodeRec root{};
+		if (scene.nodeCount() > 0)
+			OCRT_HIP(hipMemcpy(&root, scene.buffers().nodes, sizeof root, hipMemcpyDeviceToHost));
+		for (int k = 0; k < 3; ++k) {
+			const float extent = root.hi[k] - root.lo[k];
+			const bool usable = std::isfinite(root.lo[k]) && std::isfinite(extent) && extent > 0.0f;
+			box_lo[k] = usable ? root.lo[k] : -1.0f;
+			box_scale[k] = usable ? 8.0f / extent : 4.0f;
+			if (!std::isfinite(box_scale[k]))
+				box_scale[k] = 4.0f, box_lo[k] = -1.0f;
+		}
+		boxed = current;
+	}
+	for (int k = 0; k < 3; ++k) {
+		lo[k] = box_lo[k];
+		scale[k] = box_scale[k];
+	}
+}
+
+void RayQueries::traceDevice(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
+                             uint32_t flags, const QueryOutputs &out, void *stream) {
+	if (!dev.sceneReady() || !dev.deviceScene())
+		throw std::logic_error("ray query before a scene was uploaded");
+	if (n == 0)
+		return;
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
+	const DeviceScene &scene = *dev.deviceScene();
+	// one set of scratch per host: a query on another stream waits for the one before it
+	if (timed)
+		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	const bool sort = !(flags & QUERY_NO_SORT) && n >= QUERY_SORT_MIN;
+	if (sort) {
+		size_t count_bytes = d_count ? QUERY_COUNT_BYTES : 0;
+		grow(d_count, count_bytes, QUERY_COUNT_BYTES);
+		grow(d_order, order_bytes, (size_t) n * sizeof(uint32_t));
+	}
+	float lo[3], scale[3];
+	if (sort)
+		sceneBox(scene, lo, scale);
+	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
+	if (sort)
+		launch_query_sort(origins4, directions4, n, lo, scale, d_count, d_order, s);
+	launch_query(scene.buffers(), dev.params().node_count, closest, origins4, directions4, sort ? d_order : nullptr, n, max_distance,
+	             out.hit, out.distance, out.leaf, out.barycentric, out.position, out.normal, s);
+	OCRT_HIP(hipGetLastError());
+	OCRT_HIP(hipEventRecord((hipEvent_t) ev_stop, s));
+	timed = true;
+	have_ms = false;
+}
+
+void RayQueries::traceHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
+                           uint32_t flags, unsigned char *hit, float *distance, uint32_t *leaf, float *barycentric, float *position,
+                           float *normal) {
+	if (!dev.sceneReady() || !dev.deviceScene())
+		throw std::logic_error("ray query before a scene was uploaded");
+	if (n == 0)
+		return;
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	hipStream_t s = (hipStream_t) dev.streamHandle();
+	// staging: origins, directions, then the outputs asked for
+	const size_t ray_bytes = (size_t) n * 16u, word_bytes = round16((size_t) n * 4u), vec_bytes = round16((size_t) n * 12u);
+	size_t at = 2 * ray_bytes;
+	QueryOutputs out;
+	auto place = [&](bool wanted, size_t bytes) -> size_t {
+		if (!wanted)
+			return (size_t) -1;
+		const size_t here = at;
+		at += bytes;
+		return here;
+	};
+	const size_t o_hit = place(hit != nullptr, round16(n)), o_dist = place(closest && distance, word_bytes);
+	const size_t o_leaf = place(closest && leaf, word_bytes), o_bary = place(closest && barycentric, vec_bytes);
+	const size_t o_pos = place(closest && position, vec_bytes), o_norm = place(closest && normal, vec_bytes);
+	grow(d_stage, stage_bytes, at);
+	char *base = (char *) d_stage;
+	auto dptr = [&](size_t offset) -> void * { return offset == (size_t) -1 ? nullptr : base + offset; };
+	out.hit = (unsigned char *) dptr(o_hit);
+	out.distance = (float *) dptr(o_dist);
+	out.leaf = (uint32_t *) dptr(o_leaf);
+	out.barycentric = (float *) dptr(o_bary);
+	out.position = (float *) dptr(o_pos);
+	out.normal = (float *) dptr(o_norm);
+	OCRT_HIP(hipMemcpyAsync(base, origins4, ray_bytes, hipMemcpyHostToDevice, s));
+	OCRT_HIP(hipMemcpyAsync(base + ray_bytes, directions4, ray_bytes, hipMemcpyHostToDevice, s));
+	traceDevice(closest, (const float *) base, (const float *) (base + ray_bytes), n, max_distance, flags, out, s);
+	auto back = [&](void *host, const void *device, size_t bytes) {
+		if (host && device)
+			OCRT_HIP(hipMemcpyAsync(host, device, bytes, hipMemcpyDeviceToHost, s));
+	};
+	back(hit, out.hit, n);
+	back(distance, out.distance, (size_t) n * 4u);
+	back(leaf, out.leaf, (size_t) n * 4u);
+	back(barycentric, out.barycentric, (size_t) n * 12u);
+	back(position, out.position, (size_t) n * 12u);
+	back(normal, out.normal, (size_t) n * 12u);
+	OCRT_HIP(hipStreamSynchronize(s));
+}
+
+float RayQueries::lastMs() {
+	if (!timed)
+		return 0.0f;
+	if (!have_ms) {
+		OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
+		OCRT_HIP(hipEventElapsedTime(&last_ms, (hipEvent_t) ev_start, (hipEvent_t) ev_stop));
+		have_ms = true;
+	}
+	return last_ms;
+}
+
+}  // namespace ocrt

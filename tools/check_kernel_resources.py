@@ -13,7 +13,10 @@ Hot kernels (must have VGPR spill 0, scratch 0, occupancy 8): the default path, 
 shared-walk instantiations primary_kernel<true> and ao_kernel<1, true> (1 = UNIFORM).  The
 first-generation instantiations (<.., false>, debug knob OCRT_NO_SHARED_WALK) and the RANDOM
 mode (ao_kernel<2, ..>, outside the bit-exact contract) must keep the occupancy; their
-spills are reported, not fatal.  SGPR spills go to VGPR lanes (v_writelane / v_readlane), not
+spills are reported, not fatal.  The ray-query kernels (query_kernel<true> / <false>, query_key_kernel,
+query_scatter_kernel, query_scan_kernel: kernels/query.hip.h) must be present, with VGPR spill 0 and scratch 0; they do
+not use walk_collect's fixed registers (their walk is the exact form, plain C++ around one scalar load per node), so no
+occupancy is pinned for them -- a spill there would still be memory traffic on every node of every query.  SGPR spills go to VGPR lanes (v_writelane / v_readlane), not
 to memory -- but those are vector instructions, the very resource the walk is bound by, so
 WHERE they land matters: with `--isa` (the device assembly of the same translation unit,
 `hipcc --cuda-device-only -S`) the tool locates every lane operation of the hot kernels by
@@ -126,6 +129,15 @@ def main():
         if hot and (k.get("VGPRs Spill") != "0" or k.get("ScratchSize [bytes/lane]") != "0"):
             errors.append(f"{name}: VGPR spill {k.get('VGPRs Spill')}, scratch {k.get('ScratchSize [bytes/lane]')} B/lane "
                           "in a hot kernel (walk_collect's fixed registers v56-v62 need the 64-VGPR budget to hold)")
+    queries = ("query_kernel<true>", "query_kernel<false>", "query_key_kernel", "query_scatter_kernel", "query_scan_kernel")
+    names = [k["name"].replace("ocrt::", "").replace("void ", "") for k in kernels]
+    for q in queries:
+        found = [k for k, n in zip(kernels, names) if n.startswith(q)]
+        if not found:
+            errors.append(f"{q}: not in the remarks (the ray-query kernels must be built)")
+        for k in found:
+            if k.get("VGPRs Spill") != "0" or k.get("ScratchSize [bytes/lane]") != "0":
+                errors.append(f"{q}: VGPR spill {k.get('VGPRs Spill')}, scratch {k.get('ScratchSize [bytes/lane]')} B/lane in a ray-query kernel")
     if "--isa" in sys.argv:
         places = lane_ops_by_place(open(sys.argv[sys.argv.index("--isa") + 1]).read())
         lines.append("")
