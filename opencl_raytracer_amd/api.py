@@ -1,4 +1,5 @@
-"""ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h and rt_hip_query.h (see those headers for the contract)."""
+"""ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h, rt_hip_query.h and rt_hip_camera.h (see those headers
+for the contract)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -75,6 +76,38 @@ class _Stats(C.Structure):
         ("ao_rays", C.c_uint64),
         ("ao_occluded", C.c_uint64),
     ]
+
+
+class Camera(C.Structure):
+    """rt_camera (include/rt_hip_camera.h): eye, right, up, forward -- four float triples, used as given."""
+
+    _fields_ = [("eye", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3), ("forward", C.c_float * 3)]
+
+    @classmethod
+    def default(cls) -> "Camera":
+        """The reference's camera: eye (0, 0, 2), right (1, 0, 0), up (0, 1, 0), forward (0, 0, -1)."""
+        c = cls()
+        load_library().rt_camera_default(C.byref(c))
+        return c
+
+    @classmethod
+    def look_at(cls, eye, target, up=(0.0, 1.0, 0.0)) -> "Camera":
+        """An orthonormal, right-handed pose at `eye` looking at `target` (rt_camera_look_at); RtError -1 where there is none."""
+        c = cls()
+        _check(load_library().rt_camera_look_at((C.c_float * 3)(*eye), (C.c_float * 3)(*target), (C.c_float * 3)(*up), C.byref(c)))
+        return c
+
+    @classmethod
+    def from_vectors(cls, eye, right, up, forward) -> "Camera":
+        """The four triples as given (float32): nothing is normalised or checked."""
+        c = cls()
+        for name, v in (("eye", eye), ("right", right), ("up", up), ("forward", forward)):
+            setattr(c, name, (C.c_float * 3)(*np.asarray(v, dtype=np.float32).tolist()))
+        return c
+
+    def as_array(self) -> np.ndarray:
+        """(4, 3) float32: eye, right, up, forward."""
+        return np.frombuffer(bytes(self), dtype=np.float32).reshape(4, 3).copy()
 
 
 _LIB: Optional[C.CDLL] = None
@@ -192,6 +225,12 @@ _SIGNATURES = {
     "rt_trace_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
                                            C.c_void_p]),
     "rt_last_query_ms": (C.c_float, [C.c_void_p]),
+    # include/rt_hip_camera.h
+    "rt_camera_default": (None, [C.POINTER(Camera)]),
+    "rt_camera_look_at": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Camera)]),
+    "rt_set_camera": (C.c_int, [C.c_void_p, C.POINTER(Camera)]),
+    "rt_get_camera": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(C.c_int)]),
+    "rt_ring_set_camera": (C.c_int, [C.c_void_p, C.POINTER(Camera)]),
 }
 
 
@@ -428,6 +467,23 @@ class Host:
     def upload_scene(self, scene: Scene) -> None:
         _check(load_library().rt_upload_scene(self._h, scene._h))
 
+    def set_camera(self, camera: Camera) -> None:
+        """Gives the host its pose (include/rt_hip_camera.h, rt_set_camera): before the upload only, RtError -4 afterwards
+        and on the hosts of a frame ring."""
+        _check(load_library().rt_set_camera(self._h, C.byref(camera)))
+
+    def camera(self) -> Camera:
+        """The host's pose -- the reference's camera if none was set (`camera_is_set`)."""
+        c = Camera()
+        _check(load_library().rt_get_camera(self._h, C.byref(c), None))
+        return c
+
+    @property
+    def camera_is_set(self) -> bool:
+        c, flag = Camera(), C.c_int()
+        _check(load_library().rt_get_camera(self._h, C.byref(c), C.byref(flag)))
+        return bool(flag.value)
+
     def render(self) -> None:
         _check(load_library().rt_render(self._h))
 
@@ -635,13 +691,19 @@ class FrameRing:
     once, `collect()` waits for the oldest one, `run(k)` is k steps of a steady stream in ONE call into the library."""
 
     def __init__(self, options: Options, scene: Optional["Scene"] = None, device: int = 0, rank: int = 0, nranks: int = 1,
-                 hosts: int = 3):
+                 hosts: int = 3, camera: Optional[Camera] = None):
         self.options = options
         self._r = load_library().rt_ring_create(C.byref(options), device, rank, nranks, hosts)
         if not self._r:
             _raise_last()
+        if camera is not None:  # (before the upload: the pose is fixed per upload)
+            self.set_camera(camera)
         if scene is not None:
             self.upload_scene(scene)
+
+    def set_camera(self, camera: Camera) -> None:
+        """The pose of all the ring's hosts (include/rt_hip_camera.h, rt_ring_set_camera): before the upload only."""
+        _check(load_library().rt_ring_set_camera(self._r, C.byref(camera)))
 
     def close(self) -> None:
         if getattr(self, "_r", None):

@@ -1,5 +1,7 @@
-// c_api.cc -- the extern "C" boundary declared in include/rt_hip.h (the seam), rt_hip_ring.h (streams of frames, several GPUs) and rt_hip_debug.h.
+// c_api.cc -- the extern "C" boundary declared in include/rt_hip.h (the seam), rt_hip_ring.h (streams of frames, several GPUs), rt_hip_debug.h,
+// rt_hip_query.h and rt_hip_camera.h.
 #include "../../include/rt_hip.h"
+#include "../../include/rt_hip_camera.h"
 #include "../../include/rt_hip_debug.h"
 #include "../../include/rt_hip_query.h"
 
@@ -13,6 +15,7 @@
 
 #include "bvh.h"
 #include "band_gather.h"
+#include "camera.h"
 #include "device_renderer.h"
 #include "frame_ring.h"
 #include "hip_host.h"
@@ -109,6 +112,14 @@ RayTracer::Options to_options(const rt_options &o) {
 	r.bvhMethod = o.bvh_method == 0 ? BVH::Method::CUT_LONGEST_AXIS : BVH::Method::SURFACE_AREA_HEURISTIC;
 	return r;
 }
+
+static_assert(sizeof(rt_camera) == sizeof(ocrt::CameraPose), "rt_camera is CameraPose");
+ocrt::CameraPose to_pose(const rt_camera &c) {
+	ocrt::CameraPose p;
+	std::memcpy(&p, &c, sizeof p);
+	return p;
+}
+void from_pose(const ocrt::CameraPose &p, rt_camera *out) { std::memcpy(out, &p, sizeof p); }
 
 template <class F> int guarded(F &&body) {
 	try {
@@ -862,5 +873,48 @@ float rt_last_query_ms(const rt_host *h) {
 }
 
 int rt_device_count(void) { return ocrt::visible_device_count(); }
+
+// ---- rt_hip_camera.h ----
+void rt_camera_default(rt_camera *out) {
+	if (out)
+		from_pose(ocrt::default_camera_pose(), out);
+}
+
+int rt_camera_look_at(const float eye[3], const float target[3], const float up_hint[3], rt_camera *out) {
+	if (!eye || !target || !up_hint || !out)
+		return fail(RT_E_INVALID, "null argument");
+	ocrt::CameraPose pose;
+	if (!ocrt::camera_look_at(eye, target, up_hint, &pose))
+		return fail(RT_E_INVALID, "no camera there: the eye, the target and the up hint must be finite, the eye must differ from the target, and the up hint must not lie along the view direction");
+	from_pose(pose, out);
+	return RT_OK;
+}
+
+int rt_set_camera(rt_host *h, const rt_camera *cam) {
+	if (!h || !cam)
+		return fail(RT_E_INVALID, "null argument");
+	if (!h->owned)
+		return fail(RT_E_STATE, "the hosts of a frame ring take the ring's camera (rt_ring_set_camera)");
+	if (h->dev->sceneReady())
+		return fail(RT_E_STATE, "set the camera first: rt_set_camera comes before rt_upload (an upload prepares the scene for one view)");
+	return guarded([&] { h->dev->setCamera(to_pose(*cam)); });
+}
+
+int rt_get_camera(const rt_host *h, rt_camera *out, int *is_set) {
+	if (!h || !out)
+		return fail(RT_E_INVALID, "null argument");
+	from_pose(h->dev->camera(), out);
+	if (is_set)
+		*is_set = h->dev->cameraIsSet() ? 1 : 0;
+	return RT_OK;
+}
+
+int rt_ring_set_camera(rt_ring *r, const rt_camera *cam) {
+	if (!r || !cam)
+		return fail(RT_E_INVALID, "null argument");
+	if (r->ring->host(0).sceneReady())
+		return fail(RT_E_STATE, "set the camera first: rt_ring_set_camera comes before rt_ring_upload (an upload prepares the scene for one view)");
+	return guarded([&] { r->ring->setCamera(to_pose(*cam)); });
+}
 
 }  // extern "C"

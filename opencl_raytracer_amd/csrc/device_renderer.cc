@@ -213,7 +213,7 @@ size_t DeviceRenderer::upload(const PackedScene &scene) {
 	useDevice();
 	synchronize();
 	freeScene();
-	std::shared_ptr<const DeviceScene> made = DeviceScene::create(device, scene, opts, expected_frames >= FRAMES_WORTH_INTERVALS);
+	std::shared_ptr<const DeviceScene> made = DeviceScene::create(device, scene, opts, expected_frames >= FRAMES_WORTH_INTERVALS, pose_set ? pose.eye : nullptr);
 	const size_t scene_bytes = made->bytes();
 	return scene_bytes + adopt(std::move(made));
 }
@@ -223,10 +223,13 @@ size_t DeviceRenderer::adopt(std::shared_ptr<const DeviceScene> scene, const Dev
 		throw std::invalid_argument("the scene lives on another device than the renderer");
 	if (!scene->servesOptions(opts))
 		throw std::invalid_argument("the scene on the device was made for other ambient-occlusion options than the renderer's");
+	// (the walk array's margins, child order and pruning bound are the eye's: two renderers with different eyes never share one)
+	if (!scene->servesEye(pose_set ? pose.eye : nullptr))
+		throw std::invalid_argument("the scene on the device was made for another eye than the renderer's camera");
 	useDevice();
 	synchronize();
 	freeScene();
-	kp = make_kernel_params(rt, scene->nodeCount(), scene->triCount(), scene->aoDirs(), part, &scene->facts());
+	kp = make_kernel_params(rt, scene->nodeCount(), scene->triCount(), scene->aoDirs(), part, &scene->facts(), pose_set ? &pose : nullptr);
 	kp.shared_device = device_share > 1u ? 1 : 0;
 	// How wide the strips are that the image is dealt to the eight XCD groups in (kernels.hip, "Tile <-> workgroup
 	// mapping").  Two tiles while the scene fits the caches -- the finest deal balances best.  A scene several times the
@@ -264,7 +267,8 @@ size_t DeviceRenderer::adopt(std::shared_ptr<const DeviceScene> scene, const Dev
 	                    layout_from->tile_count != tile_count || layout_from->part.rank != part.rank ||
 	                    layout_from->part.nranks != part.nranks || layout_from->rt.totalWidth != rt.totalWidth ||
 	                    layout_from->rt.totalHeight != rt.totalHeight || layout_from->kp.entry_stride != kp.entry_stride ||
-	                    (layout_from->expected_frames >= FRAMES_WORTH_INTERVALS) != (expected_frames >= FRAMES_WORTH_INTERVALS)))
+	                    (layout_from->expected_frames >= FRAMES_WORTH_INTERVALS) != (expected_frames >= FRAMES_WORTH_INTERVALS) ||
+	                    layout_from->pose_set != pose_set || std::memcmp(&layout_from->pose, &pose, sizeof pose) != 0))
 		layout_from = nullptr;  // (not the same frame after all: count)
 	sizeHitList(layout_from);
 	return image_bytes + (size_t) local_out_rows * opts.width + hit_slots * (sizeof(HitRec) + sizeof(uint32_t)) +
@@ -393,8 +397,18 @@ void DeviceRenderer::sizeHitList(const DeviceRenderer *layout_from) {
 	clock.mark("entries of the tiles' any-hit walks");
 }
 
+void DeviceRenderer::setCamera(const CameraPose &given) {
+	if (scene_ready)
+		throw std::logic_error("the camera is set before the upload: what an upload prepares -- walk array, hit list, tile order -- is made for one view");
+	pose = given;
+	pose_set = true;
+	kp = make_kernel_params(rt, 0, 0, 0, part, nullptr, &pose);
+	kp.shared_device = device_share > 1u ? 1 : 0;
+}
+
 bool DeviceRenderer::fusedFrame() const {
-	const bool possible = kp.ao_mode == AO_UNIFORM && kp.ao_dirs > 0 && kp.shared_walk && tile_count > 0 && kp.tiles_x < 65536u &&
+	// (the fused frame experiment has no posed form: a renderer with a camera pose renders its frames as two kernels)
+	const bool possible = !pose_set && kp.ao_mode == AO_UNIFORM && kp.ao_dirs > 0 && kp.shared_walk && tile_count > 0 && kp.tiles_x < 65536u &&
 	                      kp.local_tile_rows < 65536u && !primary_order_host.empty();
 	// Measured and NOT the rule (profiles/r05_notes.md): the fused frame renders the same bits, but a frame on its own takes
 	// 2-9 % LONGER with it than as two kernels -- headline 1.09 against 1.07 ms, interior 1080p 1.08 against 1.02, 4K 3.74

@@ -40,7 +40,10 @@ class DeviceScene {
 		// (AO_MAX_DISTANCE, which sizes the walk array's margins) are baked in -- servesOptions() says whether another
 		// renderer's options agree.
 		// (`for_a_stream`: make_walk_array's -- what only pays over many frames of the scene)
-		static std::shared_ptr<const DeviceScene> create(int device, const PackedScene &scene, const RayTracer::Options &options, bool for_a_stream = true);
+		// (`eye`: make_walk_array's -- where the primary rays of the renderers that will adopt the scene start; nullptr: the
+		// reference's camera.  The walk array is made for that eye: servesEye() says whether a renderer's agrees.)
+		static std::shared_ptr<const DeviceScene> create(int device, const PackedScene &scene, const RayTracer::Options &options, bool for_a_stream = true,
+		                                                 const float *eye = nullptr);
 		// A scene's arrays live in ONE device allocation.  A front end that knows the size of what is coming before it has
 		// the arrays (the triangle count of a mesh file's header) can have that allocation made ahead of time -- on the
 		// thread that brings the device up -- and create() takes it over if it is large enough (else it is dropped).
@@ -51,6 +54,7 @@ class DeviceScene {
 		DeviceScene(const DeviceScene &) = delete;
 		DeviceScene &operator=(const DeviceScene &) = delete;
 		bool servesOptions(const RayTracer::Options &options) const;
+		bool servesEye(const float *eye) const { return same_eye(walk_eye, eye); }
 
 		SceneBuffers buffers() const { return SceneBuffers{ d_nodes, d_walk, d_tris, d_shade, d_ao }; }
 		int device() const { return device_index; }
@@ -74,6 +78,7 @@ class DeviceScene {
 		unsigned int ao_samples = 0;
 		int ao_alpha_min = 0, ao_alpha_max = 0;
 		float walk_distance = 0.0f;
+		float walk_eye[3] = { 0.0f, 0.0f, 2.0f };  // the eye the walk array was made for
 };
 
 class DeviceRenderer {
@@ -96,6 +101,13 @@ class DeviceRenderer {
 		// host): the hit list's layout is copied from it instead of being counted again.
 		size_t adopt(std::shared_ptr<const DeviceScene> scene, const DeviceRenderer *layout_from = nullptr);
 		const std::shared_ptr<const DeviceScene> &deviceScene() const { return scene_on_device; }
+		// The camera pose (device_types.h: CameraPose): where this renderer's primary rays start and the basis their
+		// directions are made in, used as given.  BEFORE the upload only (std::logic_error afterwards): the walk array, the
+		// hit list's size, the tile order and the walk intervals are all made once per upload, for one view.  A renderer
+		// that is never given a pose renders the reference's view with the kernels that hold it as constants.
+		void setCamera(const CameraPose &pose);
+		bool cameraIsSet() const { return pose_set; }
+		const CameraPose &camera() const { return pose; }
 
 		// Enqueues the ray-casting kernel for this rank's bands on the stream.
 		void enqueueRender();
@@ -235,6 +247,8 @@ class DeviceRenderer {
 		RayTracer rt;
 		int device;
 		Partition part;
+		CameraPose pose = default_camera_pose();
+		bool pose_set = false;
 		KernelParams kp;
 		uint32_t grid;            // supersample grid side
 		uint32_t local_out_rows;

@@ -156,7 +156,25 @@ struct KernelParams {
 	uint32_t tiles_x;      // tiles per image row
 	uint32_t local_tile_rows;  // tile rows this rank owns
 	Partition part;
+	// The camera pose of a host that was given one (CameraPose below; DeviceRenderer::setCamera): the posed instantiation
+	// of the primary pass reads these where it makes its rays.  posed = 0: no pose was given -- the kernels with the
+	// reference's camera folded in are launched and none of these is read.
+	int32_t posed;
+	float eye_x, eye_y, eye_z;
+	float right_x, right_y, right_z;
+	float up_x, up_y, up_z;
+	float forward_x, forward_y, forward_z;
 };
+
+// A camera pose: where the primary rays start and the basis their directions are made in.  Used AS GIVEN -- not
+// normalised, not orthogonalised --: for the camera-space terms cx, cy of a sub-pixel (reference
+// src/intersect_kernel.cl:284-291) the ray's direction is normalize(((right * cx) + (up * cy)) + forward), every
+// product and sum rounded on its own, and its origin is eye.  The reference's camera is eye (0, 0, 2), right (1, 0, 0),
+// up (0, 1, 0), forward (0, 0, -1).
+struct CameraPose {
+	float eye[3], right[3], up[3], forward[3];
+};
+inline CameraPose default_camera_pose() { return CameraPose{ { 0.0f, 0.0f, 2.0f }, { 1.0f, 0.0f, 0.0f }, { 0.0f, 1.0f, 0.0f }, { 0.0f, 0.0f, -1.0f } }; }
 
 // Device pointers of one uploaded scene, as the launchers of kernels.hip take them.
 struct SceneBuffers {  // device pointers of one uploaded scene

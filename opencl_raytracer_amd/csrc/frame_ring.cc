@@ -81,7 +81,8 @@ size_t FrameRing::upload(const PackedScene &scene) {
 	// ONE copy of the scene on the GPU, whatever the number of hosts: they all walk the same arrays
 	for (auto &h : hosts)
 		h->synchronize();
-	std::shared_ptr<const DeviceScene> on_device = DeviceScene::create(hosts.front()->deviceIndex(), scene, hosts.front()->rayTracer().options);
+	std::shared_ptr<const DeviceScene> on_device = DeviceScene::create(hosts.front()->deviceIndex(), scene, hosts.front()->rayTracer().options, true,
+	                                                                   hosts.front()->cameraIsSet() ? hosts.front()->camera().eye : nullptr);
 	size_t bytes = on_device->bytes();
 	for (auto &h : hosts)
 		bytes += h->adopt(on_device, h == hosts.front() ? nullptr : hosts.front().get());  // (the hit list's layout is counted once)
@@ -103,6 +104,13 @@ size_t FrameRing::upload(const PackedScene &scene) {
 		hosts[slot % hosts.size()]->prepareFrame(bufferOf(slot));
 	uploaded_bytes = bytes;
 	return bytes;
+}
+
+void FrameRing::setCamera(const CameraPose &pose) {
+	if (hosts.front()->sceneReady())
+		throw std::logic_error("the camera is set before the upload: what an upload prepares -- walk array, hit list, tile order -- is made for one view");
+	for (auto &h : hosts)
+		h->setCamera(pose);
 }
 
 void FrameRing::setGraphMode(bool on) {

@@ -31,6 +31,9 @@ class FrameRing {
 		FrameRing &operator=(const FrameRing &) = delete;
 
 		size_t upload(const PackedScene &scene);  // every renderer of the ring; returns the bytes requested on the device
+		// The camera pose of ALL the ring's renderers (DeviceRenderer::setCamera), before the upload: they share one scene
+		// on the device, and with it one walk array, made for one eye.
+		void setCamera(const CameraPose &pose);
 		size_t uploadedBytes() const { return uploaded_bytes; }  // what the last upload() returned
 		// upload() measures which form of the ambient-occlusion pass suits the scene (on by default); what it found:
 		// ms per ao_kernel without / with the look-ahead loads (0: not measured) and the form the hosts now launch.

@@ -72,6 +72,8 @@ void HipHost::upload(const std::vector<uint32_t> &faces, const std::vector<uint3
                      const std::vector<Vec3f> &vnormals) {
 	try {
 		const ocrt::PackedScene packed = ocrt::pack_scene(faces, nodes, aabbs, vertices, vnormals);
+		if (camera_set && !impl->sceneReady())  // (the pose of the first upload holds for later ones)
+			impl->setCamera(camera);
 		const size_t bytes = impl->upload(packed);
 		std::cout << "Requested " << bytes / 1024 << " kB of memory." << std::endl;
 	} catch (const std::exception &e) {
@@ -81,6 +83,8 @@ void HipHost::upload(const std::vector<uint32_t> &faces, const std::vector<uint3
 
 void HipHost::upload(const ocrt::PackedScene &packed) {
 	try {
+		if (camera_set && !impl->sceneReady())
+			impl->setCamera(camera);
 		const size_t bytes = impl->upload(packed);
 		std::cout << "Requested " << bytes / 1024 << " kB of memory." << std::endl;
 	} catch (const std::exception &e) {
@@ -148,6 +152,8 @@ void HipHostRing::upload(const std::vector<uint32_t> &faces, const std::vector<u
                          const std::vector<Vec3f> &vnormals) {
 	try {
 		const ocrt::PackedScene packed = ocrt::pack_scene(faces, nodes, aabbs, vertices, vnormals);  // once; every host gets it
+		if (camera_set && !ring->host(0).sceneReady())
+			ring->setCamera(camera);
 		const size_t bytes = ring->upload(packed);
 		std::cout << "Requested " << bytes / 1024 << " kB of memory." << std::endl;
 	} catch (const std::exception &e) {
@@ -157,6 +163,8 @@ void HipHostRing::upload(const std::vector<uint32_t> &faces, const std::vector<u
 
 void HipHostRing::upload(const ocrt::PackedScene &packed) {
 	try {
+		if (camera_set && !ring->host(0).sceneReady())
+			ring->setCamera(camera);
 		const size_t bytes = ring->upload(packed);
 		std::cout << "Requested " << bytes / 1024 << " kB of memory." << std::endl;
 	} catch (const std::exception &e) {
@@ -308,8 +316,11 @@ void HipHostGroup::upload(const std::vector<uint32_t> &faces, const std::vector<
 	try {
 		const ocrt::PackedScene packed = ocrt::pack_scene(faces, nodes, aabbs, vertices, vnormals);  // once; replicated
 		size_t bytes = 0;
-		for (auto &h : hosts)
+		for (auto &h : hosts) {
+			if (camera_set && !h->sceneReady())
+				h->setCamera(camera);
 			bytes += h->upload(packed);
+		}
 		std::cout << "Requested " << bytes / 1024 << " kB of memory on " << hosts.size() << " devices." << std::endl;
 	} catch (const std::exception &e) {
 		die(e.what());
@@ -319,8 +330,11 @@ void HipHostGroup::upload(const std::vector<uint32_t> &faces, const std::vector<
 void HipHostGroup::upload(const ocrt::PackedScene &packed) {
 	try {
 		size_t bytes = 0;
-		for (auto &h : hosts)
+		for (auto &h : hosts) {
+			if (camera_set && !h->sceneReady())
+				h->setCamera(camera);
 			bytes += h->upload(packed);
+		}
 		std::cout << "Requested " << bytes / 1024 << " kB of memory on " << hosts.size() << " devices." << std::endl;
 	} catch (const std::exception &e) {
 		die(e.what());

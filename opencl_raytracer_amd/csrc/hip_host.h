@@ -61,6 +61,14 @@ class HipHost {
 		// an upload, which a caller can run while the device is still coming up (HipHost::warmUp).
 		void upload(const ocrt::PackedScene &packed);
 
+		// New: a camera pose (device_types.h: ocrt::CameraPose; camera.h makes one from eye, target and up hint), given
+		// BEFORE the upload, which prepares the scene for that one view.  Without one the host renders the reference's view
+		// (src/intersect_kernel.cl:284-291) exactly as it always did.  The pose is only kept here; upload() hands it on.
+		void setCamera(const ocrt::CameraPose &pose) {
+			camera = pose;
+			camera_set = true;
+		}
+
 		// Renders the whole frame (this rank's bands) and blocks until it is done;
 		// false means the caller should exit (reference src/opencl_host.cc:137-149).
 		bool operator()();
@@ -94,6 +102,8 @@ class HipHost {
 	private:
 		const RayTracer &rt;
 		std::unique_ptr<ocrt::DeviceRenderer> impl;
+		ocrt::CameraPose camera = ocrt::default_camera_pose();
+		bool camera_set = false;
 };
 
 // A steady stream of frames behind the same seam: `hosts` render hosts of one scene on one GPU that take frames in
@@ -111,6 +121,10 @@ class HipHostRing {
 		            const std::vector<Vec3f> &aabbs, const std::vector<Vec3f> &vertices,
 		            const std::vector<Vec3f> &vnormals);
 		void upload(const ocrt::PackedScene &packed);
+		void setCamera(const ocrt::CameraPose &pose) {  // (HipHost::setCamera: every host of the ring, before the upload)
+			camera = pose;
+			camera_set = true;
+		}
 		bool operator()();                            // one frame, blocking
 		bool frames(unsigned int count);              // `count` frames, up to size() - 1 in flight; blocks until all are done
 		void download(float *image);                  // the float image of the last frame
@@ -124,6 +138,8 @@ class HipHostRing {
 		const RayTracer &rt;
 		std::unique_ptr<ocrt::FrameRing> ring;
 		unsigned int last_host;
+		ocrt::CameraPose camera = ocrt::default_camera_pose();
+		bool camera_set = false;
 };
 
 // One frame on several GPUs of a node, in ONE process (`render --gpus N`): the scene is replicated, the image is cut
@@ -147,6 +163,10 @@ class HipHostGroup {
 		            const std::vector<Vec3f> &aabbs, const std::vector<Vec3f> &vertices,
 		            const std::vector<Vec3f> &vnormals);
 		void upload(const ocrt::PackedScene &packed);
+		void setCamera(const ocrt::CameraPose &pose) {  // (HipHost::setCamera: every rank gets the same pose, before the upload)
+			camera = pose;
+			camera_set = true;
+		}
 		bool operator()();                            // all devices render their bands; blocks until every one is done
 		void downloadResized(unsigned char *image);   // resize on every device, gather, assemble width x height bytes
 		float lastKernelMs() const;                   // slowest device's kernel time of the last frame
@@ -161,6 +181,8 @@ class HipHostGroup {
 		void *staging;        // peer-copy form, on hosts[0]'s device: the ranks' band buffers, one stride apart
 		void *assembled;      // ... and the assembled image
 		size_t staging_bytes;
+		ocrt::CameraPose camera = ocrt::default_camera_pose();
+		bool camera_set = false;
 };
 
 // Source compatibility with callers written against the reference.  (-DOCRT_DROPIN_RING: the same callers on a frame

@@ -166,10 +166,13 @@ void launch_primary(const SceneBuffers &scene, float *image, void *hits, void *o
 		args.P = P;
 		hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * PRIMARY_WAVES), 0, s, args);
 	};
+	// (a host with a camera pose: the instantiations that read the pose; the default ones hold the reference's camera as constants)
 #ifdef OCRT_DEBUG_KNOBS
 	if (!P.shared_walk)
-		return launch(primary_kernel<false>);
+		return P.posed ? launch(primary_posed_kernel<false>) : launch(primary_kernel<false>);
 #endif
+	if (P.posed)
+		return launch(primary_posed_kernel<true>);
 	launch(primary_kernel<true>);
 }
 

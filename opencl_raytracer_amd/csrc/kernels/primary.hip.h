@@ -88,7 +88,20 @@ __device__ __forceinline__ float lane_value(float x) {
 	asm volatile("" : "+v"(x));
 	return x;
 }
-template <bool SHARED, bool HANDOFF = false>
+// POSED: the host was given a camera pose (KernelParams::posed, device_types.h: CameraPose).  The eye and the basis are
+// launch constants like the others: read from the kernel-argument segment where a ray is made and -- the eye -- again
+// where a leaf stop needs the origin (posed_origin), so that no scalar register holds them across the walks.  The
+// default instantiation keeps the reference's camera as folded constants.
+template <bool POSED>
+__device__ __forceinline__ Ray posed_origin(Ray r) {
+	if (POSED) {
+		r.ox = OCRT_COLD_F32(P.eye_x);
+		r.oy = OCRT_COLD_F32(P.eye_y);
+		r.oz = OCRT_COLD_F32(P.eye_z);
+	}
+	return r;
+}
+template <bool SHARED, bool HANDOFF = false, bool POSED = false>
 __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &cb, uint32_t tile_x, uint32_t local_row, uint32_t part = WHOLE_TILE,
                                              unsigned long long *quarter_hits = nullptr) {
 	// What the tile needs of the launch constants is READ HERE, by loads the compiler can neither hoist nor merge (cold_u32):
@@ -129,8 +142,18 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 	float dx = ((float) x + 0.5f) / P.a - P.half_w;
 	float dy = -(((float) y + 0.5f) / P.a - P.half_h);
 	float dz = -1.0f;
+	if (POSED) {
+		// direction = normalize(((right * cx) + (up * cy)) + forward), every product and sum rounded on its own (this
+		// file is compiled without contraction); the basis is used as given
+		const float cx = dx, cy = dy;
+		dx = (OCRT_COLD_F32(P.right_x) * cx + OCRT_COLD_F32(P.up_x) * cy) + OCRT_COLD_F32(P.forward_x);
+		dy = (OCRT_COLD_F32(P.right_y) * cx + OCRT_COLD_F32(P.up_y) * cy) + OCRT_COLD_F32(P.forward_y);
+		dz = (OCRT_COLD_F32(P.right_z) * cx + OCRT_COLD_F32(P.up_z) * cy) + OCRT_COLD_F32(P.forward_z);
+	}
 	normalize3(dx, dy, dz);
-	const Ray ray = make_ray(0.0f, 0.0f, 2.0f, dx, dy, dz);
+	// (the posed form: the origin in `ray` serves what comes before the walk -- the choice of its form, oi = -(o * inv) per
+	// lane --; the leaf stops read the eye again, posed_origin)
+	const Ray ray = POSED ? posed_origin<POSED>(make_ray(0.0f, 0.0f, 0.0f, dx, dy, dz)) : make_ray(0.0f, 0.0f, 2.0f, dx, dy, dz);
 	Hit best;
 	best.distance = __builtin_inff();
 	best.leaf = 0;
@@ -145,7 +168,7 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 			const float4 *tri = tris_ptr + LEAF_F4 * leaf + LEAF_TRI_F4;
 			const float4 q0 = tri[0], q1 = tri[1], q2 = tri[2], q3 = tri[3];
 			if (box) {
-				const TriResult tr = tri_eval<true>(q0, q1, q2, q3, ray);
+				const TriResult tr = tri_eval<true>(q0, q1, q2, q3, posed_origin<POSED>(ray));
 				if (tr.accepted) {
 					hit = true;
 					if (nearer(tr.distance, leaf, best)) {
@@ -172,7 +195,7 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 				wave_lds_sync();
 				const uint32_t pair = cb.entry[lane < n ? lane : 0u];
 				const int owner = (int) (pair >> 26);
-				Ray theirs = ray;  // (all primary rays start at the eye)
+				Ray theirs = posed_origin<POSED>(ray);  // (all primary rays start at the eye)
 				theirs.dx = __shfl(ray.dx, owner); theirs.dy = __shfl(ray.dy, owner); theirs.dz = __shfl(ray.dz, owner);
 				theirs.ix = __shfl(ray.ix, owner); theirs.iy = __shfl(ray.iy, owner); theirs.iz = __shfl(ray.iz, owner);
 				if (lane < n) {
@@ -223,8 +246,9 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 				if (status == 1u) {
 					const float4 *rec = tris_ptr + LEAF_F4 * leaf;
 					const float4 lo = rec[0], hi = rec[1], q0 = rec[2], q1 = rec[3], q2 = rec[4], q3 = rec[5];
-					if (((hit_mask >> lane) & 1ull) && exact_leaf_gate(lo, hi, ray, P.primary_below)) {
-						const Candidate tr = tri_candidate(q0, q1, q2, q3, hi.w, ray);
+					const Ray here = posed_origin<POSED>(ray);
+					if (((hit_mask >> lane) & 1ull) && exact_leaf_gate(lo, hi, here, P.primary_below)) {
+						const Candidate tr = tri_candidate(q0, q1, q2, q3, hi.w, here);
 						if (tr.accepted) {
 							hit = true;
 							const unsigned long long key = key_of(tr.distance, leaf);
@@ -257,7 +281,7 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 			// distance of +inf or NaN never satisfies the reference's `best.distance > distance`: `best` stays as it is.)
 			if (hit && (uint32_t) (key >> 32) < INF_BITS) {
 				const uint32_t leaf = (uint32_t) key;
-				const TriResult tr = tri_test<true>(scene.tris, leaf, ray);
+				const TriResult tr = tri_test<true>(scene.tris, leaf, posed_origin<POSED>(ray));
 				best.distance = tr.distance;
 				best.leaf = leaf;
 				best.s = tr.s;
@@ -267,12 +291,13 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 		} else {
 			uint32_t mine = 0u;
 			uint32_t at = 0u;
+			const Ray exact_ray = posed_origin<POSED>(ray);  // (no hand-scheduled loop here: the eye may stay in registers)
 			while (at < count) {
 				const u32x8 node = scalar_load_node(nodes_ptr, at);
 				const float4 lo = make_float4(__uint_as_float(node[0]), __uint_as_float(node[1]), __uint_as_float(node[2]), 0.0f);
 				const float4 hi = make_float4(__uint_as_float(node[4]), __uint_as_float(node[5]), __uint_as_float(node[6]), 0.0f);
 				const uint32_t skip = node[3], leaf = node[7];
-				const bool box = exact_box(lo, hi, ray, 100000.0f, active, at, skip, mine);
+				const bool box = exact_box(lo, hi, exact_ray, 100000.0f, active, at, skip, mine);
 				const bool any = wave_ballot(box) != 0ull;
 				if (any && leaf != NONE) {
 					leaf_test(leaf, box);
@@ -397,8 +422,9 @@ constexpr uint32_t PRIMARY_WAVES = OCRT_PRIMARY_WAVES;  // 4, 8 or 16: a workgro
 constexpr uint32_t PRIMARY_ROWS = PRIMARY_WAVES / 2u;
 constexpr uint32_t PRIMARY_NO_ENTRY = 0xFFFFFFFFu;  // (an empty place in primary_kernel's list)
 
-template <bool SHARED>
-__global__ __launch_bounds__(64 * PRIMARY_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void primary_kernel(PrimaryArgs A) {
+// (the body of the pass; POSED: primary_tile's.  Two kernels below, so that the default one keeps its name and its ISA.)
+template <bool SHARED, bool POSED>
+__device__ __forceinline__ void primary_pass(const PrimaryArgs &A) {
 	__shared__ ClosestBatch closest_batches[PRIMARY_WAVES];
 	const uint32_t wave = threadIdx.x >> 6;
 	if (blockIdx.x == 0u && threadIdx.x < XCD_GROUPS) {
@@ -453,12 +479,22 @@ __global__ __launch_bounds__(64 * PRIMARY_WAVES) __attribute__((amdgpu_waves_per
 	}
 #endif
 	if (there)
-		primary_tile<SHARED>(A, closest_batches[wave], tile_x, local_row, part, quarter_hits);
+		primary_tile<SHARED, false, POSED>(A, closest_batches[wave], tile_x, local_row, part, quarter_hits);
 #ifdef OCRT_PRIMARY_TICKS
 	uint32_t *const ticks_out = *(uint32_t *const volatile *) ((const char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(FrameArgs, tile_cost));
 	if (ticks_out && (threadIdx.x & 63u) == 0u && tick0[threadIdx.x >> 6][1] != 0xFFFFFFFFu)
 		ticks_out[tick0[threadIdx.x >> 6][1]] = (uint32_t) __builtin_amdgcn_s_memrealtime() - tick0[threadIdx.x >> 6][0];
 #endif
+}
+
+template <bool SHARED>
+__global__ __launch_bounds__(64 * PRIMARY_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void primary_kernel(PrimaryArgs A) {
+	primary_pass<SHARED, false>(A);
+}
+// ... for a host with a camera pose (DeviceRenderer::setCamera): the same pass, eye and basis read from the launch constants
+template <bool SHARED>
+__global__ __launch_bounds__(64 * PRIMARY_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void primary_posed_kernel(PrimaryArgs A) {
+	primary_pass<SHARED, true>(A);
 }
 
 // ---------------------------------------------------------------------------

@@ -4,7 +4,8 @@
 // `--help` only.  New: `--device N`, `--gpus N` (one frame on N GPUs of the node, bands gathered over RCCL / xGMI;
 // `--gather rccl|peer|auto`), `--frames K` / `--in-flight H` (a steady stream of K frames through a ring of H render
 // hosts on the one GPU: throughput instead of one blocking frame), `--host-resize` (the reference's own download +
-// RayTracer::resize instead of the fused device resize), and a Mrays/s summary line.
+// RayTracer::resize instead of the fused device resize), `--eye x,y,z` / `--look-at x,y,z` / `--up x,y,z` (a camera
+// pose instead of the reference's fixed camera; none of the three: the reference's view, as ever), and a Mrays/s summary line.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "bvh.h"
+#include "camera.h"
 #include "cli_support.h"
 #include "hip_host.h"
 #include "mesh.h"
@@ -52,6 +54,9 @@ const OptionSpec OPTIONS[] = {
 	{ 0, "frames", "Renders the frame this many times in a row (the image written is the last one)." },
 	{ 0, "in-flight", "Render hosts taking those frames in turn on the GPU (default 3 when --frames > 1, else 1)." },
 	{ 0, "host-resize", "Downloads the float image and resizes it on the host, as the reference does [0|1]." },
+	{ 0, "eye", "Specifies the eye point of the camera as x,y,z (default 0,0,2; any of --eye, --look-at, --up poses the camera)." },
+	{ 0, "look-at", "Specifies the point the camera looks at as x,y,z (default 0,0,0)." },
+	{ 0, "up", "Specifies the camera's up direction as x,y,z (default 0,1,0)." },
 	{ 0, "timings", "Prints one more line with the phases' wall-clock times in milliseconds [0|1]." },
 	{ 0, "warm-up", "Brings up the HIP device on a second thread while the mesh is loaded and the BVH built [0|1] (default 1)." },
 };
@@ -89,6 +94,10 @@ struct CliOptions : RayTracer::Options {
 	std::string gather = "auto";
 	bool host_resize = false;
 	bool timings = false, warm_up = true;
+	// the camera: with none of --eye / --look-at / --up the reference's, on the path it always took
+	bool posed = false;
+	float eye[3] = { 0.0f, 0.0f, 2.0f }, look_at[3] = { 0.0f, 0.0f, 0.0f }, up[3] = { 0.0f, 1.0f, 0.0f };
+	ocrt::CameraPose pose = ocrt::default_camera_pose();
 
 	CliOptions(int argc, const char **argv) : RayTracer::Options(RayTracer::defaults()) {
 		std::vector<std::string> positional;
@@ -136,11 +145,24 @@ struct CliOptions : RayTracer::Options {
 		}
 		if (positional.size() < 2)
 			usage_error(argv[0], "Too few non-optional arguments");
+		if (posed && !ocrt::camera_look_at(eye, look_at, up, &pose))
+			usage_error(argv[0], "Invalid camera (--eye equals --look-at, or --up lies along the view direction)");
 		in = positional[0];
 		out = positional[1];
 	}
 
 	private:
+	// "x,y,z": three numbers, nothing else
+	static void triple(const char *argv0, const char *value, float out[3]) {
+		const char *at = value;
+		for (int k = 0; k < 3; ++k) {
+			char *end = nullptr;
+			out[k] = std::strtof(at, &end);
+			if (end == at || *end != (k < 2 ? ',' : '\0'))
+				usage_error(argv0, std::string("Invalid triple ") + value + " (expected x,y,z)");
+			at = end + 1;
+		}
+	}
 	void apply(const char *argv0, const OptionSpec &spec, const char *value) {
 		const std::string name = spec.long_name;
 		// Integers via atoi, floats via atof, as the reference's parser does
@@ -173,6 +195,10 @@ struct CliOptions : RayTracer::Options {
 			timings = std::atoi(value) != 0;
 		else if (name == "warm-up")
 			warm_up = std::atoi(value) != 0;
+		else if (name == "eye" || name == "look-at" || name == "up") {
+			triple(argv0, value, name == "eye" ? eye : name == "up" ? up : look_at);
+			posed = true;
+		}
 		else if (name == "ambient-occlusion-method") {
 			if (std::strcmp(value, "uniform") == 0)
 				aoMethod = RayTracer::AmbientOcclusionMethod::UNIFORM;
@@ -230,6 +256,8 @@ template <class Host>
 void render_frame(Host &host, const CliOptions &options, const RayTracer &rt, const ocrt::PackedScene &packed,
                   std::vector<unsigned char> &image) {
 	phase_clock.mark("host");
+	if (options.posed)
+		host.setCamera(options.pose);
 	std::size_t total_time = 0;
 	total_time += Info::measure("Loading OpenCL kernel", [&] {
 		host.upload(packed);  // (the face sort and the packing of the scene ran while the device came up, main())
@@ -380,7 +408,7 @@ int main(int argc, const char **argv) {
 		packed = ocrt::pack_scene(sorted_faces, bvh.nodes, bvh.aabbs, mesh.vertices, mesh.vnormals);
 		// (one frame, the reference's use: nothing that only pays over a stream of frames -- scene_pack.h, make_walk_array)
 		ocrt::prepare_walk_array(packed, options.enableAO && options.aoNumSamples > 0 ? ocrt::kernel_float(options.aoMaxDistance) : 0.0f,
-		                         options.frames >= 16);
+		                         options.frames >= 16, options.posed ? options.pose.eye : nullptr);
 	} catch (const std::exception &e) {
 		if (warm_up.joinable())
 			warm_up.join();

@@ -5,6 +5,7 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <future>
 #include <limits>
 #include <sstream>
@@ -225,10 +226,16 @@ PackedScene pack_scene(const std::vector<uint32_t> &faces, const std::vector<uin
 // the conservative near value never exceeds the reference's, the far value never falls below it.
 // |o| for a pair that PASSES the reference's test: t_near < max_distance and t_far > 0 put the origin within
 // max_distance (|d| <= 1 per axis) of the box on every axis, |o_k| <= B_k + D with B_k the box's largest magnitude on
-// axis k and D the ambient-occlusion rays' max_distance; the primary rays all start at the camera.  Hence per box and
-// axis  O_k = max(|camera_k|, B_k + D),  capped by the global origin_limit the kernel checks per packet (rays beyond it,
+// axis k and D the ambient-occlusion rays' max_distance; the primary rays all start at the eye -- the reference's camera
+// (0, 0, 2), or wherever the host's pose puts it (make_walk_array's `eye`).  Hence per box and
+// axis  O_k = max(|eye_k|, B_k + D),  capped by the global origin_limit the kernel checks per packet (rays beyond it,
 // and rays with a reciprocal direction that is neither infinite nor below 1e30 -- o * inv could overflow -- take the
-// exact form).  Margin used: 1.5 u (|b| + 2 O_k), rounded outward.
+// exact form).  Margin used: 1.5 u (|b| + 2 O_k), rounded outward.  Nothing in the argument asks where the eye is: an eye
+// inside a box, on its surface or a thousand extents away only changes O_k, and with it the margin.  origin_limit is
+// raised to the eye's largest coordinate where that lies beyond the scene's own limit -- as long as the overflow
+// conditions still hold (|eye_k| <= 2e6 + 4, the largest limit a scene of extent 1e6 gets, and walk_scale_usable for the
+// any-hit rays' scale); an eye beyond that, or one that is not a number, is not covered: its packets fail
+// ray_is_selectable and take the exact form, whatever this array holds.
 // An infinite inv (a zero direction component) is replaced by +-2^100 for the walk (kernels.hip, WalkRay): the
 // argument above holds for every finite inv, so 2^100 (b' - o) is <= 0 whenever the reference's (b - o) * inf is -inf
 // or NaN (no constraint), and where the reference gives +inf (the origin's coordinate outside the slab: reject) ours
@@ -316,8 +323,16 @@ static NodeRec ce_record(const NodeRec &padded, const double origin_bound[3]) {
 	return r;
 }
 
-WalkArray make_walk_array(const PackedScene &scene, float ao_max_distance, bool for_a_stream) {
+bool same_eye(const float *a, const float *b) {
+	const float reference[3] = { 0.0f, 0.0f, 2.0f };
+	return std::memcmp(a ? a : reference, b ? b : reference, sizeof reference) == 0;
+}
+
+WalkArray make_walk_array(const PackedScene &scene, float ao_max_distance, bool for_a_stream, const float *eye) {
 	WalkArray out;
+	if (eye)
+		for (unsigned k = 0; k < 3; ++k)
+			out.eye[k] = eye[k];
 	const std::vector<NodeRec> &nodes = scene.nodes;
 	if (!(scene.regular && scene.nested) || nodes.empty())
 		return out;
@@ -329,12 +344,32 @@ WalkArray make_walk_array(const PackedScene &scene, float ao_max_distance, bool 
 	// reach of the rays whose origin is not the camera; no ambient occlusion, or an unusable distance: the scene itself
 	const bool ao_bounded = ao_max_distance > 0.0f && ao_max_distance <= extent;
 	const double reach = ao_bounded ? (double) ao_max_distance * 1.001 : 2.0 * (double) extent;
-	// ray origins: the camera at (0, 0, 2) and hit points, which lie in the root box up to the triangle test's slack
+	// ray origins: the eye -- the reference's camera at (0, 0, 2) unless the host has a pose -- and hit points, which lie in
+	// the root box up to the triangle test's slack
 	out.origin_limit = 2.0f * extent + 4.0f;
 	out.ao_scale = walk_scale_for(ao_max_distance);
 	if (!walk_scale_usable(out.ao_scale, out.origin_limit))
 		out.ao_scale = 0.0f;
-	const double camera[3] = { 0.0, 0.0, 2.0 };  // reference src/intersect_kernel.cl:284
+	// An eye beyond the scene's own limit raises the limit to its largest coordinate, if the conditions the limit stands for
+	// still hold there (padded_bound's comment); an eye they do not hold for is not covered: the array is then made as for
+	// the reference's camera -- the any-hit rays still walk it -- and every primary packet takes the exact form.
+	const double reference_camera[3] = { 0.0, 0.0, 2.0 };  // reference src/intersect_kernel.cl:284
+	float eye_reach = 0.0f;
+	bool eye_finite = true;
+	for (unsigned k = 0; k < 3; ++k) {
+		eye_finite = eye_finite && std::isfinite(out.eye[k]);
+		eye_reach = std::fmax(eye_reach, std::fabs(out.eye[k]));
+	}
+	out.eye_covered = eye_finite && eye_reach <= out.origin_limit;
+	if (!out.eye_covered && eye_finite && eye_reach <= 2.0e6f + 4.0f && (!(out.ao_scale > 0.0f) || walk_scale_usable(out.ao_scale, eye_reach))) {
+		out.origin_limit = eye_reach;
+		out.eye_covered = true;
+	}
+	const double camera[3] = { out.eye_covered ? (double) out.eye[0] : reference_camera[0], out.eye_covered ? (double) out.eye[1] : reference_camera[1],
+		                       out.eye_covered ? (double) out.eye[2] : reference_camera[2] };
+	// how far from the origin the eye is: what the rounding of a hit point and of the two distances compared scales with
+	// (2 for the reference's camera)
+	const double eye_distance = std::sqrt(camera[0] * camera[0] + camera[1] * camera[1] + camera[2] * camera[2]);
 	// (both copies of the records are made in one sweep, the sweep cut into slices for a few threads: an upload's CPU
 	// time is the walk-tree rebuild and this)
 	if (2 * (nodes.size() + 4) * sizeof(NodeRec) >= (size_t) 1 << 32)
@@ -358,17 +393,19 @@ WalkArray make_walk_array(const PackedScene &scene, float ao_max_distance, bool 
 	//     products and the difference of X, the same for D, the division; |w| <= rho (|u| + |v|)); with eta = 128 * 2^-24 * k * r
 	//     < 1/4 a point that passes has rho <= (1 + 1e-5) / (1 - eta) < 4/3 and lies within (1e-5 + 4/3 eta) (|u| + |v|) of
 	//     the triangle: grown by (2e-5 + 4 eta) (|u| + |v|) -- used up to eta = 1/32 --, plus 32 * 2^-24 of the coordinates (the hit point itself is
-	//     rounded);
+	//     rounded: its error is 2^-24 of the eye's distance from the origin plus that of its own coordinates -- the `eye_distance`
+	//     below, 2 for the reference's camera --, and with the box grown by that much the REAL point of the ray at the hit's
+	//     parameter lies in the box too, on every axis, however large the reciprocal direction);
 	//   * a triangle with |n| < 9.9e-7 is never accepted (|dot(n, d)| < 1e-6 for every unit d, :80) and needs nothing;
-	// and the inner boxes are the unions of their children's again.  In a scene with a triangle that can be accepted and
-	// whose eta is 1/4 or more (needles, long slivers: Cramer's rule makes their accepted region fuzzy by whole edge
-	// lengths) the closest-hit walk does NOT prune (prune_margin = +inf; both interior stand-ins are such scenes).  What
-	// is left for prune_margin otherwise: the rounding of the two distances compared, 1e-5 of the largest coordinate.
-	//   * the triangles left over -- needles, long slivers: Cramer's rule makes their accepted region fuzzy by a good part of
-	//     their edge lengths or more -- get no box that could promise anything.  They are taken out of this copy's tree and put into
-	//     a small tree of their own (their own boxes), which becomes the FIRST child of the root: the walk meets them before
-	//     anything else, and while it is in there (`unpruned_bytes`) no lane's limit is lowered -- they are tested as the
-	//     reference tests them.  (Both interior stand-ins have a few dozen such faces among 75 000.)
+	// and the inner boxes are the unions of their children's again.
+	// The rule for the triangles this gives no usable bound for (eta of 1/32 or more: needles, long slivers, whose accepted
+	// region Cramer's rule makes fuzzy by a good part of their edge lengths): they get no box that could promise anything.
+	// They are taken out of this copy's tree and put into a small tree of their own (their own boxes), which becomes the
+	// FIRST child of the root: the walk meets them before anything else, and while it is in there (`unpruned_bytes`) no
+	// lane's limit is lowered -- they are tested as the reference tests them.  (Both interior stand-ins have a few dozen
+	// such faces among 75 000.)  Only a scene of nothing but such faces, or a tree this cannot be done to, is not pruned at
+	// all (prune_margin = +inf).  What is left for prune_margin: the rounding of the two distances compared, 1e-5 of the
+	// largest magnitude that enters them -- the boxes' coordinates and the eye's distance from the origin.
 	bool prunable = for_a_stream;
 	out.unpruned_bytes = 0;
 	if (!prunable) {
@@ -398,7 +435,7 @@ WalkArray make_walk_array(const PackedScene &scene, float ao_max_distance, bool 
 			// primary pass from 0.098 to 0.156 ms --: from 1/32 on a face counts as one without a bound and keeps its own box)
 			if (!(eta < 1.0 / 32.0))  // (NaN too)
 				return std::numeric_limits<double>::infinity();
-			const double grow = (2e-5 + 4.0 * eta) * (lu + lv) + 32.0 * std::ldexp(1.0, -24) * (coordinate + lu + lv + 2.0);
+			const double grow = (2e-5 + 4.0 * eta) * (lu + lv) + 32.0 * std::ldexp(1.0, -24) * (coordinate + lu + lv + eye_distance);
 			return grow < 1e30 ? grow : std::numeric_limits<double>::infinity();
 		};
 		// (once per triangle)
@@ -442,7 +479,7 @@ WalkArray make_walk_array(const PackedScene &scene, float ao_max_distance, bool 
 				}
 		}
 		// the others' boxes grown, leaves first, the inner ones as the unions of their children's
-		double largest = 2.0;  // (the camera's z)
+		double largest = eye_distance;  // (2: the reference camera's z)
 		for (size_t i = rest.size(); i-- > 0;) {
 			NodeRec &n = rest[i];
 			if (n.skip == 1) {
@@ -498,11 +535,13 @@ WalkArray make_walk_array(const PackedScene &scene, float ao_max_distance, bool 
 	const size_t records = by_camera.size() + 2;
 	out.primary_bytes = (uint32_t) (by_camera.size() * sizeof(NodeRec));
 	out.nodes.resize(with_ce ? records + nodes.size() + 2 : records);
-	auto padded = [&](const NodeRec &n, double origin[3]) {
+	// (`from`: where the rays that do not start inside the scene start -- the eye for the primary rays' records; the any-hit
+	// rays' copy keeps the reference camera's bound, which its margins have always held: a far eye must not widen them)
+	auto padded = [&](const NodeRec &n, double origin[3], const double from[3]) {
 		NodeRec w = n;
 		for (unsigned k = 0; k < 3; ++k) {
 			const double box = std::fmax(std::fabs((double) n.lo[k]), std::fabs((double) n.hi[k]));
-			origin[k] = std::fmin((double) out.origin_limit, std::fmax(camera[k], box + reach));
+			origin[k] = std::fmin((double) out.origin_limit, std::fmax(std::fabs(from[k]), box + reach));
 			w.lo[k] = padded_bound(n.lo[k], (float) origin[k], false, scaled_reach_of);
 			w.hi[k] = padded_bound(n.hi[k], (float) origin[k], true, scaled_reach_of);
 		}
@@ -513,9 +552,9 @@ WalkArray make_walk_array(const PackedScene &scene, float ao_max_distance, bool 
 		for (size_t i = from; i < to; ++i) {
 			double origin[3];
 			if (i < by_camera.size())
-				out.nodes[i] = padded(by_camera[i], origin);
+				out.nodes[i] = padded(by_camera[i], origin, camera);
 			if (with_ce && i < nodes.size())
-				out.nodes[records + i] = ce_record(padded(nodes[i], origin), origin);
+				out.nodes[records + i] = ce_record(padded(nodes[i], origin, reference_camera), origin);
 		}
 	};
 	{
@@ -558,8 +597,8 @@ WalkArray make_walk_array(const PackedScene &scene, float ao_max_distance, bool 
 	return out;
 }
 
-void prepare_walk_array(PackedScene &scene, float ao_max_distance, bool for_a_stream) {
-	scene.walk = std::make_shared<const WalkArray>(make_walk_array(scene, ao_max_distance, for_a_stream));
+void prepare_walk_array(PackedScene &scene, float ao_max_distance, bool for_a_stream, const float *eye) {
+	scene.walk = std::make_shared<const WalkArray>(make_walk_array(scene, ao_max_distance, for_a_stream, eye));
 	scene.walk_max_distance = ao_max_distance;
 	scene.walk_for_a_stream = for_a_stream;
 }
@@ -638,8 +677,16 @@ SceneFacts scene_facts(const PackedScene &scene, const WalkArray &walk) {
 }
 
 KernelParams make_kernel_params(const RayTracer &rt, uint32_t node_count, uint32_t tri_count, uint32_t ao_dirs,
-                                const Partition &part, const SceneFacts *facts) {
+                                const Partition &part, const SceneFacts *facts, const CameraPose *pose) {
 	KernelParams p{};
+	{  // (the fields always hold a pose: the reference's for a host without one, which launches the kernels that do not read them)
+		const CameraPose c = pose ? *pose : default_camera_pose();
+		p.posed = pose ? 1 : 0;
+		p.eye_x = c.eye[0]; p.eye_y = c.eye[1]; p.eye_z = c.eye[2];
+		p.right_x = c.right[0]; p.right_y = c.right[1]; p.right_z = c.right[2];
+		p.up_x = c.up[0]; p.up_y = c.up[1]; p.up_z = c.up[2];
+		p.forward_x = c.forward[0]; p.forward_y = c.forward[1]; p.forward_z = c.forward[2];
+	}
 	p.width = rt.totalWidth;
 	p.height = rt.totalHeight;
 	const float focal = kernel_float(rt.options.focalLength);

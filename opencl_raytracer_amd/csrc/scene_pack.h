@@ -26,7 +26,15 @@ struct WalkArray {
 	uint32_t unpruned_bytes = 0;  // ... and the part at the head of the primary rays' records inside which no limit is lowered (the root and the faces without a bound)
 	float ao_scale = 0.0f;      // walk_scale_for(ao_max_distance) the margins were sized for (0: none)
 	uint32_t ce_offset = 0;     // byte offset of the same records in centre / half-extent form (0: none; ao_scale > 0 only)
+	// The eye the array was made for (make_walk_array's `eye`; the reference's camera without one): the primary rays' records
+	// are ordered, padded and grown for rays that start THERE.  `eye_covered`: origin_limit covers it -- an eye with a
+	// coordinate beyond what the limit can be raised to, or one that is not a number, is not: every packet of such a host
+	// takes the exact form of the walk (ray_is_selectable), and the array is the default eye's.
+	float eye[3] = { 0.0f, 0.0f, 2.0f };
+	bool eye_covered = true;
 };
+// Whether two eyes are the same one for a walk array: the same bits (nullptr: the reference's camera, (0, 0, 2)).
+bool same_eye(const float *a, const float *b);
 struct PackedScene {
 	std::vector<NodeRec> nodes;
 	std::vector<TriRec> tris;
@@ -45,7 +53,7 @@ struct PackedScene {
 	// another distance.
 	std::shared_ptr<const WalkArray> walk;
 	float walk_max_distance = -1.0f;
-	bool walk_for_a_stream = false;  // (what `walk` was made for)
+	bool walk_for_a_stream = false;  // (what `walk` was made for; its eye: WalkArray::eye)
 };
 
 // Validates the arrays against each other (every index and skip count is
@@ -60,9 +68,12 @@ PackedScene pack_scene(const std::vector<uint32_t> &faces, const std::vector<uin
 // `for_a_stream`: also what only pays over many frames of the scene -- the primary rays' copy re-ordered and its boxes grown
 // so that the closest-hit walk may prune (2-3 ms of CPU for the bunny, ~0.02 ms per frame): a one-shot host (the
 // reference's use) gets the records in the builder's order and prune_margin = +inf.
-WalkArray make_walk_array(const PackedScene &scene, float ao_max_distance, bool for_a_stream = true);
+// `eye`: where the primary rays start (three floats; nullptr: the reference's camera, (0, 0, 2)).  The primary rays' records
+// follow it -- child order, per-axis origin bounds, origin_limit, the leaves' growth and prune_margin --; the any-hit rays'
+// centre / half-extent copy does not (those rays start on the surfaces).
+WalkArray make_walk_array(const PackedScene &scene, float ao_max_distance, bool for_a_stream = true, const float *eye = nullptr);
 // make_walk_array into scene.walk (see PackedScene::walk).
-void prepare_walk_array(PackedScene &scene, float ao_max_distance, bool for_a_stream = true);
+void prepare_walk_array(PackedScene &scene, float ao_max_distance, bool for_a_stream = true, const float *eye = nullptr);
 // The margin itself: the padded value of a box's lower (upper = false) or upper bound `b` for ray origins of
 // magnitude up to `origin_bound` on that axis; always < b resp. > b.
 // `scaled_reach`: the max_distance (x 1.001) of the rays that use the SCALED node test on this array, 0 if none do.
@@ -104,7 +115,8 @@ struct SceneFacts {
 	uint32_t unpruned_bytes = 0, primary_bytes = 0, ce_offset = 0;
 };
 SceneFacts scene_facts(const PackedScene &scene, const WalkArray &walk);
+// `pose`: the host's camera pose (nullptr: none was given -- KernelParams::posed = 0, the reference's camera).
 KernelParams make_kernel_params(const RayTracer &rt, uint32_t node_count, uint32_t tri_count, uint32_t ao_dirs,
-                                const Partition &part, const SceneFacts *facts);
+                                const Partition &part, const SceneFacts *facts, const CameraPose *pose = nullptr);
 
 }  // namespace ocrt

@@ -9,6 +9,9 @@ box-filters its own bands into a compact uint8 buffer; ONE gather moves them to
 rank 0, which scatters the rows to their place.  There is no other exchange
 step in this path (the scene is replicated), so no other collective is used.
 
+A posed camera (include/rt_hip_camera.h) is a property of the hosts, not of the gather: every rank gives its Host or
+FrameRing the SAME pose before its upload, and the gathered image is the whole-image result for that pose.
+
 torch is used for the collective and for device memory only.
 """
 from __future__ import annotations

@@ -1,0 +1,448 @@
+"""GPU: frames from a posed camera (include/rt_hip_camera.h) against the CPU oracle of tests/camera_oracle.c: the float
+image, the 8-bit image and the ray statistics, bit for bit and count for count.  The reference has no movable camera,
+so the oracle is the truth here; tests/test_camera_cpu.py ties it to the reference's goldens through the default pose."""
+import hashlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import camera_oracle as co
+import orc
+from conftest import ROOT, bits, mesh_file, options_for
+
+pytestmark = pytest.mark.gpu
+
+STREAM = 16  # frames announced before the upload: what an upload prepares for a stream of frames (walk intervals, pruning)
+
+
+def look(rt, eye, target, up=(0, 1, 0)):
+    return rt.Camera.look_at(eye, target, up)
+
+
+def root_box(arrays):
+    return arrays.aabbs[0, :3].astype(np.float64), arrays.aabbs[1, :3].astype(np.float64)
+
+
+def nave_pose(rt, arrays):
+    """An eye inside the interior stand-ins, near the +z end of the nave at a third of its height, looking along it."""
+    lo, hi = root_box(arrays)
+    c = 0.5 * (lo + hi)
+    eye = (c[0] + 0.1 * (hi[0] - lo[0]), lo[1] + 0.35 * (hi[1] - lo[1]), hi[2] - 0.15 * (hi[2] - lo[2]))
+    target = (c[0], lo[1] + 0.4 * (hi[1] - lo[1]), lo[2])
+    return look(rt, eye, target)
+
+
+def poses_for(rt, arrays):
+    """name -> Camera, for the bunny (a model of unit size around the origin, the reference's eye 2 away)."""
+    out = {}
+    for k, deg in enumerate((40, 90, 135, 180, 225, 300)):  # an orbit at the default distance; 180: straight behind
+        a = np.radians(deg)
+        out[f"orbit_{deg}"] = look(rt, (2 * np.sin(a), 0.3 if k % 2 else 0.0, 2 * np.cos(a)), (0, 0, 0))
+    out["above"] = look(rt, (0, 2, 0), (0, 0, 0), up=(0, 0, -1))
+    out["below"] = look(rt, (0, -2, 0), (0, 0, 0), up=(0, 0, 1))
+    # roll: the basis of an oblique pose rotated about its forward axis by 33 degrees
+    base = look(rt, (1.2, 0.8, 1.4), (0, 0.1, 0)).as_array().astype(np.float64)
+    c, s = np.cos(np.radians(33)), np.sin(np.radians(33))
+    out["roll"] = rt.Camera.from_vectors(base[0], c * base[1] + s * base[2], -s * base[1] + c * base[2], base[3])
+    # neither orthogonal nor of unit length: used as given
+    out["skewed"] = rt.Camera.from_vectors((0.4, 0.2, 1.9), (1.3, 0.2, 0.1), (0.15, 0.7, -0.1), (-0.2, -0.05, -1.6))
+    lo, hi = root_box(arrays)
+    out["inside_root_box"] = look(rt, (0.6 * hi[0], 0.5 * (lo[1] + hi[1]) + 0.3, 0.7 * hi[2]), (0, 0, 0))
+    # far eyes with a long lens (forward is used as given: its length is the zoom).  1e7 lies beyond any origin_limit: the
+    # exact form of the walk; 100 is ten extents away and still on the fast walk
+    # (nothing is hit from 1e7: the primary rays' max_distance is 100000.  far_5e4 is for a frame whose any-hit rays reach
+    # 1e-4 only: their scaled node test does not admit an origin_limit of 5e4, so that eye is not covered either -- the exact
+    # form again, this time with hits)
+    for name, eye, zoom in (("far_1e7", (0.6e7, 0.2e7, 1.0e7), 4.0e5), ("far_100", (60.0, 20.0, 100.0), 12.0), ("far_5e4", (3.0e4, 1.0e4, 5.0e4), 2.0e4)):
+        m = look(rt, eye, (0, 0, 0)).as_array()
+        out[name] = rt.Camera.from_vectors(m[0], m[1], m[2], m[3] * np.float32(zoom))
+    out["infinite"] = rt.Camera.from_vectors((np.inf, 0.0, 2.0), (1, 0, 0), (0, 1, 0), (0, 0, -1))
+    return out
+
+
+BUNNY_POSES = ["orbit_40", "orbit_90", "orbit_135", "orbit_180", "orbit_225", "orbit_300", "above", "below", "roll", "skewed",
+               "inside_root_box", "far_1e7", "far_100", "infinite"]
+
+_ORACLE = {}
+
+
+def oracle_frame(oracle, opt, arrays, cam, key):
+    """(float image, 8-bit image, counters) of the camera oracle; cached per test-chosen key."""
+    if key not in _ORACLE:
+        img, counters = co.render(orc.params_from_options(opt), arrays, cam)
+        _ORACLE[key] = (img, oracle.resize(img, opt.width, opt.height, opt.n_super_samples), counters)
+    return _ORACLE[key]
+
+
+def same_float_words(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return ((bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))).all()
+
+
+def assert_host_equals(host, want):
+    img, u8, counters = want
+    got = host.download()
+    mism = int(np.count_nonzero(bits(got) != bits(img)))
+    assert same_float_words(got, img), f"{mism} float words differ from the camera oracle"
+    assert np.array_equal(host.download_u8(), u8)
+    st = host.stats()
+    for k in ("primary_rays", "primary_hits", "ao_rays", "ao_occluded"):
+        assert st[k] == counters[k], (k, st[k], counters[k])
+
+
+def run_mode(rt, mode, scene, opt, cam, want):
+    """one_shot: the reference's use; stream: a host that announced frames before its upload; ring: three hosts replaying
+    their captured graphs, every collected frame equal."""
+    if mode == "ring":
+        ring = rt.FrameRing(opt, scene, device=0, hosts=3, camera=cam)
+        try:
+            for _ in range(5):
+                ring.submit()
+                assert np.array_equal(ring.collect(), want[1])
+            ring.run(4)
+            ring.drain()
+            assert np.array_equal(ring.download_last(), want[1])
+            for k in range(3):
+                assert_host_equals(ring.host(k), want)
+                assert same_float_words(ring.host(k).camera().as_array(), cam.as_array())
+        finally:
+            ring.close()
+        return
+    host = rt.Host(opt, 0)
+    try:
+        if mode == "stream":
+            host.expect_frames(STREAM)
+        host.set_camera(cam)
+        host.upload_scene(scene)
+        host.render()
+        assert_host_equals(host, want)
+        if mode == "stream":  # again: nothing a frame leaves behind changes the next one
+            host.render()
+            assert_host_equals(host, want)
+    finally:
+        host.close()
+
+
+@pytest.mark.parametrize("mode", ["one_shot", "stream", "ring"])
+@pytest.mark.parametrize("name", BUNNY_POSES)
+def test_bunny_poses(rt, oracle, scene_for, name, mode):
+    scene, arrays = scene_for("bunny", "longest")
+    opt = rt.Options.defaults(width=96, height=64, n_super_samples=1, ao_num_samples=3)
+    cam = poses_for(rt, arrays)[name]
+    run_mode(rt, mode, scene, opt, cam, oracle_frame(oracle, opt, arrays, cam, ("bunny", name)))
+
+
+@pytest.mark.parametrize("mode", ["one_shot", "stream", "ring"])
+@pytest.mark.parametrize("mesh", ["interior", "interior_hard"])
+def test_inside_the_interiors(rt, oracle, scene_for, mesh, mode):
+    scene, arrays = scene_for(mesh, "longest")
+    opt = rt.Options.defaults(width=96, height=54, n_super_samples=1, ao_num_samples=3)
+    cam = nave_pose(rt, arrays)
+    want = oracle_frame(oracle, opt, arrays, cam, (mesh, "nave"))
+    assert want[2]["primary_hits"] > 0.9 * want[2]["primary_rays"]  # inside: walls all around
+    run_mode(rt, mode, scene, opt, cam, want)
+
+
+# mesh, tree, width, height, supersamples, AO rings, AO distance, pose
+OPTION_CASES = [
+    ("bunny", "longest", 96, 64, 1, 0, 0.2, "orbit_135"),     # AO off
+    ("bunny", "sah", 96, 64, 1, 3, 0.2, "orbit_135"),         # the other tree
+    ("bunny", "longest", 128, 96, 4, 3, 0.2, "roll"),         # -s 4
+    ("bunny", "sah", 64, 48, 4, 2, 0.35, "orbit_225"),
+    ("bunny", "longest", 33, 17, 1, 3, 0.2, "orbit_40"),      # odd sizes, part tiles
+    ("blob", "longest", 128, 96, 4, 3, 0.2, "orbit_300"),
+    ("blob", "sah", 80, 80, 1, 5, 0.5, "skewed"),
+    ("ties", "longest", 64, 64, 4, 3, 1.0, "orbit_90"),
+    ("ties", "sah", 33, 33, 1, 3, 1.0, "roll"),
+    ("single", "longest", 32, 32, 1, 3, 0.2, "orbit_180"),
+    ("bunny", "longest", 96, 64, 1, 3, 1e-4, "far_5e4"),       # an eye the fast walk cannot cover that still sees the model
+    ("bunny", "longest", 96, 64, 1, 3, 0.2, "far_5e4"),        # ... and the same eye covered
+    ("interior", "longest", 96, 54, 4, 3, 0.2, "nave"),
+    ("interior_hard", "sah", 80, 45, 1, 0, 0.2, "nave"),
+]
+
+
+@pytest.mark.parametrize("case", OPTION_CASES, ids=lambda c: "_".join(str(x) for x in c))
+def test_options_and_meshes(rt, oracle, scene_for, case):
+    mesh, bvh, w, h, ss, ao, aod, pose = case
+    scene, arrays = scene_for(mesh, bvh)
+    _, bunny_arrays = scene_for("bunny", "longest")
+    opt = rt.Options.defaults(width=w, height=h, n_super_samples=ss, ao_num_samples=ao, ao_max_distance=aod, bvh_method=0 if bvh == "longest" else 1)
+    cam = nave_pose(rt, arrays) if pose == "nave" else poses_for(rt, bunny_arrays)[pose]
+    want = oracle_frame(oracle, opt, arrays, cam, case)
+    for mode in ("one_shot", "stream"):
+        run_mode(rt, mode, scene, opt, cam, want)
+    if ss == 4 and mesh in ("bunny", "blob"):
+        run_mode(rt, "ring", scene, opt, cam, want)
+
+
+def test_bunny_640x360(rt, oracle, scene_for):
+    scene, arrays = scene_for("bunny", "longest")
+    opt = rt.Options.defaults(width=640, height=360, n_super_samples=1, ao_num_samples=3)
+    cam = look(rt, (-1.1, 0.9, -1.5), (0, 0.05, 0))
+    want = oracle_frame(oracle, opt, arrays, cam, "bunny_640x360")
+    assert want[2]["primary_hits"] > 10000
+    for mode in ("one_shot", "stream", "ring"):
+        run_mode(rt, mode, scene, opt, cam, want)
+
+
+def test_random_ao_statistical_parity_posed(rt, oracle, scene_for):
+    """`-m random` is outside the bit-exact contract (tests/test_hip_parity.py, test_random_ao_statistical_parity); a posed
+    frame gets that test's check and that test's tolerance against the camera oracle: identical ray counts, mean |delta|
+    <= 0.25 grey levels, >= 97 % of the pixels identical, none off by more than three occlusion steps."""
+    samples = 4
+    opt = rt.Options.defaults(width=160, height=120, n_super_samples=1, ao_num_samples=samples, ao_method=1, ao_max_distance=0.3)
+    scene, arrays = scene_for("bunny", "longest")
+    cam = poses_for(rt, arrays)["orbit_135"]
+    host = rt.Host(opt, 0)
+    host.set_camera(cam)
+    host.upload_scene(scene)
+    host.render()
+    gpu = host.download_u8().astype(np.int32)
+    st = host.stats()
+    ref_img, counters = co.render(orc.params_from_options(opt), arrays, cam)
+    ref = oracle.resize(ref_img, opt.width, opt.height, 1).astype(np.int32)
+    assert st["primary_hits"] == counters["primary_hits"]
+    assert st["ao_rays"] == counters["ao_rays"] == counters["primary_hits"] * (samples + 2)
+    delta = np.abs(gpu - ref)
+    print(f"posed RANDOM: mean |delta| {delta.mean():.4f}, identical {(delta == 0).mean():.4f}, max {delta.max()}")
+    assert delta.mean() <= 0.25, delta.mean()
+    assert (delta == 0).mean() >= 0.97, (delta == 0).mean()
+    assert delta.max() <= 3 * 255 // (samples + 1) + 1, delta.max()
+    assert abs(st["ao_occluded"] - counters["ao_occluded"]) <= 0.002 * counters["ao_rays"] + 8
+    host.close()
+
+
+@pytest.mark.parametrize("frames", [None, STREAM], ids=["one_shot", "stream"])
+@pytest.mark.parametrize("name", ["bunny_64_s1_a3", "blob_128x96_s4_a3", "blob_40x24_s4_a2_d03_f08", "bunny_256_s1_a0"])
+def test_default_pose_is_the_unposed_frame(rt, golden, scene_for, name, frames):
+    """set_camera(Camera.default()) on even sizes: the posed path renders what the host without a camera renders, and
+    what the committed goldens hold."""
+    c = golden["renders"][name]
+    opt = options_for(rt, c)
+    scene, _ = scene_for(c["mesh"], c["bvh"])
+    images = []
+    for cam in (None, rt.Camera.default()):
+        host = rt.Host(opt, 0)
+        if frames:
+            host.expect_frames(frames)
+        if cam is not None:
+            host.set_camera(cam)
+        assert host.camera_is_set == (cam is not None)
+        host.upload_scene(scene)
+        host.render()
+        images.append((host.download(), host.download_u8(), host.stats()))
+        host.close()
+    assert np.array_equal(bits(images[0][0]), bits(images[1][0]))
+    assert np.array_equal(images[0][1], images[1][1])
+    assert images[0][2] == images[1][2]
+    assert hashlib.sha256(images[1][0].tobytes()).hexdigest() == c["float_sha256"]
+    assert hashlib.md5(rt.pgm_bytes(images[1][1])).hexdigest() == c["pgm_md5"]
+
+
+def test_no_state_leaks_into_an_unposed_host(rt, oracle, golden, scene_for):
+    """A host created after posed hosts have rendered in this process still renders its golden."""
+    scene, arrays = scene_for("bunny", "longest")
+    opt = rt.Options.defaults(width=96, height=64, n_super_samples=1, ao_num_samples=3)
+    cam = poses_for(rt, arrays)["orbit_180"]
+    run_mode(rt, "stream", scene, opt, cam, oracle_frame(oracle, opt, arrays, cam, ("bunny", "orbit_180")))
+    run_mode(rt, "ring", scene, opt, cam, oracle_frame(oracle, opt, arrays, cam, ("bunny", "orbit_180")))
+    c = golden["renders"]["bunny_64_s1_a3"]
+    for frames in (None, STREAM):
+        host = rt.Host(options_for(rt, c), 0)
+        if frames:
+            host.expect_frames(frames)
+        host.upload_scene(scene)
+        host.render()
+        assert not host.camera_is_set
+        assert hashlib.sha256(host.download().tobytes()).hexdigest() == c["float_sha256"]
+        assert hashlib.md5(rt.pgm_bytes(host.download_u8())).hexdigest() == c["pgm_md5"]
+        host.close()
+
+
+def test_hosts_with_different_poses_side_by_side(rt, oracle, scene_for):
+    """Two hosts alive at once on one GPU, the same scene, different poses, their frames interleaved -- and a posed ring
+    beside an unposed host: each renders its own view."""
+    scene, arrays = scene_for("bunny", "longest")
+    opt = rt.Options.defaults(width=96, height=64, n_super_samples=1, ao_num_samples=3)
+    poses = poses_for(rt, arrays)
+    names = ("orbit_90", "orbit_225")
+    hosts = []
+    for name in names:
+        h = rt.Host(opt, 0)
+        h.expect_frames(STREAM)
+        h.set_camera(poses[name])
+        h.upload_scene(scene)
+        hosts.append(h)
+    for _ in range(3):
+        for h in hosts:
+            h.render_async()
+        for h, name in zip(hosts, names):
+            h.sync()
+            assert_host_equals(h, oracle_frame(oracle, opt, arrays, poses[name], ("bunny", name)))
+    for h in hosts:
+        h.close()
+    plain = rt.Host(opt, 0)
+    plain.expect_frames(STREAM)
+    plain.upload_scene(scene)
+    ring = rt.FrameRing(opt, scene, device=0, hosts=3, camera=poses["orbit_135"])
+    want_ring = oracle_frame(oracle, opt, arrays, poses["orbit_135"], ("bunny", "orbit_135"))
+    want_plain = oracle_frame(oracle, opt, arrays, rt.Camera.default(), ("bunny", "default"))
+    for _ in range(4):
+        ring.submit()
+        plain.render_async()
+        assert np.array_equal(ring.collect(), want_ring[1])
+        plain.sync()
+        assert_host_equals(plain, want_plain)
+    assert_host_equals(ring.host(0), want_ring)
+    ring.close()
+    plain.close()
+
+
+@pytest.mark.parametrize("nranks", [2, 3])
+def test_bands_reassemble(rt, oracle, scene_for, nranks):
+    scene, arrays = scene_for("bunny", "longest")
+    opt = rt.Options.defaults(width=96, height=64, n_super_samples=4, ao_num_samples=3)
+    cam = poses_for(rt, arrays)["roll"]
+    img, u8, counters = oracle_frame(oracle, opt, arrays, cam, ("bunny", "roll", "s4"))
+    whole = np.zeros_like(bits(img))
+    whole_u8 = np.zeros_like(u8)
+    seen = np.zeros(opt.height, np.int32)
+    stats = {"primary_rays": 0, "primary_hits": 0, "ao_rays": 0, "ao_occluded": 0}
+    for rank in range(nranks):
+        host = rt.Host(opt, 0, rank, nranks)
+        host.set_camera(cam)
+        host.upload_scene(scene)
+        host.render()
+        whole |= bits(host.download())  # (the other ranks' rows are 0)
+        rows = host.local_to_global_rows()
+        local = host.download_u8_local()
+        keep = rows < opt.height
+        whole_u8[rows[keep]] = local[keep]
+        seen[rows[keep]] += 1
+        for k, v in host.stats().items():
+            stats[k] += v
+        host.close()
+    assert (seen == 1).all()
+    assert np.array_equal(whole, bits(img))
+    assert np.array_equal(whole_u8, u8)
+    assert stats == {k: counters[k] for k in stats}
+
+
+def test_queries_do_not_depend_on_the_camera(rt, scene_for):
+    import query_oracle as qo
+
+    scene, arrays = scene_for("bunny", "longest")
+    opt = rt.Options.defaults(width=64, height=48, n_super_samples=1, ao_num_samples=3)
+    rng = np.random.default_rng(11)
+    o = rng.uniform(-1.5, 1.5, size=(20000, 3)).astype(np.float32)
+    d = rng.normal(size=(20000, 3)).astype(np.float32)
+    results = []
+    for cam in (None, poses_for(rt, arrays)["orbit_180"]):
+        host = rt.Host(opt, 0)
+        if cam is not None:
+            host.set_camera(cam)
+        host.upload_scene(scene)
+        host.render()
+        results.append((host.trace_closest(o, d, 100000.0), host.trace_occluded(o, d, 0.5)))
+        host.close()
+    for f in results[0][0]:
+        assert qo.same_words(results[0][0][f], results[1][0][f]).all(), f
+    assert np.array_equal(results[0][1], results[1][1])
+    assert results[0][0]["hit"].sum() > 100
+
+
+def test_call_order_and_round_trip(rt, scene_for):
+    scene, arrays = scene_for("blob", "longest")
+    opt = rt.Options.defaults(width=32, height=32, n_super_samples=1, ao_num_samples=0)
+    odd = rt.Camera.from_vectors((-0.0, np.inf, 1e-42), (np.nan, 3e38, -1), (0, 0, 0), (1, 2, 3))
+    host = rt.Host(opt, 0)
+    assert not host.camera_is_set
+    assert np.array_equal(bits(host.camera().as_array()), bits(co.DEFAULT_POSE))
+    host.set_camera(odd)  # no float value is rejected
+    assert host.camera_is_set
+    assert np.array_equal(bits(host.camera().as_array()), bits(odd.as_array()))
+    cam = poses_for(rt, arrays)["orbit_90"]
+    host.set_camera(cam)  # (before the upload the pose may still change)
+    host.upload_scene(scene)
+    with pytest.raises(rt.RtError) as e:
+        host.set_camera(cam)
+    assert e.value.code == -4 and "set the camera first" in e.value.message
+    assert np.array_equal(bits(host.camera().as_array()), bits(cam.as_array()))
+    host.upload_scene(scene)  # a later upload keeps the pose
+    host.render()
+    want, _ = co.render(orc.params_from_options(opt), arrays, cam)
+    assert np.array_equal(bits(host.download()), bits(want))
+    host.close()
+    ring = rt.FrameRing(opt, device=0, hosts=2)
+    with pytest.raises(rt.RtError) as e:
+        ring.host(0).set_camera(cam)
+    assert e.value.code == -4
+    ring.set_camera(cam)
+    ring.upload_scene(scene)
+    with pytest.raises(rt.RtError) as e:
+        ring.set_camera(cam)
+    assert e.value.code == -4
+    ring.submit()
+    ring.collect()
+    assert np.array_equal(bits(ring.host(0).download()), bits(want))
+    ring.close()
+
+
+def test_fused_frame_form_falls_back_for_a_pose(rt, oracle, scene_for):
+    """The fused frame experiment has no posed form: asked for on a posed host, the frame is rendered as two kernels --
+    never the default view."""
+    scene, arrays = scene_for("bunny", "longest")
+    opt = rt.Options.defaults(width=96, height=64, n_super_samples=1, ao_num_samples=3)
+    cam = poses_for(rt, arrays)["orbit_180"]
+    host = rt.Host(opt, 0)
+    host.expect_frames(STREAM)
+    host.set_camera(cam)
+    host.upload_scene(scene)
+    host.set_frame_form("fused")
+    assert not host.frame_is_fused
+    host.render()
+    assert_host_equals(host, oracle_frame(oracle, opt, arrays, cam, ("bunny", "orbit_180")))
+    host.close()
+
+
+def read_pgm(path):
+    data = open(path, "rb").read()
+    head, _, body = data.partition(b"\n")
+    magic, w, h, top = head.split()
+    assert magic == b"P5" and top == b"255"
+    return np.frombuffer(body, np.uint8).reshape(int(h), int(w))
+
+
+@pytest.mark.parametrize("extra", [[], ["--frames", "20"], ["--host-resize", "1"]], ids=["one_frame", "frames_20", "host_resize"])
+def test_cli_renders_the_pose(rt, oracle, scene_for, tmp_path, extra):
+    exe = os.path.join(ROOT, "opencl_raytracer_amd", "bin", "render")
+    scene, arrays = scene_for("bunny", "longest")
+    opt = rt.Options.defaults(width=96, height=64, n_super_samples=4, ao_num_samples=3)
+    eye, target, up = (1.25, 0.75, -1.5), (0.0, 0.125, 0.0), (0.0, 1.0, 0.25)
+    cam = look(rt, eye, target, up)
+    want = oracle_frame(oracle, opt, arrays, cam, "cli")
+    out = tmp_path / "posed.pgm"
+    triple = lambda v: ",".join(repr(float(x)) for x in v)
+    r = subprocess.run([exe, "-w", "96", "-h", "64", "-s", "4", "-a", "3", "--eye", triple(eye), "--look-at=" + triple(target), "--up", triple(up)] + extra +
+                       [mesh_file("bunny"), str(out)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-1000:]
+    assert np.array_equal(read_pgm(out), want[1])
+    if not extra:  # --eye 0,0,2 alone: the default view through the posed path (an even size)
+        plain, posed = tmp_path / "plain.pgm", tmp_path / "default_posed.pgm"
+        for path, flags in ((plain, []), (posed, ["--eye", "0,0,2"])):
+            r = subprocess.run([exe, "-w", "96", "-h", "64", "-s", "4", "-a", "3"] + flags + [mesh_file("bunny"), str(path)], capture_output=True, text=True)
+            assert r.returncode == 0, r.stderr[-1000:]
+        assert open(plain, "rb").read() == open(posed, "rb").read()
+
+
+def test_smoke_sized_posed_frame(rt, oracle, scene_for):
+    """What __graft_entry__.smoke() renders (bunny, 96 x 64, 4 supersamples, 3 AO rings), from behind."""
+    scene, arrays = scene_for("bunny", "longest")
+    opt = rt.Options.defaults(width=96, height=64, n_super_samples=4, ao_num_samples=3)
+    cam = look(rt, (0.0, 0.0, -2.0), (0, 0, 0))
+    want = oracle_frame(oracle, opt, arrays, cam, "smoke")
+    assert want[2]["primary_hits"] > 1000
+    run_mode(rt, "one_shot", scene, opt, cam, want)

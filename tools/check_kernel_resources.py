@@ -10,7 +10,10 @@ would otherwise turn into silent scratch traffic in the hottest loop.
     check_kernel_resources.py <remarks.txt> [--table out.txt] [--isa kernels.s] [--report-only]
 
 Hot kernels (must have VGPR spill 0, scratch 0, occupancy 8): the default path, i.e. the
-shared-walk instantiations primary_kernel<true> and ao_kernel<1, true> (1 = UNIFORM).  The
+shared-walk instantiations primary_kernel<true>, its posed form primary_posed_kernel<true> (a host with a camera
+pose: the same pass, eye and basis read from the launch constants) and ao_kernel<1, true> (1 = UNIFORM).  The build
+fails, too, when one of the two primary kernels is not found in the remarks at all: the kernels are matched by the prefix
+of their demangled names, and a gate that matches nothing guards nothing.  The
 first-generation instantiations (<.., false>, debug knob OCRT_NO_SHARED_WALK) and the RANDOM
 mode (ao_kernel<2, ..>, outside the bit-exact contract) must keep the occupancy; their
 spills are reported, not fatal.  The ray-query kernels (query_kernel<true> / <false>, query_key_kernel,
@@ -32,6 +35,10 @@ import sys
 LANE_OPS_PER_WALK_TURN = 10  # v_readlane / v_writelane per turn of the loop around walk_collect, i.e. per leaf stop or batch (measured: 6 primary;
                              # 9 AO: four in the batch block, five single reloads on paths that exclude each other)
 LANE_OPS_PER_PACKET = 40     # ... in the per-packet code around that loop (measured: 38 of ~700 vector instructions)
+# ... and for the posed form of the primary pass (primary_posed_kernel<true>), which holds more launch constants around the walk
+POSED_LANE_OPS_PER_WALK_TURN = 4  # (measured: 2 -- the eye is read again at every leaf stop instead of being held, kernels/primary.hip.h)
+POSED_LANE_OPS_PER_PACKET = 8     # (measured: 5 of ~700 vector instructions)
+HOT_PRIMARY = ("primary_kernel<true>", "primary_posed_kernel<true>")
 
 FIELDS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill",
           "VGPRs Spill", "LDS Size [bytes/block]")
@@ -122,8 +129,8 @@ def main():
                f"{k.get('SGPRs Spill', '?'):>10s} {k.get('VGPRs Spill', '?'):>10s} {k.get('LDS Size [bytes/block]', '?'):>7s}")
         lines.append(row)
         # hot: the default path = shared-walk instantiations of the primary pass and of the UNIFORM ambient-occlusion pass
-        hot = name.startswith("primary_kernel<true>") or name.startswith("ao_kernel<1, true")
-        walker = hot or name.startswith("ao_kernel<") or name.startswith("primary_kernel<")
+        hot = name.startswith(HOT_PRIMARY) or name.startswith("ao_kernel<1, true")
+        walker = hot or name.startswith("ao_kernel<") or name.startswith("primary_kernel<") or name.startswith("primary_posed_kernel<")
         if walker and k.get("Occupancy [waves/SIMD]") != "8":
             errors.append(f"{name}: occupancy {k.get('Occupancy [waves/SIMD]')} waves/SIMD, the walk is scheduled for 8")
         if hot and (k.get("VGPRs Spill") != "0" or k.get("ScratchSize [bytes/lane]") != "0"):
@@ -131,6 +138,9 @@ def main():
                           "in a hot kernel (walk_collect's fixed registers v56-v62 need the 64-VGPR budget to hold)")
     queries = ("query_kernel<true>", "query_kernel<false>", "query_key_kernel", "query_scatter_kernel", "query_scan_kernel")
     names = [k["name"].replace("ocrt::", "").replace("void ", "") for k in kernels]
+    for p in HOT_PRIMARY:
+        if not any(n.startswith(p) for n in names):
+            errors.append(f"{p}: not in the remarks (the gate would guard no such kernel: were the kernels renamed?)")
     for q in queries:
         found = [k for k, n in zip(kernels, names) if n.startswith(q)]
         if not found:
@@ -146,14 +156,20 @@ def main():
         for kname, p in places.items():
             short = kname.replace("ocrt::", "").replace("void ", "")
             lines.append(f"{short:44s} {p['total']:5d} {p['in_node_loop']:5d} {p['walk_turn']:5d} {p['per_packet']:5d}   {p['depths']}")
-            if not (short.startswith("primary_kernel<true>") or short.startswith("ao_kernel<1, true")):
+            if not (short.startswith(HOT_PRIMARY) or short.startswith("ao_kernel<1, true")):
                 continue
+            posed = short.startswith("primary_posed_kernel<true>")
+            turn_limit = POSED_LANE_OPS_PER_WALK_TURN if posed else LANE_OPS_PER_WALK_TURN
+            packet_limit = POSED_LANE_OPS_PER_PACKET if posed else LANE_OPS_PER_PACKET
             if p["in_node_loop"]:
                 errors.append(f"{short}: {p['in_node_loop']} SGPR spill instructions inside the node loop")
-            if p["walk_turn"] > LANE_OPS_PER_WALK_TURN:
-                errors.append(f"{short}: {p['walk_turn']} SGPR spill instructions per turn of the loop around the node loop (limit {LANE_OPS_PER_WALK_TURN})")
-            if p["per_packet"] > LANE_OPS_PER_PACKET:
-                errors.append(f"{short}: {p['per_packet']} SGPR spill instructions in the per-packet code (limit {LANE_OPS_PER_PACKET})")
+            if p["walk_turn"] > turn_limit:
+                errors.append(f"{short}: {p['walk_turn']} SGPR spill instructions per turn of the loop around the node loop (limit {turn_limit})")
+            if p["per_packet"] > packet_limit:
+                errors.append(f"{short}: {p['per_packet']} SGPR spill instructions in the per-packet code (limit {packet_limit})")
+        for want in HOT_PRIMARY:
+            if not any(k.replace("ocrt::", "").replace("void ", "").startswith(want) for k in places):
+                errors.append(f"{want}: no hand-scheduled node loop found in the device assembly")
     table = "\n".join(lines) + "\n"
     if "--table" in sys.argv:
         with open(sys.argv[sys.argv.index("--table") + 1], "w") as f:
