@@ -72,7 +72,9 @@ int rt_trace_closest_device(rt_host *h, const float *origins4, const float *dire
 int rt_trace_occluded_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
                              uint32_t flags, uint8_t *occluded, void *hip_stream);
 
-/* HIP-event time in ms of the last query's kernels (sort + walk; waits for that query to end); 0 before the first. */
+/* HIP-event time in ms of the last query's kernels (sort + walk; waits for that query to end); 0 before the first.  The
+ * last query of either kind: a ray query of this header or an ambient-occlusion query (rt_hip_ao.h: sort + walk + the
+ * finishing kernel). */
 float rt_last_query_ms(const rt_host *h);
 
 #ifdef __cplusplus

@@ -225,6 +225,11 @@ _SIGNATURES = {
     "rt_trace_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
                                            C.c_void_p]),
     "rt_last_query_ms": (C.c_float, [C.c_void_p]),
+    # include/rt_hip_ao.h
+    "rt_ao_rays_per_point": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rt_trace_ao": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_trace_ao_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
     # include/rt_hip_camera.h
     "rt_camera_default": (None, [C.POINTER(Camera)]),
     "rt_camera_look_at": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Camera)]),
@@ -245,6 +250,8 @@ QUERY_OUTPUTS = ("hit", "distance", "leaf", "barycentric", "position", "normal")
 # per output: numpy dtype, values per ray
 _QUERY_LAYOUT = {"hit": (np.uint8, 1), "distance": (np.float32, 1), "leaf": (np.uint32, 1), "barycentric": (np.float32, 3),
                  "position": (np.float32, 3), "normal": (np.float32, 3)}
+AO_OUTPUTS = ("ao", "occluded")
+_AO_LAYOUT = {"ao": np.float32, "occluded": np.uint32}
 
 
 def _is_torch(x) -> bool:
@@ -680,8 +687,75 @@ class Host:
 
     @property
     def last_query_ms(self) -> float:
-        """HIP-event time of the last query's kernels (sort + walk), ms."""
+        """HIP-event time of the last query's kernels (sort + walk), ms: a ray query or an ambient-occlusion query."""
         return float(load_library().rt_last_query_ms(self._h))
+
+    # ---- ambient-occlusion queries (include/rt_hip_ao.h) ----
+    @property
+    def ao_rays_per_point(self) -> tuple:
+        """(rays the reference casts per point with this host's options, the n of `1 - hits / n`)."""
+        rays, divisor = C.c_uint32(), C.c_uint32()
+        _check(load_library().rt_ao_rays_per_point(self._h, C.byref(rays), C.byref(divisor)))
+        return int(rays.value), int(divisor.value)
+
+    def ambient_occlusion(self, points, normals, seeds=None, outputs=AO_OUTPUTS, sort: bool = True) -> dict:
+        """The reference's ambient_occlusion() at every point with this host's AO options: {"ao": float32 (N,), "occluded":
+        uint32 (N,)} (those named in `outputs`).  points / normals: (N, 3) / (N, 4) float32, the normals used as given;
+        seeds: uint32 (N,) -- the reference's `index` of a point, used by the RANDOM method only -- or None: 0 .. N-1.
+        numpy in, numpy out (blocking); torch tensors on the host's GPU in, torch tensors out, enqueued on
+        torch.cuda.current_stream() without waiting (as for the ray queries, the default stream's handle is NULL, which
+        the library reads as the host's own stream: work under a stream of your own, or synchronise around the call)."""
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in AO_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {AO_OUTPUTS}")
+        flags = 0 if sort else RT_QUERY_NO_SORT
+        lib = load_library()
+        if _is_torch(points) or _is_torch(normals) or _is_torch(seeds):
+            if not (_is_torch(points) and _is_torch(normals) and (seeds is None or _is_torch(seeds))):
+                raise ValueError("points, normals and seeds must all be torch tensors or all numpy arrays")
+            import torch
+
+            p4, n4 = _rays4_torch(points, "points"), _rays4_torch(normals, "normals")
+            if p4.shape[0] != n4.shape[0] or p4.device != n4.device:
+                raise ValueError("points and normals must hold the same number of points on the same device")
+            n = int(p4.shape[0])
+            if seeds is not None:
+                if seeds.dtype not in (torch.uint32, torch.int32) or seeds.dim() != 1 or seeds.shape[0] != n:
+                    raise ValueError("seeds: expected a uint32 tensor of shape (N,)")
+                if not seeds.is_contiguous() or seeds.device != p4.device:
+                    raise ValueError("seeds: the tensor must be contiguous and on the points' device")
+            tdtype = {np.float32: torch.float32, np.uint32: torch.uint32}
+            out = {name: torch.empty((n,), dtype=tdtype[_AO_LAYOUT[name]], device=p4.device) for name in outputs}
+            stream = torch.cuda.current_stream(p4.device).cuda_stream
+            _check(lib.rt_trace_ao_device(self._h, p4.data_ptr(), n4.data_ptr(), seeds.data_ptr() if seeds is not None and n else None,
+                                          n, flags, out["ao"].data_ptr() if "ao" in out and n else None,
+                                          out["occluded"].data_ptr() if "occluded" in out and n else None, stream))
+            # (the padded copies must live until the kernels have read them)
+            if p4 is not points:
+                p4.record_stream(torch.cuda.current_stream(p4.device))
+            if n4 is not normals:
+                n4.record_stream(torch.cuda.current_stream(n4.device))
+            return out
+        p4, n4 = _rays4_numpy(points, "points"), _rays4_numpy(normals, "normals")
+        if p4.shape[0] != n4.shape[0]:
+            raise ValueError("points and normals must hold the same number of points")
+        n = int(p4.shape[0])
+        if seeds is not None:
+            if not isinstance(seeds, np.ndarray) or seeds.dtype != np.uint32 or seeds.shape != (n,):
+                raise ValueError("seeds: expected a uint32 array of shape (N,)")
+            seeds = np.ascontiguousarray(seeds)
+        out = {name: np.empty((n,), dtype=_AO_LAYOUT[name]) for name in outputs}
+        _check(lib.rt_trace_ao(self._h, p4.ctypes.data, n4.ctypes.data, seeds.ctypes.data if seeds is not None and n else None, n,
+                               flags, out["ao"].ctypes.data if "ao" in out and n else None,
+                               out["occluded"].ctypes.data if "occluded" in out and n else None))
+        return out
+
+    def vertex_ao(self, scene: "Scene") -> np.ndarray:
+        """Per-vertex AO baking: ambient_occlusion(scene.vertices, scene.vnormals)["ao"], one value per vertex of the file, in
+        its order.  A vertex with a zero normal (one no face uses) gets the reference's answer for a zero normal: its
+        tangent frame is not a number, none of its rays hits anything, the value is 1.0."""
+        return self.ambient_occlusion(scene.vertices, scene.vnormals, outputs=("ao",))["ao"]
 
 
 class FrameRing:

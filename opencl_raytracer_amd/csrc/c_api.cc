@@ -1,6 +1,7 @@
 // c_api.cc -- the extern "C" boundary declared in include/rt_hip.h (the seam), rt_hip_ring.h (streams of frames, several GPUs), rt_hip_debug.h,
-// rt_hip_query.h and rt_hip_camera.h.
+// rt_hip_query.h, rt_hip_ao.h and rt_hip_camera.h.
 #include "../../include/rt_hip.h"
+#include "../../include/rt_hip_ao.h"
 #include "../../include/rt_hip_camera.h"
 #include "../../include/rt_hip_debug.h"
 #include "../../include/rt_hip_query.h"
@@ -74,6 +75,28 @@ ocrt::RayQueries &queries_of(rt_host *h) {
 	if (!h->queries)
 		h->queries.reset(new ocrt::RayQueries(*h->dev));
 	return *h->queries;
+}
+
+// ... and every ambient-occlusion query (include/rt_hip_ao.h, "Errors"); `rays`: the rays per point, for the caller.
+int ao_precheck(const rt_host *h, const float *points4, const float *normals4, uint32_t n, bool device, uint32_t *rays) {
+	if (!h)
+		return fail(RT_E_INVALID, "null host");
+	if (!h->owned)
+		return fail(RT_E_STATE, "ambient-occlusion queries are not available on the hosts of a frame ring");
+	if (!h->dev->sceneReady())
+		return fail(RT_E_STATE, "ambient-occlusion query before a scene was uploaded");
+	const uint32_t per_point = ocrt::RayQueries::aoRaysPerPoint(*h->dev);
+	if (per_point == 0)
+		return fail(RT_E_STATE, "ambient-occlusion query on a host whose options have ambient occlusion off");
+	if (n > RT_QUERY_MAX_RAYS / per_point)
+		return fail(RT_E_INVALID, "more points than RT_QUERY_MAX_RAYS / rays per point in one call");
+	if (n > 0 && (!points4 || !normals4))
+		return fail(RT_E_INVALID, "null point or normal arrays");
+	if (device && n > 0 && (((uintptr_t) points4 | (uintptr_t) normals4) & 15u))
+		return fail(RT_E_INVALID, "device point and normal arrays must be 16-byte aligned");
+	if (rays)
+		*rays = per_point;
+	return RT_OK;
 }
 
 // Maps the exception in flight to an RT_E_* code.
@@ -859,6 +882,37 @@ int rt_trace_occluded_device(rt_host *h, const float *origins4, const float *dir
 	ocrt::QueryOutputs q;
 	q.hit = occluded;
 	return guarded([&] { queries_of(h).traceDevice(false, origins4, directions4, n, max_distance, flags, q, hip_stream); });
+}
+
+// ---- rt_hip_ao.h ----
+int rt_ao_rays_per_point(const rt_host *h, uint32_t *rays, uint32_t *divisor) {
+	uint32_t per_point = 0;
+	const int rc = ao_precheck(h, nullptr, nullptr, 0, false, &per_point);
+	if (rc != RT_OK)
+		return rc;
+	if (rays)
+		*rays = per_point;
+	if (divisor)
+		*divisor = ocrt::RayQueries::aoDivisor(*h->dev);
+	return RT_OK;
+}
+
+int rt_trace_ao(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
+                uint32_t *occluded) {
+	const int rc = ao_precheck(h, points4, normals4, n, false, nullptr);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	return guarded([&] { queries_of(h).aoHost(points4, normals4, seeds, n, flags, ao, occluded); });
+}
+
+int rt_trace_ao_device(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
+                       float *ao, uint32_t *occluded, void *hip_stream) {
+	const int rc = ao_precheck(h, points4, normals4, n, true, nullptr);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	if ((((uintptr_t) seeds | (uintptr_t) ao | (uintptr_t) occluded) & 3u) != 0)
+		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).aoDevice(points4, normals4, seeds, n, flags, ao, occluded, hip_stream); });
 }
 
 float rt_last_query_ms(const rt_host *h) {

@@ -30,6 +30,8 @@
 //                   quantisation of the same sweep (n = 1: a thread per pixel; n >= 2: along the sub-pixel rows).
 //   (queries)       query_key_kernel / query_scan_kernel / query_scatter_kernel order caller-supplied rays by a coherence
 //                   key, query_kernel<CLOSEST> casts them (kernels/query.hip.h, include/rt_hip_query.h): not part of a frame.
+//                   ao_query_kernel<MODE> makes, casts and counts the ambient-occlusion rays of caller-supplied points,
+//                   ao_query_finish_kernel writes their 1 - hits / n (kernels/ao_query.hip.h, include/rt_hip_ao.h).
 //   (on demand)     entry_kernel: the walk intervals, once per upload; occluded_sum_kernel: the frame's occlusion
 //                   total when the statistics are asked for; resize_kernel: a box filter on its own.
 // Why not one fused launch (it was, see profiles/r01_notes.md): cost per tile
@@ -67,6 +69,7 @@
 #include "kernels/entry.hip.h"
 #include "kernels/finish.hip.h"
 #include "kernels/query.hip.h"
+#include "kernels/ao_query.hip.h"
 
 
 namespace ocrt {
@@ -405,6 +408,39 @@ void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, 
 	} else {
 		hipLaunchKernelGGL(query_kernel<false>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
 	}
+}
+
+// Ambient-occlusion queries (kernels/ao_query.hip.h).  `count`: n words on the device (the caller's `occluded` array or
+// scratch), zeroed here on the stream; `order`: launch_query_sort's order of the POINTS or null; `ao`: null = not written.
+void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
+                     float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
+                     uint32_t *count, float *ao, void *stream) {
+	if (n == 0 || rays_per_point == 0)
+		return;
+	hipStream_t s = (hipStream_t) stream;
+	AoQueryArgs a{};
+	a.nodes_ptr = (const float4 *) scene.nodes;
+	a.tris_ptr = (const float4 *) scene.tris;
+	a.ao_table = (const float4 *) scene.ao_table;
+	a.points = (const float4 *) points;
+	a.normals = (const float4 *) normals;
+	a.seeds = seeds;
+	a.order = (const uint32_t *) order;
+	a.count = count;
+	a.n = n;
+	a.rays = rays_per_point;
+	a.total = n * rays_per_point;  // (<= RT_QUERY_MAX_RAYS: checked at the boundary)
+	a.node_count = node_count;
+	a.max_distance = max_distance;
+	(void) hipMemsetAsync(count, 0, (size_t) n * sizeof(uint32_t), s);
+	const uint32_t blocks = (a.total + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
+	if (ao_mode == AO_RANDOM)
+		hipLaunchKernelGGL(ao_query_kernel<AO_RANDOM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+	else
+		hipLaunchKernelGGL(ao_query_kernel<AO_UNIFORM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+	if (ao)
+		hipLaunchKernelGGL(ao_query_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, (const uint32_t *) count, ao, n,
+		                   divisor ? divisor : 1u);
 }
 
 }  // namespace ocrt

@@ -1,4 +1,4 @@
-// ray_query.cc -- ray queries on a render host's uploaded scene (ray_query.h).
+// ray_query.cc -- ray queries and ambient-occlusion queries on a render host's uploaded scene (ray_query.h).
 #include "ray_query.h"
 
 #include <cmath>
@@ -28,6 +28,7 @@ RayQueries::~RayQueries() {
 	device_free(d_count);
 	device_free(d_order);
 	device_free(d_stage);
+	device_free(d_ao_hits);
 	(void) hipEventDestroy((hipEvent_t) ev_start);
 	(void) hipEventDestroy((hipEvent_t) ev_stop);
 }
@@ -143,6 +144,81 @@ void RayQueries::traceHost(bool closest, const float *origins4, const float *dir
 	back(barycentric, out.barycentric, (size_t) n * 12u);
 	back(position, out.position, (size_t) n * 12u);
 	back(normal, out.normal, (size_t) n * 12u);
+	OCRT_HIP(hipStreamSynchronize(s));
+}
+
+uint32_t RayQueries::aoRaysPerPoint(const DeviceRenderer &renderer) {
+	const KernelParams &kp = renderer.params();
+	const bool available = renderer.sceneReady() && renderer.deviceScene() && kp.ao_mode != AO_NONE && kp.ao_dirs > 0 &&
+	                       renderer.deviceScene()->aoDirs() == kp.ao_dirs;
+	return available ? kp.ao_dirs : 0u;
+}
+uint32_t RayQueries::aoDivisor(const DeviceRenderer &renderer) { return aoRaysPerPoint(renderer) ? renderer.params().ao_divisor : 0u; }
+
+void RayQueries::aoDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
+                          uint32_t *occluded, void *stream) {
+	if (!dev.sceneReady() || !dev.deviceScene())
+		throw std::logic_error("ambient-occlusion query before a scene was uploaded");
+	if (aoRaysPerPoint(dev) == 0)
+		throw std::logic_error("ambient-occlusion query on a host whose options have ambient occlusion off");
+	if (n == 0 || (!ao && !occluded))
+		return;
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
+	const DeviceScene &scene = *dev.deviceScene();
+	const KernelParams &kp = dev.params();
+	// one set of scratch per host: a query on another stream waits for the one before it
+	if (timed)
+		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	// the POINTS are ordered (key: point and normal) from as many on as make RT_QUERY_SORT_MIN rays
+	const bool sort = !(flags & QUERY_NO_SORT) && (uint64_t) n * kp.ao_dirs >= QUERY_SORT_MIN;
+	if (sort) {
+		size_t count_bytes = d_count ? QUERY_COUNT_BYTES : 0;
+		grow(d_count, count_bytes, QUERY_COUNT_BYTES);
+		grow(d_order, order_bytes, (size_t) n * sizeof(uint32_t));
+	}
+	if (!occluded)
+		grow(d_ao_hits, ao_hits_bytes, (size_t) n * sizeof(uint32_t));
+	float lo[3], scale[3];
+	if (sort)
+		sceneBox(scene, lo, scale);
+	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
+	if (sort)
+		launch_query_sort(points4, normals4, n, lo, scale, d_count, d_order, s);
+	launch_ao_query(scene.buffers(), kp.node_count, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4, normals4, seeds,
+	                sort ? d_order : nullptr, n, occluded ? occluded : (uint32_t *) d_ao_hits, ao, s);
+	OCRT_HIP(hipGetLastError());
+	OCRT_HIP(hipEventRecord((hipEvent_t) ev_stop, s));
+	timed = true;
+	have_ms = false;
+}
+
+void RayQueries::aoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
+                        uint32_t *occluded) {
+	if (!dev.sceneReady() || !dev.deviceScene())
+		throw std::logic_error("ambient-occlusion query before a scene was uploaded");
+	if (aoRaysPerPoint(dev) == 0)
+		throw std::logic_error("ambient-occlusion query on a host whose options have ambient occlusion off");
+	if (n == 0 || (!ao && !occluded))
+		return;
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	hipStream_t s = (hipStream_t) dev.streamHandle();
+	// staging: points, normals, the counts, then the seeds and the values if there are any
+	const size_t vec_bytes = (size_t) n * 16u, word_bytes = round16((size_t) n * 4u);
+	const size_t o_count = 2 * vec_bytes, o_seeds = o_count + word_bytes, o_ao = o_seeds + (seeds ? word_bytes : 0);
+	grow(d_stage, stage_bytes, o_ao + (ao ? word_bytes : 0));
+	char *base = (char *) d_stage;
+	uint32_t *d_occluded = (uint32_t *) (base + o_count), *d_seeds = seeds ? (uint32_t *) (base + o_seeds) : nullptr;
+	float *d_value = ao ? (float *) (base + o_ao) : nullptr;
+	OCRT_HIP(hipMemcpyAsync(base, points4, vec_bytes, hipMemcpyHostToDevice, s));
+	OCRT_HIP(hipMemcpyAsync(base + vec_bytes, normals4, vec_bytes, hipMemcpyHostToDevice, s));
+	if (seeds)
+		OCRT_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t) n * 4u, hipMemcpyHostToDevice, s));
+	aoDevice((const float *) base, (const float *) (base + vec_bytes), d_seeds, n, flags, d_value, d_occluded, s);
+	if (ao)
+		OCRT_HIP(hipMemcpyAsync(ao, d_value, (size_t) n * 4u, hipMemcpyDeviceToHost, s));
+	if (occluded)
+		OCRT_HIP(hipMemcpyAsync(occluded, d_occluded, (size_t) n * 4u, hipMemcpyDeviceToHost, s));
 	OCRT_HIP(hipStreamSynchronize(s));
 }
 

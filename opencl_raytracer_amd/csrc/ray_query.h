@@ -1,4 +1,5 @@
-// ray_query.h -- ray queries on a render host's uploaded scene (include/rt_hip_query.h; kernels/query.hip.h).
+// ray_query.h -- ray queries and ambient-occlusion queries on a render host's uploaded scene (include/rt_hip_query.h,
+// include/rt_hip_ao.h; kernels/query.hip.h, kernels/ao_query.hip.h).
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -31,7 +32,19 @@ class RayQueries {
 		// Host memory, blocking: the rays go through the staging buffers on the renderer's stream.
 		void traceHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
 		               unsigned char *hit, float *distance, uint32_t *leaf, float *barycentric, float *position, float *normal);
-		float lastMs();
+		// Ambient-occlusion queries (include/rt_hip_ao.h): the reference's ambient_occlusion() of n points with the options
+		// the scene was uploaded for -- table, mode, rays per point, divisor and reach come from the renderer's launch
+		// constants and its DeviceScene.  std::logic_error where those options have ambient occlusion off.
+		// (static: what a renderer's uploaded scene answers, before any query has made scratch for it)
+		static uint32_t aoRaysPerPoint(const DeviceRenderer &renderer);  // 0: not available
+		static uint32_t aoDivisor(const DeviceRenderer &renderer);
+		// Device memory, enqueued on `stream` (null: the renderer's); `seeds`, `ao`, `occluded` may be null.
+		void aoDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
+		              uint32_t *occluded, void *stream);
+		// Host memory, blocking.
+		void aoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
+		            uint32_t *occluded);
+		float lastMs();  // the last query of either kind
 
 	private:
 		void grow(void *&buffer, size_t &capacity, size_t bytes);
@@ -39,7 +52,8 @@ class RayQueries {
 
 		DeviceRenderer &dev;
 		void *d_count = nullptr, *d_order = nullptr, *d_stage = nullptr;
-		size_t order_bytes = 0, stage_bytes = 0;
+		void *d_ao_hits = nullptr;  // aoDevice without an `occluded` array: the points' counts
+		size_t order_bytes = 0, stage_bytes = 0, ao_hits_bytes = 0;
 		void *ev_start = nullptr, *ev_stop = nullptr;
 		bool timed = false, have_ms = false;
 		float last_ms = 0.0f;
@@ -53,5 +67,8 @@ void launch_query_sort(const void *origins, const void *directions, uint32_t n, 
 void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *origins, const void *directions,
                   const void *order, uint32_t n, float max_distance, unsigned char *hit, float *distance, uint32_t *leaf,
                   float *barycentric, float *position, float *normal, void *stream);
+void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
+                     float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
+                     uint32_t *count, float *ao, void *stream);
 
 }  // namespace ocrt
