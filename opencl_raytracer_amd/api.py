@@ -225,6 +225,10 @@ _SIGNATURES = {
     "rt_trace_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
                                            C.c_void_p]),
     "rt_last_query_ms": (C.c_float, [C.c_void_p]),
+    # include/rt_hip_multihit.h
+    "rt_trace_multihit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_trace_multihit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32,
+                                           C.c_void_p, C.c_void_p]),
     # include/rt_hip_ao.h
     "rt_ao_rays_per_point": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rt_trace_ao": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
@@ -245,7 +249,18 @@ class _HitArrays(C.Structure):
                 ("position", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class _MultiHitArrays(C.Structure):
+    """rt_multihit_arrays (include/rt_hip_multihit.h)."""
+    _fields_ = [("count", C.c_void_p), ("distance", C.c_void_p), ("leaf", C.c_void_p), ("barycentric", C.c_void_p),
+                ("position", C.c_void_p), ("normal", C.c_void_p)]
+
+
 RT_QUERY_NO_SORT = 1
+RT_MULTIHIT_MAX_K = 16
+MULTIHIT_OUTPUTS = ("count", "distance", "leaf", "barycentric", "position", "normal")
+# per output: numpy dtype, values per slot (count: per ray)
+_MULTIHIT_LAYOUT = {"count": (np.uint32, 1), "distance": (np.float32, 1), "leaf": (np.uint32, 1), "barycentric": (np.float32, 3),
+                    "position": (np.float32, 3), "normal": (np.float32, 3)}
 QUERY_OUTPUTS = ("hit", "distance", "leaf", "barycentric", "position", "normal")
 # per output: numpy dtype, values per ray
 _QUERY_LAYOUT = {"hit": (np.uint8, 1), "distance": (np.float32, 1), "leaf": (np.uint32, 1), "barycentric": (np.float32, 3),
@@ -685,9 +700,70 @@ class Host:
                                          out["hit"].ctypes.data if n else None))
         return out
 
+    # ---- multi-hit queries (include/rt_hip_multihit.h) ----
+    def trace_multihit(self, origins, directions, max_distance: float = 100000.0, k: int = 4, outputs=MULTIHIT_OUTPUTS,
+                       sort: bool = True) -> dict:
+        """Everything a ray crosses: {"count": uint32 (N,), the number of triangles the reference's walk accepts for the ray
+        (all of them, whatever k); "distance" / "leaf": (N, k), "barycentric" / "position" / "normal": (N, k, 3), the first
+        k of them by (distance, leaf index), unused slots filled with +inf / 0xFFFFFFFF / 0} (those named in `outputs`).
+        0 <= k <= RT_MULTIHIT_MAX_K; with k = 0 only "count" can be asked for.  numpy (N, 3) / (N, 4) float32 in, numpy
+        out (blocking); torch tensors on the host's GPU in, torch tensors out, enqueued on torch.cuda.current_stream()
+        without waiting (as for trace_closest)."""
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in MULTIHIT_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {MULTIHIT_OUTPUTS}")
+        k = int(k)
+        if k < 0:
+            raise ValueError("k must not be negative")
+        flags = 0 if sort else RT_QUERY_NO_SORT
+        lib = load_library()
+
+        def shape(name, n):
+            per = _MULTIHIT_LAYOUT[name][1]
+            return (n,) if name == "count" else ((n, k, per) if per > 1 else (n, k))
+
+        if _is_torch(origins) or _is_torch(directions):
+            if not (_is_torch(origins) and _is_torch(directions)):
+                raise ValueError("origins and directions must both be torch tensors or both numpy arrays")
+            import torch
+
+            o4, d4 = _rays4_torch(origins, "origins"), _rays4_torch(directions, "directions")
+            if o4.shape[0] != d4.shape[0] or o4.device != d4.device:
+                raise ValueError("origins and directions must hold the same number of rays on the same device")
+            n = int(o4.shape[0])
+            tdtype = {np.float32: torch.float32, np.uint32: torch.uint32}
+            out = {name: torch.empty(shape(name, n), dtype=tdtype[_MULTIHIT_LAYOUT[name][0]], device=o4.device) for name in outputs}
+            stream = torch.cuda.current_stream(o4.device).cuda_stream
+            # (an array is named even where it holds nothing -- n = 0, or a slot array with k = 0: the library then says
+            # what is wrong with the call, as it would for a caller in C)
+            arrays = _MultiHitArrays(*[out[name].data_ptr() or 4 if name in out else None for name in MULTIHIT_OUTPUTS])
+            _check(lib.rt_trace_multihit_device(self._h, o4.data_ptr(), d4.data_ptr(), n, float(max_distance), k, flags,
+                                                C.byref(arrays), stream))
+            # (the padded copies must live until the kernels have read them)
+            if o4 is not origins:
+                o4.record_stream(torch.cuda.current_stream(o4.device))
+            if d4 is not directions:
+                d4.record_stream(torch.cuda.current_stream(d4.device))
+            return out
+        o4, d4 = _rays4_numpy(origins, "origins"), _rays4_numpy(directions, "directions")
+        if o4.shape[0] != d4.shape[0]:
+            raise ValueError("origins and directions must hold the same number of rays")
+        n = int(o4.shape[0])
+        out = {name: np.empty(shape(name, n), dtype=_MULTIHIT_LAYOUT[name][0]) for name in outputs}
+        arrays = _MultiHitArrays(*[out[name].ctypes.data or 4 if name in out else None for name in MULTIHIT_OUTPUTS])
+        _check(lib.rt_trace_multihit(self._h, o4.ctypes.data, d4.ctypes.data, n, float(max_distance), k, flags, C.byref(arrays)))
+        return out
+
+    def count_hits(self, origins, directions, max_distance: float = 100000.0, sort: bool = True):
+        """The number of triangles the reference's walk accepts for every ray (trace_multihit's "count", the k = 0 form
+        that keeps no list): uint32 (N,)."""
+        return self.trace_multihit(origins, directions, max_distance, k=0, outputs=("count",), sort=sort)["count"]
+
     @property
     def last_query_ms(self) -> float:
-        """HIP-event time of the last query's kernels (sort + walk), ms: a ray query or an ambient-occlusion query."""
+        """HIP-event time of the last query's kernels (sort + walk), ms: a ray query, a multi-hit query or an ambient-occlusion
+        query."""
         return float(load_library().rt_last_query_ms(self._h))
 
     # ---- ambient-occlusion queries (include/rt_hip_ao.h) ----

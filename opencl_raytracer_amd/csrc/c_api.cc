@@ -1,9 +1,10 @@
 // c_api.cc -- the extern "C" boundary declared in include/rt_hip.h (the seam), rt_hip_ring.h (streams of frames, several GPUs), rt_hip_debug.h,
-// rt_hip_query.h, rt_hip_ao.h and rt_hip_camera.h.
+// rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h and rt_hip_camera.h.
 #include "../../include/rt_hip.h"
 #include "../../include/rt_hip_ao.h"
 #include "../../include/rt_hip_camera.h"
 #include "../../include/rt_hip_debug.h"
+#include "../../include/rt_hip_multihit.h"
 #include "../../include/rt_hip_query.h"
 
 #include <algorithm>
@@ -882,6 +883,61 @@ int rt_trace_occluded_device(rt_host *h, const float *origins4, const float *dir
 	ocrt::QueryOutputs q;
 	q.hit = occluded;
 	return guarded([&] { queries_of(h).traceDevice(false, origins4, directions4, n, max_distance, flags, q, hip_stream); });
+}
+
+// ---- rt_hip_multihit.h ----
+namespace {
+
+// The checks of include/rt_hip_multihit.h ("Errors") beyond query_precheck's; `out` null: no output at all.
+int multihit_precheck(rt_host *h, const float *origins4, const float *directions4, uint32_t n, uint32_t k, const rt_multihit_arrays *out,
+                      bool device) {
+	const int rc = query_precheck(h, origins4, directions4, n, device);
+	if (rc != RT_OK)
+		return rc;
+	if (k > RT_MULTIHIT_MAX_K)
+		return fail(RT_E_INVALID, "more slots per ray than RT_MULTIHIT_MAX_K");
+	if (k == 0 && out && (out->distance || out->leaf || out->barycentric || out->position || out->normal))
+		return fail(RT_E_INVALID, "k == 0 asks for the count alone: the slot arrays must be null");
+	if ((uint64_t) n * (k ? k : 1u) > RT_QUERY_MAX_RAYS)
+		return fail(RT_E_INVALID, "more than RT_QUERY_MAX_RAYS slots (n * k) in one call");
+	if (device && out &&
+	    (((uintptr_t) out->count | (uintptr_t) out->distance | (uintptr_t) out->leaf | (uintptr_t) out->barycentric |
+	      (uintptr_t) out->position | (uintptr_t) out->normal) & 3u) != 0)
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	return RT_OK;
+}
+
+void multihit_outputs(const rt_multihit_arrays *out, ocrt::MultiHitOutputs &q) {
+	if (out) {
+		q.count = out->count;
+		q.distance = out->distance;
+		q.leaf = out->leaf;
+		q.barycentric = out->barycentric;
+		q.position = out->position;
+		q.normal = out->normal;
+	}
+}
+
+}  // namespace
+
+int rt_trace_multihit(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
+                      uint32_t flags, const rt_multihit_arrays *out) {
+	const int rc = multihit_precheck(h, origins4, directions4, n, k, out, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	ocrt::MultiHitOutputs q;
+	multihit_outputs(out, q);
+	return guarded([&] { queries_of(h).multihitHost(origins4, directions4, n, max_distance, k, flags, q); });
+}
+
+int rt_trace_multihit_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
+                             uint32_t flags, const rt_multihit_arrays *out, void *hip_stream) {
+	const int rc = multihit_precheck(h, origins4, directions4, n, k, out, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	ocrt::MultiHitOutputs q;
+	multihit_outputs(out, q);
+	return guarded([&] { queries_of(h).multihitDevice(origins4, directions4, n, max_distance, k, flags, q, hip_stream); });
 }
 
 // ---- rt_hip_ao.h ----

@@ -32,6 +32,8 @@
 //                   key, query_kernel<CLOSEST> casts them (kernels/query.hip.h, include/rt_hip_query.h): not part of a frame.
 //                   ao_query_kernel<MODE> makes, casts and counts the ambient-occlusion rays of caller-supplied points,
 //                   ao_query_finish_kernel writes their 1 - hits / n (kernels/ao_query.hip.h, include/rt_hip_ao.h).
+//                   multihit_walk_kernel<K> counts every triangle a caller-supplied ray's walk accepts and keeps the first K,
+//                   multihit_resolve_kernel writes their records (kernels/multihit.hip.h, include/rt_hip_multihit.h).
 //   (on demand)     entry_kernel: the walk intervals, once per upload; occluded_sum_kernel: the frame's occlusion
 //                   total when the statistics are asked for; resize_kernel: a box filter on its own.
 // Why not one fused launch (it was, see profiles/r01_notes.md): cost per tile
@@ -70,6 +72,7 @@
 #include "kernels/finish.hip.h"
 #include "kernels/query.hip.h"
 #include "kernels/ao_query.hip.h"
+#include "kernels/multihit.hip.h"
 
 
 namespace ocrt {
@@ -441,6 +444,50 @@ void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode
 	if (ao)
 		hipLaunchKernelGGL(ao_query_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, (const uint32_t *) count, ao, n,
 		                   divisor ? divisor : 1u);
+}
+
+// Multi-hit queries (kernels/multihit.hip.h).  `k` <= MULTIHIT_MAX_K slots per ray (0: the count alone); `list`: n * k
+// uint2 of scratch on the device; `count` and the slot arrays: null = not written.  The resolve pass is launched only if
+// a slot array is given.
+void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void *origins, const void *directions, const void *order,
+                     uint32_t n, float max_distance, uint32_t k, void *list, uint32_t *count, float *distance, uint32_t *leaf,
+                     float *barycentric, float *position, float *normal, void *stream) {
+	if (n == 0 || k > MULTIHIT_MAX_K)
+		return;
+	hipStream_t s = (hipStream_t) stream;
+	MultiHitArgs a{};
+	a.nodes_ptr = (const float4 *) scene.nodes;
+	a.tris_ptr = (const float4 *) scene.tris;
+	a.shade = (const float4 *) scene.shade;
+	a.origins = (const float4 *) origins;
+	a.directions = (const float4 *) directions;
+	a.order = (const uint32_t *) order;
+	a.n = n;
+	a.node_count = node_count;
+	a.k = k;
+	a.max_distance = max_distance;
+	a.list = (uint2 *) list;
+	a.count = count;
+	a.distance = distance;
+	a.leaf = leaf;
+	a.barycentric = barycentric;
+	a.position = position;
+	a.normal = normal;
+	const dim3 blocks((n + MULTIHIT_LANES - 1u) / MULTIHIT_LANES), lanes(MULTIHIT_LANES);
+	if (k == 0u)
+		hipLaunchKernelGGL(multihit_walk_kernel<0u>, blocks, lanes, 0, s, a);
+	else if (k == 1u)
+		hipLaunchKernelGGL(multihit_walk_kernel<1u>, blocks, lanes, 0, s, a);
+	else if (k <= 2u)
+		hipLaunchKernelGGL(multihit_walk_kernel<2u>, blocks, lanes, 0, s, a);
+	else if (k <= 4u)
+		hipLaunchKernelGGL(multihit_walk_kernel<4u>, blocks, lanes, 0, s, a);
+	else if (k <= 8u)
+		hipLaunchKernelGGL(multihit_walk_kernel<8u>, blocks, lanes, 0, s, a);
+	else
+		hipLaunchKernelGGL(multihit_walk_kernel<16u>, blocks, lanes, 0, s, a);
+	if (k > 0u && (distance || leaf || barycentric || position || normal))
+		hipLaunchKernelGGL(multihit_resolve_kernel, dim3((n * k + 255u) / 256u), dim3(256), 0, s, a);
 }
 
 }  // namespace ocrt

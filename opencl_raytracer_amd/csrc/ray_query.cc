@@ -1,4 +1,4 @@
-// ray_query.cc -- ray queries and ambient-occlusion queries on a render host's uploaded scene (ray_query.h).
+// ray_query.cc -- ray queries, multi-hit queries and ambient-occlusion queries on a render host's uploaded scene (ray_query.h).
 #include "ray_query.h"
 
 #include <cmath>
@@ -11,6 +11,7 @@ namespace ocrt {
 namespace {
 constexpr size_t QUERY_COUNT_BYTES = (size_t) 1 << 18;  // kernels/query.hip.h: QUERY_BUCKETS words
 constexpr uint32_t QUERY_NO_SORT = 1u, QUERY_SORT_MIN = 16384u;  // include/rt_hip_query.h
+constexpr uint32_t MULTIHIT_MAX_SLOTS = 16u;                     // include/rt_hip_multihit.h, kernels/multihit.hip.h
 size_t round16(size_t bytes) { return (bytes + 15u) & ~(size_t) 15u; }
 }  // namespace
 
@@ -29,6 +30,7 @@ RayQueries::~RayQueries() {
 	device_free(d_order);
 	device_free(d_stage);
 	device_free(d_ao_hits);
+	device_free(d_list);
 	(void) hipEventDestroy((hipEvent_t) ev_start);
 	(void) hipEventDestroy((hipEvent_t) ev_stop);
 }
@@ -144,6 +146,93 @@ void RayQueries::traceHost(bool closest, const float *origins4, const float *dir
 	back(barycentric, out.barycentric, (size_t) n * 12u);
 	back(position, out.position, (size_t) n * 12u);
 	back(normal, out.normal, (size_t) n * 12u);
+	OCRT_HIP(hipStreamSynchronize(s));
+}
+
+void RayQueries::multihitDevice(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
+                                uint32_t flags, const MultiHitOutputs &out, void *stream) {
+	if (!dev.sceneReady() || !dev.deviceScene())
+		throw std::logic_error("multi-hit query before a scene was uploaded");
+	if (k > MULTIHIT_MAX_SLOTS)
+		throw std::invalid_argument("more slots per ray than RT_MULTIHIT_MAX_K");
+	// without a slot array the lists are not wanted: the count-only walk
+	const uint32_t slots = out.anySlot() ? k : 0u;
+	if (n == 0 || (slots == 0 && !out.count))
+		return;
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
+	const DeviceScene &scene = *dev.deviceScene();
+	// one set of scratch per host: a query on another stream waits for the one before it
+	if (timed)
+		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	const bool sort = !(flags & QUERY_NO_SORT) && n >= QUERY_SORT_MIN;
+	if (sort) {
+		size_t count_bytes = d_count ? QUERY_COUNT_BYTES : 0;
+		grow(d_count, count_bytes, QUERY_COUNT_BYTES);
+		grow(d_order, order_bytes, (size_t) n * sizeof(uint32_t));
+	}
+	if (slots)
+		grow(d_list, list_bytes, (size_t) n * slots * 8u);
+	float lo[3], scale[3];
+	if (sort)
+		sceneBox(scene, lo, scale);
+	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
+	if (sort)
+		launch_query_sort(origins4, directions4, n, lo, scale, d_count, d_order, s);
+	launch_multihit(scene.buffers(), dev.params().node_count, origins4, directions4, sort ? d_order : nullptr, n, max_distance, slots,
+	                d_list, out.count, out.distance, out.leaf, out.barycentric, out.position, out.normal, s);
+	OCRT_HIP(hipGetLastError());
+	OCRT_HIP(hipEventRecord((hipEvent_t) ev_stop, s));
+	timed = true;
+	have_ms = false;
+}
+
+void RayQueries::multihitHost(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
+                              const MultiHitOutputs &host) {
+	if (!dev.sceneReady() || !dev.deviceScene())
+		throw std::logic_error("multi-hit query before a scene was uploaded");
+	if (k > MULTIHIT_MAX_SLOTS)
+		throw std::invalid_argument("more slots per ray than RT_MULTIHIT_MAX_K");
+	if (n == 0 || (!host.count && !host.anySlot()))
+		return;
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	hipStream_t s = (hipStream_t) dev.streamHandle();
+	// staging: origins, directions, then the outputs asked for
+	const size_t ray_bytes = (size_t) n * 16u, slots = (size_t) n * k;
+	size_t at = 2 * ray_bytes;
+	auto place = [&](const void *wanted, size_t bytes) -> size_t {
+		if (!wanted)
+			return (size_t) -1;
+		const size_t here = at;
+		at += round16(bytes);
+		return here;
+	};
+	const size_t o_count = place(host.count, (size_t) n * 4u), o_dist = place(host.distance, slots * 4u);
+	const size_t o_leaf = place(host.leaf, slots * 4u), o_bary = place(host.barycentric, slots * 12u);
+	const size_t o_pos = place(host.position, slots * 12u), o_norm = place(host.normal, slots * 12u);
+	grow(d_stage, stage_bytes, at);
+	char *base = (char *) d_stage;
+	auto dptr = [&](size_t offset) -> void * { return offset == (size_t) -1 ? nullptr : base + offset; };
+	MultiHitOutputs out;
+	out.count = (uint32_t *) dptr(o_count);
+	out.distance = (float *) dptr(o_dist);
+	out.leaf = (uint32_t *) dptr(o_leaf);
+	out.barycentric = (float *) dptr(o_bary);
+	out.position = (float *) dptr(o_pos);
+	out.normal = (float *) dptr(o_norm);
+	OCRT_HIP(hipMemcpyAsync(base, origins4, ray_bytes, hipMemcpyHostToDevice, s));
+	OCRT_HIP(hipMemcpyAsync(base + ray_bytes, directions4, ray_bytes, hipMemcpyHostToDevice, s));
+	multihitDevice((const float *) base, (const float *) (base + ray_bytes), n, max_distance, k, flags, out, s);
+	auto back = [&](void *to, const void *device, size_t bytes) {
+		if (to && device && bytes)
+			OCRT_HIP(hipMemcpyAsync(to, device, bytes, hipMemcpyDeviceToHost, s));
+	};
+	back(host.count, out.count, (size_t) n * 4u);
+	back(host.distance, out.distance, slots * 4u);
+	back(host.leaf, out.leaf, slots * 4u);
+	back(host.barycentric, out.barycentric, slots * 12u);
+	back(host.position, out.position, slots * 12u);
+	back(host.normal, out.normal, slots * 12u);
 	OCRT_HIP(hipStreamSynchronize(s));
 }
 

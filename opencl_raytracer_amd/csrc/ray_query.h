@@ -1,5 +1,6 @@
-// ray_query.h -- ray queries and ambient-occlusion queries on a render host's uploaded scene (include/rt_hip_query.h,
-// include/rt_hip_ao.h; kernels/query.hip.h, kernels/ao_query.hip.h).
+// ray_query.h -- ray queries, multi-hit queries and ambient-occlusion queries on a render host's uploaded scene
+// (include/rt_hip_query.h, include/rt_hip_multihit.h, include/rt_hip_ao.h; kernels/query.hip.h, kernels/multihit.hip.h,
+// kernels/ao_query.hip.h).
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -14,6 +15,16 @@ struct QueryOutputs {
 	float *distance = nullptr;
 	uint32_t *leaf = nullptr;
 	float *barycentric = nullptr, *position = nullptr, *normal = nullptr;
+};
+
+// Outputs of a multi-hit query, device pointers; null: not written.  `count` by ray index, the others by ray and slot
+// (slot j of ray i at i * k + j).
+struct MultiHitOutputs {
+	uint32_t *count = nullptr;
+	float *distance = nullptr;
+	uint32_t *leaf = nullptr;
+	float *barycentric = nullptr, *position = nullptr, *normal = nullptr;
+	bool anySlot() const { return distance || leaf || barycentric || position || normal; }
 };
 
 // What one render host needs beyond its renderer to answer queries: scratch of its own (the sort's counts and order,
@@ -32,6 +43,13 @@ class RayQueries {
 		// Host memory, blocking: the rays go through the staging buffers on the renderer's stream.
 		void traceHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
 		               unsigned char *hit, float *distance, uint32_t *leaf, float *barycentric, float *position, float *normal);
+		// Multi-hit queries (include/rt_hip_multihit.h): the count of accepted triangles per ray and the first k of them.
+		// Device memory, enqueued on `stream` (null: the renderer's); k <= RT_MULTIHIT_MAX_K, 0 = the count alone.
+		void multihitDevice(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
+		                    const MultiHitOutputs &out, void *stream);
+		// Host memory, blocking.
+		void multihitHost(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
+		                  const MultiHitOutputs &out);
 		// Ambient-occlusion queries (include/rt_hip_ao.h): the reference's ambient_occlusion() of n points with the options
 		// the scene was uploaded for -- table, mode, rays per point, divisor and reach come from the renderer's launch
 		// constants and its DeviceScene.  std::logic_error where those options have ambient occlusion off.
@@ -44,7 +62,7 @@ class RayQueries {
 		// Host memory, blocking.
 		void aoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
 		            uint32_t *occluded);
-		float lastMs();  // the last query of either kind
+		float lastMs();  // the last query of any kind
 
 	private:
 		void grow(void *&buffer, size_t &capacity, size_t bytes);
@@ -53,7 +71,8 @@ class RayQueries {
 		DeviceRenderer &dev;
 		void *d_count = nullptr, *d_order = nullptr, *d_stage = nullptr;
 		void *d_ao_hits = nullptr;  // aoDevice without an `occluded` array: the points' counts
-		size_t order_bytes = 0, stage_bytes = 0, ao_hits_bytes = 0;
+		void *d_list = nullptr;  // multihitDevice: the rays' key lists, n * k * 8 bytes
+		size_t order_bytes = 0, stage_bytes = 0, ao_hits_bytes = 0, list_bytes = 0;
 		void *ev_start = nullptr, *ev_stop = nullptr;
 		bool timed = false, have_ms = false;
 		float last_ms = 0.0f;
@@ -67,6 +86,9 @@ void launch_query_sort(const void *origins, const void *directions, uint32_t n, 
 void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *origins, const void *directions,
                   const void *order, uint32_t n, float max_distance, unsigned char *hit, float *distance, uint32_t *leaf,
                   float *barycentric, float *position, float *normal, void *stream);
+void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void *origins, const void *directions, const void *order,
+                     uint32_t n, float max_distance, uint32_t k, void *list, uint32_t *count, float *distance, uint32_t *leaf,
+                     float *barycentric, float *position, float *normal, void *stream);
 void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
                      float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
                      uint32_t *count, float *ao, void *stream);

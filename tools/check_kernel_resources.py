@@ -136,7 +136,9 @@ def main():
         if hot and (k.get("VGPRs Spill") != "0" or k.get("ScratchSize [bytes/lane]") != "0"):
             errors.append(f"{name}: VGPR spill {k.get('VGPRs Spill')}, scratch {k.get('ScratchSize [bytes/lane]')} B/lane "
                           "in a hot kernel (walk_collect's fixed registers v56-v62 need the 64-VGPR budget to hold)")
-    queries = ("query_kernel<true>", "query_kernel<false>", "query_key_kernel", "query_scatter_kernel", "query_scan_kernel")
+    queries = ("query_kernel<true>", "query_kernel<false>", "query_key_kernel", "query_scatter_kernel", "query_scan_kernel",
+               "multihit_walk_kernel<0", "multihit_walk_kernel<1u", "multihit_walk_kernel<2", "multihit_walk_kernel<4",
+               "multihit_walk_kernel<8", "multihit_walk_kernel<16", "multihit_resolve_kernel")
     names = [k["name"].replace("ocrt::", "").replace("void ", "") for k in kernels]
     for p in HOT_PRIMARY:
         if not any(n.startswith(p) for n in names):

@@ -6,10 +6,12 @@
       with ao_max_distance (beside: the frame's ao_kernel time)
   (c) 4 M uniformly random rays with origins in the scene box: both queries, sorted and unsorted
   (d) the host-memory entry point end to end (wall clock, copies included) for (c)
+  (m) multi-hit queries (include/rt_hip_multihit.h) on the rays of (a) and (c): count_hits and k = 1, 4, 16 with every
+      output, beside trace_closest on the same rays in the same run (ratio_to_closest: time over the closest hit's)
 Device entry points on pre-loaded buffers; the time of a call is rt_last_query_ms (HIP events around sort + walk); the
 median of --reps calls after --warmup.
 
-    python3 tools/query_bench.py [--reps 20] [--warmup 3] [--random 4194304]
+    python3 tools/query_bench.py [--reps 20] [--warmup 3] [--random 4194304] [--sets abcdm]
 """
 import argparse
 import ctypes as C
@@ -26,7 +28,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import opencl_raytracer_amd as rt  # noqa: E402
 import orc  # noqa: E402
 import query_oracle as qo  # noqa: E402
-from opencl_raytracer_amd.api import RT_QUERY_NO_SORT, _HitArrays  # noqa: E402
+from opencl_raytracer_amd.api import RT_QUERY_NO_SORT, _HitArrays, _MultiHitArrays  # noqa: E402
 from tools.meshes import bunny_path  # noqa: E402
 
 
@@ -68,7 +70,10 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--random", type=int, default=4 << 20)
+    ap.add_argument("--sets", default="abcdm", help="which of the sets (a) (b) (c) (d) (m) to run")
     args = ap.parse_args()
+    if "b" in args.sets and not set("am") & set(args.sets):
+        ap.error("--sets: (b) starts from the camera hits, which (a) or (m) cast")
     lib = rt.load_library()
     dev = torch.device("cuda:0")
     scene = rt.Scene.load_off(bunny_path()).build_bvh(0)
@@ -107,17 +112,54 @@ def main():
     def emit(**kv):
         print(json.dumps(kv), flush=True)
 
+    def multihit_leg(name, o, d, n, out):
+        """(m) on rays already on the device: closest hit, then the count alone and k = 1, 4, 16, sorted."""
+        closest_ms, _ = timed(host, device_call(True, o, d, n, 100000.0, 0, out), args.reps, args.warmup)
+        emit(set="m_" + name, query="closest", rays=n, median_ms=closest_ms, grays_per_s=n / closest_ms / 1e6)
+        count = torch.empty(n, dtype=torch.uint32, device=dev)
+        for k in (0, 1, 4, 16):
+            slots = {"distance": torch.empty((n, k), dtype=torch.float32, device=dev),
+                     "leaf": torch.empty((n, k), dtype=torch.uint32, device=dev),
+                     "barycentric": torch.empty((n, k, 3), dtype=torch.float32, device=dev),
+                     "position": torch.empty((n, k, 3), dtype=torch.float32, device=dev),
+                     "normal": torch.empty((n, k, 3), dtype=torch.float32, device=dev)} if k else {}
+            arrays = _MultiHitArrays(count.data_ptr(), *[slots[f].data_ptr() if k else None for f in qo_fields[1:]])
+
+            def call(k=k, arrays=arrays):
+                rc = lib.rt_trace_multihit_device(host._h, o.data_ptr(), d.data_ptr(), n, 100000.0, k, 0, C.byref(arrays), None)
+                assert rc == 0, rc
+
+            med, best = timed(host, call, args.reps, args.warmup)
+            c = count.cpu().numpy()
+            emit(set="m_" + name, query="count_hits" if k == 0 else f"multihit_k{k}", rays=n, median_ms=med, min_ms=best,
+                 grays_per_s=n / med / 1e6, ratio_to_closest=med / closest_ms, mean_count=float(c.mean()), max_count=int(c.max()),
+                 share_of_rays_with_more_than_k=float((c > k).mean()))
+            del slots
+
     # (a) camera rays
     p = orc.params_from_options(opt)
     o4, d4 = qo.camera_rays(p)
     n = o4.shape[0]
     to, td = torch.from_numpy(o4).to(dev), torch.from_numpy(d4).to(dev)
     out = outputs(n)
-    a0_ms, _ = frame_ms(0)
-    for flags, name in ((0, "sorted"), (RT_QUERY_NO_SORT, "unsorted")):
+    if "a" in args.sets:
+        a0_ms, _ = frame_ms(0)
+    for flags, name in ((0, "sorted"), (RT_QUERY_NO_SORT, "unsorted")) if "a" in args.sets else ():
         med, best = timed(host, device_call(True, to, td, n, 100000.0, flags, out), args.reps, args.warmup)
         emit(set="a_camera_closest", order=name, rays=n, median_ms=med, min_ms=best, grays_per_s=n / med / 1e6,
              frame_a0_ms=a0_ms, ratio_to_frame_a0=med / a0_ms)
+    if "m" in args.sets:
+        multihit_leg("camera", to, td, n, out)
+    if "b" in args.sets:
+        ao_like_rays(out, dev, opt, host, args, device_call, frame_ms, emit)
+    del to, td, out
+    random_rays(scene, dev, host, args, device_call, outputs, emit, multihit_leg)
+    host.close()
+
+
+def ao_like_rays(out, dev, opt, host, args, device_call, frame_ms, emit):
+    import torch
+
     # (b) AO-like rays around the camera hits
     hit = out["hit"].cpu().numpy().astype(bool)
     pos, nrm = out["position"].cpu().numpy()[hit], out["normal"].cpu().numpy()[hit]
@@ -138,6 +180,13 @@ def main():
         emit(set="b_ao_like_occluded", order=name, rays=nb, directions_per_hit=len(table), median_ms=med, min_ms=best,
              grays_per_s=nb / med / 1e6, frame_ao_kernel_ms=ao_ms, ratio_to_ao_kernel=med / ao_ms if ao_ms else None)
     del to, td, ob
+
+
+def random_rays(scene, dev, host, args, device_call, outputs, emit, multihit_leg):
+    import torch
+
+    if not set("cdm") & set(args.sets):
+        return
     # (c) random rays in the scene box
     nr = args.random
     lo, hi = scene.aabbs[0, :3], scene.aabbs[1, :3]
@@ -150,13 +199,15 @@ def main():
     o4[:, :3], d4[:, :3] = o, d
     to, td = torch.from_numpy(o4).to(dev), torch.from_numpy(d4).to(dev)
     out = outputs(nr)
-    for closest in (True, False):
+    for closest in (True, False) if "c" in args.sets else ():
         for flags, name in ((0, "sorted"), (RT_QUERY_NO_SORT, "unsorted")):
             med, best = timed(host, device_call(closest, to, td, nr, 100000.0, flags, out), args.reps, args.warmup)
             emit(set="c_random_" + ("closest" if closest else "occluded"), order=name, rays=nr, median_ms=med, min_ms=best,
                  grays_per_s=nr / med / 1e6)
+    if "m" in args.sets:
+        multihit_leg("random", to, td, nr, out)
     # (d) host memory, end to end
-    for closest in (True, False):
+    for closest in (True, False) if "d" in args.sets else ():
         wall = []
         for i in range(2 + 5):
             t0 = time.perf_counter()
@@ -168,7 +219,6 @@ def main():
                 wall.append((time.perf_counter() - t0) * 1e3)
         emit(set="d_host_memory_" + ("closest" if closest else "occluded"), rays=nr, median_wall_ms=float(np.median(wall)),
              kernels_ms=host.last_query_ms, grays_per_s_end_to_end=nr / float(np.median(wall)) / 1e6)
-    host.close()
 
 
 if __name__ == "__main__":
