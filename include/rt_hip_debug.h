@@ -86,6 +86,11 @@ uint32_t rt_debug_tile_order_slots(rt_host *h);
 uint32_t rt_debug_tiles(rt_host *h);
 int rt_debug_tile_order(rt_host *h, uint32_t *order, uint32_t *constants24, uint32_t *tile_words, float *tile_costs);
 int rt_debug_set_tile_order(rt_host *h, const uint32_t *order, uint32_t slots, const uint32_t *constants24);
+/* Per XCD group, how many tiles at the head of its list the pass claims HALF A TILE at a time (orderByMeasuredCost's
+ * `split`; all 0 without measured costs, with an odd direction count, and with 0x8000 directions or more -- the cursor
+ * that ends a half-tile claim holds 15 bits).  A read-only copy: a test that means to exercise those claims asserts from
+ * it that there were some. */
+int rt_debug_split_tiles(rt_host *h, uint32_t out[8]);
 
 /* Which form a frame with UNIFORM ambient occlusion takes on this host: 0 = the library's rule (two kernels), 1 = the
  * fused frame kernel (primary rays and ambient occlusion in one persistent launch, kernels/frame.hip.h: an experiment

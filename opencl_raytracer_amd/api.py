@@ -214,6 +214,7 @@ _SIGNATURES = {
     "rt_debug_tiles": (C.c_uint32, [C.c_void_p]),
     "rt_debug_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_set_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rt_debug_split_tiles": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_debug_set_frame_form": (C.c_int, [C.c_void_p, C.c_int]),
     "rt_debug_frame_is_fused": (C.c_int, [C.c_void_p]),
     "rt_debug_poison_hit_list": (C.c_int, [C.c_void_p]),
@@ -604,6 +605,13 @@ class Host:
         order = np.ascontiguousarray(order, np.uint32)
         constants = np.ascontiguousarray(constants, np.uint32).reshape(24)
         _check(load_library().rt_debug_set_tile_order(self._h, order.ctypes.data, len(order), constants.ctypes.data))
+
+    def split_tiles(self) -> np.ndarray:
+        """Per XCD group, the tiles at the head of its list that the AO pass claims half a tile at a time
+        (include/rt_hip_debug.h, rt_debug_split_tiles)."""
+        out = np.zeros(8, np.uint32)
+        _check(load_library().rt_debug_split_tiles(self._h, out.ctypes.data))
+        return out
 
     def walk_entries(self) -> dict:
         """The intervals of the node array the tiles' any-hit packets walk (include/rt_hip_debug.h, rt_walk_entries)."""

@@ -608,6 +608,15 @@ int rt_debug_set_tile_order(rt_host *h, const uint32_t *order, uint32_t slots, c
 	});
 }
 
+int rt_debug_split_tiles(rt_host *h, uint32_t out[8]) {
+	if (!h || !out)
+		return fail(RT_E_INVALID, "null argument");
+	return guarded([&] {
+		const auto &splits = h->dev->splitTiles();
+		std::copy(splits.begin(), splits.end(), out);
+	});
+}
+
 int rt_debug_set_frame_form(rt_host *h, int form) {
 	if (!h)
 		return fail(RT_E_INVALID, "null argument");

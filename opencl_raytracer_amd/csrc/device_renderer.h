@@ -202,6 +202,8 @@ class DeviceRenderer {
 		// any order of the same tiles renders the same image)
 		void tileOrder(std::vector<uint32_t> &order, std::vector<uint32_t> &constants, std::vector<uint32_t> &words, std::vector<float> &cost) const;
 		void setTileOrder(const std::vector<uint32_t> &order, const std::vector<uint32_t> &constants);
+		// (... per group: how many tiles at the head of its list the pass claims half a tile at a time)
+		const std::array<uint32_t, XCD_GROUPS> &splitTiles() const { return split_tiles; }
 		bool calibrateAoPrefetch(float *ms_without = nullptr, float *ms_with = nullptr);
 		// (A scene far beyond the caches is another matter: its pass waits for memory, and what it needs is loads in
 		// flight -- every host keeps the full grid: 2 M-triangle field, three hosts, 11.93 ms per frame with 4.5 per CU,

@@ -109,7 +109,8 @@ __global__ void ocml_ao_table_kernel(float4 *table, uint32_t *count, uint32_t ri
 	for (uint32_t ring = 0; ring < rings; ++ring) {
 		const float step = amax / rings;
 		const float angle = (step * ring) + amin;
-		const uint32_t ray_count = (uint32_t) ((2.0f * M_PI * ocl_cos(angle)) / step);
+		const double rays_in_ring = (2.0f * M_PI * ocl_cos(angle)) / step;
+		const uint32_t ray_count = rays_in_ring > 0.0 ? (uint32_t) rays_in_ring : 0u;  // (negative beyond 90 degrees: uniform_ao_table)
 		const float theta = (float) (M_PI_2 - angle);
 		for (uint32_t k = 0; k <= ray_count; ++k) {
 			const float phi = (float) ((2.0f * M_PI * k) / ray_count);

@@ -619,7 +619,12 @@ std::vector<float> uniform_ao_table(unsigned int rings, int alpha_min, int alpha
 	for (unsigned int ring = 0; ring < rings; ++ring) {
 		const float step = amax / rings;
 		const float elevation = (step * ring) + amin;
-		const unsigned int ray_count = (unsigned int) ((2.0f * M_PI * std::cos(elevation)) / step);
+		// A ring beyond 90 degrees of elevation (23 or more rings with the default angles) has a NEGATIVE count: the
+		// reference converts it to unsigned all the same (src/intersect_kernel.cl:241), which no language defines.  Here it
+		// is 0, what the GPU's own conversion gives: the ring casts one ray, whose azimuth 0 / 0 is NaN and which hits nothing.
+		// (The host's conversion wrapped to 2^32 - n: a table of 64 GiB.)
+		const double rays_in_ring = (2.0f * M_PI * std::cos(elevation)) / step;
+		const unsigned int ray_count = rays_in_ring > 0.0 ? (unsigned int) rays_in_ring : 0u;
 		const float theta = (float) (M_PI_2 - elevation);
 		for (unsigned int k = 0; k <= ray_count; ++k) {
 			// The reference hands an angle that already contains 2*pi to

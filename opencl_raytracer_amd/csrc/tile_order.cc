@@ -131,7 +131,10 @@ std::vector<uint32_t> DeviceRenderer::orderByMeasuredCost(const std::vector<floa
 		(cost[i] > heavy_from ? heavy : rest).push_back(i);
 	std::stable_sort(heavy.begin(), heavy.end(), falling);
 	const uint32_t workgroups = aoWorkgroups() / XCD_GROUPS ? aoWorkgroups() / XCD_GROUPS : 1u;
-	if (split && order_policy.split_above > 0.0f && kp.shared_walk && (kp.ao_dirs & 1u) == 0u && kp.ao_dirs >= 2u) {
+	// (half-tile claims end where the LDS cursor says, and the pass takes the cursor form below 0x8000 directions only --
+	// its word holds end << 16 | next --: from there on fixed shares would run up to three units past a half, into the
+	// next claim's, and those rays would be cast and counted twice.  No tile is split then.)
+	if (split && order_policy.split_above > 0.0f && kp.shared_walk && (kp.ao_dirs & 1u) == 0u && kp.ao_dirs >= 2u && kp.ao_dirs < 0x8000u) {
 		double total = 0.0;
 		for (float c : cost)
 			total += c;

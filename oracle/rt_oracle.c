@@ -200,7 +200,11 @@ uint32_t orc_ao_table(const orc_params *p, float *xyz, uint32_t cap) {
 	for (uint32_t c = 0; c < circle_count; ++c) {
 		const float step = alpha_max / circle_count;
 		const float angle = (step * c) + alpha_min;
-		const uint32_t ray_count = (uint32_t) ((2.0f * M_PI * cosf(angle)) / step);
+		/* a ring beyond 90 degrees has a negative count, whose conversion to unsigned no language defines: 0 here, as
+		 * the GPU's conversion gives (one ray with a NaN azimuth); the host's wrapped to 2^32 - n and the loop below ran
+		 * four thousand million times per such ring */
+		const double rays_in_ring = (2.0f * M_PI * cosf(angle)) / step;
+		const uint32_t ray_count = rays_in_ring > 0.0 ? (uint32_t) rays_in_ring : 0u;
 		const float theta = (float) (M_PI_2 - angle);
 		for (uint32_t k = 0; k <= ray_count; ++k) {
 			const float phi = (float) ((2.0f * M_PI * k) / ray_count);
