@@ -259,15 +259,14 @@ class _MultiHitArrays(C.Structure):
 RT_QUERY_NO_SORT = 1
 RT_MULTIHIT_MAX_K = 16
 MULTIHIT_OUTPUTS = ("count", "distance", "leaf", "barycentric", "position", "normal")
-# per output: numpy dtype, values per slot (count: per ray)
-_MULTIHIT_LAYOUT = {"count": (np.uint32, 1), "distance": (np.float32, 1), "leaf": (np.uint32, 1), "barycentric": (np.float32, 3),
-                    "position": (np.float32, 3), "normal": (np.float32, 3)}
 QUERY_OUTPUTS = ("hit", "distance", "leaf", "barycentric", "position", "normal")
-# per output: numpy dtype, values per ray
-_QUERY_LAYOUT = {"hit": (np.uint8, 1), "distance": (np.float32, 1), "leaf": (np.uint32, 1), "barycentric": (np.float32, 3),
-                 "position": (np.float32, 3), "normal": (np.float32, 3)}
 AO_OUTPUTS = ("ao", "occluded")
-_AO_LAYOUT = {"ao": np.float32, "occluded": np.uint32}
+# per output of any query: numpy dtype, values per record.  The first four are one value per ray or point; the others are
+# the fields of a hit record: one record per ray (closest hit) or k of them (multi-hit).
+_OUTPUT_LAYOUT = {"hit": (np.uint8, 1), "count": (np.uint32, 1), "ao": (np.float32, 1), "occluded": (np.uint32, 1),
+                  "distance": (np.float32, 1), "leaf": (np.uint32, 1), "barycentric": (np.float32, 3), "position": (np.float32, 3),
+                  "normal": (np.float32, 3)}
+_RECORD_FIELDS = ("distance", "leaf", "barycentric", "position", "normal")
 
 
 def _is_torch(x) -> bool:
@@ -296,6 +295,79 @@ def _rays4_torch(t, what: str):
     if t.shape[1] == 4:
         return t
     return torch.nn.functional.pad(t, (0, 1))  # (N, 4), on the device, stream-ordered
+
+
+class _QueryArrays:
+    """The arrays of one query call: the two (N, 3) / (N, 4) inputs padded to (N, 4), the outputs made from
+    _OUTPUT_LAYOUT, their addresses, and the call itself.  numpy arrays in host memory go to the library's blocking entry
+    points; torch tensors on the host's GPU go to its *_device entry points, enqueued on torch.cuda.current_stream()
+    without waiting.  The inputs a, b (and `also`, if given) must be of one kind."""
+
+    def __init__(self, a, b, names, items: str, also=None):
+        given = [a, b] + ([] if also is None else [also])
+        self.torch = any(_is_torch(x) for x in given)
+        if self.torch and not all(_is_torch(x) for x in given):
+            both = "all" if len(names) > 2 else "both"
+            raise ValueError(f"{', '.join(names[:-1])} and {names[-1]} must {both} be torch tensors or {both} numpy arrays")
+        pad = _rays4_torch if self.torch else _rays4_numpy
+        self.a, self.b = pad(a, names[0]), pad(b, names[1])
+        if self.a.shape[0] != self.b.shape[0] or (self.torch and self.a.device != self.b.device):
+            raise ValueError(f"{names[0]} and {names[1]} must hold the same number of {items}"
+                             + (" on the same device" if self.torch else ""))
+        self.n = int(self.a.shape[0])
+        self.suffix, self.stream, self.padded = "", (), []
+        if self.torch:
+            import torch
+
+            self.current = torch.cuda.current_stream(self.a.device)
+            self.suffix, self.stream = "_device", (self.current.cuda_stream,)
+            self.padded = [t for t, was in ((self.a, a), (self.b, b)) if t is not was]
+
+    def ptr(self, x) -> int:
+        return x.data_ptr() if self.torch else x.ctypes.data
+
+    def seeds(self, seeds):
+        """The uint32 (N,) seeds of an ambient-occlusion call, checked."""
+        if self.torch:
+            import torch
+
+            if seeds.dtype not in (torch.uint32, torch.int32) or seeds.dim() != 1 or seeds.shape[0] != self.n:
+                raise ValueError("seeds: expected a uint32 tensor of shape (N,)")
+            if not seeds.is_contiguous() or seeds.device != self.a.device:
+                raise ValueError("seeds: the tensor must be contiguous and on the points' device")
+            return seeds
+        if not isinstance(seeds, np.ndarray) or seeds.dtype != np.uint32 or seeds.shape != (self.n,):
+            raise ValueError("seeds: expected a uint32 array of shape (N,)")
+        return np.ascontiguousarray(seeds)
+
+    def outputs(self, names, k=None) -> dict:
+        """{name: (N,) or (N, 3)}; with k the fields of a hit record are (N, k) or (N, k, 3)."""
+        out = {}
+        for name in names:
+            dtype, per = _OUTPUT_LAYOUT[name]
+            slots = (k,) if k is not None and name in _RECORD_FIELDS else ()
+            shape = (self.n,) + slots + ((per,) if per > 1 else ())
+            if self.torch:
+                import torch
+
+                out[name] = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=self.a.device)
+            else:
+                out[name] = np.empty(shape, dtype=dtype)
+        return out
+
+    def pointers(self, out: dict, names, name_empty: bool = False) -> list:
+        """The addresses of the outputs in the order of `names`; None: not asked for, or the call has nothing to work on
+        (N = 0).  name_empty: an array is named even where it holds nothing -- N = 0, or a slot array with k = 0 --, so
+        that the library says what is wrong with the call, as it would for a caller in C."""
+        if name_empty:
+            return [self.ptr(out[name]) or 4 if name in out else None for name in names]
+        return [self.ptr(out[name]) if name in out and self.n else None for name in names]
+
+    def call(self, h, function: str, *args) -> None:
+        """function(h, the two inputs, *args) -- or function_device(..., the current stream)."""
+        _check(getattr(load_library(), function + self.suffix)(h, self.ptr(self.a), self.ptr(self.b), *args, *self.stream))
+        for t in self.padded:  # (the padded copies must live until the kernels have read them)
+            t.record_stream(self.current)
 
 
 def load_library() -> C.CDLL:
@@ -662,50 +734,13 @@ class Host:
         unknown = [o for o in outputs if o not in QUERY_OUTPUTS]
         if unknown:
             raise ValueError(f"unknown outputs {unknown}; choose from {QUERY_OUTPUTS}")
-        flags = 0 if sort else RT_QUERY_NO_SORT
-        lib = load_library()
-        if _is_torch(origins) or _is_torch(directions):
-            if not (_is_torch(origins) and _is_torch(directions)):
-                raise ValueError("origins and directions must both be torch tensors or both numpy arrays")
-            import torch
-
-            o4, d4 = _rays4_torch(origins, "origins"), _rays4_torch(directions, "directions")
-            if o4.shape[0] != d4.shape[0] or o4.device != d4.device:
-                raise ValueError("origins and directions must hold the same number of rays on the same device")
-            n = int(o4.shape[0])
-            tdtype = {np.uint8: torch.uint8, np.float32: torch.float32, np.uint32: torch.uint32}
-            out = {}
-            for name in outputs:
-                dt, per = _QUERY_LAYOUT[name]
-                out[name] = torch.empty((n, per) if per > 1 else (n,), dtype=tdtype[dt], device=o4.device)
-            stream = torch.cuda.current_stream(o4.device).cuda_stream
-            if closest:
-                arrays = _HitArrays(*[out[name].data_ptr() if name in out and n else None for name in QUERY_OUTPUTS])
-                _check(lib.rt_trace_closest_device(self._h, o4.data_ptr(), d4.data_ptr(), n, float(max_distance), flags,
-                                                   C.byref(arrays), stream))
-            else:
-                _check(lib.rt_trace_occluded_device(self._h, o4.data_ptr(), d4.data_ptr(), n, float(max_distance), flags,
-                                                    out["hit"].data_ptr() if n else None, stream))
-            # (the padded copies must live until the kernels have read them)
-            if o4 is not origins:
-                o4.record_stream(torch.cuda.current_stream(o4.device))
-            if d4 is not directions:
-                d4.record_stream(torch.cuda.current_stream(d4.device))
-            return out
-        o4, d4 = _rays4_numpy(origins, "origins"), _rays4_numpy(directions, "directions")
-        if o4.shape[0] != d4.shape[0]:
-            raise ValueError("origins and directions must hold the same number of rays")
-        n = int(o4.shape[0])
-        out = {}
-        for name in outputs:
-            dt, per = _QUERY_LAYOUT[name]
-            out[name] = np.empty((n, per) if per > 1 else (n,), dtype=dt)
+        io = _QueryArrays(origins, directions, ("origins", "directions"), "rays")
+        out = io.outputs(outputs)
+        args = (io.n, float(max_distance), 0 if sort else RT_QUERY_NO_SORT)
         if closest:
-            arrays = _HitArrays(*[out[name].ctypes.data if name in out and n else None for name in QUERY_OUTPUTS])
-            _check(lib.rt_trace_closest(self._h, o4.ctypes.data, d4.ctypes.data, n, float(max_distance), flags, C.byref(arrays)))
+            io.call(self._h, "rt_trace_closest", *args, C.byref(_HitArrays(*io.pointers(out, QUERY_OUTPUTS))))
         else:
-            _check(lib.rt_trace_occluded(self._h, o4.ctypes.data, d4.ctypes.data, n, float(max_distance), flags,
-                                         out["hit"].ctypes.data if n else None))
+            io.call(self._h, "rt_trace_occluded", *args, *io.pointers(out, ("hit",)))
         return out
 
     # ---- multi-hit queries (include/rt_hip_multihit.h) ----
@@ -724,43 +759,10 @@ class Host:
         k = int(k)
         if k < 0:
             raise ValueError("k must not be negative")
-        flags = 0 if sort else RT_QUERY_NO_SORT
-        lib = load_library()
-
-        def shape(name, n):
-            per = _MULTIHIT_LAYOUT[name][1]
-            return (n,) if name == "count" else ((n, k, per) if per > 1 else (n, k))
-
-        if _is_torch(origins) or _is_torch(directions):
-            if not (_is_torch(origins) and _is_torch(directions)):
-                raise ValueError("origins and directions must both be torch tensors or both numpy arrays")
-            import torch
-
-            o4, d4 = _rays4_torch(origins, "origins"), _rays4_torch(directions, "directions")
-            if o4.shape[0] != d4.shape[0] or o4.device != d4.device:
-                raise ValueError("origins and directions must hold the same number of rays on the same device")
-            n = int(o4.shape[0])
-            tdtype = {np.float32: torch.float32, np.uint32: torch.uint32}
-            out = {name: torch.empty(shape(name, n), dtype=tdtype[_MULTIHIT_LAYOUT[name][0]], device=o4.device) for name in outputs}
-            stream = torch.cuda.current_stream(o4.device).cuda_stream
-            # (an array is named even where it holds nothing -- n = 0, or a slot array with k = 0: the library then says
-            # what is wrong with the call, as it would for a caller in C)
-            arrays = _MultiHitArrays(*[out[name].data_ptr() or 4 if name in out else None for name in MULTIHIT_OUTPUTS])
-            _check(lib.rt_trace_multihit_device(self._h, o4.data_ptr(), d4.data_ptr(), n, float(max_distance), k, flags,
-                                                C.byref(arrays), stream))
-            # (the padded copies must live until the kernels have read them)
-            if o4 is not origins:
-                o4.record_stream(torch.cuda.current_stream(o4.device))
-            if d4 is not directions:
-                d4.record_stream(torch.cuda.current_stream(d4.device))
-            return out
-        o4, d4 = _rays4_numpy(origins, "origins"), _rays4_numpy(directions, "directions")
-        if o4.shape[0] != d4.shape[0]:
-            raise ValueError("origins and directions must hold the same number of rays")
-        n = int(o4.shape[0])
-        out = {name: np.empty(shape(name, n), dtype=_MULTIHIT_LAYOUT[name][0]) for name in outputs}
-        arrays = _MultiHitArrays(*[out[name].ctypes.data or 4 if name in out else None for name in MULTIHIT_OUTPUTS])
-        _check(lib.rt_trace_multihit(self._h, o4.ctypes.data, d4.ctypes.data, n, float(max_distance), k, flags, C.byref(arrays)))
+        io = _QueryArrays(origins, directions, ("origins", "directions"), "rays")
+        out = io.outputs(outputs, k)
+        arrays = _MultiHitArrays(*io.pointers(out, MULTIHIT_OUTPUTS, name_empty=True))
+        io.call(self._h, "rt_trace_multihit", io.n, float(max_distance), k, 0 if sort else RT_QUERY_NO_SORT, C.byref(arrays))
         return out
 
     def count_hits(self, origins, directions, max_distance: float = 100000.0, sort: bool = True):
@@ -793,46 +795,12 @@ class Host:
         unknown = [o for o in outputs if o not in AO_OUTPUTS]
         if unknown:
             raise ValueError(f"unknown outputs {unknown}; choose from {AO_OUTPUTS}")
-        flags = 0 if sort else RT_QUERY_NO_SORT
-        lib = load_library()
-        if _is_torch(points) or _is_torch(normals) or _is_torch(seeds):
-            if not (_is_torch(points) and _is_torch(normals) and (seeds is None or _is_torch(seeds))):
-                raise ValueError("points, normals and seeds must all be torch tensors or all numpy arrays")
-            import torch
-
-            p4, n4 = _rays4_torch(points, "points"), _rays4_torch(normals, "normals")
-            if p4.shape[0] != n4.shape[0] or p4.device != n4.device:
-                raise ValueError("points and normals must hold the same number of points on the same device")
-            n = int(p4.shape[0])
-            if seeds is not None:
-                if seeds.dtype not in (torch.uint32, torch.int32) or seeds.dim() != 1 or seeds.shape[0] != n:
-                    raise ValueError("seeds: expected a uint32 tensor of shape (N,)")
-                if not seeds.is_contiguous() or seeds.device != p4.device:
-                    raise ValueError("seeds: the tensor must be contiguous and on the points' device")
-            tdtype = {np.float32: torch.float32, np.uint32: torch.uint32}
-            out = {name: torch.empty((n,), dtype=tdtype[_AO_LAYOUT[name]], device=p4.device) for name in outputs}
-            stream = torch.cuda.current_stream(p4.device).cuda_stream
-            _check(lib.rt_trace_ao_device(self._h, p4.data_ptr(), n4.data_ptr(), seeds.data_ptr() if seeds is not None and n else None,
-                                          n, flags, out["ao"].data_ptr() if "ao" in out and n else None,
-                                          out["occluded"].data_ptr() if "occluded" in out and n else None, stream))
-            # (the padded copies must live until the kernels have read them)
-            if p4 is not points:
-                p4.record_stream(torch.cuda.current_stream(p4.device))
-            if n4 is not normals:
-                n4.record_stream(torch.cuda.current_stream(n4.device))
-            return out
-        p4, n4 = _rays4_numpy(points, "points"), _rays4_numpy(normals, "normals")
-        if p4.shape[0] != n4.shape[0]:
-            raise ValueError("points and normals must hold the same number of points")
-        n = int(p4.shape[0])
+        io = _QueryArrays(points, normals, ("points", "normals", "seeds"), "points", also=seeds)
         if seeds is not None:
-            if not isinstance(seeds, np.ndarray) or seeds.dtype != np.uint32 or seeds.shape != (n,):
-                raise ValueError("seeds: expected a uint32 array of shape (N,)")
-            seeds = np.ascontiguousarray(seeds)
-        out = {name: np.empty((n,), dtype=_AO_LAYOUT[name]) for name in outputs}
-        _check(lib.rt_trace_ao(self._h, p4.ctypes.data, n4.ctypes.data, seeds.ctypes.data if seeds is not None and n else None, n,
-                               flags, out["ao"].ctypes.data if "ao" in out and n else None,
-                               out["occluded"].ctypes.data if "occluded" in out and n else None))
+            seeds = io.seeds(seeds)
+        out = io.outputs(outputs)
+        io.call(self._h, "rt_trace_ao", io.ptr(seeds) if seeds is not None and io.n else None, io.n,
+                0 if sort else RT_QUERY_NO_SORT, *io.pointers(out, AO_OUTPUTS))
         return out
 
     def vertex_ao(self, scene: "Scene") -> np.ndarray:

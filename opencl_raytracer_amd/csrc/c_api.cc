@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <new>
 #include <string>
@@ -55,19 +56,34 @@ int fail(int code, const std::string &message) {
 	return code;
 }
 
-// What every query entry point checks before it touches the device (include/rt_hip_query.h, "Errors").
-int query_precheck(rt_host *h, const float *origins4, const float *directions4, uint32_t n, bool device) {
+// What every query entry point checks first; `family` names the queries in the messages ("ray", "ambient-occlusion").
+int host_precheck(const rt_host *h, const char *family) {
 	if (!h)
 		return fail(RT_E_INVALID, "null host");
 	if (!h->owned)
-		return fail(RT_E_STATE, "ray queries are not available on the hosts of a frame ring");
+		return fail(RT_E_STATE, std::string(family) + " queries are not available on the hosts of a frame ring");
 	if (!h->dev->sceneReady())
-		return fail(RT_E_STATE, "ray query before a scene was uploaded");
+		return fail(RT_E_STATE, std::string(family) + " query before a scene was uploaded");
+	return RT_OK;
+}
+
+bool aligned(std::initializer_list<const void *> pointers, uintptr_t bytes) {
+	uintptr_t all = 0;
+	for (const void *p : pointers)
+		all |= (uintptr_t) p;
+	return (all & (bytes - 1u)) == 0;
+}
+
+// ... and what every ray query checks before it touches the device (include/rt_hip_query.h, "Errors").
+int query_precheck(rt_host *h, const float *origins4, const float *directions4, uint32_t n, bool device) {
+	const int rc = host_precheck(h, "ray");
+	if (rc != RT_OK)
+		return rc;
 	if (n > RT_QUERY_MAX_RAYS)
 		return fail(RT_E_INVALID, "more rays than RT_QUERY_MAX_RAYS in one call");
 	if (n > 0 && (!origins4 || !directions4))
 		return fail(RT_E_INVALID, "null ray arrays");
-	if (device && n > 0 && (((uintptr_t) origins4 | (uintptr_t) directions4) & 15u))
+	if (device && n > 0 && !aligned({ origins4, directions4 }, 16))
 		return fail(RT_E_INVALID, "device ray arrays must be 16-byte aligned");
 	return RT_OK;
 }
@@ -80,12 +96,9 @@ ocrt::RayQueries &queries_of(rt_host *h) {
 
 // ... and every ambient-occlusion query (include/rt_hip_ao.h, "Errors"); `rays`: the rays per point, for the caller.
 int ao_precheck(const rt_host *h, const float *points4, const float *normals4, uint32_t n, bool device, uint32_t *rays) {
-	if (!h)
-		return fail(RT_E_INVALID, "null host");
-	if (!h->owned)
-		return fail(RT_E_STATE, "ambient-occlusion queries are not available on the hosts of a frame ring");
-	if (!h->dev->sceneReady())
-		return fail(RT_E_STATE, "ambient-occlusion query before a scene was uploaded");
+	const int rc = host_precheck(h, "ambient-occlusion");
+	if (rc != RT_OK)
+		return rc;
 	const uint32_t per_point = ocrt::RayQueries::aoRaysPerPoint(*h->dev);
 	if (per_point == 0)
 		return fail(RT_E_STATE, "ambient-occlusion query on a host whose options have ambient occlusion off");
@@ -93,12 +106,36 @@ int ao_precheck(const rt_host *h, const float *points4, const float *normals4, u
 		return fail(RT_E_INVALID, "more points than RT_QUERY_MAX_RAYS / rays per point in one call");
 	if (n > 0 && (!points4 || !normals4))
 		return fail(RT_E_INVALID, "null point or normal arrays");
-	if (device && n > 0 && (((uintptr_t) points4 | (uintptr_t) normals4) & 15u))
+	if (device && n > 0 && !aligned({ points4, normals4 }, 16))
 		return fail(RT_E_INVALID, "device point and normal arrays must be 16-byte aligned");
 	if (rays)
 		*rays = per_point;
 	return RT_OK;
 }
+
+// rt_hit_arrays / rt_multihit_arrays as the query code takes them; null: no output at all.
+template <class Arrays> void record_outputs(const Arrays *from, ocrt::RecordOutputs &to) {
+	if (!from)
+		return;
+	to.distance = from->distance;
+	to.leaf = from->leaf;
+	to.barycentric = from->barycentric;
+	to.position = from->position;
+	to.normal = from->normal;
+}
+ocrt::QueryOutputs hit_outputs(const rt_hit_arrays *from) {
+	ocrt::QueryOutputs q;
+	q.hit = from ? from->hit : nullptr;
+	record_outputs(from, q);
+	return q;
+}
+ocrt::MultiHitOutputs multihit_outputs(const rt_multihit_arrays *from) {
+	ocrt::MultiHitOutputs q;
+	q.count = from ? from->count : nullptr;
+	record_outputs(from, q);
+	return q;
+}
+bool records_aligned(const ocrt::RecordOutputs &q) { return aligned({ q.distance, q.leaf, q.barycentric, q.position, q.normal }, 4); }
 
 // Maps the exception in flight to an RT_E_* code.
 int fail_from_exception() {
@@ -152,6 +189,27 @@ template <class F> int guarded(F &&body) {
 	} catch (...) {
 		return fail_from_exception();
 	}
+}
+
+// rt_upload / rt_ring_upload: the caller's arrays (four floats per box corner, vertex and normal), validated and packed,
+// into `target` (a renderer or a ring).
+template <class Target>
+int upload_arrays(Target *target, const uint32_t *faces, uint32_t num_faces, const uint32_t *nodes, uint32_t num_nodes, const float *aabbs,
+                  const float *vertices, uint32_t num_vertices, const float *vnormals) {
+	if (!target || !faces || !nodes || !aabbs || !vertices || !vnormals)
+		return fail(RT_E_INVALID, "null argument");
+	return guarded([&] {
+		auto as_vec3 = [](const float *p, size_t n) {
+			std::vector<Vec3f> v(n);
+			for (size_t i = 0; i < n; ++i)
+				v[i] = Vec3f(p[4 * i], p[4 * i + 1], p[4 * i + 2]);
+			return v;
+		};
+		const std::vector<uint32_t> f(faces, faces + 3 * (size_t) num_faces);
+		const std::vector<uint32_t> n(nodes, nodes + num_nodes);
+		target->upload(ocrt::pack_scene(f, n, as_vec3(aabbs, 2 * (size_t) num_nodes), as_vec3(vertices, num_vertices),
+		                                as_vec3(vnormals, num_vertices)));
+	});
 }
 
 }  // namespace
@@ -272,20 +330,7 @@ void rt_destroy(rt_host *h) {
 
 int rt_upload(rt_host *h, const uint32_t *faces, uint32_t num_faces, const uint32_t *nodes, uint32_t num_nodes,
               const float *aabbs, const float *vertices, uint32_t num_vertices, const float *vnormals) {
-	if (!h || !faces || !nodes || !aabbs || !vertices || !vnormals)
-		return fail(RT_E_INVALID, "null argument");
-	return guarded([&] {
-		auto as_vec3 = [](const float *p, size_t n) {
-			std::vector<Vec3f> v(n);
-			for (size_t i = 0; i < n; ++i)
-				v[i] = Vec3f(p[4 * i], p[4 * i + 1], p[4 * i + 2]);
-			return v;
-		};
-		const std::vector<uint32_t> f(faces, faces + 3 * (size_t) num_faces);
-		const std::vector<uint32_t> n(nodes, nodes + num_nodes);
-		h->dev->upload(ocrt::pack_scene(f, n, as_vec3(aabbs, 2 * (size_t) num_nodes), as_vec3(vertices, num_vertices),
-		                                as_vec3(vnormals, num_vertices)));
-	});
+	return upload_arrays(h ? h->dev : nullptr, faces, num_faces, nodes, num_nodes, aabbs, vertices, num_vertices, vnormals);
 }
 
 int rt_upload_scene(rt_host *h, const rt_scene *s) {
@@ -448,20 +493,7 @@ void rt_ring_destroy(rt_ring *r) { delete r; }
 
 int rt_ring_upload(rt_ring *r, const uint32_t *faces, uint32_t num_faces, const uint32_t *nodes, uint32_t num_nodes,
                    const float *aabbs, const float *vertices, uint32_t num_vertices, const float *vnormals) {
-	if (!r || !faces || !nodes || !aabbs || !vertices || !vnormals)
-		return fail(RT_E_INVALID, "null argument");
-	return guarded([&] {
-		auto as_vec3 = [](const float *p, size_t n) {
-			std::vector<Vec3f> v(n);
-			for (size_t i = 0; i < n; ++i)
-				v[i] = Vec3f(p[4 * i], p[4 * i + 1], p[4 * i + 2]);
-			return v;
-		};
-		const std::vector<uint32_t> f(faces, faces + 3 * (size_t) num_faces);
-		const std::vector<uint32_t> n(nodes, nodes + num_nodes);
-		r->ring->upload(ocrt::pack_scene(f, n, as_vec3(aabbs, 2 * (size_t) num_nodes), as_vec3(vertices, num_vertices),
-		                                 as_vec3(vnormals, num_vertices)));
-	});
+	return upload_arrays(r ? r->ring.get() : nullptr, faces, num_faces, nodes, num_nodes, aabbs, vertices, num_vertices, vnormals);
 }
 
 int rt_ring_upload_scene(rt_ring *r, const rt_scene *s) {
@@ -845,12 +877,7 @@ int rt_trace_closest(rt_host *h, const float *origins4, const float *directions4
 	const int rc = query_precheck(h, origins4, directions4, n, false);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	const rt_hit_arrays none{};
-	const rt_hit_arrays &o = out ? *out : none;
-	return guarded([&] {
-		queries_of(h).traceHost(true, origins4, directions4, n, max_distance, flags, o.hit, o.distance, o.leaf, o.barycentric,
-		                        o.position, o.normal);
-	});
+	return guarded([&] { queries_of(h).traceHost(true, origins4, directions4, n, max_distance, flags, hit_outputs(out)); });
 }
 
 int rt_trace_occluded(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
@@ -858,10 +885,9 @@ int rt_trace_occluded(rt_host *h, const float *origins4, const float *directions
 	const int rc = query_precheck(h, origins4, directions4, n, false);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	return guarded([&] {
-		queries_of(h).traceHost(false, origins4, directions4, n, max_distance, flags, occluded, nullptr, nullptr, nullptr, nullptr,
-		                        nullptr);
-	});
+	ocrt::QueryOutputs q;
+	q.hit = occluded;
+	return guarded([&] { queries_of(h).traceHost(false, origins4, directions4, n, max_distance, flags, q); });
 }
 
 int rt_trace_closest_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
@@ -869,18 +895,9 @@ int rt_trace_closest_device(rt_host *h, const float *origins4, const float *dire
 	const int rc = query_precheck(h, origins4, directions4, n, true);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	ocrt::QueryOutputs q;
-	if (out) {
-		if ((((uintptr_t) out->distance | (uintptr_t) out->leaf | (uintptr_t) out->barycentric | (uintptr_t) out->position |
-		      (uintptr_t) out->normal) & 3u) != 0)
-			return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
-		q.hit = out->hit;
-		q.distance = out->distance;
-		q.leaf = out->leaf;
-		q.barycentric = out->barycentric;
-		q.position = out->position;
-		q.normal = out->normal;
-	}
+	const ocrt::QueryOutputs q = hit_outputs(out);
+	if (!records_aligned(q))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
 	return guarded([&] { queries_of(h).traceDevice(true, origins4, directions4, n, max_distance, flags, q, hip_stream); });
 }
 
@@ -897,55 +914,40 @@ int rt_trace_occluded_device(rt_host *h, const float *origins4, const float *dir
 // ---- rt_hip_multihit.h ----
 namespace {
 
-// The checks of include/rt_hip_multihit.h ("Errors") beyond query_precheck's; `out` null: no output at all.
-int multihit_precheck(rt_host *h, const float *origins4, const float *directions4, uint32_t n, uint32_t k, const rt_multihit_arrays *out,
+// The checks of include/rt_hip_multihit.h ("Errors") beyond query_precheck's; `q`: the outputs asked for.
+int multihit_precheck(rt_host *h, const float *origins4, const float *directions4, uint32_t n, uint32_t k, const ocrt::MultiHitOutputs &q,
                       bool device) {
 	const int rc = query_precheck(h, origins4, directions4, n, device);
 	if (rc != RT_OK)
 		return rc;
 	if (k > RT_MULTIHIT_MAX_K)
 		return fail(RT_E_INVALID, "more slots per ray than RT_MULTIHIT_MAX_K");
-	if (k == 0 && out && (out->distance || out->leaf || out->barycentric || out->position || out->normal))
+	if (k == 0 && q.anySlot())
 		return fail(RT_E_INVALID, "k == 0 asks for the count alone: the slot arrays must be null");
 	if ((uint64_t) n * (k ? k : 1u) > RT_QUERY_MAX_RAYS)
 		return fail(RT_E_INVALID, "more than RT_QUERY_MAX_RAYS slots (n * k) in one call");
-	if (device && out &&
-	    (((uintptr_t) out->count | (uintptr_t) out->distance | (uintptr_t) out->leaf | (uintptr_t) out->barycentric |
-	      (uintptr_t) out->position | (uintptr_t) out->normal) & 3u) != 0)
+	if (device && !(aligned({ q.count }, 4) && records_aligned(q)))
 		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
 	return RT_OK;
-}
-
-void multihit_outputs(const rt_multihit_arrays *out, ocrt::MultiHitOutputs &q) {
-	if (out) {
-		q.count = out->count;
-		q.distance = out->distance;
-		q.leaf = out->leaf;
-		q.barycentric = out->barycentric;
-		q.position = out->position;
-		q.normal = out->normal;
-	}
 }
 
 }  // namespace
 
 int rt_trace_multihit(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
                       uint32_t flags, const rt_multihit_arrays *out) {
-	const int rc = multihit_precheck(h, origins4, directions4, n, k, out, false);
+	const ocrt::MultiHitOutputs q = multihit_outputs(out);
+	const int rc = multihit_precheck(h, origins4, directions4, n, k, q, false);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	ocrt::MultiHitOutputs q;
-	multihit_outputs(out, q);
 	return guarded([&] { queries_of(h).multihitHost(origins4, directions4, n, max_distance, k, flags, q); });
 }
 
 int rt_trace_multihit_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
                              uint32_t flags, const rt_multihit_arrays *out, void *hip_stream) {
-	const int rc = multihit_precheck(h, origins4, directions4, n, k, out, true);
+	const ocrt::MultiHitOutputs q = multihit_outputs(out);
+	const int rc = multihit_precheck(h, origins4, directions4, n, k, q, true);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	ocrt::MultiHitOutputs q;
-	multihit_outputs(out, q);
 	return guarded([&] { queries_of(h).multihitDevice(origins4, directions4, n, max_distance, k, flags, q, hip_stream); });
 }
 
@@ -975,7 +977,7 @@ int rt_trace_ao_device(rt_host *h, const float *points4, const float *normals4, 
 	const int rc = ao_precheck(h, points4, normals4, n, true, nullptr);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	if ((((uintptr_t) seeds | (uintptr_t) ao | (uintptr_t) occluded) & 3u) != 0)
+	if (!aligned({ seeds, ao, occluded }, 4))
 		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
 	return guarded([&] { queries_of(h).aoDevice(points4, normals4, seeds, n, flags, ao, occluded, hip_stream); });
 }

@@ -185,6 +185,21 @@ struct SceneBuffers {  // device pointers of one uploaded scene
 	const void *ao_table;    // float4[ao_dirs] (UNIFORM)
 };
 
+// Outputs of the ray queries (ray_query.h) as their launchers take them: device pointers, null = not written.
+// What a closest-hit query and a multi-hit query both write, by ray index or by ray and slot (slot j of ray i at i * k + j):
+struct RecordOutputs {
+	float *distance = nullptr;
+	uint32_t *leaf = nullptr;
+	float *barycentric = nullptr, *position = nullptr, *normal = nullptr;  // three values each
+	bool anySlot() const { return distance || leaf || barycentric || position || normal; }
+};
+struct QueryOutputs : RecordOutputs {
+	unsigned char *hit = nullptr;  // by ray index
+};
+struct MultiHitOutputs : RecordOutputs {
+	uint32_t *count = nullptr;  // by ray index
+};
+
 // Waves per workgroup of the ambient-occlusion pass: they take consecutive parts of a claim (kernels.hip), which is
 // why the host deals the UNIFORM direction table to that many groups (device_renderer.cc).
 constexpr uint32_t AO_WORKGROUP_WAVES = 4;

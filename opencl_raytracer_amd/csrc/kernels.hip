@@ -386,8 +386,7 @@ void launch_query_sort(const void *origins, const void *directions, uint32_t n, 
 }
 
 void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *origins, const void *directions,
-                  const void *order, uint32_t n, float max_distance, unsigned char *hit, float *distance, uint32_t *leaf,
-                  float *barycentric, float *position, float *normal, void *stream) {
+                  const void *order, uint32_t n, float max_distance, const QueryOutputs &out, void *stream) {
 	if (n == 0)
 		return;
 	QueryArgs a{};
@@ -400,14 +399,14 @@ void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, 
 	a.n = n;
 	a.node_count = node_count;
 	a.max_distance = max_distance;
-	a.hit = hit;
+	a.hit = out.hit;
+	a.distance = out.distance;
+	a.leaf = out.leaf;
+	a.barycentric = out.barycentric;
+	a.position = out.position;
+	a.normal = out.normal;
 	const uint32_t blocks = (n + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
 	if (closest) {
-		a.distance = distance;
-		a.leaf = leaf;
-		a.barycentric = barycentric;
-		a.position = position;
-		a.normal = normal;
 		hipLaunchKernelGGL(query_kernel<true>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
 	} else {
 		hipLaunchKernelGGL(query_kernel<false>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
@@ -451,8 +450,7 @@ void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode
 // uint2 of scratch on the device; `count` and the slot arrays: null = not written.  The resolve pass is launched only if
 // a slot array is given.
 void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void *origins, const void *directions, const void *order,
-                     uint32_t n, float max_distance, uint32_t k, void *list, uint32_t *count, float *distance, uint32_t *leaf,
-                     float *barycentric, float *position, float *normal, void *stream) {
+                     uint32_t n, float max_distance, uint32_t k, void *list, const MultiHitOutputs &out, void *stream) {
 	if (n == 0 || k > MULTIHIT_MAX_K)
 		return;
 	hipStream_t s = (hipStream_t) stream;
@@ -468,12 +466,12 @@ void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void 
 	a.k = k;
 	a.max_distance = max_distance;
 	a.list = (uint2 *) list;
-	a.count = count;
-	a.distance = distance;
-	a.leaf = leaf;
-	a.barycentric = barycentric;
-	a.position = position;
-	a.normal = normal;
+	a.count = out.count;
+	a.distance = out.distance;
+	a.leaf = out.leaf;
+	a.barycentric = out.barycentric;
+	a.position = out.position;
+	a.normal = out.normal;
 	const dim3 blocks((n + MULTIHIT_LANES - 1u) / MULTIHIT_LANES), lanes(MULTIHIT_LANES);
 	if (k == 0u)
 		hipLaunchKernelGGL(multihit_walk_kernel<0u>, blocks, lanes, 0, s, a);
@@ -487,7 +485,7 @@ void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void 
 		hipLaunchKernelGGL(multihit_walk_kernel<8u>, blocks, lanes, 0, s, a);
 	else
 		hipLaunchKernelGGL(multihit_walk_kernel<16u>, blocks, lanes, 0, s, a);
-	if (k > 0u && (distance || leaf || barycentric || position || normal))
+	if (k > 0u && out.anySlot())
 		hipLaunchKernelGGL(multihit_resolve_kernel, dim3((n * k + 255u) / 256u), dim3(256), 0, s, a);
 }
 

@@ -3,6 +3,7 @@
 
 #include <cmath>
 #include <stdexcept>
+#include <string>
 
 #include "device_internal.h"
 
@@ -13,6 +14,10 @@ constexpr size_t QUERY_COUNT_BYTES = (size_t) 1 << 18;  // kernels/query.hip.h: 
 constexpr uint32_t QUERY_NO_SORT = 1u, QUERY_SORT_MIN = 16384u;  // include/rt_hip_query.h
 constexpr uint32_t MULTIHIT_MAX_SLOTS = 16u;                     // include/rt_hip_multihit.h, kernels/multihit.hip.h
 size_t round16(size_t bytes) { return (bytes + 15u) & ~(size_t) 15u; }
+// The staged pieces of the host-memory forms.  Rays: the two inputs, the family's first output (hit flags or counts),
+// then the five record arrays.  Ambient occlusion: the counts come third, so that they are placed as they always were.
+enum { RAY_ORIGINS, RAY_DIRECTIONS, RAY_FIRST, RAY_RECORDS, RAY_PIECES = RAY_RECORDS + 5 };
+enum { AO_POINTS, AO_NORMALS, AO_COUNTS, AO_SEEDS, AO_VALUES, AO_PIECES };
 }  // namespace
 
 RayQueries::RayQueries(DeviceRenderer &renderer) : dev(renderer) {
@@ -26,23 +31,37 @@ RayQueries::~RayQueries() {
 		return;
 	if (timed)
 		(void) hipEventSynchronize((hipEvent_t) ev_stop);
-	device_free(d_count);
-	device_free(d_order);
-	device_free(d_stage);
-	device_free(d_ao_hits);
-	device_free(d_list);
+	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &list })
+		device_free(scratch->ptr);
 	(void) hipEventDestroy((hipEvent_t) ev_start);
 	(void) hipEventDestroy((hipEvent_t) ev_stop);
 }
 
 // (hipFree waits for the device: a query still running on the old buffer finishes first)
-void RayQueries::grow(void *&buffer, size_t &capacity, size_t bytes) {
-	if (bytes <= capacity && buffer)
+void RayQueries::grow(Scratch &scratch, size_t bytes) {
+	if (bytes <= scratch.bytes && scratch.ptr)
 		return;
-	device_free(buffer);
-	capacity = 0;
-	buffer = device_alloc(bytes);
-	capacity = bytes;
+	device_free(scratch.ptr);
+	scratch.bytes = 0;
+	scratch.ptr = device_alloc(bytes);
+	scratch.bytes = bytes;
+}
+
+void RayQueries::requireScene(const char *query) const {
+	if (!dev.sceneReady() || !dev.deviceScene())
+		throw std::logic_error(std::string(query) + " before a scene was uploaded");
+}
+
+void RayQueries::requireSlots(uint32_t k) const {
+	requireScene("multi-hit query");
+	if (k > MULTIHIT_MAX_SLOTS)
+		throw std::invalid_argument("more slots per ray than RT_MULTIHIT_MAX_K");
+}
+
+void RayQueries::requireAo() const {
+	requireScene("ambient-occlusion query");
+	if (aoRaysPerPoint(dev) == 0)
+		throw std::logic_error("ambient-occlusion query on a host whose options have ambient occlusion off");
 }
 
 // The sort key's origin cells: 8 per axis over the root's box (exact records, read once per uploaded scene).  A box that
@@ -69,171 +88,144 @@ void RayQueries::sceneBox(const DeviceScene &scene, float lo[3], float scale[3])
 	}
 }
 
-void RayQueries::traceDevice(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
-                             uint32_t flags, const QueryOutputs &out, void *stream) {
-	if (!dev.sceneReady() || !dev.deviceScene())
-		throw std::logic_error("ray query before a scene was uploaded");
-	if (n == 0)
-		return;
+// The way into every device-memory form, up to its own launches: the stream (null: the renderer's), the wait for the
+// query before -- one set of scratch per host, so a query on another stream waits before any scratch is touched --, the
+// scratch (the sort's, and what the family needs of its own: every grow comes before ev_start, because hipFree
+// synchronises), ev_start, and the sort of the n items keyed by (keys_a4, keys_b4) where the call allows it and makes
+// RT_QUERY_SORT_MIN `rays` or more.
+RayQueries::Enqueue RayQueries::begin(void *stream, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags,
+                                      Need need) {
 	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
 	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
-	const DeviceScene &scene = *dev.deviceScene();
-	// one set of scratch per host: a query on another stream waits for the one before it
 	if (timed)
 		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
-	const bool sort = !(flags & QUERY_NO_SORT) && n >= QUERY_SORT_MIN;
+	const bool sort = !(flags & QUERY_NO_SORT) && rays >= QUERY_SORT_MIN;
 	if (sort) {
-		size_t count_bytes = d_count ? QUERY_COUNT_BYTES : 0;
-		grow(d_count, count_bytes, QUERY_COUNT_BYTES);
-		grow(d_order, order_bytes, (size_t) n * sizeof(uint32_t));
+		grow(count, QUERY_COUNT_BYTES);
+		grow(order, (size_t) n * sizeof(uint32_t));
 	}
+	if (need.scratch)
+		grow(*need.scratch, need.bytes);
 	float lo[3], scale[3];
 	if (sort)
-		sceneBox(scene, lo, scale);
+		sceneBox(*dev.deviceScene(), lo, scale);
 	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
 	if (sort)
-		launch_query_sort(origins4, directions4, n, lo, scale, d_count, d_order, s);
-	launch_query(scene.buffers(), dev.params().node_count, closest, origins4, directions4, sort ? d_order : nullptr, n, max_distance,
-	             out.hit, out.distance, out.leaf, out.barycentric, out.position, out.normal, s);
+		launch_query_sort(keys_a4, keys_b4, n, lo, scale, count.ptr, order.ptr, s);
+	return Enqueue{ s, sort ? order.ptr : nullptr };
+}
+
+// ... and the way out, after them.
+void RayQueries::end(const Enqueue &q) {
 	OCRT_HIP(hipGetLastError());
-	OCRT_HIP(hipEventRecord((hipEvent_t) ev_stop, s));
+	OCRT_HIP(hipEventRecord((hipEvent_t) ev_stop, (hipStream_t) q.stream));
 	timed = true;
 	have_ms = false;
 }
 
-void RayQueries::traceHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
-                           uint32_t flags, unsigned char *hit, float *distance, uint32_t *leaf, float *barycentric, float *position,
-                           float *normal) {
-	if (!dev.sceneReady() || !dev.deviceScene())
-		throw std::logic_error("ray query before a scene was uploaded");
-	if (n == 0)
-		return;
+// The host-memory forms run on the renderer's own stream through one staging buffer: stageIn places the wanted pieces
+// one behind the other, each rounded up to 16 bytes, and uploads the inputs; stageOut copies the outputs back and waits.
+void *RayQueries::stageIn(Staged *pieces, size_t n) {
 	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
 	hipStream_t s = (hipStream_t) dev.streamHandle();
-	// staging: origins, directions, then the outputs asked for
-	const size_t ray_bytes = (size_t) n * 16u, word_bytes = round16((size_t) n * 4u), vec_bytes = round16((size_t) n * 12u);
-	size_t at = 2 * ray_bytes;
+	size_t total = 0;
+	for (size_t i = 0; i < n; ++i)
+		if (pieces[i].wanted)
+			total += round16(pieces[i].bytes);
+	grow(stage, total);
+	char *at = (char *) stage.ptr;
+	for (size_t i = 0; i < n; ++i) {
+		Staged &piece = pieces[i];
+		if (!piece.wanted)
+			continue;
+		piece.device = at;
+		at += round16(piece.bytes);
+		if (piece.from)
+			OCRT_HIP(hipMemcpyAsync(piece.device, piece.from, piece.bytes, hipMemcpyHostToDevice, s));
+	}
+	return s;
+}
+
+void RayQueries::stageOut(const Staged *pieces, size_t n, void *stream) {
+	for (size_t i = 0; i < n; ++i)
+		if (pieces[i].to && pieces[i].device && pieces[i].bytes)
+			OCRT_HIP(hipMemcpyAsync(pieces[i].to, pieces[i].device, pieces[i].bytes, hipMemcpyDeviceToHost, (hipStream_t) stream));
+	OCRT_HIP(hipStreamSynchronize((hipStream_t) stream));
+}
+
+void RayQueries::recordPieces(Staged *p, const RecordOutputs &host, size_t records) {
+	p[0] = output(host.distance, records * 4u);
+	p[1] = output(host.leaf, records * 4u);
+	p[2] = output(host.barycentric, records * 12u);
+	p[3] = output(host.position, records * 12u);
+	p[4] = output(host.normal, records * 12u);
+}
+
+void RayQueries::recordDevice(const Staged *p, RecordOutputs &out) {
+	out.distance = (float *) p[0].device;
+	out.leaf = (uint32_t *) p[1].device;
+	out.barycentric = (float *) p[2].device;
+	out.position = (float *) p[3].device;
+	out.normal = (float *) p[4].device;
+}
+
+void RayQueries::traceDevice(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
+                             uint32_t flags, const QueryOutputs &out, void *stream) {
+	requireScene("ray query");
+	if (n == 0)
+		return;
+	const Enqueue q = begin(stream, origins4, directions4, n, n, flags);
+	launch_query(dev.deviceScene()->buffers(), dev.params().node_count, closest, origins4, directions4, q.order, n, max_distance, out,
+	             q.stream);
+	end(q);
+}
+
+void RayQueries::traceHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
+                           uint32_t flags, const QueryOutputs &host) {
+	requireScene("ray query");
+	if (n == 0)
+		return;
+	QueryOutputs want;  // (occlusion: the flags alone)
+	if (closest)
+		want = host;
+	want.hit = host.hit;
+	Staged p[RAY_PIECES] = { input(origins4, (size_t) n * 16u), input(directions4, (size_t) n * 16u), output(want.hit, n) };
+	recordPieces(p + RAY_RECORDS, want, n);
+	void *s = stageIn(p, RAY_PIECES);
 	QueryOutputs out;
-	auto place = [&](bool wanted, size_t bytes) -> size_t {
-		if (!wanted)
-			return (size_t) -1;
-		const size_t here = at;
-		at += bytes;
-		return here;
-	};
-	const size_t o_hit = place(hit != nullptr, round16(n)), o_dist = place(closest && distance, word_bytes);
-	const size_t o_leaf = place(closest && leaf, word_bytes), o_bary = place(closest && barycentric, vec_bytes);
-	const size_t o_pos = place(closest && position, vec_bytes), o_norm = place(closest && normal, vec_bytes);
-	grow(d_stage, stage_bytes, at);
-	char *base = (char *) d_stage;
-	auto dptr = [&](size_t offset) -> void * { return offset == (size_t) -1 ? nullptr : base + offset; };
-	out.hit = (unsigned char *) dptr(o_hit);
-	out.distance = (float *) dptr(o_dist);
-	out.leaf = (uint32_t *) dptr(o_leaf);
-	out.barycentric = (float *) dptr(o_bary);
-	out.position = (float *) dptr(o_pos);
-	out.normal = (float *) dptr(o_norm);
-	OCRT_HIP(hipMemcpyAsync(base, origins4, ray_bytes, hipMemcpyHostToDevice, s));
-	OCRT_HIP(hipMemcpyAsync(base + ray_bytes, directions4, ray_bytes, hipMemcpyHostToDevice, s));
-	traceDevice(closest, (const float *) base, (const float *) (base + ray_bytes), n, max_distance, flags, out, s);
-	auto back = [&](void *host, const void *device, size_t bytes) {
-		if (host && device)
-			OCRT_HIP(hipMemcpyAsync(host, device, bytes, hipMemcpyDeviceToHost, s));
-	};
-	back(hit, out.hit, n);
-	back(distance, out.distance, (size_t) n * 4u);
-	back(leaf, out.leaf, (size_t) n * 4u);
-	back(barycentric, out.barycentric, (size_t) n * 12u);
-	back(position, out.position, (size_t) n * 12u);
-	back(normal, out.normal, (size_t) n * 12u);
-	OCRT_HIP(hipStreamSynchronize(s));
+	out.hit = (unsigned char *) p[RAY_FIRST].device;
+	recordDevice(p + RAY_RECORDS, out);
+	traceDevice(closest, (const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, max_distance, flags, out, s);
+	stageOut(p, RAY_PIECES, s);
 }
 
 void RayQueries::multihitDevice(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
                                 uint32_t flags, const MultiHitOutputs &out, void *stream) {
-	if (!dev.sceneReady() || !dev.deviceScene())
-		throw std::logic_error("multi-hit query before a scene was uploaded");
-	if (k > MULTIHIT_MAX_SLOTS)
-		throw std::invalid_argument("more slots per ray than RT_MULTIHIT_MAX_K");
+	requireSlots(k);
 	// without a slot array the lists are not wanted: the count-only walk
 	const uint32_t slots = out.anySlot() ? k : 0u;
 	if (n == 0 || (slots == 0 && !out.count))
 		return;
-	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
-	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
-	const DeviceScene &scene = *dev.deviceScene();
-	// one set of scratch per host: a query on another stream waits for the one before it
-	if (timed)
-		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
-	const bool sort = !(flags & QUERY_NO_SORT) && n >= QUERY_SORT_MIN;
-	if (sort) {
-		size_t count_bytes = d_count ? QUERY_COUNT_BYTES : 0;
-		grow(d_count, count_bytes, QUERY_COUNT_BYTES);
-		grow(d_order, order_bytes, (size_t) n * sizeof(uint32_t));
-	}
-	if (slots)
-		grow(d_list, list_bytes, (size_t) n * slots * 8u);
-	float lo[3], scale[3];
-	if (sort)
-		sceneBox(scene, lo, scale);
-	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
-	if (sort)
-		launch_query_sort(origins4, directions4, n, lo, scale, d_count, d_order, s);
-	launch_multihit(scene.buffers(), dev.params().node_count, origins4, directions4, sort ? d_order : nullptr, n, max_distance, slots,
-	                d_list, out.count, out.distance, out.leaf, out.barycentric, out.position, out.normal, s);
-	OCRT_HIP(hipGetLastError());
-	OCRT_HIP(hipEventRecord((hipEvent_t) ev_stop, s));
-	timed = true;
-	have_ms = false;
+	const Enqueue q = begin(stream, origins4, directions4, n, n, flags, Need{ slots ? &list : nullptr, (size_t) n * slots * 8u });
+	launch_multihit(dev.deviceScene()->buffers(), dev.params().node_count, origins4, directions4, q.order, n, max_distance, slots,
+	                list.ptr, out, q.stream);
+	end(q);
 }
 
 void RayQueries::multihitHost(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
                               const MultiHitOutputs &host) {
-	if (!dev.sceneReady() || !dev.deviceScene())
-		throw std::logic_error("multi-hit query before a scene was uploaded");
-	if (k > MULTIHIT_MAX_SLOTS)
-		throw std::invalid_argument("more slots per ray than RT_MULTIHIT_MAX_K");
+	requireSlots(k);
 	if (n == 0 || (!host.count && !host.anySlot()))
 		return;
-	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
-	hipStream_t s = (hipStream_t) dev.streamHandle();
-	// staging: origins, directions, then the outputs asked for
-	const size_t ray_bytes = (size_t) n * 16u, slots = (size_t) n * k;
-	size_t at = 2 * ray_bytes;
-	auto place = [&](const void *wanted, size_t bytes) -> size_t {
-		if (!wanted)
-			return (size_t) -1;
-		const size_t here = at;
-		at += round16(bytes);
-		return here;
-	};
-	const size_t o_count = place(host.count, (size_t) n * 4u), o_dist = place(host.distance, slots * 4u);
-	const size_t o_leaf = place(host.leaf, slots * 4u), o_bary = place(host.barycentric, slots * 12u);
-	const size_t o_pos = place(host.position, slots * 12u), o_norm = place(host.normal, slots * 12u);
-	grow(d_stage, stage_bytes, at);
-	char *base = (char *) d_stage;
-	auto dptr = [&](size_t offset) -> void * { return offset == (size_t) -1 ? nullptr : base + offset; };
+	Staged p[RAY_PIECES] = { input(origins4, (size_t) n * 16u), input(directions4, (size_t) n * 16u),
+		                     output(host.count, (size_t) n * 4u) };
+	recordPieces(p + RAY_RECORDS, host, (size_t) n * k);
+	void *s = stageIn(p, RAY_PIECES);
 	MultiHitOutputs out;
-	out.count = (uint32_t *) dptr(o_count);
-	out.distance = (float *) dptr(o_dist);
-	out.leaf = (uint32_t *) dptr(o_leaf);
-	out.barycentric = (float *) dptr(o_bary);
-	out.position = (float *) dptr(o_pos);
-	out.normal = (float *) dptr(o_norm);
-	OCRT_HIP(hipMemcpyAsync(base, origins4, ray_bytes, hipMemcpyHostToDevice, s));
-	OCRT_HIP(hipMemcpyAsync(base + ray_bytes, directions4, ray_bytes, hipMemcpyHostToDevice, s));
-	multihitDevice((const float *) base, (const float *) (base + ray_bytes), n, max_distance, k, flags, out, s);
-	auto back = [&](void *to, const void *device, size_t bytes) {
-		if (to && device && bytes)
-			OCRT_HIP(hipMemcpyAsync(to, device, bytes, hipMemcpyDeviceToHost, s));
-	};
-	back(host.count, out.count, (size_t) n * 4u);
-	back(host.distance, out.distance, slots * 4u);
-	back(host.leaf, out.leaf, slots * 4u);
-	back(host.barycentric, out.barycentric, slots * 12u);
-	back(host.position, out.position, slots * 12u);
-	back(host.normal, out.normal, slots * 12u);
-	OCRT_HIP(hipStreamSynchronize(s));
+	out.count = (uint32_t *) p[RAY_FIRST].device;
+	recordDevice(p + RAY_RECORDS, out);
+	multihitDevice((const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, max_distance, k, flags, out, s);
+	stageOut(p, RAY_PIECES, s);
 }
 
 uint32_t RayQueries::aoRaysPerPoint(const DeviceRenderer &renderer) {
@@ -246,69 +238,30 @@ uint32_t RayQueries::aoDivisor(const DeviceRenderer &renderer) { return aoRaysPe
 
 void RayQueries::aoDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
                           uint32_t *occluded, void *stream) {
-	if (!dev.sceneReady() || !dev.deviceScene())
-		throw std::logic_error("ambient-occlusion query before a scene was uploaded");
-	if (aoRaysPerPoint(dev) == 0)
-		throw std::logic_error("ambient-occlusion query on a host whose options have ambient occlusion off");
+	requireAo();
 	if (n == 0 || (!ao && !occluded))
 		return;
-	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
-	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
-	const DeviceScene &scene = *dev.deviceScene();
 	const KernelParams &kp = dev.params();
-	// one set of scratch per host: a query on another stream waits for the one before it
-	if (timed)
-		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
 	// the POINTS are ordered (key: point and normal) from as many on as make RT_QUERY_SORT_MIN rays
-	const bool sort = !(flags & QUERY_NO_SORT) && (uint64_t) n * kp.ao_dirs >= QUERY_SORT_MIN;
-	if (sort) {
-		size_t count_bytes = d_count ? QUERY_COUNT_BYTES : 0;
-		grow(d_count, count_bytes, QUERY_COUNT_BYTES);
-		grow(d_order, order_bytes, (size_t) n * sizeof(uint32_t));
-	}
-	if (!occluded)
-		grow(d_ao_hits, ao_hits_bytes, (size_t) n * sizeof(uint32_t));
-	float lo[3], scale[3];
-	if (sort)
-		sceneBox(scene, lo, scale);
-	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
-	if (sort)
-		launch_query_sort(points4, normals4, n, lo, scale, d_count, d_order, s);
-	launch_ao_query(scene.buffers(), kp.node_count, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4, normals4, seeds,
-	                sort ? d_order : nullptr, n, occluded ? occluded : (uint32_t *) d_ao_hits, ao, s);
-	OCRT_HIP(hipGetLastError());
-	OCRT_HIP(hipEventRecord((hipEvent_t) ev_stop, s));
-	timed = true;
-	have_ms = false;
+	const Enqueue q = begin(stream, points4, normals4, n, (uint64_t) n * kp.ao_dirs, flags,
+	                        Need{ occluded ? nullptr : &ao_hits, (size_t) n * sizeof(uint32_t) });
+	launch_ao_query(dev.deviceScene()->buffers(), kp.node_count, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4,
+	                normals4, seeds, q.order, n, occluded ? occluded : (uint32_t *) ao_hits.ptr, ao, q.stream);
+	end(q);
 }
 
 void RayQueries::aoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
                         uint32_t *occluded) {
-	if (!dev.sceneReady() || !dev.deviceScene())
-		throw std::logic_error("ambient-occlusion query before a scene was uploaded");
-	if (aoRaysPerPoint(dev) == 0)
-		throw std::logic_error("ambient-occlusion query on a host whose options have ambient occlusion off");
+	requireAo();
 	if (n == 0 || (!ao && !occluded))
 		return;
-	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
-	hipStream_t s = (hipStream_t) dev.streamHandle();
-	// staging: points, normals, the counts, then the seeds and the values if there are any
-	const size_t vec_bytes = (size_t) n * 16u, word_bytes = round16((size_t) n * 4u);
-	const size_t o_count = 2 * vec_bytes, o_seeds = o_count + word_bytes, o_ao = o_seeds + (seeds ? word_bytes : 0);
-	grow(d_stage, stage_bytes, o_ao + (ao ? word_bytes : 0));
-	char *base = (char *) d_stage;
-	uint32_t *d_occluded = (uint32_t *) (base + o_count), *d_seeds = seeds ? (uint32_t *) (base + o_seeds) : nullptr;
-	float *d_value = ao ? (float *) (base + o_ao) : nullptr;
-	OCRT_HIP(hipMemcpyAsync(base, points4, vec_bytes, hipMemcpyHostToDevice, s));
-	OCRT_HIP(hipMemcpyAsync(base + vec_bytes, normals4, vec_bytes, hipMemcpyHostToDevice, s));
-	if (seeds)
-		OCRT_HIP(hipMemcpyAsync(d_seeds, seeds, (size_t) n * 4u, hipMemcpyHostToDevice, s));
-	aoDevice((const float *) base, (const float *) (base + vec_bytes), d_seeds, n, flags, d_value, d_occluded, s);
-	if (ao)
-		OCRT_HIP(hipMemcpyAsync(ao, d_value, (size_t) n * 4u, hipMemcpyDeviceToHost, s));
-	if (occluded)
-		OCRT_HIP(hipMemcpyAsync(occluded, d_occluded, (size_t) n * 4u, hipMemcpyDeviceToHost, s));
-	OCRT_HIP(hipStreamSynchronize(s));
+	// (the counts are staged whether they are copied back or not: the kernel counts into them)
+	Staged p[AO_PIECES] = { input(points4, (size_t) n * 16u), input(normals4, (size_t) n * 16u), scratch(occluded, (size_t) n * 4u),
+		                    input(seeds, (size_t) n * 4u), output(ao, (size_t) n * 4u) };
+	void *s = stageIn(p, AO_PIECES);
+	aoDevice((const float *) p[AO_POINTS].device, (const float *) p[AO_NORMALS].device, (const uint32_t *) p[AO_SEEDS].device, n, flags,
+	         (float *) p[AO_VALUES].device, (uint32_t *) p[AO_COUNTS].device, s);
+	stageOut(p, AO_PIECES, s);
 }
 
 float RayQueries::lastMs() {

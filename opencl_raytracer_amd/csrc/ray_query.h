@@ -9,23 +9,7 @@
 
 namespace ocrt {
 
-// Outputs of a closest-hit query by ray index, device pointers; null: not written.
-struct QueryOutputs {
-	unsigned char *hit = nullptr;
-	float *distance = nullptr;
-	uint32_t *leaf = nullptr;
-	float *barycentric = nullptr, *position = nullptr, *normal = nullptr;
-};
-
-// Outputs of a multi-hit query, device pointers; null: not written.  `count` by ray index, the others by ray and slot
-// (slot j of ray i at i * k + j).
-struct MultiHitOutputs {
-	uint32_t *count = nullptr;
-	float *distance = nullptr;
-	uint32_t *leaf = nullptr;
-	float *barycentric = nullptr, *position = nullptr, *normal = nullptr;
-	bool anySlot() const { return distance || leaf || barycentric || position || normal; }
-};
+// (QueryOutputs, MultiHitOutputs: device_types.h)
 
 // What one render host needs beyond its renderer to answer queries: scratch of its own (the sort's counts and order,
 // the staging buffers of the host-memory form), grown on demand and never shared with the frame's buffers, and the
@@ -42,7 +26,7 @@ class RayQueries {
 		                 uint32_t flags, const QueryOutputs &out, void *stream);
 		// Host memory, blocking: the rays go through the staging buffers on the renderer's stream.
 		void traceHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
-		               unsigned char *hit, float *distance, uint32_t *leaf, float *barycentric, float *position, float *normal);
+		               const QueryOutputs &out);
 		// Multi-hit queries (include/rt_hip_multihit.h): the count of accepted triangles per ray and the first k of them.
 		// Device memory, enqueued on `stream` (null: the renderer's); k <= RT_MULTIHIT_MAX_K, 0 = the count alone.
 		void multihitDevice(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
@@ -65,14 +49,49 @@ class RayQueries {
 		float lastMs();  // the last query of any kind
 
 	private:
-		void grow(void *&buffer, size_t &capacity, size_t bytes);
+		struct Scratch {  // device memory of this host's own, grown on demand
+			void *ptr = nullptr;
+			size_t bytes = 0;
+		};
+		// A piece of the staging buffer of the host-memory forms: `from` is copied in before the query, `to` is copied
+		// back to after it (either may be null); not `wanted`: no piece, `device` stays null.
+		struct Staged {
+			const void *from;
+			void *to;
+			size_t bytes;
+			bool wanted;
+			void *device = nullptr;
+		};
+		static Staged input(const void *from, size_t bytes) { return Staged{ from, nullptr, bytes, from != nullptr }; }
+		static Staged output(void *to, size_t bytes) { return Staged{ nullptr, to, bytes, to != nullptr }; }
+		static Staged scratch(void *to, size_t bytes) { return Staged{ nullptr, to, bytes, true }; }  // staged even if `to` is null
+		// The five record arrays of `host`, `records` records each, as pieces p[0..4]; and those pieces' device pointers.
+		static void recordPieces(Staged *p, const RecordOutputs &host, size_t records);
+		static void recordDevice(const Staged *p, RecordOutputs &out);
+		struct Need {  // scratch of a family's own that begin() grows with the sort's
+			Scratch *scratch;  // (null: none)
+			size_t bytes;
+		};
+		struct Enqueue {
+			void *stream;
+			const void *order;  // the sort's order of the n items, or null: unsorted
+		};
+
+		void requireScene(const char *query) const;
+		void requireSlots(uint32_t k) const;
+		void requireAo() const;
+		void grow(Scratch &scratch, size_t bytes);
 		void sceneBox(const DeviceScene &scene, float lo[3], float scale[3]);
+		Enqueue begin(void *stream, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags, Need need = Need{ nullptr, 0 });
+		void end(const Enqueue &q);
+		void *stageIn(Staged *pieces, size_t n);  // returns the stream
+		void stageOut(const Staged *pieces, size_t n, void *stream);
 
 		DeviceRenderer &dev;
-		void *d_count = nullptr, *d_order = nullptr, *d_stage = nullptr;
-		void *d_ao_hits = nullptr;  // aoDevice without an `occluded` array: the points' counts
-		void *d_list = nullptr;  // multihitDevice: the rays' key lists, n * k * 8 bytes
-		size_t order_bytes = 0, stage_bytes = 0, ao_hits_bytes = 0, list_bytes = 0;
+		Scratch count, order;  // the sort's histogram and the order it makes
+		Scratch stage;         // the host-memory forms' inputs and outputs
+		Scratch ao_hits;       // aoDevice without an `occluded` array: the points' counts
+		Scratch list;          // multihitDevice: the rays' key lists, n * k * 8 bytes
 		void *ev_start = nullptr, *ev_stop = nullptr;
 		bool timed = false, have_ms = false;
 		float last_ms = 0.0f;
@@ -84,11 +103,9 @@ class RayQueries {
 void launch_query_sort(const void *origins, const void *directions, uint32_t n, const float lo[3], const float scale[3], void *count,
                        void *order, void *stream);
 void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *origins, const void *directions,
-                  const void *order, uint32_t n, float max_distance, unsigned char *hit, float *distance, uint32_t *leaf,
-                  float *barycentric, float *position, float *normal, void *stream);
+                  const void *order, uint32_t n, float max_distance, const QueryOutputs &out, void *stream);
 void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void *origins, const void *directions, const void *order,
-                     uint32_t n, float max_distance, uint32_t k, void *list, uint32_t *count, float *distance, uint32_t *leaf,
-                     float *barycentric, float *position, float *normal, void *stream);
+                     uint32_t n, float max_distance, uint32_t k, void *list, const MultiHitOutputs &out, void *stream);
 void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
                      float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
                      uint32_t *count, float *ao, void *stream);

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import ao_oracle as aoo
+import multihit_oracle as mo
 import orc
 import query_oracle as qo
 from conftest import bits
@@ -215,6 +216,48 @@ def test_ao_queries_leave_frames_alone(rt, oracle, scene_for):
     assert host.stats() == stats
     assert host.stats()["ao_occluded"] == counters["ao_occluded"]
     assert_same(before, during)
+    assert host.last_query_ms > 0.0
+    host.close()
+
+
+def test_interleaved_families_share_one_host(rt, scene_for):
+    """Closest-hit, occlusion, multi-hit and AO queries in turn on ONE host, sorted and unsorted, with fewer and with more
+    items than the call before: the families share the sort's scratch, the staging buffer and the events, so what one call
+    leaves behind (an order for more items, a histogram, a staging layout for other outputs) must not reach the next.
+    Every result is compared with its CPU oracle, computed once per ray set."""
+    scene, arrays = scene_for("blob", "longest")
+    host, opt = make_host(rt, scene)
+    assert host.ao_rays_per_point == (28, 28)
+    md = 100000.0
+    o, d = mo.random_rays(arrays, 16384 + 65, seed=17)  # RT_QUERY_SORT_MIN and a partial last packet
+    cam_o, cam_d = qo.camera_rays(orc.params_from_options(rt.Options.defaults(width=W, height=H, n_super_samples=1)))
+    cam = qo.closest(arrays, cam_o, cam_d, md)
+    on = cam["hit"].astype(bool)
+    assert on.any()
+    points, normals = np.resize(cam["position"][on], (600, 3)), np.resize(cam["normal"][on], (600, 3))  # 600 x 28 >= 16384
+    want_closest, want_occluded = qo.closest(arrays, o, d, md), qo.occluded(arrays, o, d, md)
+    want_multi = mo.multihit(arrays, o, d, md, mo.MAX_K)
+    want_ao = aoo.ambient_occlusion(orc.params_from_options(opt), arrays, points, normals)
+    assert want_closest["hit"].any() and want_ao["occluded"].any() and (want_multi["count"] > 1).any()
+
+    def same(got, want, fields, what):
+        assert set(got) == set(fields), (what, sorted(got))
+        for f in fields:
+            assert got[f].shape == want[f].shape, (what, f, got[f].shape, want[f].shape)
+            words = qo.same_words(got[f], want[f])
+            assert words.all(), (what, f, int((~words).sum()), np.argwhere(~words)[:5].tolist())
+
+    def closest_then_ao(what):
+        same(host.trace_closest(o, d, md, sort=True), want_closest, rt.api.QUERY_OUTPUTS, (what, "closest"))
+        same(host.ambient_occlusion(points, normals, sort=True), want_ao, rt.api.AO_OUTPUTS, (what, "ao"))
+
+    closest_then_ao("first")
+    same(host.trace_multihit(o[:257], d[:257], md, k=4, sort=False), {f: v[:257] for f, v in mo.first_slots(want_multi, 4).items()},
+         mo.FIELDS, "multihit k=4")
+    same(host.ambient_occlusion(points[:65], normals[:65], outputs=("ao",), sort=False), {"ao": want_ao["ao"][:65]}, ("ao",), "ao alone")
+    same({"hit": host.trace_occluded(o, d, md, sort=True)}, {"hit": want_occluded}, ("hit",), "occluded")
+    same(host.trace_multihit(o, d, md, k=16, sort=True), mo.first_slots(want_multi, 16), mo.FIELDS, "multihit k=16")
+    closest_then_ao("again")
     assert host.last_query_ms > 0.0
     host.close()
 

@@ -138,7 +138,8 @@ def main():
                           "in a hot kernel (walk_collect's fixed registers v56-v62 need the 64-VGPR budget to hold)")
     queries = ("query_kernel<true>", "query_kernel<false>", "query_key_kernel", "query_scatter_kernel", "query_scan_kernel",
                "multihit_walk_kernel<0", "multihit_walk_kernel<1u", "multihit_walk_kernel<2", "multihit_walk_kernel<4",
-               "multihit_walk_kernel<8", "multihit_walk_kernel<16", "multihit_resolve_kernel")
+               "multihit_walk_kernel<8", "multihit_walk_kernel<16", "multihit_resolve_kernel", "ao_query_kernel<1",
+               "ao_query_kernel<2", "ao_query_finish_kernel")
     names = [k["name"].replace("ocrt::", "").replace("void ", "") for k in kernels]
     for p in HOT_PRIMARY:
         if not any(n.startswith(p) for n in names):
