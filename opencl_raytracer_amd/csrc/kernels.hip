@@ -385,11 +385,9 @@ void launch_query_sort(const void *origins, const void *directions, uint32_t n, 
 	hipLaunchKernelGGL(query_scatter_kernel, dim3(blocks), dim3(256), 0, s, a);
 }
 
-void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *origins, const void *directions,
-                  const void *order, uint32_t n, float max_distance, const QueryOutputs &out, void *stream) {
-	if (n == 0)
-		return;
-	QueryArgs a{};
+// (what query_kernel and the multi-hit kernels are launched with alike)
+static void fill(RayQueryArgs &a, const SceneBuffers &scene, uint32_t node_count, const void *origins, const void *directions,
+                 const void *order, uint32_t n, float max_distance, const RecordOutputs &out) {
 	a.nodes_ptr = (const float4 *) scene.nodes;
 	a.tris_ptr = (const float4 *) scene.tris;
 	a.shade = (const float4 *) scene.shade;
@@ -399,12 +397,16 @@ void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, 
 	a.n = n;
 	a.node_count = node_count;
 	a.max_distance = max_distance;
+	a.out = out;
+}
+
+void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *origins, const void *directions,
+                  const void *order, uint32_t n, float max_distance, const QueryOutputs &out, void *stream) {
+	if (n == 0)
+		return;
+	QueryArgs a{};
+	fill(a, scene, node_count, origins, directions, order, n, max_distance, out);
 	a.hit = out.hit;
-	a.distance = out.distance;
-	a.leaf = out.leaf;
-	a.barycentric = out.barycentric;
-	a.position = out.position;
-	a.normal = out.normal;
 	const uint32_t blocks = (n + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
 	if (closest) {
 		hipLaunchKernelGGL(query_kernel<true>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
@@ -455,23 +457,10 @@ void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void 
 		return;
 	hipStream_t s = (hipStream_t) stream;
 	MultiHitArgs a{};
-	a.nodes_ptr = (const float4 *) scene.nodes;
-	a.tris_ptr = (const float4 *) scene.tris;
-	a.shade = (const float4 *) scene.shade;
-	a.origins = (const float4 *) origins;
-	a.directions = (const float4 *) directions;
-	a.order = (const uint32_t *) order;
-	a.n = n;
-	a.node_count = node_count;
+	fill(a, scene, node_count, origins, directions, order, n, max_distance, out);
 	a.k = k;
-	a.max_distance = max_distance;
 	a.list = (uint2 *) list;
 	a.count = out.count;
-	a.distance = out.distance;
-	a.leaf = out.leaf;
-	a.barycentric = out.barycentric;
-	a.position = out.position;
-	a.normal = out.normal;
 	const dim3 blocks((n + MULTIHIT_LANES - 1u) / MULTIHIT_LANES), lanes(MULTIHIT_LANES);
 	if (k == 0u)
 		hipLaunchKernelGGL(multihit_walk_kernel<0u>, blocks, lanes, 0, s, a);

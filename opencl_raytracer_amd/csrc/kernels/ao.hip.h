@@ -28,6 +28,27 @@ __device__ __forceinline__ Rng rng_seed(uint32_t seed) {
 }
 __device__ __forceinline__ float rng_float(Rng &v) { return 2.32830643653869629E-10f * rng_next(v); }
 
+// Sample j >= 1 of the RANDOM hemisphere sampler for the point whose reference `index` is `seed_index` (reference
+// :153-183, :257-276): draws 2j-2 and 2j-1 of the point's generator, in the tangent frame's coordinates.  (Ray 0 goes
+// along the normal: the callers' business.)  Device libm rounds differently from the host's: this mode is outside the
+// bit-exact contract with the CPU -- but not with the reference kernel on this GPU: in the test-only library-builtins
+// build the trigonometry is ROCm's OpenCL library's own (OCRT_SIN ..., kernels/common.hip.h) and the frame equals the
+// reference's bit for bit (tests/test_ocml_pin.py).
+__device__ __forceinline__ void random_sample(uint32_t seed_index, uint32_t j, float &xs, float &ys, float &zs) {
+	Rng rng = rng_seed(536870923u * seed_index);
+	for (uint32_t skip = 1; skip < j; ++skip) {
+		rng_next(rng);
+		rng_next(rng);
+	}
+	const float xi1 = rng_float(rng);
+	const float xi2 = rng_float(rng);
+	const float theta = OCRT_ACOS(sqrtf(1.0f - xi1));
+	const float phi = (float) (2.0 * (double) xi2);
+	xs = OCRT_SIN(theta) * OCRT_COSPI(phi);
+	ys = OCRT_COS(theta);
+	zs = OCRT_SIN(theta) * OCRT_SINPI(phi);
+}
+
 // ---------------------------------------------------------------------------
 // Pass 2: ambient occlusion.  Persistent, independent waves; one tile at a time.
 // ---------------------------------------------------------------------------
@@ -330,22 +351,8 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 					sh.pixel[lane] = __float_as_uint(q1.w);
 					if (MODE == AO_RANDOM)
 						normalize3(nx, ny, nz);  // hemisphere_sampler normalises once more, reference :155
-					// tangent frame: the smallest |component| of the normal is replaced by 1
-					float hx = nx, hy = ny, hz = nz;
-					const float ax = fabsf(nx), ay = fabsf(ny), az = fabsf(nz);
-					if (ax <= ay && ax <= az)
-						hx = 1.0f;
-					else if (ay <= ax && ay <= az)
-						hy = 1.0f;
-					else if (az <= ax && az <= ay)
-						hz = 1.0f;
-					// basis_x = normalize(cross(h, basis_y)), basis_z = normalize(cross(basis_x, basis_y))
-					float bxx, bxy, bxz;
-					cross3(hx, hy, hz, nx, ny, nz, bxx, bxy, bxz);
-					normalize3(bxx, bxy, bxz);
-					float bzx, bzy, bzz;
-					cross3(bxx, bxy, bxz, nx, ny, nz, bzx, bzy, bzz);
-					normalize3(bzx, bzy, bzz);
+					float bxx, bxy, bxz, bzx, bzy, bzz;
+					tangent_frame(nx, ny, nz, bxx, bxy, bxz, bzx, bzy, bzz);
 					sh.frame[3][lane] = bxx; sh.frame[4][lane] = bxy; sh.frame[5][lane] = bxz;
 					sh.frame[6][lane] = nx;  sh.frame[7][lane] = ny;  sh.frame[8][lane] = nz;
 					sh.frame[9][lane] = bzx; sh.frame[10][lane] = bzy; sh.frame[11][lane] = bzz;
@@ -389,29 +396,13 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 						}
 					}
 					if (MODE != AO_UNIFORM) {
-						// RANDOM (reference :153-183, :257-276): ray 0 goes along the normal, ray
-						// j >= 1 uses draws 2j-2 and 2j-1 of the sub-pixel's generator.  Device libm
-						// rounds differently from the host's: this mode is outside the bit-exact contract with the CPU
-						// -- but not with the reference kernel on this GPU: in the test-only library-builtins build the
-						// trigonometry below is ROCm's OpenCL library's own (OCRT_SIN ..., kernels/common.hip.h) and the
-						// frame equals the reference's bit for bit (tests/test_ocml_pin.py).
+						// RANDOM: ray 0 goes along the normal (below), ray j >= 1 is sample j of the sub-pixel's generator
 						const uint32_t j = dir0 + k;
 						along_normal = j == 0u;
 						// the generator is seeded with the sub-pixel's index in the WHOLE image (reference :169, :279-281)
 						const uint32_t local_y = sh.pixel[h] / A.P.width, x = sh.pixel[h] - local_y * A.P.width;
 						const uint32_t y = global_tile_row(A.P.part, local_y / TILE_H) * TILE_H + (local_y & (TILE_H - 1u));
-						Rng rng = rng_seed(536870923u * (y * A.P.width + x));
-						for (uint32_t skip = 1; skip < j; ++skip) {
-							rng_next(rng);
-							rng_next(rng);
-						}
-						const float xi1 = rng_float(rng);
-						const float xi2 = rng_float(rng);
-						const float theta = OCRT_ACOS(sqrtf(1.0f - xi1));
-						const float phi = (float) (2.0 * (double) xi2);
-						xs = OCRT_SIN(theta) * OCRT_COSPI(phi);
-						ys = OCRT_COS(theta);
-						zs = OCRT_SIN(theta) * OCRT_SINPI(phi);
+						random_sample(y * A.P.width + x, j, xs, ys, zs);
 					}
 					// ray_dir = basis_x * xs + basis_y * ys + basis_z * zs, lane by lane
 					float rx = (sh.frame[3][h] * xs + sh.frame[6][h] * ys) + sh.frame[9][h] * zs;

@@ -7,10 +7,10 @@
 // normal).  ao_query_kernel<MODE> casts one packet of 64 CONSECUTIVE rays per wave: a run of directions from one point
 // or from a few neighbouring ones, all within the AO reach of each other -- what the shared walk wants -- and no ray is
 // ever read: every lane makes its own from its point, its normal and the direction table (UNIFORM) or the point's
-// generator (RANDOM), with the arithmetic of the frame's own pass (kernels/ao.hip.h, reference
-// src/intersect_kernel.cl:215-248 and :153-183), restated here so that ao_kernel's code stays as it is.
+// generator (RANDOM), with the arithmetic of the frame's own pass (reference src/intersect_kernel.cl:215-248 and
+// :153-183): the tangent frame is tangent_frame (kernels/common.hip.h), the RANDOM sample random_sample (kernels/ao.hip.h).
 //
-// The walk is the EXACT form over the uploaded scene's exact node records, any-hit, as query_kernel<false> has it:
+// The walk is the EXACT form (walk.hip.h, exact_walk) over the uploaded scene's exact node records, any-hit:
 // lane by lane the reference's scene_intersect whatever the point and the normal hold.  The padded records of the fast
 // form are not used: their margins are proven for the frame's own hit points, not for points from anywhere.
 //
@@ -57,41 +57,15 @@ __global__ __launch_bounds__(64 * QUERY_WAVES) void ao_query_kernel(AoQueryArgs 
 		oz = p.z + nz * eps;
 		if (MODE == AO_RANDOM)
 			normalize3(nx, ny, nz);  // hemisphere_sampler normalises once more, reference :155
-		// tangent frame (:224-236): the smallest |component| of the normal is replaced by 1
-		float hx = nx, hy = ny, hz = nz;
-		const float ax = fabsf(nx), ay = fabsf(ny), az = fabsf(nz);
-		if (ax <= ay && ax <= az)
-			hx = 1.0f;
-		else if (ay <= ax && ay <= az)
-			hy = 1.0f;
-		else if (az <= ax && az <= ay)
-			hz = 1.0f;
-		// basis_x = normalize(cross(h, basis_y)), basis_z = normalize(cross(basis_x, basis_y))
-		float bxx, bxy, bxz;
-		cross3(hx, hy, hz, nx, ny, nz, bxx, bxy, bxz);
-		normalize3(bxx, bxy, bxz);
-		float bzx, bzy, bzz;
-		cross3(bxx, bxy, bxz, nx, ny, nz, bzx, bzy, bzz);
-		normalize3(bzx, bzy, bzz);
+		float bxx, bxy, bxz, bzx, bzy, bzz;
+		tangent_frame(nx, ny, nz, bxx, bxy, bxz, bzx, bzy, bzz);
 		float xs, ys, zs;
 		if (MODE == AO_UNIFORM) {
 			const float4 dir = a.ao_table[k];
 			xs = dir.x; ys = dir.y; zs = dir.z;
 		} else {
-			// RANDOM (reference :153-183, :257-276): ray 0 goes along the normal, ray k >= 1 uses draws 2k-2 and 2k-1 of the
-			// point's generator.  Device libm: outside the bit-exact contract with the CPU, as for frames (kernels/ao.hip.h).
-			Rng rng = rng_seed(536870923u * (a.seeds ? a.seeds[idx] : idx));
-			for (uint32_t skip = 1; skip < k; ++skip) {
-				rng_next(rng);
-				rng_next(rng);
-			}
-			const float xi1 = rng_float(rng);
-			const float xi2 = rng_float(rng);
-			const float theta = OCRT_ACOS(sqrtf(1.0f - xi1));
-			const float phi = (float) (2.0 * (double) xi2);
-			xs = OCRT_SIN(theta) * OCRT_COSPI(phi);
-			ys = OCRT_COS(theta);
-			zs = OCRT_SIN(theta) * OCRT_SINPI(phi);
+			// RANDOM: ray 0 goes along the normal (below), ray k >= 1 is sample k of the point's generator
+			random_sample(a.seeds ? a.seeds[idx] : idx, k, xs, ys, zs);
 		}
 		// ray_dir = basis_x * xs + basis_y * ys + basis_z * zs
 		rx = (bxx * xs + nx * ys) + bzx * zs;
@@ -105,34 +79,20 @@ __global__ __launch_bounds__(64 * QUERY_WAVES) void ao_query_kernel(AoQueryArgs 
 		}
 	}
 	const Ray ray = make_ray(ox, oy, oz, rx, ry, rz);
-	const float max_distance = a.max_distance;
 	bool alive = live, hit = false;
-	// the exact form of the shared walk, any-hit (query_kernel<false>): one wave-uniform node index `at`, each lane's own
-	// walk in `mine`; a lane leaves at its first accepted triangle
-	const uint32_t count = a.node_count;
-	uint32_t mine = 0u, at = 0u;
-	while (at < count) {
-		const u32x8 node = scalar_load_node(a.nodes_ptr, at);
-		const float4 lo = make_float4(__uint_as_float(node[0]), __uint_as_float(node[1]), __uint_as_float(node[2]), 0.0f);
-		const float4 hi = make_float4(__uint_as_float(node[4]), __uint_as_float(node[5]), __uint_as_float(node[6]), 0.0f);
-		const uint32_t skip = node[3], leaf = node[7];
-		const bool box = exact_box(lo, hi, ray, max_distance, alive, at, skip, mine);
-		const unsigned long long hit_mask = wave_ballot(box);
-		if (hit_mask != 0ull && leaf != NONE) {
-			const float4 *tri = a.tris_ptr + LEAF_F4 * leaf + LEAF_TRI_F4;
-			const float4 q0 = tri[0], q1 = tri[1], q2 = tri[2], q3 = tri[3];
-			if (box) {
-				const TriResult tr = tri_eval<false>(q0, q1, q2, q3, ray);
-				if (tr.accepted) {
-					hit = true;
-					alive = false;
-				}
+	// a lane leaves at its first accepted triangle
+	exact_walk(a.nodes_ptr, a.node_count, ray, a.max_distance, alive, [&](uint32_t leaf, bool box) {
+		const float4 *tri = a.tris_ptr + LEAF_F4 * leaf + LEAF_TRI_F4;
+		const float4 q0 = tri[0], q1 = tri[1], q2 = tri[2], q3 = tri[3];
+		if (box) {
+			const TriResult tr = tri_eval<false>(q0, q1, q2, q3, ray);
+			if (tr.accepted) {
+				hit = true;
+				alive = false;
 			}
-			if (wave_ballot(alive) == 0ull)
-				break;
 		}
-		at = (uint32_t) __builtin_amdgcn_readfirstlane((int) (at + (hit_mask != 0ull ? 1u : skip)));
-	}
+		return wave_ballot(alive) == 0ull;
+	});
 	// the packet's hits by point: the first lane of a point's run adds the run's share of the ballot
 	const unsigned long long hits = wave_ballot(hit);
 	if (!live)

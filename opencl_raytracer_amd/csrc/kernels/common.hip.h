@@ -229,6 +229,38 @@ __device__ __forceinline__ void normalize3(float &x, float &y, float &z) {
 #endif
 }
 
+// The reference's tangent frame around a normal (src/intersect_kernel.cl:224-236).  basis_y is the normal as given;
+// basis_x = normalize(cross(h, basis_y)), where h is the normal with its smallest |component| replaced by 1;
+// basis_z = normalize(cross(basis_x, basis_y)).
+__device__ __forceinline__ void tangent_frame(float nx, float ny, float nz, float &bxx, float &bxy, float &bxz, float &bzx, float &bzy,
+                                              float &bzz) {
+	float hx = nx, hy = ny, hz = nz;
+	const float ax = fabsf(nx), ay = fabsf(ny), az = fabsf(nz);
+	if (ax <= ay && ax <= az)
+		hx = 1.0f;
+	else if (ay <= ax && ay <= az)
+		hy = 1.0f;
+	else if (az <= ax && az <= ay)
+		hz = 1.0f;
+	cross3(hx, hy, hz, nx, ny, nz, bxx, bxy, bxz);
+	normalize3(bxx, bxy, bxz);
+	cross3(bxx, bxy, bxz, nx, ny, nz, bzx, bzy, bzz);
+	normalize3(bzx, bzy, bzz);
+}
+
+// The reference's get_smooth_normal (src/intersect_kernel.cl:118-127) of a leaf at barycentrics (b0, b1, b2): the three
+// vertex normals of its ShadeRec weighted, the sums in the reference's association, then normalised.
+__device__ __forceinline__ void smooth_normal(const float4 *shade, uint32_t leaf, float b0, float b1, float b2, float &nx, float &ny,
+                                              float &nz) {
+	const float4 n0 = shade[3 * (size_t) leaf + 0];
+	const float4 n1 = shade[3 * (size_t) leaf + 1];
+	const float4 n2 = shade[3 * (size_t) leaf + 2];
+	nx = (n0.x * b0 + n1.x * b1) + n2.x * b2;
+	ny = (n0.y * b0 + n1.y * b1) + n2.y * b2;
+	nz = (n0.z * b0 + n1.z * b1) + n2.z * b2;
+	normalize3(nx, ny, nz);
+}
+
 // Maps a rank-local tile row to the global tile row under the band partition.
 __device__ __forceinline__ uint32_t global_tile_row(const Partition &p, uint32_t local_row) {
 	const uint32_t band_local = local_row / p.band_tile_rows;
@@ -289,6 +321,15 @@ __device__ __forceinline__ TriResult tri_eval(const float4 q0, const float4 q1, 
 		out.distance = length3(ex, ey, ez);
 	}
 	return out;
+}
+
+// The accepted triangle `tr` of `leaf` becomes the ray's record (reference :106-112; the caller has asked nearer()).
+__device__ __forceinline__ void take(Hit &best, const TriResult &tr, uint32_t leaf) {
+	best.distance = tr.distance;
+	best.leaf = leaf;
+	best.s = tr.s;
+	best.t = tr.t;
+	best.px = tr.px; best.py = tr.py; best.pz = tr.pz;
 }
 
 // The any-hit form of the test: the same plane half (a, b, r = a / b, the point, wu, wv -- the reference's operations

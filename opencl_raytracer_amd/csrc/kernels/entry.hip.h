@@ -48,20 +48,8 @@ __global__ __launch_bounds__(64 * ENTRY_WAVES) void entry_kernel(const NodeRec *
 		origin[wave][0][lane] = rec.ox + nx * eps;
 		origin[wave][1][lane] = rec.oy + ny * eps;
 		origin[wave][2][lane] = rec.oz + nz * eps;
-		float hx = nx, hy = ny, hz = nz;
-		const float ax = fabsf(nx), ay = fabsf(ny), az = fabsf(nz);
-		if (ax <= ay && ax <= az)
-			hx = 1.0f;
-		else if (ay <= ax && ay <= az)
-			hy = 1.0f;
-		else if (az <= ax && az <= ay)
-			hz = 1.0f;
-		float bxx, bxy, bxz;
-					cross3(hx, hy, hz, nx, ny, nz, bxx, bxy, bxz);
-		normalize3(bxx, bxy, bxz);
-		float bzx, bzy, bzz;
-					cross3(bxx, bxy, bxz, nx, ny, nz, bzx, bzy, bzz);
-		normalize3(bzx, bzy, bzz);
+		float bxx, bxy, bxz, bzx, bzy, bzz;
+		tangent_frame(nx, ny, nz, bxx, bxy, bxz, bzx, bzy, bzz);
 		frame[wave][0][lane] = bxx; frame[wave][1][lane] = bxy; frame[wave][2][lane] = bxz;
 		frame[wave][3][lane] = nx;  frame[wave][4][lane] = ny;  frame[wave][5][lane] = nz;
 		frame[wave][6][lane] = bzx; frame[wave][7][lane] = bzy; frame[wave][8][lane] = bzz;

@@ -163,7 +163,8 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 	uint32_t leaf_stops = 0u;  // leaves the tile's shared walk stopped at: how dense the geometry is along these rays
 	if (SHARED) {
 		const bool exact = !P.fast_walk || wave_ballot(active && !ray_is_selectable(ray, P.origin_limit)) != 0ull;
-		// closest hit = minimum of (distance, reference leaf), see nearer(); reference :106-112
+		// the exact form's leaf step (exact_walk): closest hit = minimum of (distance, reference leaf), see nearer();
+		// reference :106-112
 		auto leaf_test = [&](uint32_t leaf, bool box) {
 			const float4 *tri = tris_ptr + LEAF_F4 * leaf + LEAF_TRI_F4;
 			const float4 q0 = tri[0], q1 = tri[1], q2 = tri[2], q3 = tri[3];
@@ -171,15 +172,12 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 				const TriResult tr = tri_eval<true>(q0, q1, q2, q3, posed_origin<POSED>(ray));
 				if (tr.accepted) {
 					hit = true;
-					if (nearer(tr.distance, leaf, best)) {
-						best.distance = tr.distance;
-						best.leaf = leaf;
-						best.s = tr.s;
-						best.t = tr.t;
-						best.px = tr.px; best.py = tr.py; best.pz = tr.pz;
-					}
+					if (nearer(tr.distance, leaf, best))
+						take(best, tr, leaf);
 				}
 			}
+			++leaf_stops;
+			return false;  // (closest hit: nobody leaves the walk)
 		};
 		if (!exact) {
 			// Leaves hit by few lanes are collected and tested 64 pairs at a time (see ClosestBatch).
@@ -281,30 +279,11 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 			// distance of +inf or NaN never satisfies the reference's `best.distance > distance`: `best` stays as it is.)
 			if (hit && (uint32_t) (key >> 32) < INF_BITS) {
 				const uint32_t leaf = (uint32_t) key;
-				const TriResult tr = tri_test<true>(scene.tris, leaf, posed_origin<POSED>(ray));
-				best.distance = tr.distance;
-				best.leaf = leaf;
-				best.s = tr.s;
-				best.t = tr.t;
-				best.px = tr.px; best.py = tr.py; best.pz = tr.pz;
+				take(best, tri_test<true>(scene.tris, leaf, posed_origin<POSED>(ray)), leaf);
 			}
 		} else {
-			uint32_t mine = 0u;
-			uint32_t at = 0u;
 			const Ray exact_ray = posed_origin<POSED>(ray);  // (no hand-scheduled loop here: the eye may stay in registers)
-			while (at < count) {
-				const u32x8 node = scalar_load_node(nodes_ptr, at);
-				const float4 lo = make_float4(__uint_as_float(node[0]), __uint_as_float(node[1]), __uint_as_float(node[2]), 0.0f);
-				const float4 hi = make_float4(__uint_as_float(node[4]), __uint_as_float(node[5]), __uint_as_float(node[6]), 0.0f);
-				const uint32_t skip = node[3], leaf = node[7];
-				const bool box = exact_box(lo, hi, exact_ray, 100000.0f, active, at, skip, mine);
-				const bool any = wave_ballot(box) != 0ull;
-				if (any && leaf != NONE) {
-					leaf_test(leaf, box);
-					++leaf_stops;
-				}
-				at = (uint32_t) __builtin_amdgcn_readfirstlane((int) (at + (any ? 1u : skip)));
-			}
+			exact_walk(nodes_ptr, count, exact_ray, 100000.0f, active, leaf_test);
 		}
 	}
 #ifdef OCRT_DEBUG_KNOBS
@@ -321,13 +300,8 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 					// closest hit = minimum of (distance, reference leaf), see nearer(); reference :106-112
 					if (tr.accepted) {
 						hit = true;
-						if (nearer(tr.distance, pending.first, best)) {
-							best.distance = tr.distance;
-							best.leaf = pending.first;
-							best.s = tr.s;
-							best.t = tr.t;
-							best.px = tr.px; best.py = tr.py; best.pz = tr.pz;
-						}
+						if (nearer(tr.distance, pending.first, best))
+							take(best, tr, pending.first);
 					}
 					pending.first = pending.second;
 					pending.second = NONE;
@@ -347,15 +321,7 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 	float value = 0.0f;
 	float nx = 0.0f, ny = 0.0f, nz = 0.0f;
 	if (hit) {
-		const float4 *const shade = OCRT_PCOLD_PTR(const float4 *, shade);
-		const float4 n0 = shade[3 * (size_t) best.leaf + 0];
-		const float4 n1 = shade[3 * (size_t) best.leaf + 1];
-		const float4 n2 = shade[3 * (size_t) best.leaf + 2];
-		const float b0 = 1.0f - best.s - best.t, b1 = best.s, b2 = best.t;
-		nx = (n0.x * b0 + n1.x * b1) + n2.x * b2;
-		ny = (n0.y * b0 + n1.y * b1) + n2.y * b2;
-		nz = (n0.z * b0 + n1.z * b1) + n2.z * b2;
-		normalize3(nx, ny, nz);
+		smooth_normal(OCRT_PCOLD_PTR(const float4 *, shade), best.leaf, 1.0f - best.s - best.t, best.s, best.t, nx, ny, nz);
 		value = 1.0f;
 		if (OCRT_PCOLD_U32(P.shading))
 			value = fminf(fmaxf(-dot3(nx, ny, nz, dx, dy, dz), 0.0f), 1.0f);

@@ -7,7 +7,7 @@
 // result is the ray's own, so any order gives the same bits (and the order inside a bucket, which depends on how the
 // waves' atomics land, is free to vary from call to call).
 //
-// The walk is the EXACT form of the shared walk (walk.hip.h, shared_walk_any_hit<true>) over the uploaded scene's
+// The walk is the EXACT form of the shared walk (walk.hip.h, exact_walk) over the uploaded scene's
 // exact node records (SceneBuffers::nodes, builder order): every lane runs the reference's own slab test
 // (src/intersect_kernel.cl:21-61, slab_hit) where its own walk stands, so lane by lane it is the reference's
 // scene_intersect (:184-213) whatever the ray holds -- zero, tiny, huge or non-finite components, far origins, any
@@ -129,7 +129,8 @@ __global__ __launch_bounds__(256) void query_scatter_kernel(QueryKeyArgs a) {
 }
 
 // ---- the queries ----------------------------------------------------------------------------------------------------
-struct QueryArgs {
+// What the kernels that cast caller-supplied rays are launched with (query_kernel, kernels/multihit.hip.h).
+struct RayQueryArgs {
 	const float4 *nodes_ptr;  // SceneBuffers::nodes: exact boxes, builder order (NodeRec)
 	const float4 *tris_ptr;   // TriRec by leaf
 	const float4 *shade;      // ShadeRec by leaf
@@ -137,26 +138,19 @@ struct QueryArgs {
 	const uint32_t *order;    // [n] ray of packet lane k, or null: ray k
 	uint32_t n, node_count;
 	float max_distance;
-	// outputs by ray index; null: not written
-	uint8_t *hit;          // CLOSEST: the hit flag; ANY: the occlusion flag
-	float *distance;
-	uint32_t *leaf;
-	float *barycentric, *position, *normal;  // [3n]
+	RecordOutputs out;        // by ray index, or by ray and slot; null: not written
+};
+struct QueryArgs : RayQueryArgs {
+	uint8_t *hit;  // by ray index, or null.  CLOSEST: the hit flag; ANY: the occlusion flag
 };
 
 constexpr uint32_t QUERY_WAVES = 4u;
 
-// CLOSEST: the reference's scene_intersect with isect.distance = INFINITY on entry (the other fields 0, as the CPU oracle
-// starts them): the boolean, and the record of the nearest accepted triangle with the lowest leaf index among equal
-// distances (nearer()); where some triangle is accepted but none replaces the record (a distance of +inf or NaN) the
-// record keeps its entry values -- leaf 0, barycentrics and point 0, distance +inf.  The smooth normal is the reference's
-// get_smooth_normal for that record (src/intersect_kernel.cl:118-127, as the primary pass computes it).
-// ANY: the same boolean; a lane leaves the walk at its first accepted triangle.
-template <bool CLOSEST>
-__global__ __launch_bounds__(64 * QUERY_WAVES) void query_kernel(QueryArgs a) {
-	const uint32_t k = blockIdx.x * (64u * QUERY_WAVES) + threadIdx.x;
-	const bool live = k < a.n;  // (a partial last packet: its dead lanes walk nothing and write nothing)
-	uint32_t idx = k;
+// The ray of packet lane `k`: ray `idx` of the call.  A partial last packet's dead lanes (`live` false) get a ray that
+// walks nothing and write nothing.
+__device__ __forceinline__ Ray packet_ray(const RayQueryArgs &a, uint32_t k, bool &live, uint32_t &idx) {
+	live = k < a.n;
+	idx = k;
 	if (live && a.order)
 		idx = a.order[k];
 	float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f), d = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
@@ -164,49 +158,67 @@ __global__ __launch_bounds__(64 * QUERY_WAVES) void query_kernel(QueryArgs a) {
 		o = a.origins[idx];
 		d = a.directions[idx];
 	}
-	const Ray ray = make_ray(o.x, o.y, o.z, d.x, d.y, d.z);
-	const float max_distance = a.max_distance;
+	return make_ray(o.x, o.y, o.z, d.x, d.y, d.z);
+}
+
+// Barycentrics, point and smooth normal of a record into `slot` of the arrays that were asked for; `shaded` false: a
+// zero normal.
+__device__ __forceinline__ void store_record(const RecordOutputs &out, size_t slot, const float4 *shade, uint32_t leaf, bool shaded,
+                                             float b0, float b1, float b2, float px, float py, float pz) {
+	if (out.barycentric) {
+		out.barycentric[3u * slot + 0u] = b0;
+		out.barycentric[3u * slot + 1u] = b1;
+		out.barycentric[3u * slot + 2u] = b2;
+	}
+	if (out.position) {
+		out.position[3u * slot + 0u] = px;
+		out.position[3u * slot + 1u] = py;
+		out.position[3u * slot + 2u] = pz;
+	}
+	if (out.normal) {
+		float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+		if (shaded)
+			smooth_normal(shade, leaf, b0, b1, b2, nx, ny, nz);
+		out.normal[3u * slot + 0u] = nx;
+		out.normal[3u * slot + 1u] = ny;
+		out.normal[3u * slot + 2u] = nz;
+	}
+}
+
+// CLOSEST: the reference's scene_intersect with isect.distance = INFINITY on entry (the other fields 0, as the CPU oracle
+// starts them): the boolean, and the record of the nearest accepted triangle with the lowest leaf index among equal
+// distances (nearer()); where some triangle is accepted but none replaces the record (a distance of +inf or NaN) the
+// record keeps its entry values -- leaf 0, barycentrics and point 0, distance +inf.  The smooth normal is the reference's
+// get_smooth_normal for that record (smooth_normal, as the primary pass computes it).
+// ANY: the same boolean; a lane leaves the walk at its first accepted triangle.
+template <bool CLOSEST>
+__global__ __launch_bounds__(64 * QUERY_WAVES) void query_kernel(QueryArgs a) {
+	bool live;
+	uint32_t idx;
+	const Ray ray = packet_ray(a, blockIdx.x * (64u * QUERY_WAVES) + threadIdx.x, live, idx);
 	bool alive = live, hit = false;
 	Hit best;
 	best.distance = __builtin_inff();
 	best.leaf = 0u;
 	best.s = best.t = 0.0f;
 	best.px = best.py = best.pz = 0.0f;
-	// the exact form of the shared walk: one wave-uniform node index `at`, each lane's own walk in `mine`
-	const uint32_t count = a.node_count;
-	uint32_t mine = 0u, at = 0u;
-	while (at < count) {
-		const u32x8 node = scalar_load_node(a.nodes_ptr, at);
-		const float4 lo = make_float4(__uint_as_float(node[0]), __uint_as_float(node[1]), __uint_as_float(node[2]), 0.0f);
-		const float4 hi = make_float4(__uint_as_float(node[4]), __uint_as_float(node[5]), __uint_as_float(node[6]), 0.0f);
-		const uint32_t skip = node[3], leaf = node[7];
-		const bool box = exact_box(lo, hi, ray, max_distance, alive, at, skip, mine);
-		const unsigned long long hit_mask = wave_ballot(box);
-		if (hit_mask != 0ull && leaf != NONE) {
-			const float4 *tri = a.tris_ptr + LEAF_F4 * leaf + LEAF_TRI_F4;
-			const float4 q0 = tri[0], q1 = tri[1], q2 = tri[2], q3 = tri[3];
-			if (box) {
-				const TriResult tr = tri_eval<CLOSEST>(q0, q1, q2, q3, ray);
-				if (tr.accepted) {
-					hit = true;
-					if (CLOSEST) {
-						if (nearer(tr.distance, leaf, best)) {  // reference :106-112
-							best.distance = tr.distance;
-							best.leaf = leaf;
-							best.s = tr.s;
-							best.t = tr.t;
-							best.px = tr.px; best.py = tr.py; best.pz = tr.pz;
-						}
-					} else {
-						alive = false;
-					}
+	exact_walk(a.nodes_ptr, a.node_count, ray, a.max_distance, alive, [&](uint32_t leaf, bool box) {
+		const float4 *tri = a.tris_ptr + LEAF_F4 * leaf + LEAF_TRI_F4;
+		const float4 q0 = tri[0], q1 = tri[1], q2 = tri[2], q3 = tri[3];
+		if (box) {
+			const TriResult tr = tri_eval<CLOSEST>(q0, q1, q2, q3, ray);
+			if (tr.accepted) {
+				hit = true;
+				if (CLOSEST) {
+					if (nearer(tr.distance, leaf, best))
+						take(best, tr, leaf);
+				} else {
+					alive = false;
 				}
 			}
-			if (!CLOSEST && wave_ballot(alive) == 0ull)
-				break;
 		}
-		at = (uint32_t) __builtin_amdgcn_readfirstlane((int) (at + (hit_mask != 0ull ? 1u : skip)));
-	}
+		return !CLOSEST && wave_ballot(alive) == 0ull;
+	});
 	if (!live)
 		return;
 	if (a.hit)
@@ -214,36 +226,12 @@ __global__ __launch_bounds__(64 * QUERY_WAVES) void query_kernel(QueryArgs a) {
 	if (!CLOSEST)
 		return;
 	const bool kept = hit && best.distance < __builtin_inff();  // (the record was replaced at least once)
-	const float b0 = kept ? 1.0f - best.s - best.t : 0.0f, b1 = kept ? best.s : 0.0f, b2 = kept ? best.t : 0.0f;
-	if (a.distance)
-		a.distance[idx] = best.distance;
-	if (a.leaf)
-		a.leaf[idx] = hit ? best.leaf : NONE;
-	if (a.barycentric) {
-		a.barycentric[3u * (size_t) idx + 0u] = b0;
-		a.barycentric[3u * (size_t) idx + 1u] = b1;
-		a.barycentric[3u * (size_t) idx + 2u] = b2;
-	}
-	if (a.position) {
-		a.position[3u * (size_t) idx + 0u] = kept ? best.px : 0.0f;
-		a.position[3u * (size_t) idx + 1u] = kept ? best.py : 0.0f;
-		a.position[3u * (size_t) idx + 2u] = kept ? best.pz : 0.0f;
-	}
-	if (a.normal) {
-		float nx = 0.0f, ny = 0.0f, nz = 0.0f;
-		if (hit) {
-			const float4 n0 = a.shade[3 * (size_t) best.leaf + 0];
-			const float4 n1 = a.shade[3 * (size_t) best.leaf + 1];
-			const float4 n2 = a.shade[3 * (size_t) best.leaf + 2];
-			nx = (n0.x * b0 + n1.x * b1) + n2.x * b2;
-			ny = (n0.y * b0 + n1.y * b1) + n2.y * b2;
-			nz = (n0.z * b0 + n1.z * b1) + n2.z * b2;
-			normalize3(nx, ny, nz);
-		}
-		a.normal[3u * (size_t) idx + 0u] = nx;
-		a.normal[3u * (size_t) idx + 1u] = ny;
-		a.normal[3u * (size_t) idx + 2u] = nz;
-	}
+	if (a.out.distance)
+		a.out.distance[idx] = best.distance;
+	if (a.out.leaf)
+		a.out.leaf[idx] = hit ? best.leaf : NONE;
+	store_record(a.out, idx, a.shade, best.leaf, hit, kept ? 1.0f - best.s - best.t : 0.0f, kept ? best.s : 0.0f, kept ? best.t : 0.0f,
+	             kept ? best.px : 0.0f, kept ? best.py : 0.0f, kept ? best.pz : 0.0f);
 }
 
 }  // namespace ocrt

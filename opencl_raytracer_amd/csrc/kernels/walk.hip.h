@@ -64,6 +64,30 @@ __device__ __forceinline__ u32x8 scalar_load_node(const float4 *nodes_ptr, uint3
 	return r;
 }
 
+// The exact form for one packet, from the root to the end of the `count` records at `nodes_ptr`: the wave-uniform node
+// index `at`, each lane's own walk in `mine`, a node by one scalar load, exact_box, and the step to the first child if
+// some lane's test passed, else past the subtree.  Every leaf some lane's test passed goes to `leaf_step(leaf, box)`
+// (`box`: this lane's test passed), which says -- wave-uniformly -- whether the walk ends there.  A lane leaves the walk
+// when the caller clears `alive` in its leaf step.
+template <class LeafStep>
+__device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t count, const Ray &ray, float max_distance, const bool &alive,
+                                           LeafStep &&leaf_step) {
+	uint32_t at = 0u, mine = 0u;
+	while (at < count) {
+		const u32x8 node = scalar_load_node(nodes_ptr, at);
+		const float4 lo = make_float4(__uint_as_float(node[0]), __uint_as_float(node[1]), __uint_as_float(node[2]), 0.0f);
+		const float4 hi = make_float4(__uint_as_float(node[4]), __uint_as_float(node[5]), __uint_as_float(node[6]), 0.0f);
+		const uint32_t skip = node[3], leaf = node[7];
+		const bool box = exact_box(lo, hi, ray, max_distance, alive, at, skip, mine);
+		const bool any = wave_ballot(box) != 0ull;
+		if (any && leaf != NONE) {
+			if (leaf_step(leaf, box))
+				break;
+		}
+		at = (uint32_t) __builtin_amdgcn_readfirstlane((int) (at + (any ? 1u : skip)));
+	}
+}
+
 // The node steps of the fast form, hand-scheduled.  From byte offset `at` on it walks the packet through the
 // PADDED copy of the tree (scene_pack.cc, pad_walk_boxes): per node a conservative slab test on values fetched by a
 // scalar load -- t = fma(plane, inv, oi) with oi = -(o * inv) rounded once, near/far planes picked by the sign of
@@ -521,33 +545,18 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 		return;
 	}
 	const Ray ray = ray_in;
-	uint32_t mine = 0u;
-	uint32_t at = 0u;
-	while (at < count) {
-		const u32x8 node = scalar_load_node(nodes_ptr, at);
-		const float4 lo = make_float4(__uint_as_float(node[0]), __uint_as_float(node[1]), __uint_as_float(node[2]), 0.0f);
-		const float4 hi = make_float4(__uint_as_float(node[4]), __uint_as_float(node[5]), __uint_as_float(node[6]), 0.0f);
-		const uint32_t skip = node[3], leaf = node[7];
-		const bool here = alive && mine == at;
-		const bool box = here && slab_hit(lo, hi, ray, max_distance);
-		mine = here ? (box ? at + 1u : at + skip) : mine;
-		const unsigned long long hit_mask = wave_ballot(box);
-		if (hit_mask != 0ull && leaf != NONE) {
-			const float4 *tri = tris_ptr + LEAF_F4 * leaf + LEAF_TRI_F4;
-			const float4 q0 = tri[0], q1 = tri[1], q2 = tri[2], q3 = tri[3];
-			if (box) {
-				const TriResult tr = tri_eval<false>(q0, q1, q2, q3, ray);
-				if (tr.accepted) {
-					atomicAdd(occluded, 1u);
-					alive = false;
-				}
+	exact_walk(nodes_ptr, count, ray, max_distance, alive, [&](uint32_t leaf, bool box) {
+		const float4 *tri = tris_ptr + LEAF_F4 * leaf + LEAF_TRI_F4;
+		const float4 q0 = tri[0], q1 = tri[1], q2 = tri[2], q3 = tri[3];
+		if (box) {
+			const TriResult tr = tri_eval<false>(q0, q1, q2, q3, ray);
+			if (tr.accepted) {
+				atomicAdd(occluded, 1u);
+				alive = false;
 			}
-			if (wave_ballot(alive) == 0ull)
-				break;
 		}
-		at = (uint32_t) __builtin_amdgcn_readfirstlane((int) (at + (hit_mask != 0ull ? 1u : skip)));
-	}
+		return wave_ballot(alive) == 0ull;
+	});
 }
-
 
 }  // namespace ocrt

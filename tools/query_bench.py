@@ -8,10 +8,12 @@
   (d) the host-memory entry point end to end (wall clock, copies included) for (c)
   (m) multi-hit queries (include/rt_hip_multihit.h) on the rays of (a) and (c): count_hits and k = 1, 4, 16 with every
       output, beside trace_closest on the same rays in the same run (ratio_to_closest: time over the closest hit's)
+  (o) ambient-occlusion queries (include/rt_hip_ao.h) at the closest hits of (a), position and smooth normal in image order,
+      with the default AO options (UNIFORM): host.ambient_occlusion on device tensors, sorted and sort=False
 Device entry points on pre-loaded buffers; the time of a call is rt_last_query_ms (HIP events around sort + walk); the
 median of --reps calls after --warmup.
 
-    python3 tools/query_bench.py [--reps 20] [--warmup 3] [--random 4194304] [--sets abcdm]
+    python3 tools/query_bench.py [--reps 20] [--warmup 3] [--random 4194304] [--sets abcdmo]
 """
 import argparse
 import ctypes as C
@@ -70,7 +72,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--random", type=int, default=4 << 20)
-    ap.add_argument("--sets", default="abcdm", help="which of the sets (a) (b) (c) (d) (m) to run")
+    ap.add_argument("--sets", default="abcdmo", help="which of the sets (a) (b) (c) (d) (m) (o) to run")
     args = ap.parse_args()
     if "b" in args.sets and not set("am") & set(args.sets):
         ap.error("--sets: (b) starts from the camera hits, which (a) or (m) cast")
@@ -152,6 +154,8 @@ def main():
         multihit_leg("camera", to, td, n, out)
     if "b" in args.sets:
         ao_like_rays(out, dev, opt, host, args, device_call, frame_ms, emit)
+    if "o" in args.sets:
+        ao_queries(out, to, td, n, host, args, device_call, emit)
     del to, td, out
     random_rays(scene, dev, host, args, device_call, outputs, emit, multihit_leg)
     host.close()
@@ -180,6 +184,26 @@ def ao_like_rays(out, dev, opt, host, args, device_call, frame_ms, emit):
         emit(set="b_ao_like_occluded", order=name, rays=nb, directions_per_hit=len(table), median_ms=med, min_ms=best,
              grays_per_s=nb / med / 1e6, frame_ao_kernel_ms=ao_ms, ratio_to_ao_kernel=med / ao_ms if ao_ms else None)
     del to, td, ob
+
+
+def ao_queries(out, to, td, n, host, args, device_call, emit):
+    import torch
+
+    # (o) the fused AO query at the camera's closest hits
+    device_call(True, to, td, n, 100000.0, 0, out)()
+    torch.cuda.synchronize()
+    hit = out["hit"].bool()
+    # (N, 4) already, so that a call pads nothing; ready before the first call: the queries run on the host's own stream
+    points = torch.nn.functional.pad(out["position"][hit], (0, 1)).contiguous()
+    normals = torch.nn.functional.pad(out["normal"][hit], (0, 1)).contiguous()
+    torch.cuda.synchronize()
+    rays_per_point, _ = host.ao_rays_per_point
+    np_, nr = int(points.shape[0]), int(points.shape[0]) * rays_per_point
+    for sort, name in ((True, "sorted"), (False, "unsorted")):
+        med, best = timed(host, lambda sort=sort: host.ambient_occlusion(points, normals, sort=sort), args.reps, args.warmup)
+        emit(set="o_ao_query", order=name, points=np_, rays_per_point=rays_per_point, rays=nr, median_ms=med, min_ms=best,
+             grays_per_s=nr / med / 1e6)
+    del points, normals
 
 
 def random_rays(scene, dev, host, args, device_call, outputs, emit, multihit_leg):
