@@ -92,6 +92,12 @@ int rt_debug_set_tile_order(rt_host *h, const uint32_t *order, uint32_t slots, c
  * it that there were some. */
 int rt_debug_split_tiles(rt_host *h, uint32_t out[8]);
 
+/* What the closest-hit walk's pruning rests on in the uploaded scene (scene_pack.h, WalkArray): `prune_margin` (+inf: this
+ * host does not prune -- a one-shot host, or a scene no prunable tree can be formed of), the bytes at the head of the primary
+ * rays' records inside which no limit is lowered (the faces without a bound) and the bytes of those records.  A read-only
+ * copy; out pointers may be NULL.  RT_E_STATE without a scene. */
+int rt_debug_prune_facts(rt_host *h, float *prune_margin, uint32_t *unpruned_bytes, uint32_t *primary_bytes);
+
 /* Which form a frame with UNIFORM ambient occlusion takes on this host: 0 = the library's rule (two kernels), 1 = the
  * fused frame kernel (primary rays and ambient occlusion in one persistent launch, kernels/frame.hip.h: an experiment
  * that renders the same bits and measured 2-9 % slower, profiles/r05_notes.md), 2 = two kernels.  Same image either way.

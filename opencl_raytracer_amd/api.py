@@ -215,6 +215,7 @@ _SIGNATURES = {
     "rt_debug_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_set_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rt_debug_split_tiles": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_debug_prune_facts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_set_frame_form": (C.c_int, [C.c_void_p, C.c_int]),
     "rt_debug_frame_is_fused": (C.c_int, [C.c_void_p]),
     "rt_debug_poison_hit_list": (C.c_int, [C.c_void_p]),
@@ -684,6 +685,13 @@ class Host:
         out = np.zeros(8, np.uint32)
         _check(load_library().rt_debug_split_tiles(self._h, out.ctypes.data))
         return out
+
+    def prune_facts(self) -> dict:
+        """What the closest-hit walk's pruning rests on in the uploaded scene (include/rt_hip_debug.h, rt_debug_prune_facts):
+        `prune_margin` is finite on a host that prunes (a stream host) and +inf on one that does not (a one-shot host)."""
+        margin, unpruned, primary = C.c_float(), C.c_uint32(), C.c_uint32()
+        _check(load_library().rt_debug_prune_facts(self._h, C.byref(margin), C.byref(unpruned), C.byref(primary)))
+        return {"prune_margin": float(margin.value), "unpruned_bytes": unpruned.value, "primary_bytes": primary.value}
 
     def walk_entries(self) -> dict:
         """The intervals of the node array the tiles' any-hit packets walk (include/rt_hip_debug.h, rt_walk_entries)."""

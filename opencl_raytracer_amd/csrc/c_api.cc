@@ -649,6 +649,21 @@ int rt_debug_split_tiles(rt_host *h, uint32_t out[8]) {
 	});
 }
 
+int rt_debug_prune_facts(rt_host *h, float *prune_margin, uint32_t *unpruned_bytes, uint32_t *primary_bytes) {
+	if (!h)
+		return fail(RT_E_INVALID, "null argument");
+	if (!h->dev->deviceScene())
+		return fail(RT_E_STATE, "no scene on the device");
+	const ocrt::KernelParams &kp = h->dev->params();  // (as the launches get them)
+	if (prune_margin)
+		*prune_margin = kp.prune_margin;
+	if (unpruned_bytes)
+		*unpruned_bytes = kp.unpruned_bytes;
+	if (primary_bytes)
+		*primary_bytes = kp.primary_walk_bytes;
+	return RT_OK;
+}
+
 int rt_debug_set_frame_form(rt_host *h, int form) {
 	if (!h)
 		return fail(RT_E_INVALID, "null argument");

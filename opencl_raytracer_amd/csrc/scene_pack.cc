@@ -17,7 +17,8 @@ namespace ocrt {
 namespace {
 
 // Debug knobs are environment variables that only the A/B build reads (make EXTRA_DEFS=-DOCRT_DEBUG_KNOBS): the
-// product library never looks at the environment for them.  None changes results.
+// product library never looks at the environment for them.  None changes results but ONE, on purpose: OCRT_PRUNE_GROWTH
+// (leaf_growth below) scales what the closest-hit walk's pruning rests on, so that a test can show that a frame notices.
 const char *debug_knob(const char *name) {
 #ifdef OCRT_DEBUG_KNOBS
 	return std::getenv(name);
@@ -28,6 +29,32 @@ const char *debug_knob(const char *name) {
 }
 
 }  // namespace
+
+// scene_pack.h; the comment in make_walk_array argues the bound, tests/prune_bound_sweep.cc sweeps it
+double leaf_growth(const TriRec &t, double eye_distance) {
+	const double inf = std::numeric_limits<double>::infinity();
+	if (std::sqrt((double) t.n[0] * t.n[0] + (double) t.n[1] * t.n[1] + (double) t.n[2] * t.n[2]) < 9.9e-7)
+		return 0.0;  // never accepted
+	const double uu = t.uu, vv = t.vv, area2 = std::fabs((double) t.D);
+	const double lu = std::sqrt(uu), lv = std::sqrt(vv);
+	double coordinate = 0.0;
+	for (unsigned k = 0; k < 3; ++k)
+		coordinate = std::fmax(coordinate, std::fabs((double) t.ta[k]));
+	const double k = area2 > 0.0 ? uu * vv / area2 : inf;
+	const double r = lu > lv ? lu / lv : lv / lu;
+	const double eta = 128.0 * std::ldexp(1.0, -24) * k * r;
+	// (the bound holds up to eta = 1/4; but a box grown by a good part of its triangle's size is entered by packets that
+	// have no business with it -- the HARDER interior stand-in's 17-unit slivers at eta = 0.2 grew by 27 units and its
+	// primary pass from 0.098 to 0.156 ms --: from 1/32 on a face counts as one without a bound and keeps its own box)
+	if (!(eta < 1.0 / 32.0))  // (NaN too)
+		return inf;
+	double grow = (2e-5 + 4.0 * eta) * (lu + lv) + 32.0 * std::ldexp(1.0, -24) * (coordinate + lu + lv + eye_distance);
+	if (!(grow < 1e30))
+		return inf;
+	if (const char *factor = debug_knob("OCRT_PRUNE_GROWTH"))  // (debug knob, the A/B build's alone: the one that changes results)
+		grow *= std::atof(factor);
+	return grow;
+}
 
 PackedScene pack_scene(const std::vector<uint32_t> &faces, const std::vector<uint32_t> &nodes,
                        const std::vector<Vec3f> &aabbs, const std::vector<Vec3f> &vertices,
@@ -398,50 +425,26 @@ WalkArray make_walk_array(const PackedScene &scene, float ao_max_distance, bool 
 	//     parameter lies in the box too, on every axis, however large the reciprocal direction);
 	//   * a triangle with |n| < 9.9e-7 is never accepted (|dot(n, d)| < 1e-6 for every unit d, :80) and needs nothing;
 	// and the inner boxes are the unions of their children's again.
-	// The rule for the triangles this gives no usable bound for (eta of 1/32 or more: needles, long slivers, whose accepted
-	// region Cramer's rule makes fuzzy by a good part of their edge lengths): they get no box that could promise anything.
-	// They are taken out of this copy's tree and put into a small tree of their own (their own boxes), which becomes the
-	// FIRST child of the root: the walk meets them before anything else, and while it is in there (`unpruned_bytes`) no
-	// lane's limit is lowered -- they are tested as the reference tests them.  (Both interior stand-ins have a few dozen
-	// such faces among 75 000.)  Only a scene of nothing but such faces, or a tree this cannot be done to, is not pruned at
-	// all (prune_margin = +inf).  What is left for prune_margin: the rounding of the two distances compared, 1e-5 of the
-	// largest magnitude that enters them -- the boxes' coordinates and the eye's distance from the origin.
+	// ONE rule (leaf_growth, scene_pack.h): a face with eta < 1/32 gets a grown box; any other face (needles, long slivers,
+	// whose accepted region Cramer's rule makes fuzzy by a good part of their edge lengths) gets no box that could promise
+	// anything.  Those are taken out of this copy's tree and put into a small tree of their own (their own boxes), which
+	// becomes the FIRST child of the root: the walk meets them before anything else, and while it is in there
+	// (`unpruned_bytes`) no lane's limit is lowered -- they are tested as the reference tests them -- and the scene is pruned
+	// all the same.  (Both interior stand-ins have a few dozen such faces among 75 000.)  prune_margin is +inf only when no
+	// prunable tree can be formed: a scene of nothing but such faces, or a tree this cannot be done to.
+	// tests/prune_bound_sweep.cc throws adversarial triangles and rays at the rule.  What is left for prune_margin: the
+	// rounding of the two distances compared, 1e-5 of the largest magnitude that enters them -- the boxes' coordinates and
+	// the eye's distance from the origin.
 	bool prunable = for_a_stream;
 	out.unpruned_bytes = 0;
 	if (!prunable) {
 		by_camera = nodes;  // (a one-shot host: nothing re-ordered, nothing grown, nothing pruned)
 		out.prune_margin = std::numeric_limits<float>::infinity();
 	} else {
-		const auto never_accepted = [&](const TriRec &t) {
-			return std::sqrt((double) t.n[0] * t.n[0] + (double) t.n[1] * t.n[1] + (double) t.n[2] * t.n[2]) < 9.9e-7;
-		};
-		// how far a leaf's box has to grow; +inf: no bound
-		const auto growth_of = [&](uint32_t leaf) {
-			if (leaf >= scene.tris.size())
-				return std::numeric_limits<double>::infinity();
-			const TriRec &t = scene.tris[leaf];
-			if (never_accepted(t))
-				return 0.0;
-			const double uu = t.uu, vv = t.vv, area2 = std::fabs((double) t.D);
-			const double lu = std::sqrt(uu), lv = std::sqrt(vv);
-			double coordinate = 0.0;
-			for (unsigned k = 0; k < 3; ++k)
-				coordinate = std::fmax(coordinate, std::fabs((double) t.ta[k]));
-			const double k = area2 > 0.0 ? uu * vv / area2 : std::numeric_limits<double>::infinity();
-			const double r = lu > lv ? lu / lv : lv / lu;
-			const double eta = 128.0 * std::ldexp(1.0, -24) * k * r;
-			// (the bound holds up to eta = 1/4; but a box grown by a good part of its triangle's size is entered by packets that
-			// have no business with it -- the HARDER interior stand-in's 17-unit slivers at eta = 0.2 grew by 27 units and its
-			// primary pass from 0.098 to 0.156 ms --: from 1/32 on a face counts as one without a bound and keeps its own box)
-			if (!(eta < 1.0 / 32.0))  // (NaN too)
-				return std::numeric_limits<double>::infinity();
-			const double grow = (2e-5 + 4.0 * eta) * (lu + lv) + 32.0 * std::ldexp(1.0, -24) * (coordinate + lu + lv + eye_distance);
-			return grow < 1e30 ? grow : std::numeric_limits<double>::infinity();
-		};
-		// (once per triangle)
+		// how far each leaf's box has to grow (+inf: no bound), once per triangle
 		std::vector<float> growth(scene.tris.size());
 		for (size_t t = 0; t < scene.tris.size(); ++t) {
-			const double g = growth_of((uint32_t) t);
+			const double g = leaf_growth(scene.tris[t], eye_distance);
 			growth[t] = g < 1e30 ? std::nextafterf((float) g, std::numeric_limits<float>::infinity()) : std::numeric_limits<float>::infinity();
 		}
 		const auto grown_by = [&](uint32_t leaf) { return leaf < growth.size() ? (double) growth[leaf] : std::numeric_limits<double>::infinity(); };

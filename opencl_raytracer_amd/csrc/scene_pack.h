@@ -72,6 +72,12 @@ PackedScene pack_scene(const std::vector<uint32_t> &faces, const std::vector<uin
 // follow it -- child order, per-axis origin bounds, origin_limit, the leaves' growth and prune_margin --; the any-hit rays'
 // centre / half-extent copy does not (those rays start on the surfaces).
 WalkArray make_walk_array(const PackedScene &scene, float ao_max_distance, bool for_a_stream = true, const float *eye = nullptr);
+// How far a leaf's box grows in the primary rays' copy so that it holds every hit the reference's triangle test can accept
+// (make_walk_array's comment argues the bound): 0 for a face that is never accepted (|n| < 9.9e-7), +inf for a face without a
+// bound (eta >= 1/32: it goes to the unpruned head of that copy).  `eye_distance`: the eye's distance from the origin.
+// make_walk_array rounds the value to float, one ulp up.  (A/B build only: OCRT_PRUNE_GROWTH=<float> multiplies every finite
+// growth -- the test-only factor that shows that a too small growth is noticed.)
+double leaf_growth(const TriRec &t, double eye_distance);
 // make_walk_array into scene.walk (see PackedScene::walk).
 void prepare_walk_array(PackedScene &scene, float ao_max_distance, bool for_a_stream = true, const float *eye = nullptr);
 // The margin itself: the padded value of a box's lower (upper = false) or upper bound `b` for ray origins of

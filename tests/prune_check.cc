@@ -18,53 +18,17 @@
 
 #include "bvh.h"
 #include "mesh.h"
+#include "reference_tests.h"
 #include "scene_pack.h"
 
 using namespace ocrt;
 
-struct Accepted {
-	bool ok;
-	double distance;
-};
-// the reference's test on a TriRec, float operations in its order (the build: -ffp-contract=off)
-static Accepted reference_triangle(const TriRec &t, const float o[3], const float d[3]) {
-	const float w0[3] = { o[0] - t.ta[0], o[1] - t.ta[1], o[2] - t.ta[2] };
-	const float a = -((t.n[0] * w0[0] + t.n[1] * w0[1]) + t.n[2] * w0[2]);
-	const float b = (t.n[0] * d[0] + t.n[1] * d[1]) + t.n[2] * d[2];
-	if (std::fabs(b) < 0.000001f)
-		return { false, 0 };
-	const float r = a / b;
-	if (r < 0.0f)
-		return { false, 0 };
-	const float ip[3] = { o[0] + r * d[0], o[1] + r * d[1], o[2] + r * d[2] };
-	const float w[3] = { ip[0] - t.ta[0], ip[1] - t.ta[1], ip[2] - t.ta[2] };
-	const float wu = (t.u[0] * w[0] + t.u[1] * w[1]) + t.u[2] * w[2];
-	const float wv = (w[0] * t.v[0] + w[1] * t.v[1]) + w[2] * t.v[2];
-	const float s = (t.uv * wv - t.vv * wu) / t.D;
-	if (s < -0.00001f || (double) s > 1.00001)
-		return { false, 0 };
-	const float q = (t.uv * wu - t.uu * wv) / t.D;
-	if (q < -0.00001f || (double) (s + q) > 1.00001)
-		return { false, 0 };
-	const float e[3] = { ip[0] - o[0], ip[1] - o[1], ip[2] - o[2] };
-	return { true, (double) std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]) };
-}
+using reference_tests::Accepted;
+using reference_tests::reference_triangle;  // (the reference's test on a TriRec, float operations in its order: reference_tests.h)
 
 // near distance of a box along a ray, in double (the walk's own value is a lower bound of it: walk_margin_check.cc)
 static bool box_near(const NodeRec &n, const float o[3], const float d[3], double *near_out) {
-	double near = 0.0, far = std::numeric_limits<double>::infinity();
-	for (int k = 0; k < 3; ++k) {
-		if (d[k] == 0.0f) {
-			if (o[k] < n.lo[k] || o[k] > n.hi[k])
-				return false;
-			continue;
-		}
-		const double a = ((double) n.lo[k] - o[k]) / d[k], b = ((double) n.hi[k] - o[k]) / d[k];
-		near = std::fmax(near, std::fmin(a, b));
-		far = std::fmin(far, std::fmax(a, b));
-	}
-	*near_out = near;
-	return near <= far;
+	return reference_tests::box_near(n.lo, n.hi, o, d, near_out);
 }
 
 static PackedScene pack(Mesh &m) {
