@@ -98,14 +98,10 @@ int rt_debug_split_tiles(rt_host *h, uint32_t out[8]);
  * copy; out pointers may be NULL.  RT_E_STATE without a scene. */
 int rt_debug_prune_facts(rt_host *h, float *prune_margin, uint32_t *unpruned_bytes, uint32_t *primary_bytes);
 
-/* Which form a frame with UNIFORM ambient occlusion takes on this host: 0 = the library's rule (two kernels), 1 = the
- * fused frame kernel (primary rays and ambient occlusion in one persistent launch, kernels/frame.hip.h: an experiment
- * that renders the same bits and measured 2-9 % slower, profiles/r05_notes.md), 2 = two kernels.  Same image either way.
- * rt_debug_frame_is_fused: what the next frame will be.  rt_debug_poison_hit_list: overwrites the hit list (the hand-over
- * between the two ray passes) with NaN patterns -- a fused frame that read a record before its own primary work had
- * written it would show; frames of one scene are otherwise identical, and a stale record could never be seen. */
-int rt_debug_set_frame_form(rt_host *h, int form);
-int rt_debug_frame_is_fused(rt_host *h);
+/* Test aid for the hand-over between the two ray passes: overwrites the hit list (the records the primary pass leaves for
+ * the ambient-occlusion pass) and the per-hit occlusion counts with 0xFF bytes -- NaN patterns and counts of 2^32 - 1.
+ * Every frame must write both again before it reads them; frames of one scene are otherwise identical, so a frame that
+ * leaned on what the one before it left there could never be seen without this.  Waits for the host's frames first. */
 int rt_debug_poison_hit_list(rt_host *h);
 
 #ifdef __cplusplus

@@ -216,8 +216,6 @@ _SIGNATURES = {
     "rt_debug_set_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rt_debug_split_tiles": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_debug_prune_facts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "rt_debug_set_frame_form": (C.c_int, [C.c_void_p, C.c_int]),
-    "rt_debug_frame_is_fused": (C.c_int, [C.c_void_p]),
     "rt_debug_poison_hit_list": (C.c_int, [C.c_void_p]),
     # include/rt_hip_query.h
     "rt_trace_closest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
@@ -638,15 +636,8 @@ class Host:
         """Which form of the AO pass's node loop this host launches (include/rt_hip_debug.h, rt_set_ao_prefetch); same results."""
         _check(load_library().rt_set_ao_prefetch(self._h, int(on)))
 
-    def set_frame_form(self, form: str) -> None:
-        """"auto" (the library's rule), "fused" (both ray passes in one persistent launch) or "separate" (two kernels)."""
-        _check(load_library().rt_debug_set_frame_form(self._h, {"auto": 0, "fused": 1, "separate": 2}[form]))
-
-    @property
-    def frame_is_fused(self) -> bool:
-        return bool(load_library().rt_debug_frame_is_fused(self._h))
-
     def poison_hit_list(self) -> None:
+        """Test aid (include/rt_hip_debug.h): overwrites the hit list and the occlusion counts with 0xFF between frames."""
         _check(load_library().rt_debug_poison_hit_list(self._h))
 
     def expect_frames(self, frames: int) -> None:

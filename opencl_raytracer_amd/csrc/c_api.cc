@@ -664,14 +664,6 @@ int rt_debug_prune_facts(rt_host *h, float *prune_margin, uint32_t *unpruned_byt
 	return RT_OK;
 }
 
-int rt_debug_set_frame_form(rt_host *h, int form) {
-	if (!h)
-		return fail(RT_E_INVALID, "null argument");
-	return guarded([&] { h->dev->setFrameForm(form); });
-}
-
-int rt_debug_frame_is_fused(rt_host *h) { return h && h->dev->frameIsFused() ? 1 : 0; }
-
 int rt_debug_poison_hit_list(rt_host *h) {
 	if (!h)
 		return fail(RT_E_INVALID, "null argument");

@@ -138,15 +138,11 @@ DeviceRenderer::DeviceRenderer(const RayTracer::Options &options, int device_, u
 	d_tile_hits = device_alloc(tile_count * sizeof(uint32_t));
 	d_tile_base = device_alloc(tile_count * sizeof(uint32_t));
 	d_order = device_alloc(order_slots * sizeof(uint32_t));
-	d_order_need = device_alloc((order_slots ? order_slots : 1) * sizeof(uint32_t));
 	{  // (2 x 2 tile blocks: whole strips x pairs of rows)
 		const size_t padded_x = (size_t) ((kp.tiles_x + MAX_STRIP_TILES - 1) / MAX_STRIP_TILES) * MAX_STRIP_TILES;
-		d_primary_order = device_alloc((padded_x / 2 * ((kp.local_tile_rows + 1) / 2) + 1) * sizeof(uint32_t));
 		blocks_by_cost_capacity = padded_x / 2 * ((kp.local_tile_rows + 1) / 2) + 8;
 		d_blocks_by_cost = device_alloc(blocks_by_cost_capacity * sizeof(uint32_t));
 	}
-	d_tile_ready = device_alloc((tile_count ? tile_count : 1) * sizeof(uint32_t));
-	OCRT_HIP(hipMemsetAsync(d_tile_ready, 0, (tile_count ? tile_count : 1) * sizeof(uint32_t), (hipStream_t) stream));
 	d_counters = device_alloc(sizeof(FrameCounters));
 	OCRT_HIP(hipMemsetAsync(d_counters, 0, sizeof(FrameCounters), (hipStream_t) stream));  // (once: the kernels keep it clean, device_types.h)
 	{
@@ -186,10 +182,7 @@ DeviceRenderer::~DeviceRenderer() {
 	device_free(d_tile_hits);
 	device_free(d_tile_base);
 	device_free(d_order);
-	device_free(d_primary_order);
-	device_free(d_order_need);
 	device_free(d_blocks_by_cost);
-	device_free(d_tile_ready);
 	device_free(d_counters);
 	if (own_stream)
 		(void) hipStreamDestroy((hipStream_t) own_stream);
@@ -301,14 +294,13 @@ void DeviceRenderer::sizeHitList(const DeviceRenderer *layout_from) {
 	if (tile_count == 0 || !has_ao) {
 		blocks_by_cost_host.clear();  // (no pass has counted anything: the primary pass keeps its spatial mapping)
 		order_host.clear();
-		primary_order_host.clear();
 		d_hits = device_alloc(sizeof(HitRec));  // (never read: no sub-pixel is left pending)
 		d_occluded = device_alloc(sizeof(uint32_t));
 		allocEntries(sizeof(uint32_t) * 2);
 		OCRT_HIP(hipMemsetAsync(d_tile_base, 0, tile_count * sizeof(uint32_t), (hipStream_t) stream));
 		OCRT_HIP(hipStreamSynchronize((hipStream_t) stream));
 		// A stream of frames without ambient occlusion: one pass of the primary kernel tells what its tiles cost (the leaves
-		// their packets stop at), and the frames' workgroups take the costly 2 x 2 blocks first (orderPrimaryBlocks).
+		// their packets stop at), and the frames' workgroups take the costly 2 x 2 blocks first (orderBlocksByCost).
 		if (tile_count != 0 && expected_frames >= FRAMES_WORTH_INTERVALS && PRIMARY_BY_COST_OK(kp) && primary_by_cost && scene_on_device) {
 			launch_primary(scene_on_device->buffers(), (float *) d_image, nullptr, nullptr, d_tile_hits, d_tile_base, d_counters, kp, stream);
 			OCRT_HIP(hipGetLastError());
@@ -406,27 +398,6 @@ void DeviceRenderer::setCamera(const CameraPose &given) {
 	kp.shared_device = device_share > 1u ? 1 : 0;
 }
 
-bool DeviceRenderer::fusedFrame() const {
-	// (the fused frame experiment has no posed form: a renderer with a camera pose renders its frames as two kernels)
-	const bool possible = !pose_set && kp.ao_mode == AO_UNIFORM && kp.ao_dirs > 0 && kp.shared_walk && tile_count > 0 && kp.tiles_x < 65536u &&
-	                      kp.local_tile_rows < 65536u && !primary_order_host.empty();
-	// Measured and NOT the rule (profiles/r05_notes.md): the fused frame renders the same bits, but a frame on its own takes
-	// 2-9 % LONGER with it than as two kernels -- headline 1.09 against 1.07 ms, interior 1080p 1.08 against 1.02, 4K 3.74
-	// against 3.43 -- whether the primary work is taken at the head of a group's turn or a little ahead of the any-hit work
-	// all through the frame: primary waves that are tied to a persistent workgroup's barriers hold their wave slots for the
-	// block's slowest tile, and what the launch boundary cost (the chip draining and filling once) is less than that.  The
-	// kernel stays reachable for experiments (rt_debug_set_frame_form) and under test (tests/test_fused_frame.py).
-	return possible && frame_form == FrameForm::FUSED;
-}
-
-void DeviceRenderer::setFrameForm(int form) {
-	const FrameForm want = form == 1 ? FrameForm::FUSED : form == 2 ? FrameForm::SEPARATE : FrameForm::AUTO;
-	if (want == frame_form)
-		return;
-	frame_form = want;
-	++scene_version;  // (a captured frame bakes its kernels in)
-}
-
 void DeviceRenderer::poisonHitList() {
 	useDevice();
 	synchronize();
@@ -436,16 +407,6 @@ void DeviceRenderer::poisonHitList() {
 		OCRT_HIP(hipMemsetAsync(d_hits, 0xFF, hit_slots * sizeof(HitRec), (hipStream_t) stream));
 		OCRT_HIP(hipMemsetAsync(d_occluded, 0xFF, hit_slots * sizeof(uint32_t), (hipStream_t) stream));
 		OCRT_HIP(hipStreamSynchronize((hipStream_t) stream));
-	}
-}
-
-void DeviceRenderer::checkFrameHealth() {
-	uint32_t stalled = 0;
-	OCRT_HIP(hipMemcpy(&stalled, (const char *) d_counters + offsetof(FrameCounters, stalled), sizeof stalled, hipMemcpyDeviceToHost));
-	if (stalled) {
-		OCRT_HIP(hipMemsetAsync((char *) d_counters + offsetof(FrameCounters, stalled), 0, sizeof stalled, (hipStream_t) stream));
-		OCRT_HIP(hipStreamSynchronize((hipStream_t) stream));
-		throw DeviceError("the fused frame kernel waited in vain for a tile's hit records (" + std::to_string(stalled) + " waves gave up): the frame is not valid");
 	}
 }
 
@@ -475,22 +436,15 @@ void DeviceRenderer::launchFrame(void *device_u8, void *ao_start, void *ao_stop,
 #endif
 	const SceneBuffers scene = scene_on_device->buffers();
 	const uint32_t workgroups = ao_blocks_override ? ao_blocks_override : aoWorkgroups();
-	if (fusedFrame() && !tile_cost_out) {
-		// the two ray passes as one persistent launch (kernels/frame.hip.h); the events bracket it
-		launch_frame(scene, (float *) d_image, d_hits, d_occluded, d_tile_hits, d_order, d_primary_order, d_order_need, d_tile_ready, d_tile_base,
-		             d_tile_entry, d_counters, kp, workgroups, ao_prefetch, stream, ao_start, ao_stop);
-		OCRT_HIP(hipGetLastError());
-	} else {
-		launch_primary(scene, (float *) d_image, d_hits, d_occluded, d_tile_hits, d_tile_base, d_counters, kp, stream,
-		               primary_by_cost && PRIMARY_BY_COST_OK(kp) && kp.primary_list_stride ? d_blocks_by_cost : nullptr);
-		OCRT_HIP(hipGetLastError());
+	launch_primary(scene, (float *) d_image, d_hits, d_occluded, d_tile_hits, d_tile_base, d_counters, kp, stream,
+	               primary_by_cost && PRIMARY_BY_COST_OK(kp) && kp.primary_list_stride ? d_blocks_by_cost : nullptr);
+	OCRT_HIP(hipGetLastError());
 #ifdef OCRT_STAMPS  // (instrumented build: the AO pass takes the minimum of its waves' start times into this slot)
-		OCRT_HIP(hipMemsetAsync((char *) d_counters + offsetof(FrameCounters, stamp) + 7 * sizeof(unsigned long long), 0xFF, sizeof(unsigned long long), s));
+	OCRT_HIP(hipMemsetAsync((char *) d_counters + offsetof(FrameCounters, stamp) + 7 * sizeof(unsigned long long), 0xFF, sizeof(unsigned long long), s));
 #endif
-		launch_ao(scene, d_hits, d_occluded, d_order, d_tile_base, d_tile_entry, d_counters, kp, workgroups, ao_prefetch, stream, ao_start, ao_stop,
-		          tile_cost_out);
-		OCRT_HIP(hipGetLastError());
-	}
+	launch_ao(scene, d_hits, d_occluded, d_order, d_tile_base, d_tile_entry, d_counters, kp, workgroups, ao_prefetch, stream, ao_start, ao_stop,
+	          tile_cost_out);
+	OCRT_HIP(hipGetLastError());
 	launch_finish((float *) d_image, d_hits, d_occluded, d_tile_base, (unsigned char *) device_u8, kp, opts.width, grid, local_out_rows, stream, d_counters);
 	OCRT_HIP(hipGetLastError());
 }
@@ -774,7 +728,6 @@ void DeviceRenderer::synchronize() {
 
 void DeviceRenderer::downloadFloat(float *host_image) {
 	synchronize();
-	checkFrameHealth();
 	const size_t row_bytes = (size_t) rt.totalWidth * sizeof(float);
 	if (part.nranks == 1) {  // local rows are the image's rows (plus, possibly, padding below it)
 		OCRT_HIP(hipMemcpy(host_image, d_image, row_bytes * rt.totalHeight, hipMemcpyDeviceToHost));
@@ -839,8 +792,6 @@ RenderStats DeviceRenderer::stats() {
 	}
 	FrameCounters c{};
 	OCRT_HIP(hipMemcpy(&c, d_counters, sizeof c, hipMemcpyDeviceToHost));
-	if (c.stalled)
-		checkFrameHealth();
 	{  // hit sub-pixels: the low byte of the words the frame's primary pass left per tile
 		std::vector<uint32_t> words(tile_count);
 		OCRT_HIP(hipMemcpy(words.data(), d_tile_hits, tile_count * sizeof(uint32_t), hipMemcpyDeviceToHost));

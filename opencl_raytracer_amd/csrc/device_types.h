@@ -1,6 +1,7 @@
 // device_types.h -- records shared by the host-side scene packer and the HIP
 // kernels.  Plain structs, no HIP headers, so host-only code can include it.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 namespace ocrt {
@@ -69,20 +70,15 @@ struct alignas(128) GroupQueue {
 	uint32_t work_tiles;  // non-empty tiles of the group (per upload)
 	uint32_t cost_sum;    // sum of their AO cost classes (per upload)
 	uint32_t hits;        // hit sub-pixels in the group's tiles (per upload)
-	// the fused frame kernel's primary work of the group (kernels/frame.hip.h): 2 x 2 tile blocks, in the order of
-	// FrameArgs::primary_order
-	uint32_t primary_blocks;  // how many (per upload)
 	// The first `split_units` units of the list -- its heaviest tiles, by measured cost -- are claimed HALF A TILE at a time
 	// from a cursor of their own (kernels/ao.hip.h; per upload; 0: none).  `head` starts at split_units.
 	uint32_t split_units;
-	uint32_t pad0[26];
-	// ... the claim cursors of the beginning of a frame in a line of their own (`head` is hammered at its end): the fused
-	// kernel's block cursor, the cursor of the split tiles
-	uint32_t primary_head;
+	uint32_t pad0[27];
+	// ... the cursor of the split tiles, claimed at the beginning of a frame, in a line of its own (`head` is hammered at its end)
 	uint32_t split_head;
-	uint32_t pad1[30];
+	uint32_t pad1[31];
 };
-static_assert(sizeof(GroupQueue) == 256, "two lines per queue");
+static_assert(sizeof(GroupQueue) == 256 && offsetof(GroupQueue, split_head) == 128, "two lines per queue, a cursor in each");
 struct FrameCounters {
 	GroupQueue queue[XCD_GROUPS];
 	unsigned long long occluded;  // occluded AO rays: summed from the hit list's counts when the statistic is asked for (occluded_sum_kernel)
@@ -91,8 +87,6 @@ struct FrameCounters {
 	// replayed from a captured hipGraph has no HIP events inside it that could be timed (hipEventElapsedTime refuses
 	// event-record nodes); these say when its passes ran.
 	unsigned long long tick_begin, tick_ao_begin, tick_ao_end;
-	uint32_t frame_seq;  // frames finished on these counters (the finishing kernel counts): what the fused frame kernel's flags are compared with
-	uint32_t stalled;    // fused frame kernel: waves that gave up waiting for a tile's hit records (0 in every healthy frame; DeviceRenderer reports it)
 #if defined(OCRT_STAMPS) || defined(OCRT_TAIL)
 	unsigned long long stamp[10 + 32 + 7 + 16];  // debug build: wave-time (10 ns ticks) per phase of the AO pass, jobs, packets
 #endif
@@ -146,8 +140,7 @@ struct KernelParams {
 	uint32_t strip_tiles;  // width, in tiles, of the vertical strips the image is dealt to the XCD groups in: a power of two,
 	                       // 2 by default (the finest deal: best balance, and a cache-resident scene does not care), wider for
 	                       // scenes far beyond the L2s, whose XCDs should not all fetch the same geometry (device_renderer.cc)
-	uint32_t primary_ahead; // fused frame kernel: how many 2 x 2 blocks beyond what a claim needs the group's primary work is taken (kernels/primary.hip.h, primary_top_up)
-	uint32_t primary_list_stride;  // primary_kernel with a list of its groups' blocks (DeviceRenderer::orderPrimaryBlocks): entries per group -- the grid is 8 x this; 0: no list
+	uint32_t primary_list_stride;  // primary_kernel with a list of its groups' blocks (DeviceRenderer::orderBlocksByCost): entries per group -- the grid is 8 x this; 0: no list
 	float prune_margin;  // closest-hit walk: a lane with a hit at distance d does not enter boxes whose near distance exceeds d (1 + 1e-5) + this (scene_pack.cc, make_walk_array: the rounding of the distances; +inf: no pruning in this scene)
 	uint32_t unpruned_bytes;  // ... and while the walk is below this byte offset of the plane-form records no lane's limit is lowered (the faces no box can promise anything about: make_walk_array)
 	uint32_t primary_walk_bytes;  // bytes of the plane-form walk records (the primary rays' tree; END records behind them)

@@ -40,6 +40,8 @@
 // varies 30x (background vs model, 29 rays per hit sub-pixel), so the frame used
 // to end on a long tail of half-empty CUs.  With the tiles' costs known after the
 // primary pass, claiming the costly blocks first packs them almost perfectly.
+// (Round 5 put both ray passes into one persistent launch once more, the hit records handed from workgroup to workgroup
+// inside it: bit-exact and 2-9 % slower than the two kernels, so it was taken out again -- profiles/r05_notes.md.)
 //
 // How rays walk the tree: the 64 rays of a wave share ONE node index ("shared
 // walk", see walk_collect below) -- nodes and triangles arrive by
@@ -67,7 +69,6 @@
 #include "kernels/walk.hip.h"
 #include "kernels/primary.hip.h"
 #include "kernels/ao.hip.h"
-#include "kernels/frame.hip.h"
 #include "kernels/entry.hip.h"
 #include "kernels/finish.hip.h"
 #include "kernels/query.hip.h"
@@ -151,7 +152,7 @@ void launch_primary(const SceneBuffers &scene, float *image, void *hits, void *o
 	if (P.tiles_x * P.local_tile_rows == 0)
 		return;
 	const uint32_t strips = (P.tiles_x + P.strip_tiles - 1u) / P.strip_tiles, row_blocks = (P.local_tile_rows + PRIMARY_ROWS - 1u) / PRIMARY_ROWS;
-	// (with a list -- DeviceRenderer::orderPrimaryBlocks -- every group's workgroups take its entries one by one)
+	// (with a list -- DeviceRenderer::orderBlocksByCost -- every group's workgroups take its entries one by one)
 	const uint32_t blocks = blocks_by_cost && P.primary_list_stride && PRIMARY_WAVES == 4u ? XCD_GROUPS * P.primary_list_stride
 	                                                                                        : XCD_GROUPS * ((strips + XCD_GROUPS - 1u) >> 3) * row_blocks * (P.strip_tiles >> 1);
 	auto launch = [&](auto kernel) {
@@ -252,57 +253,6 @@ void launch_ao(const SceneBuffers &scene, void *hits, void *occluded_of, void *o
 			launch(ao_kernel<AO_UNIFORM, true, false>);
 	} else
 		launch(ao_kernel<AO_RANDOM, true>);
-}
-
-// The two ray passes as ONE persistent launch (kernels/frame.hip.h): UNIFORM ambient occlusion, the shared walk.
-// `primary_order`, `tile_ready`: DeviceRenderer::orderTiles / its flag array.
-void launch_frame(const SceneBuffers &scene, float *image, void *hits, void *occluded_of, void *tile_hits, void *order,
-                  const void *primary_order, const void *order_need, void *tile_ready, const void *tile_base, const void *tile_entry, void *counters,
-                  const KernelParams &params, uint32_t workgroups, bool prefetch, void *stream, void *event_before, void *event_after) {
-	if (params.tiles_x * params.local_tile_rows == 0)
-		return;
-	hipStream_t s = (hipStream_t) stream;
-	KernelParams P = params;
-	// persistent grid: what the chip holds, or -- a small image -- what there is to do: a workgroup per 2 x 2 tile block
-	// of the primary work or per (tile, four directions) of the ambient-occlusion work, whichever is more
-	{
-		const uint64_t blocks = (uint64_t) ((P.tiles_x + 1u) / 2u) * ((P.local_tile_rows + 1u) / 2u);
-		const uint64_t units = ((uint64_t) P.tiles_x * P.local_tile_rows * P.ao_dirs + AO_WAVES - 1) / AO_WAVES;
-		const uint64_t most = blocks > units ? blocks : units;
-		if (most < workgroups)
-			workgroups = (uint32_t) (most ? most : 1u);
-	}
-	const uint32_t waves_per_group = (workgroups * AO_WAVES + XCD_GROUPS - 1u) / XCD_GROUPS;
-	P.ao_guide = P.ao_guide * (waves_per_group ? waves_per_group : 1u);
-	P.ao_claim_div = waves_per_group ? waves_per_group : 1u;
-	FrameArgs args{};
-	args.walk_ptr = (const float4 *) scene.walk;
-	args.tris_ptr = (const float4 *) scene.tris;
-	args.nodes_ptr = (const float4 *) scene.nodes;
-	args.shade = (const float4 *) scene.shade;
-	args.ao_table = (const float4 *) scene.ao_table;
-	args.image = image;
-	args.hits = (HitRec *) hits;
-	args.occluded_of = (uint32_t *) occluded_of;
-	args.tile_hits = (uint32_t *) tile_hits;
-	args.order = (const uint32_t *) order;
-	args.tile_base = (const uint32_t *) tile_base;
-	args.tile_entry = (const uint2 *) tile_entry;
-	args.counters = (FrameCounters *) counters;
-	args.primary_order = (const uint32_t *) primary_order;
-	args.order_need = (const uint32_t *) order_need;
-	args.tile_ready = (uint32_t *) tile_ready;
-	if (P.primary_ahead == 0u)  // the rule: a block per workgroup of the group
-		P.primary_ahead = (workgroups + XCD_GROUPS - 1u) / XCD_GROUPS;
-	args.P = P;
-	if (event_before)
-		(void) hipEventRecord((hipEvent_t) event_before, s);
-	if (prefetch)
-		hipLaunchKernelGGL((frame_kernel<AO_UNIFORM, true>), dim3(workgroups), dim3(64 * AO_WAVES), 0, s, args);
-	else
-		hipLaunchKernelGGL((frame_kernel<AO_UNIFORM, false>), dim3(workgroups), dim3(64 * AO_WAVES), 0, s, args);
-	if (event_after)
-		(void) hipEventRecord((hipEvent_t) event_after, s);
 }
 
 // `out`: this rank's 8-bit bands (local_out_rows x out_width), or null for a frame without the device resize.

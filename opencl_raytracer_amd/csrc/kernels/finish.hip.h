@@ -6,17 +6,13 @@
 
 namespace ocrt {
 
-// The frame's last kernel also closes the frame's books: the claim cursors of the ray passes go back to 0 and the frame
-// is counted -- the fused frame kernel (kernels/frame.hip.h) compares its tiles' flags with that count, and a replayed
-// graph cannot be handed a new number.  Everything that claimed from those cursors has ended: this kernel follows the ray
-// passes in the stream.  One workgroup, eight lanes.
+// The frame's last kernel also closes the frame's books: the claim cursors of the ambient-occlusion pass go back to their
+// start.  Everything that claimed from those cursors has ended: this kernel follows the ray passes in the stream.  One
+// workgroup, eight lanes.
 __device__ __forceinline__ void frame_is_over(FrameCounters *counters) {
 	if (counters && blockIdx.x == 0u && blockIdx.y == 0u && threadIdx.x < XCD_GROUPS) {
 		counters->queue[threadIdx.x].head = counters->queue[threadIdx.x].split_units;
 		counters->queue[threadIdx.x].split_head = 0u;
-		counters->queue[threadIdx.x].primary_head = 0u;
-		if (threadIdx.x == 0u)
-			counters->frame_seq += 1u;
 	}
 }
 

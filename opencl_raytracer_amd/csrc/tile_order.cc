@@ -159,56 +159,6 @@ std::vector<uint32_t> DeviceRenderer::orderByMeasuredCost(const std::vector<floa
 	return out;
 }
 
-// The fused frame kernel's primary work (kernels/primary.hip.h, primary_top_up): per XCD group the 2 x 2 tile blocks of
-// its strips, entry = first tile column | first tile row << 16, IN THE ORDER THE AMBIENT-OCCLUSION CLAIMS WANT THEM --
-// a block is listed when the first of its tiles comes up in the group's claim order (`order_host`) -- and the blocks no
-// claim ever wants (the background, tiles without hits) last, in spatial order.  order_need[j], beside entry j of the claim
-// order: how many blocks the entries 0 ... j need, i.e. how far the block cursor must have come before entry j's tile may
-// be waited for.
-void DeviceRenderer::orderPrimaryBlocks() {
-	const uint32_t strip_tiles = kp.strip_tiles, columns = strip_tiles >> 1, rows = kp.local_tile_rows, tiles_x = kp.tiles_x;
-	const uint32_t strips = (tiles_x + strip_tiles - 1u) / strip_tiles, row_blocks = (rows + 1u) >> 1;
-	const uint32_t blocks_x = (tiles_x + 1u) >> 1;
-	primary_order_host.clear();
-	order_need_host.assign(order_host.size(), 0u);
-	std::vector<char> listed((size_t) blocks_x * row_blocks, 0);
-	size_t ao_segment = 0;
-	for (uint32_t group = 0; group < XCD_GROUPS; ++group) {
-		const uint32_t strips_here = (strips + XCD_GROUPS - 1u - group) >> 3;
-		const size_t segment = (size_t) strips_here * row_blocks * columns, at = primary_order_host.size();
-		primary_order_host.resize(at + segment, 0u);
-		uint32_t count = 0;
-		// in the order of the claims
-		for (uint32_t j = 0; j < queue_static[group][0]; ++j) {
-			const uint32_t tile = order_host[ao_segment + j] & 0x03FFFFFFu, x = tile % tiles_x, row = tile / tiles_x;
-			const size_t block = (size_t) (row >> 1) * blocks_x + (x >> 1);
-			if (!listed[block]) {
-				listed[block] = 1;
-				primary_order_host[at + count++] = (x & ~1u) | (row & ~1u) << 16;
-			}
-			order_need_host[ao_segment + j] = count;
-		}
-		// ... then whatever no claim wants
-		for (uint32_t strip_index = 0; strip_index < strips_here; ++strip_index)
-			for (uint32_t rb = 0; rb < row_blocks; ++rb)
-				for (uint32_t c = 0; c < columns; ++c) {
-					const uint32_t x0 = strip_tiles * (group + XCD_GROUPS * strip_index) + 2u * c, row0 = 2u * rb;
-					if (x0 >= tiles_x)
-						continue;
-					const size_t block = (size_t) rb * blocks_x + (x0 >> 1);
-					if (!listed[block]) {
-						listed[block] = 1;
-						primary_order_host[at + count++] = x0 | row0 << 16;
-					}
-				}
-		primary_blocks[group] = count;
-		ao_segment += (size_t) strips_here * strip_tiles * rows;
-	}
-	if (primary_order_host.empty())
-		primary_order_host.push_back(0u);
-	orderBlocksByCost();
-}
-
 // primary_kernel's list: workgroup `seq` of a group takes entry `seq` of the group's part -- its 2 x 2 blocks of tiles by
 // falling cost (the largest cost class among a block's tiles = the leaves its primary packet stops at; a tile without
 // ambient-occlusion work carries none: its hit count stands in), spatial order among equals, the background last.  A tile
@@ -317,22 +267,17 @@ void DeviceRenderer::installOrder(const std::vector<uint32_t> &order, const std:
 	split_tiles = splits;
 	OCRT_HIP(hipStreamSynchronize((hipStream_t) stream));
 	OCRT_HIP(hipMemcpy(d_order, order_host.data(), order_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	orderPrimaryBlocks();
-	OCRT_HIP(hipMemcpy(d_primary_order, primary_order_host.data(), primary_order_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	OCRT_HIP(hipMemcpy(d_order_need, order_need_host.data(), order_need_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+	orderBlocksByCost();
 	uploadBlocksByCost();
 	FrameCounters fresh{};
 	for (uint32_t g = 0; g < XCD_GROUPS; ++g) {
 		fresh.queue[g].work_tiles = constants[g][0];
 		fresh.queue[g].cost_sum = constants[g][1];
 		fresh.queue[g].hits = constants[g][2];
-		fresh.queue[g].primary_blocks = primary_blocks[g];
 		fresh.queue[g].split_units = std::min(split_tiles[g], constants[g][0]) * kp.ao_dirs;
 		fresh.queue[g].head = fresh.queue[g].split_units;
 	}
 	OCRT_HIP(hipMemcpy(d_counters, &fresh, sizeof fresh, hipMemcpyHostToDevice));
-	// (the frame count starts again at 0: no tile's flag may claim a frame)
-	OCRT_HIP(hipMemsetAsync(d_tile_ready, 0, (tile_count ? tile_count : 1) * sizeof(uint32_t), (hipStream_t) stream));
 	OCRT_HIP(hipStreamSynchronize((hipStream_t) stream));
 	++scene_version;  // (nothing a captured frame bakes in has changed, but a frame in flight must not see the list change: callers synchronise)
 }

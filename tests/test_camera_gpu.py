@@ -391,9 +391,9 @@ def test_call_order_and_round_trip(rt, scene_for):
     ring.close()
 
 
-def test_fused_frame_form_falls_back_for_a_pose(rt, oracle, scene_for):
-    """The fused frame experiment has no posed form: asked for on a posed host, the frame is rendered as two kernels --
-    never the default view."""
+def test_posed_frame_after_a_poisoned_hit_list(rt, oracle, scene_for):
+    """A posed host's frames write their hit list themselves: the second one starts from garbage in it (a frame that leaned
+    on the records of the one before it would show) and is the oracle's frame again -- never the default view."""
     scene, arrays = scene_for("bunny", "longest")
     opt = rt.Options.defaults(width=96, height=64, n_super_samples=1, ao_num_samples=3)
     cam = poses_for(rt, arrays)["orbit_180"]
@@ -401,10 +401,12 @@ def test_fused_frame_form_falls_back_for_a_pose(rt, oracle, scene_for):
     host.expect_frames(STREAM)
     host.set_camera(cam)
     host.upload_scene(scene)
-    host.set_frame_form("fused")
-    assert not host.frame_is_fused
+    want = oracle_frame(oracle, opt, arrays, cam, ("bunny", "orbit_180"))
     host.render()
-    assert_host_equals(host, oracle_frame(oracle, opt, arrays, cam, ("bunny", "orbit_180")))
+    assert_host_equals(host, want)
+    host.poison_hit_list()
+    host.render()
+    assert_host_equals(host, want)
     host.close()
 
 

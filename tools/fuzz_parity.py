@@ -52,7 +52,7 @@ def draw_case(rng):
         ring=rng.choice([0, 0, 0, 2]),   # (0: one blocking host; n: a ring of n hosts, graph replay, three frames)
         lookahead=rng.choice([0, 1, 2]),  # (the form of the AO pass: without / with look-ahead loads / as calibrated or by default)
         announce=rng.choice([0, 1, 1]),  # (a blocking host: one-shot, or with a stream of frames announced -- its upload then prepares the walk intervals)
-        form=rng.choice(["auto", "auto", "fused"]),  # (a blocking host's frame: two kernels, or both ray passes in one persistent launch -- kernels/frame.hip.h)
+        form=rng.choice(["auto", "auto", "poisoned"]),  # (a blocking host: one frame, or a frame, a poisoned hit list -- rt_debug_poison_hit_list -- and the frame again)
         measure=rng.choice([0, 0, 1]),  # (a blocking host: its tiles claimed by measured cost -- rt_debug_measure_tile_costs)
         quarters=rng.choice([None, None, 1, 4, 16, 40, 0]))  # (the primary pass casts tiles of this cost class or more in quarters -- rt_debug_set_primary_split; None: the default)
 
@@ -103,11 +103,9 @@ def run_case(rt, orc, oracle, scenes, case):
                 host.measure_tile_costs(1)
             if case.get("quarters") is not None and hasattr(host, "set_primary_split"):
                 host.set_primary_split(case["quarters"])
-            if case.get("form", "auto") != "auto" and hasattr(host, "set_frame_form"):
-                host.set_frame_form(case["form"])
-                if hasattr(host, "poison_hit_list"):
-                    host.render()
-                    host.poison_hit_list()  # (a fused frame must not read a record before it is handed over)
+            if case.get("form", "auto") != "auto" and hasattr(host, "poison_hit_list"):
+                host.render()
+                host.poison_hit_list()  # (the frame below must not lean on what this one left in the hit list)
             host.render()
             got, got_u8, st = host.download(), host.download_u8(), host.stats()
             host.close()

@@ -29,11 +29,11 @@ def parse(path):
     return kernels
 
 
-def frame_kernels(kernels):
+def kernels_of_a_frame(kernels):
     """The kernels of ONE frame among what a run dispatched: of the ambient-occlusion pass's two forms (with / without
     look-ahead loads: a ring's calibration at upload launches both) the one the frames were rendered with, i.e. the one with
     the most dispatches; never what an upload runs once (entry_kernel) or a statistic asks for (occluded_sum_kernel)."""
-    names = [n for n in kernels if "ocrt::" in n and "entry_kernel" not in n and "occluded_sum" not in n and "frame_kernel" not in n]
+    names = [n for n in kernels if "ocrt::" in n and "entry_kernel" not in n and "occluded_sum" not in n]
     ao = [n for n in names if "ao_kernel" in n]
     if len(ao) > 1:
         keep = max(ao, key=lambda n: kernels[n].get("_dispatches", 0))
@@ -57,7 +57,7 @@ def main():
     for w in workloads:
         kernels = parse(os.path.join(out_dir, f"pmc_{w}.txt"))
         want = "ao_kernel" if WORKLOADS[w]["ao"] else "primary_kernel"
-        names = [k for k in frame_kernels(kernels) if want in k]
+        names = [k for k in kernels_of_a_frame(kernels) if want in k]
         if not names:
             continue
         c = kernels[names[0]]
@@ -66,7 +66,7 @@ def main():
             "kernel": names[0],
             "valu_insts": c.get("SQ_INSTS_VALU"), "salu_insts": c.get("SQ_INSTS_SALU"), "smem_insts": c.get("SQ_INSTS_SMEM"),
             # every kernel of a frame together (primary pass with the ordering step, ambient-occlusion pass, finishing kernel)
-            "frame_valu_insts": sum(kernels[name].get("SQ_INSTS_VALU", 0.0) for name in frame_kernels(kernels)),
+            "frame_valu_insts": sum(kernels[name].get("SQ_INSTS_VALU", 0.0) for name in kernels_of_a_frame(kernels)),
             "vmem_rd_insts": c.get("SQ_INSTS_VMEM_RD"), "lds_insts": c.get("SQ_INSTS_LDS"), "branch_insts": c.get("SQ_INSTS_BRANCH"),
             "waves": c.get("SQ_WAVES"), "wave_quad_cycles": c.get("SQ_WAVE_CYCLES"), "busy_cycles": c.get("SQ_BUSY_CYCLES"),
             "wait_any_quad_cycles": c.get("SQ_WAIT_ANY"), "wait_inst_any_quad_cycles": c.get("SQ_WAIT_INST_ANY"),
@@ -97,7 +97,7 @@ def main():
             if names:
                 entry["shared_valu_insts"] = shared[names[0]].get("SQ_INSTS_VALU")
                 entry["shared_waves"] = shared[names[0]].get("SQ_WAVES")
-                entry["shared_frame_valu_insts"] = sum(shared[name].get("SQ_INSTS_VALU", 0.0) for name in frame_kernels(shared))
+                entry["shared_frame_valu_insts"] = sum(shared[name].get("SQ_INSTS_VALU", 0.0) for name in kernels_of_a_frame(shared))
         result["workloads"][w] = entry
     json.dump(result, sys.stdout, indent=1)
     print()
