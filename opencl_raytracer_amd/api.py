@@ -1,4 +1,4 @@
-"""ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h, rt_hip_query.h and rt_hip_camera.h (see those headers
+"""ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h, rt_hip_query.h, rt_hip_layers.h and rt_hip_camera.h (see those headers
 for the contract)."""
 from __future__ import annotations
 
@@ -234,6 +234,9 @@ _SIGNATURES = {
     "rt_trace_ao": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_trace_ao_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    # include/rt_hip_layers.h
+    "rt_render_layers": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_render_layers_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     # include/rt_hip_camera.h
     "rt_camera_default": (None, [C.POINTER(Camera)]),
     "rt_camera_look_at": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Camera)]),
@@ -255,16 +258,22 @@ class _MultiHitArrays(C.Structure):
                 ("position", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class _LayerArrays(C.Structure):
+    """rt_layer_arrays (include/rt_hip_layers.h)."""
+    _fields_ = _HitArrays._fields_ + [("direction", C.c_void_p), ("shade", C.c_void_p), ("ao", C.c_void_p), ("value", C.c_void_p)]
+
+
 RT_QUERY_NO_SORT = 1
 RT_MULTIHIT_MAX_K = 16
 MULTIHIT_OUTPUTS = ("count", "distance", "leaf", "barycentric", "position", "normal")
 QUERY_OUTPUTS = ("hit", "distance", "leaf", "barycentric", "position", "normal")
 AO_OUTPUTS = ("ao", "occluded")
+LAYER_OUTPUTS = QUERY_OUTPUTS + ("direction", "shade", "ao", "value")
 # per output of any query: numpy dtype, values per record.  The first four are one value per ray or point; the others are
 # the fields of a hit record: one record per ray (closest hit) or k of them (multi-hit).
 _OUTPUT_LAYOUT = {"hit": (np.uint8, 1), "count": (np.uint32, 1), "ao": (np.float32, 1), "occluded": (np.uint32, 1),
                   "distance": (np.float32, 1), "leaf": (np.uint32, 1), "barycentric": (np.float32, 3), "position": (np.float32, 3),
-                  "normal": (np.float32, 3)}
+                  "normal": (np.float32, 3), "direction": (np.float32, 3), "shade": (np.float32, 1), "value": (np.float32, 1)}
 _RECORD_FIELDS = ("distance", "leaf", "barycentric", "position", "normal")
 
 
@@ -520,7 +529,7 @@ class Host:
     """One render host == one OpenCLHost of the reference (ctor/upload/()/download)."""
 
     def __init__(self, options: Options, device: int = -1, rank: int = 0, nranks: int = 1):
-        self.options = options
+        self.options, self._device = options, int(device)
         self._h = load_library().rt_create_on(C.byref(options), device, rank, nranks)
         if not self._h:
             _raise_last()
@@ -800,6 +809,37 @@ class Host:
         out = io.outputs(outputs)
         io.call(self._h, "rt_trace_ao", io.ptr(seeds) if seeds is not None and io.n else None, io.n,
                 0 if sort else RT_QUERY_NO_SORT, *io.pointers(out, AO_OUTPUTS))
+        return out
+
+    # ---- frame layers (include/rt_hip_layers.h) ----
+    def render_layers(self, outputs=LAYER_OUTPUTS, as_torch: bool = False) -> dict:
+        """The layers behind the frame's grey image, per sub-pixel, for the rays the frame itself casts: {output name:
+        (H, W) or (H, W, 3) array} with H x W = total_height x total_width (those named in `outputs`; a host whose options
+        have ambient occlusion off has no "ao": leave it out).  "value" holds the bits download() returns after render().
+        numpy out (blocking), or with as_torch=True torch tensors on the host's GPU, enqueued on
+        torch.cuda.current_stream() without waiting (as for the ray queries, the default stream's handle is NULL, which the
+        library reads as the host's own stream: work under a stream of your own, or synchronise around the call)."""
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in LAYER_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {LAYER_OUTPUTS}")
+        h, w = self.options.total_height, self.options.total_width
+        shapes = {name: (h, w) + ((_OUTPUT_LAYOUT[name][1],) if _OUTPUT_LAYOUT[name][1] > 1 else ()) for name in outputs}
+        lib = load_library()
+        if as_torch:
+            import torch
+
+            # (the host's GPU: the index it was created on; -1 stands for OCRT_DEVICE or 0, as in the library)
+            index = getattr(self, "_device", -1)
+            device = torch.device("cuda", index if index >= 0 else int(os.environ.get("OCRT_DEVICE", "0")))
+            out = {name: torch.empty(shape, dtype=getattr(torch, np.dtype(_OUTPUT_LAYOUT[name][0]).name), device=device)
+                   for name, shape in shapes.items()}
+            arrays = _LayerArrays(*[out[name].data_ptr() if name in out else None for name in LAYER_OUTPUTS])
+            _check(lib.rt_render_layers_device(self._h, C.byref(arrays), torch.cuda.current_stream(device).cuda_stream))
+            return out
+        out = {name: np.empty(shape, dtype=_OUTPUT_LAYOUT[name][0]) for name, shape in shapes.items()}
+        arrays = _LayerArrays(*[out[name].ctypes.data if name in out else None for name in LAYER_OUTPUTS])
+        _check(lib.rt_render_layers(self._h, C.byref(arrays)))
         return out
 
     def vertex_ao(self, scene: "Scene") -> np.ndarray:

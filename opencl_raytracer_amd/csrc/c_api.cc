@@ -1,8 +1,9 @@
 // c_api.cc -- the extern "C" boundary declared in include/rt_hip.h (the seam), rt_hip_ring.h (streams of frames, several GPUs), rt_hip_debug.h,
-// rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h and rt_hip_camera.h.
+// rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h, rt_hip_layers.h and rt_hip_camera.h.
 #include "../../include/rt_hip.h"
 #include "../../include/rt_hip_ao.h"
 #include "../../include/rt_hip_camera.h"
+#include "../../include/rt_hip_layers.h"
 #include "../../include/rt_hip_debug.h"
 #include "../../include/rt_hip_multihit.h"
 #include "../../include/rt_hip_query.h"
@@ -987,6 +988,50 @@ int rt_trace_ao_device(rt_host *h, const float *points4, const float *normals4, 
 	if (!aligned({ seeds, ao, occluded }, 4))
 		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
 	return guarded([&] { queries_of(h).aoDevice(points4, normals4, seeds, n, flags, ao, occluded, hip_stream); });
+}
+
+// ---- rt_hip_layers.h ----
+namespace {
+
+ocrt::LayerOutputs layer_outputs(const rt_layer_arrays &from) {
+	ocrt::LayerOutputs q;
+	q.hit = from.hit;
+	record_outputs(&from, q);
+	q.direction = from.direction;
+	q.shade = from.shade;
+	q.ao = from.ao;
+	q.value = from.value;
+	return q;
+}
+
+// What both layers entry points check before they touch the device (include/rt_hip_layers.h, "Errors"); the limits that
+// depend on the host's options are RayQueries::requireLayers'.
+int layers_precheck(const rt_host *h, const rt_layer_arrays *out) {
+	const int rc = host_precheck(h, "frame-layer");
+	if (rc != RT_OK)
+		return rc;
+	if (!out)
+		return fail(RT_E_INVALID, "null layer arrays");
+	return RT_OK;
+}
+
+}  // namespace
+
+int rt_render_layers(rt_host *h, const rt_layer_arrays *out) {
+	const int rc = layers_precheck(h, out);
+	if (rc != RT_OK)
+		return rc;
+	return guarded([&] { queries_of(h).layersHost(layer_outputs(*out)); });
+}
+
+int rt_render_layers_device(rt_host *h, const rt_layer_arrays *out, void *hip_stream) {
+	const int rc = layers_precheck(h, out);
+	if (rc != RT_OK)
+		return rc;
+	const ocrt::LayerOutputs q = layer_outputs(*out);
+	if (!(records_aligned(q) && aligned({ q.direction, q.shade, q.ao, q.value }, 4)))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).layersDevice(q, hip_stream); });
 }
 
 float rt_last_query_ms(const rt_host *h) {

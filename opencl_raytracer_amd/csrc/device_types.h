@@ -192,6 +192,12 @@ struct QueryOutputs : RecordOutputs {
 struct MultiHitOutputs : RecordOutputs {
 	uint32_t *count = nullptr;  // by ray index
 };
+// Frame layers (include/rt_hip_layers.h): a closest-hit record per sub-pixel and what the frame makes of it, by y * width + x.
+struct LayerOutputs : QueryOutputs {
+	float *direction = nullptr;                                // three values each
+	float *shade = nullptr, *ao = nullptr, *value = nullptr;
+	bool any() const { return hit || anySlot() || direction || shade || ao || value; }
+};
 
 // Waves per workgroup of the ambient-occlusion pass: they take consecutive parts of a claim (kernels.hip), which is
 // why the host deals the UNIFORM direction table to that many groups (device_renderer.cc).

@@ -34,6 +34,9 @@
 //                   ao_query_finish_kernel writes their 1 - hits / n (kernels/ao_query.hip.h, include/rt_hip_ao.h).
 //                   multihit_walk_kernel<K> counts every triangle a caller-supplied ray's walk accepts and keeps the first K,
 //                   multihit_resolve_kernel writes their records (kernels/multihit.hip.h, include/rt_hip_multihit.h).
+//                   layers_kernel<POSED> casts the frame's own rays, a wave per tile, and writes every sub-pixel's record, direction
+//                   and head-light term, layers_combine_kernel their product with the ambient-occlusion factors
+//                   (kernels/layers.hip.h, include/rt_hip_layers.h).
 //   (on demand)     entry_kernel: the walk intervals, once per upload; occluded_sum_kernel: the frame's occlusion
 //                   total when the statistics are asked for; resize_kernel: a box filter on its own.
 // Why not one fused launch (it was, see profiles/r01_notes.md): cost per tile
@@ -74,6 +77,7 @@
 #include "kernels/query.hip.h"
 #include "kernels/ao_query.hip.h"
 #include "kernels/multihit.hip.h"
+#include "kernels/layers.hip.h"
 
 
 namespace ocrt {
@@ -426,6 +430,49 @@ void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void 
 		hipLaunchKernelGGL(multihit_walk_kernel<16u>, blocks, lanes, 0, s, a);
 	if (k > 0u && out.anySlot())
 		hipLaunchKernelGGL(multihit_resolve_kernel, dim3((n * k + 255u) / 256u), dim3(256), 0, s, a);
+}
+
+// Frame layers (kernels/layers.hip.h).  `points`, `normals`: n = width * height float4 of scratch each, or null -- no
+// ambient-occlusion step follows; `value`: where the head-light term goes once more (a host without ambient occlusion).
+void launch_layers(const SceneBuffers &scene, const KernelParams &P, const CameraPose &pose, bool posed, const LayerOutputs &out,
+                   float *value, void *points, void *normals, void *stream) {
+	const uint32_t tiles_x = (P.width + TILE_W - 1u) / TILE_W, tiles = tiles_x * ((P.height + TILE_H - 1u) / TILE_H);
+	if (tiles == 0)
+		return;
+	LayersArgs a{};
+	a.nodes_ptr = (const float4 *) scene.nodes;
+	a.tris_ptr = (const float4 *) scene.tris;
+	a.shade_recs = (const float4 *) scene.shade;
+	a.width = P.width;
+	a.height = P.height;
+	a.tiles_x = tiles_x;
+	a.tiles = tiles;
+	a.node_count = P.node_count;
+	a.shading = P.shading;
+	a.a = P.a;
+	a.half_w = P.half_w;
+	a.half_h = P.half_h;
+	a.pose = pose;
+	a.hit = out.hit;
+	a.out = out;
+	a.direction = out.direction;
+	a.shade = out.shade;
+	a.value = value;
+	a.points = (float4 *) points;
+	a.normals = (float4 *) normals;
+	const dim3 blocks((tiles + LAYERS_WAVES - 1u) / LAYERS_WAVES), lanes(64 * LAYERS_WAVES);
+	if (posed)
+		hipLaunchKernelGGL(layers_kernel<true>, blocks, lanes, 0, (hipStream_t) stream, a);
+	else
+		hipLaunchKernelGGL(layers_kernel<false>, blocks, lanes, 0, (hipStream_t) stream, a);
+}
+
+// ... and their last step: `ao` and `value` (either may be null) from the n factors at `factor`.
+void launch_layers_combine(const void *points, const void *normals, const float *factor, float *ao, float *value, uint32_t n, void *stream) {
+	if (n == 0 || (!ao && !value))
+		return;
+	hipLaunchKernelGGL(layers_combine_kernel, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t) stream, (const float4 *) points,
+	                   (const float4 *) normals, factor, ao, value, n);
 }
 
 }  // namespace ocrt

@@ -1,4 +1,5 @@
-// ray_query.cc -- ray queries, multi-hit queries and ambient-occlusion queries on a render host's uploaded scene (ray_query.h).
+// ray_query.cc -- ray queries, multi-hit queries, ambient-occlusion queries and frame layers on a render host's uploaded scene
+// (ray_query.h).
 #include "ray_query.h"
 
 #include <cmath>
@@ -18,6 +19,9 @@ size_t round16(size_t bytes) { return (bytes + 15u) & ~(size_t) 15u; }
 // then the five record arrays.  Ambient occlusion: the counts come third, so that they are placed as they always were.
 enum { RAY_ORIGINS, RAY_DIRECTIONS, RAY_FIRST, RAY_RECORDS, RAY_PIECES = RAY_RECORDS + 5 };
 enum { AO_POINTS, AO_NORMALS, AO_COUNTS, AO_SEEDS, AO_VALUES, AO_PIECES };
+// Frame layers: the hit flags, the five record arrays, then the four layers of their own.
+enum { LAYER_HIT, LAYER_RECORDS, LAYER_DIRECTION = LAYER_RECORDS + 5, LAYER_SHADE, LAYER_AO, LAYER_VALUE, LAYER_PIECES };
+constexpr uint32_t QUERY_MAX_RAYS = 1u << 27;  // include/rt_hip_query.h
 }  // namespace
 
 RayQueries::RayQueries(DeviceRenderer &renderer) : dev(renderer) {
@@ -31,7 +35,7 @@ RayQueries::~RayQueries() {
 		return;
 	if (timed)
 		(void) hipEventSynchronize((hipEvent_t) ev_stop);
-	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &list })
+	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &list, &layers })
 		device_free(scratch->ptr);
 	(void) hipEventDestroy((hipEvent_t) ev_start);
 	(void) hipEventDestroy((hipEvent_t) ev_stop);
@@ -90,11 +94,11 @@ void RayQueries::sceneBox(const DeviceScene &scene, float lo[3], float scale[3])
 
 // The way into every device-memory form, up to its own launches: the stream (null: the renderer's), the wait for the
 // query before -- one set of scratch per host, so a query on another stream waits before any scratch is touched --, the
-// scratch (the sort's, and what the family needs of its own: every grow comes before ev_start, because hipFree
+// scratch (the sort's, and what the family needs of its own, `needs`: every grow comes before ev_start, because hipFree
 // synchronises), ev_start, and the sort of the n items keyed by (keys_a4, keys_b4) where the call allows it and makes
 // RT_QUERY_SORT_MIN `rays` or more.
 RayQueries::Enqueue RayQueries::begin(void *stream, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags,
-                                      Need need) {
+                                      std::initializer_list<Need> needs) {
 	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
 	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
 	if (timed)
@@ -104,8 +108,9 @@ RayQueries::Enqueue RayQueries::begin(void *stream, const float *keys_a4, const 
 		grow(count, QUERY_COUNT_BYTES);
 		grow(order, (size_t) n * sizeof(uint32_t));
 	}
-	if (need.scratch)
-		grow(*need.scratch, need.bytes);
+	for (const Need &need : needs)
+		if (need.scratch)
+			grow(*need.scratch, need.bytes);
 	float lo[3], scale[3];
 	if (sort)
 		sceneBox(*dev.deviceScene(), lo, scale);
@@ -206,7 +211,7 @@ void RayQueries::multihitDevice(const float *origins4, const float *directions4,
 	const uint32_t slots = out.anySlot() ? k : 0u;
 	if (n == 0 || (slots == 0 && !out.count))
 		return;
-	const Enqueue q = begin(stream, origins4, directions4, n, n, flags, Need{ slots ? &list : nullptr, (size_t) n * slots * 8u });
+	const Enqueue q = begin(stream, origins4, directions4, n, n, flags, { Need{ slots ? &list : nullptr, (size_t) n * slots * 8u } });
 	launch_multihit(dev.deviceScene()->buffers(), dev.params().node_count, origins4, directions4, q.order, n, max_distance, slots,
 	                list.ptr, out, q.stream);
 	end(q);
@@ -244,10 +249,16 @@ void RayQueries::aoDevice(const float *points4, const float *normals4, const uin
 	const KernelParams &kp = dev.params();
 	// the POINTS are ordered (key: point and normal) from as many on as make RT_QUERY_SORT_MIN rays
 	const Enqueue q = begin(stream, points4, normals4, n, (uint64_t) n * kp.ao_dirs, flags,
-	                        Need{ occluded ? nullptr : &ao_hits, (size_t) n * sizeof(uint32_t) });
-	launch_ao_query(dev.deviceScene()->buffers(), kp.node_count, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4,
-	                normals4, seeds, q.order, n, occluded ? occluded : (uint32_t *) ao_hits.ptr, ao, q.stream);
+	                        { Need{ occluded ? nullptr : &ao_hits, (size_t) n * sizeof(uint32_t) } });
+	aoEnqueue(q, points4, normals4, seeds, n, occluded ? occluded : (uint32_t *) ao_hits.ptr, ao);
 	end(q);
+}
+
+void RayQueries::aoEnqueue(const Enqueue &q, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n,
+                           uint32_t *count, float *ao) {
+	const KernelParams &kp = dev.params();
+	launch_ao_query(dev.deviceScene()->buffers(), kp.node_count, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4,
+	                normals4, seeds, q.order, n, count, ao, q.stream);
 }
 
 void RayQueries::aoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
@@ -262,6 +273,73 @@ void RayQueries::aoHost(const float *points4, const float *normals4, const uint3
 	aoDevice((const float *) p[AO_POINTS].device, (const float *) p[AO_NORMALS].device, (const uint32_t *) p[AO_SEEDS].device, n, flags,
 	         (float *) p[AO_VALUES].device, (uint32_t *) p[AO_COUNTS].device, s);
 	stageOut(p, AO_PIECES, s);
+}
+
+// What a layers call may ask of this host; returns whether it needs the ambient-occlusion step (`ao`, or `value` on a host
+// whose options have ambient occlusion on).
+bool RayQueries::requireLayers(const LayerOutputs &out) const {
+	requireScene("frame layers");
+	const KernelParams &kp = dev.params();
+	if (kp.part.nranks > 1)
+		throw std::logic_error("frame layers on a band-partitioned host: it renders a part of the image only");
+	const uint32_t per_point = aoRaysPerPoint(dev);
+	if (out.ao && per_point == 0)
+		throw std::logic_error("the ao layer on a host whose options have ambient occlusion off");
+	const bool with_ao = per_point != 0 && (out.ao || out.value);
+	const uint64_t n = (uint64_t) kp.width * kp.height;
+	if (n > QUERY_MAX_RAYS || (with_ao && n > QUERY_MAX_RAYS / per_point))
+		throw std::invalid_argument(with_ao ? "more sub-pixels than RT_QUERY_MAX_RAYS / rays per point: ask for neither ao nor value"
+		                                    : "more sub-pixels than RT_QUERY_MAX_RAYS");
+	return with_ao;
+}
+
+void RayQueries::layersDevice(const LayerOutputs &out, void *stream) {
+	const bool with_ao = requireLayers(out);
+	const KernelParams &kp = dev.params();
+	const uint32_t n = kp.width * kp.height;
+	if (n == 0 || !out.any())
+		return;
+	// (ambient occlusion: the points and normals, then -- without an `ao` array to hold them -- the factors)
+	const size_t vectors = (size_t) n * 16u;
+	const Enqueue q = begin(stream, nullptr, nullptr, n, n, QUERY_NO_SORT,
+	                        { Need{ with_ao ? &layers : nullptr, 2u * vectors + (out.ao ? 0u : (size_t) n * sizeof(float)) },
+	                          Need{ with_ao ? &ao_hits : nullptr, (size_t) n * sizeof(uint32_t) } });
+	char *const points = with_ao ? (char *) layers.ptr : nullptr, *const normals = with_ao ? points + vectors : nullptr;
+	// (without that step `value` is the head-light term itself)
+	launch_layers(dev.deviceScene()->buffers(), kp, dev.camera(), dev.cameraIsSet(), out, with_ao ? nullptr : out.value, points, normals,
+	              q.stream);
+	if (with_ao) {
+		// the reference's ambient_occlusion(position, normal, index) of every sub-pixel, in index order: seed i for point i
+		float *const factor = out.ao ? out.ao : (float *) (normals + vectors);
+		aoEnqueue(q, (const float *) points, (const float *) normals, nullptr, n, (uint32_t *) ao_hits.ptr, factor);
+		launch_layers_combine(points, normals, factor, out.ao, out.value, n, q.stream);
+	}
+	end(q);
+}
+
+void RayQueries::layersHost(const LayerOutputs &host) {
+	requireLayers(host);
+	const KernelParams &kp = dev.params();
+	const size_t n = (size_t) kp.width * kp.height;
+	if (n == 0 || !host.any())
+		return;
+	Staged p[LAYER_PIECES];
+	p[LAYER_HIT] = output(host.hit, n);
+	recordPieces(p + LAYER_RECORDS, host, n);
+	p[LAYER_DIRECTION] = output(host.direction, n * 12u);
+	p[LAYER_SHADE] = output(host.shade, n * 4u);
+	p[LAYER_AO] = output(host.ao, n * 4u);
+	p[LAYER_VALUE] = output(host.value, n * 4u);
+	void *s = stageIn(p, LAYER_PIECES);
+	LayerOutputs out;
+	out.hit = (unsigned char *) p[LAYER_HIT].device;
+	recordDevice(p + LAYER_RECORDS, out);
+	out.direction = (float *) p[LAYER_DIRECTION].device;
+	out.shade = (float *) p[LAYER_SHADE].device;
+	out.ao = (float *) p[LAYER_AO].device;
+	out.value = (float *) p[LAYER_VALUE].device;
+	layersDevice(out, s);
+	stageOut(p, LAYER_PIECES, s);
 }
 
 float RayQueries::lastMs() {

@@ -1,8 +1,9 @@
-// ray_query.h -- ray queries, multi-hit queries and ambient-occlusion queries on a render host's uploaded scene
-// (include/rt_hip_query.h, include/rt_hip_multihit.h, include/rt_hip_ao.h; kernels/query.hip.h, kernels/multihit.hip.h,
-// kernels/ao_query.hip.h).
+// ray_query.h -- ray queries, multi-hit queries, ambient-occlusion queries and frame layers on a render host's uploaded scene
+// (include/rt_hip_query.h, include/rt_hip_multihit.h, include/rt_hip_ao.h, include/rt_hip_layers.h; kernels/query.hip.h,
+// kernels/multihit.hip.h, kernels/ao_query.hip.h, kernels/layers.hip.h).
 #pragma once
 #include <cstdint>
+#include <initializer_list>
 #include <memory>
 
 #include "device_renderer.h"
@@ -46,6 +47,14 @@ class RayQueries {
 		// Host memory, blocking.
 		void aoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
 		            uint32_t *occluded);
+		// Frame layers (include/rt_hip_layers.h): the closest-hit record of every sub-pixel's own ray -- the host's pose,
+		// DeviceRenderer::camera() / cameraIsSet() --, its direction, head-light term, ambient-occlusion factor and their
+		// product.  std::logic_error on a band-partitioned host and for out.ao where the options have ambient occlusion
+		// off; std::invalid_argument where the ambient-occlusion step would exceed a query's rays.
+		// Device memory, enqueued on `stream` (null: the renderer's).
+		void layersDevice(const LayerOutputs &out, void *stream);
+		// Host memory, blocking.
+		void layersHost(const LayerOutputs &out);
 		float lastMs();  // the last query of any kind
 
 	private:
@@ -80,10 +89,15 @@ class RayQueries {
 		void requireScene(const char *query) const;
 		void requireSlots(uint32_t k) const;
 		void requireAo() const;
+		bool requireLayers(const LayerOutputs &out) const;  // true: the call needs the ambient-occlusion step
 		void grow(Scratch &scratch, size_t bytes);
 		void sceneBox(const DeviceScene &scene, float lo[3], float scale[3]);
-		Enqueue begin(void *stream, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags, Need need = Need{ nullptr, 0 });
+		Enqueue begin(void *stream, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags,
+		              std::initializer_list<Need> needs = {});
 		void end(const Enqueue &q);
+		// aoDevice between begin() and end(): `count` holds n words (the caller's `occluded` or ao_hits).
+		void aoEnqueue(const Enqueue &q, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t *count,
+		               float *ao);
 		void *stageIn(Staged *pieces, size_t n);  // returns the stream
 		void stageOut(const Staged *pieces, size_t n, void *stream);
 
@@ -92,6 +106,8 @@ class RayQueries {
 		Scratch stage;         // the host-memory forms' inputs and outputs
 		Scratch ao_hits;       // aoDevice without an `occluded` array: the points' counts
 		Scratch list;          // multihitDevice: the rays' key lists, n * k * 8 bytes
+		Scratch layers;        // layersDevice with ambient occlusion: the sub-pixels' points and normals (float4 each), and
+		                       // their factors where the caller gave no `ao` array
 		void *ev_start = nullptr, *ev_stop = nullptr;
 		bool timed = false, have_ms = false;
 		float last_ms = 0.0f;
@@ -109,5 +125,8 @@ void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void 
 void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
                      float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
                      uint32_t *count, float *ao, void *stream);
+void launch_layers(const SceneBuffers &scene, const KernelParams &P, const CameraPose &pose, bool posed, const LayerOutputs &out,
+                   float *value, void *points, void *normals, void *stream);
+void launch_layers_combine(const void *points, const void *normals, const float *factor, float *ao, float *value, uint32_t n, void *stream);
 
 }  // namespace ocrt
