@@ -4,7 +4,9 @@ reads (profiles/pmc.json): per workload the counters of its dominant kernel -- o
 dispatches of the run -- and the HBM bytes corrected as MI355X_MICROARCH.md prescribes for gfx950 (FETCH_SIZE counts
 64 B per 128-B request: doubled; FETCH_SIZE / WRITE_SIZE are in KB).
 
-    python3 tools/pmc_to_json.py OUTDIR WORKLOAD [WORKLOAD...]  > OUTDIR/pmc.json
+    python3 tools/pmc_to_json.py [--source-prefix profiles/NAME_pmc_] OUTDIR WORKLOAD [WORKLOAD...]  > OUTDIR/pmc.json
+
+--source-prefix: under which names the summaries are kept in the repository (the file's `source` note); default: round 5's.
 """
 import json
 import os
@@ -47,10 +49,14 @@ def in_frame(name):
 
 
 def main():
-    out_dir, workloads = sys.argv[1], sys.argv[2:]
+    args = sys.argv[1:]
+    prefix = "profiles/r05_pmc_"
+    if args and args[0] == "--source-prefix":
+        prefix, args = args[1], args[2:]
+    out_dir, workloads = args[0], args[1:]
     result = {
         "kernel_source_sha256": kernel_source_sha(),
-        "source": "profiles/r05_pmc_<workload>.txt (rocprofv3 --pmc, one pass per counter group, tools/pmc_collect.sh)",
+        "source": prefix + "<workload>.txt (rocprofv3 --pmc, one pass per counter group, tools/pmc_collect.sh)",
         "units": "per launch of the dominant kernel; SQ_*_CYCLES and SQ_WAIT_* count quad-cycles",
         "workloads": {},
     }
