@@ -117,10 +117,7 @@ struct KernelParams {
 	float ao_max_distance; // AO_MAX_DISTANCE
 	uint32_t ao_dirs;      // AO rays cast per hit sub-pixel (UNIFORM: table size; RANDOM: AO_NUM_SAMPLES + 2)
 	uint32_t ao_divisor;   // n of `1 - hits / n` (UNIFORM: ao_dirs; RANDOM: AO_NUM_SAMPLES + 1, reference :260-275)
-	int32_t scene_regular; // every box finite, |coord| <= 1e37 and lo <= hi: min/max slab form allowed
 	int32_t ao_regular;    // AO_MAX_DISTANCE > 0 (needed by the folded form of the slab test)
-	int32_t scene_nested;  // every child box lies inside its parent's box: the shared walk's fast form is allowed
-	int32_t shared_walk;   // sibling subtrees tile their parent's index range (any arity): one shared node index is safe
 	int32_t fast_walk;     // the padded walk array exists (regular, nested scene): the 6-FMA box test may be used
 	float origin_limit;    // ... for rays whose origin coordinates do not exceed this magnitude
 	int32_t shared_device;  // other hosts' frames run beside this one's (DeviceRenderer::setDeviceShare)
@@ -129,8 +126,6 @@ struct KernelParams {
 	float primary_below;   // largest float below the primary rays' max_distance (100000.0f)
 	float ao_below;        // largest float below AO_MAX_DISTANCE
 	int32_t debug_no_sort; // debug knob OCRT_NO_SORT: claim tiles in arbitrary order instead of heaviest first
-	uint32_t refill_min;    // wave scheduler: refill once this many lanes are idle (debug knob OCRT_REFILL_MIN)
-	uint32_t leaf_min;      // ... test triangles once this many leaves are pending (OCRT_LEAF_MIN)
 	uint32_t batch_below;   // AO: a leaf hit by fewer lanes than this has its triangle tests deferred and batched
 	uint32_t cost_shift;    // ordering key of a block of 64 tiles = 1 + (sum of its tiles' cost classes >> cost_shift)
 	uint32_t ao_claim_max;  // most (tile, direction) units one wave's share of a claim holds; 0 = ao_kernel's rule (a quarter of a tile, or a whole tile)
@@ -171,7 +166,7 @@ inline CameraPose default_camera_pose() { return CameraPose{ { 0.0f, 0.0f, 2.0f 
 
 // Device pointers of one uploaded scene, as the launchers of kernels.hip take them.
 struct SceneBuffers {  // device pointers of one uploaded scene
-	const void *nodes;       // NodeRec[node_count + 1]: exact boxes (exact form of the walk, first-generation kernels)
+	const void *nodes;       // NodeRec[node_count + 1]: exact boxes (exact form of the walk)
 	const void *walk;        // NodeRec[node_count + 2]: padded boxes, byte skips, END records (fast form); may be null
 	const void *tris;        // TriRec[tri_count]: leaf box + triangle invariants by leaf index
 	const void *shade;       // ShadeRec[tri_count]

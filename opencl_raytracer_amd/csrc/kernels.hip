@@ -9,13 +9,13 @@
 // for the CDNA4 wave64 machine.
 //
 // Work decomposition: one 64-lane wavefront per 8x8 tile of sub-pixels, in two ray passes and a finishing sweep --
-// three kernels per frame (round 3: six), captured once per host as a hipGraph and replayed.
+// three kernels per frame, captured once per host as a hipGraph and replayed.
 //   primary_kernel  every lane casts its primary ray (closest hit) and computes
 //                   the smooth normal and head-light term.  Sub-pixels that need
 //                   no ambient occlusion are final; the tile's other hits leave a TAG in the image and
 //                   are ballot-compacted into the tile's slots of the hit list (tile_base: sized by what is hit).
-//                   Its TAIL is the ordering step: the last workgroup of each XCD group to finish sorts the
-//                   group's non-empty tiles by AO cost class (counting sort, the costly blocks first).
+//                   The order the next pass takes the tiles in is made once per upload, on the host
+//                   (DeviceRenderer::orderTiles: each XCD group's non-empty tiles, the costly blocks first).
 //   ao_kernel       persistent workgroups claim runs of (tile, table direction) units in
 //                   that order -- a tile at a time, whose directions the four waves take
 //                   from a cursor in LDS.  A wave rebuilds the tile's tangent frames in its
@@ -41,17 +41,15 @@
 //                   total when the statistics are asked for; resize_kernel: a box filter on its own.
 // Why not one fused launch (it was, see profiles/r01_notes.md): cost per tile
 // varies 30x (background vs model, 29 rays per hit sub-pixel), so the frame used
-// to end on a long tail of half-empty CUs.  With the tiles' costs known after the
-// primary pass, claiming the costly blocks first packs them almost perfectly.
+// to end on a long tail of half-empty CUs.  With the tiles' costs known from the
+// upload's primary pass, claiming the costly blocks first packs them almost perfectly.
 // (Round 5 put both ray passes into one persistent launch once more, the hit records handed from workgroup to workgroup
 // inside it: bit-exact and 2-9 % slower than the two kernels, so it was taken out again -- profiles/r05_notes.md.)
 //
 // How rays walk the tree: the 64 rays of a wave share ONE node index ("shared
 // walk", see walk_collect below) -- nodes and triangles arrive by
 // scalar loads, boxes are tested out of SGPRs, nothing diverges and nothing is
-// gathered.  The first generation, in which every lane walked on its own under a
-// wave scheduler, is only compiled into the A/B build (-DOCRT_DEBUG_KNOBS, where
-// OCRT_NO_SHARED_WALK=1 selects it); the product library does not contain it.
+// gathered.
 //
 // What bounds it: the scene (19 MB) is cache-resident, HBM traffic is negligible;
 // the walk is bound by vector-instruction issue (11 to 17 per node and primary packet, 12 per any-hit packet) and the
@@ -66,9 +64,6 @@
 #include "tri_predicate.h"
 
 #include "kernels/common.hip.h"
-#ifdef OCRT_DEBUG_KNOBS
-#include "kernels/first_generation.hip.h"
-#endif
 #include "kernels/walk.hip.h"
 #include "kernels/primary.hip.h"
 #include "kernels/ao.hip.h"
@@ -87,8 +82,8 @@ namespace ocrt {
 // launch): called from a warm-up thread while the CPU still builds the scene.
 void preload_kernels() {
 	hipFuncAttributes attr;
-	(void) hipFuncGetAttributes(&attr, (const void *) primary_kernel<true>);
-	(void) hipFuncGetAttributes(&attr, (const void *) ao_kernel<AO_UNIFORM, true, true>);
+	(void) hipFuncGetAttributes(&attr, (const void *) primary_kernel);
+	(void) hipFuncGetAttributes(&attr, (const void *) ao_kernel<AO_UNIFORM, true>);
 	(void) hipGetLastError();
 }
 
@@ -142,8 +137,8 @@ uint32_t ocml_ao_table(void *table, uint32_t rings, int alpha_min, int alpha_max
 }
 #endif
 
-// The frame is three kernels (two without ambient occlusion): primary pass (+ ordering step in its tail), the
-// ambient-occlusion pass, the finishing kernel (AO factor + box filter + quantisation).
+// The frame is three kernels (two without ambient occlusion): the primary pass, the ambient-occlusion pass, the
+// finishing kernel (AO factor + box filter + quantisation).
 #ifdef OCRT_PRIMARY_TICKS
 extern void *primary_ticks_probe;
 #endif
@@ -178,14 +173,10 @@ void launch_primary(const SceneBuffers &scene, float *image, void *hits, void *o
 		args.P = P;
 		hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * PRIMARY_WAVES), 0, s, args);
 	};
-	// (a host with a camera pose: the instantiations that read the pose; the default ones hold the reference's camera as constants)
-#ifdef OCRT_DEBUG_KNOBS
-	if (!P.shared_walk)
-		return P.posed ? launch(primary_posed_kernel<false>) : launch(primary_kernel<false>);
-#endif
+	// (a host with a camera pose: the kernel that reads the pose; the default one holds the reference's camera as constants)
 	if (P.posed)
-		return launch(primary_posed_kernel<true>);
-	launch(primary_kernel<true>);
+		return launch(primary_posed_kernel);
+	launch(primary_kernel);
 }
 
 #ifdef OCRT_PRIMARY_TICKS
@@ -242,21 +233,13 @@ void launch_ao(const SceneBuffers &scene, void *hits, void *occluded_of, void *o
 		if (event_after_ao)
 			(void) hipEventRecord((hipEvent_t) event_after_ao, s);
 	};
-#ifdef OCRT_DEBUG_KNOBS
-	if (!P.shared_walk) {
-		if (P.ao_mode == AO_UNIFORM)
-			launch(ao_kernel<AO_UNIFORM, false>);
-		else
-			launch(ao_kernel<AO_RANDOM, false>);
-	} else
-#endif
 	if (P.ao_mode == AO_UNIFORM) {
 		if (prefetch)
-			launch(ao_kernel<AO_UNIFORM, true, true>);
+			launch(ao_kernel<AO_UNIFORM, true>);
 		else
-			launch(ao_kernel<AO_UNIFORM, true, false>);
+			launch(ao_kernel<AO_UNIFORM, false>);
 	} else
-		launch(ao_kernel<AO_RANDOM, true>);
+		launch(ao_kernel<AO_RANDOM>);
 }
 
 // `out`: this rank's 8-bit bands (local_out_rows x out_width), or null for a frame without the device resize.

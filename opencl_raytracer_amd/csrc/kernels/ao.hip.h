@@ -77,16 +77,12 @@ struct TileShared {
 // PREFETCH: the node loop touches a pair's two successors ahead of time (OCRT_PF_SUCCESSORS): a launch-time choice.
 // `wg_claim`: the workgroup's current claim in LDS -- first unit, units per wave, end (if dealt by cursor), cursor;
 // [4..7]: the claim before it, for measureTileCosts.
-template <int MODE, bool SHARED, bool PREFETCH>
+template <int MODE, bool PREFETCH>
 __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_tiles, unsigned int *wg_claim) {
 	const uint32_t wave = (uint32_t) __builtin_amdgcn_readfirstlane((int) threadIdx.x) >> 6;  // (scalar)
 	TileShared &sh = shared_tiles[wave];
 	const float4 *__restrict__ const walk_ptr = A.walk_ptr, *__restrict__ const tris_ptr = A.tris_ptr;
 	const uint32_t count = A.P.node_count;
-#ifdef OCRT_DEBUG_KNOBS  // (the first-generation walk of the A/B build uses the arguments freely: its register budget is nobody's concern)
-	const KernelParams &P = A.P;
-	const SceneViews scene = make_views(A.nodes_ptr, A.tris_ptr, A.P);
-#endif
 
 #ifndef OCRT_STAMPS
 	unsigned long long *walk_prof = nullptr;
@@ -210,7 +206,7 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 				// wg_claim[2] = the claim's end, 0 for fixed shares.
 				const uint32_t end = first + per_wave * AO_WAVES < claim_limit ? first + per_wave * AO_WAVES : claim_limit;
 				const uint32_t ao_dirs = OCRT_COLD_U32(P.ao_dirs);
-				const bool one_tile = SHARED && first < units && first / ao_dirs == (end - 1u) / ao_dirs && ao_dirs < 0x8000u;
+				const bool one_tile = first < units && first / ao_dirs == (end - 1u) / ao_dirs && ao_dirs < 0x8000u;
 				wg_claim[0] = first;
 				wg_claim[1] = per_wave;
 				wg_claim[2] = one_tile ? end : 0u;
@@ -298,7 +294,7 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 					dir0 = at;
 					total = hit_count * (left < chunk ? left : chunk);
 				};
-				if (SHARED && __builtin_amdgcn_readfirstlane((int) wg_claim[2]) != 0) {
+				if (__builtin_amdgcn_readfirstlane((int) wg_claim[2]) != 0) {
 					take_from_cursor();
 					if (total == 0u)
 						continue;  // (not even the tile's table is needed)
@@ -340,12 +336,6 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 				uint32_t h = 0;
 				Ray ray;
 				bool tame = false;  // (wave-uniform) every ray of the packet set up last is "tame": ray_is_tame
-#ifdef OCRT_DEBUG_KNOBS
-				uint32_t next = 0u;  // wave-uniform queue head
-				uint32_t i = count;
-				Pending pending = { NONE, NONE };
-				bool regular = true;
-#endif
 
 				// ray number `item` of the job -> this lane
 				// `whole` (wave-uniform): the tile is full and the 64 rays are one table direction, `shared_dir`
@@ -397,108 +387,57 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 						ray.dx = rx; ray.dy = ry; ray.dz = rz;
 						ray.ix = 1.0f / rx; ray.iy = 1.0f / ry; ray.iz = 1.0f / rz;
 					}
-#ifdef OCRT_DEBUG_KNOBS
-					regular = P.scene_regular && P.ao_regular && ray_is_regular(ray);
-#endif
 				};
 
-#ifdef OCRT_DEBUG_KNOBS
-				// Every lane walks on its own; idle lanes are refilled from the job's rays while
-				// next < total.
-				auto walk_individually = [&]() {
-					for (;;) {
-						const bool idle_lane = pending.first == NONE && !(i < count);
-						const unsigned long long walking = wave_ballot(can_walk(pending, i, count));
-						const uint32_t n_leaves = (uint32_t) __popcll(wave_ballot(pending.first != NONE));
-						const unsigned long long idle_mask = wave_ballot(idle_lane);
-						const uint32_t idle = (uint32_t) __popcll(idle_mask);
-						if (next < total && idle >= P.refill_min) {
-							const uint32_t item = next + rank_in(idle_mask);
-							if (idle_lane && item < total) {
-								setup_ray(item, false, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-								i = 0u;
-							}
-							next += idle;
-							continue;
-						}
-						if (n_leaves != 0u && (n_leaves >= P.leaf_min || walking == 0ull)) {
-							if (pending.first != NONE) {
-								const TriResult tr = tri_test<false>(scene.tris, pending.first, ray);
-								pending.first = pending.second;
-								pending.second = NONE;
-								if (tr.accepted) {
-									atomicAdd(&sh.occluded[h], 1u);
-									i = count;  // any-hit: the reference walks on but only uses the boolean (:251)
-									pending.first = NONE;
-								}
-							}
-							continue;
-						}
-						if (walking == 0ull)
-							break;
-						advance_walkers(scene, ray, regular, P.ao_max_distance, P.ao_below, count, i, pending);
-						// a second node straight away while few leaves are pending: halves the scheduling overhead
-						if ((uint32_t) __popcll(wave_ballot(pending.first != NONE)) < P.leaf_min)
-							advance_walkers(scene, ray, regular, P.ao_max_distance, P.ao_below, count, i, pending);
-					}
-				};
-#endif
-
-#ifdef OCRT_DEBUG_KNOBS
-				if (!SHARED)
-					walk_individually();
-#endif
-				if (SHARED) {
-					// shared walks (see walk_collect) of 64 consecutive rays of the job at a time; a lane
-					// leaves at its first accepted triangle
-					const bool scene_fast = OCRT_COLD_U32(P.fast_walk) && OCRT_COLD_U32(P.ao_regular) && OCRT_COLD_F32(P.walk_scale) > 0.0f;
+				// shared walks (see walk_collect) of 64 consecutive rays of the job at a time; a lane
+				// leaves at its first accepted triangle
+				const bool scene_fast = OCRT_COLD_U32(P.fast_walk) && OCRT_COLD_U32(P.ao_regular) && OCRT_COLD_F32(P.walk_scale) > 0.0f;
 #ifdef OCRT_STAMPS
-					uint32_t job_exact = 0u;
+				uint32_t job_exact = 0u;
 #endif
-					do {  // (once per piece: fixed shares are one piece, the cursor hands out the others)
-					OCRT_STAMP_ADD(5, (total + 63u) / 64u);
-					for (uint32_t base = 0u; base < total; base += 64u) {
-						const uint32_t lane = fresh_lane();
-						bool alive = base + lane < total;
-						// a full tile's packet is one table direction: the entry comes by a scalar load
-						const bool whole = hit_count == 64u;
-						float4 shared_dir = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-						if (whole && MODE == AO_UNIFORM)
-							shared_dir = OCRT_COLD_PTR(const float4 *, ao_table)[dir0 + (base >> 6)];
-						// the interval of the walk array this packet has to walk (entry_kernel): the one of its table direction,
-						// or the tile's.  Two words, made scalar by hand like every load through a re-read pointer.
-						uint32_t entry_begin, entry_end;
-						{
-							const uint32_t stride = OCRT_COLD_U32(P.entry_stride);  // (1: this frame keeps the tiles' own intervals only)
-							const uint32_t which = (whole && MODE == AO_UNIFORM && stride > 1u) ? 1u + dir0 + (base >> 6) : 0u;
-							const uint2 range = OCRT_COLD_PTR(const uint2 *, tile_entry)[(size_t) tile * stride + which];
-							entry_begin = (uint32_t) __builtin_amdgcn_readfirstlane((int) range.x);
-							entry_end = (uint32_t) __builtin_amdgcn_readfirstlane((int) range.y);
-						}
-						if (alive)
-							setup_ray(base + lane, whole, shared_dir);
-						const bool exact = !scene_fast || (!tame && wave_ballot(alive && !ray_is_selectable(ray, OCRT_COLD_F32(P.origin_limit))) != 0ull);
-#ifdef OCRT_STAMPS
-						job_exact += exact ? 1u : 0u;
-#endif
-						if (exact)
-							shared_walk_any_hit<true>(OCRT_COLD_PTR(const float4 *, nodes_ptr), walk_ptr, tris_ptr, count, ray, sh.frame, h,
-							                          OCRT_COLD_F32(P.ao_max_distance), A.P.ao_below, 0.0f, alive, false, &sh.occluded[h], sh.batch,
-							                          A.P.batch_below, walk_prof);
-						else
-							shared_walk_any_hit<false, PREFETCH>(nullptr, walk_ptr, tris_ptr, count, ray, sh.frame, h,
-							                           0.0f, A.P.ao_below, OCRT_COLD_F32(P.walk_scale), alive, tame, &sh.occluded[h], sh.batch,
-							                           A.P.batch_below, walk_prof, entry_begin, entry_end, OCRT_COLD_U32(P.walk_ce_bytes));
+				do {  // (once per piece: fixed shares are one piece, the cursor hands out the others)
+				OCRT_STAMP_ADD(5, (total + 63u) / 64u);
+				for (uint32_t base = 0u; base < total; base += 64u) {
+					const uint32_t lane = fresh_lane();
+					bool alive = base + lane < total;
+					// a full tile's packet is one table direction: the entry comes by a scalar load
+					const bool whole = hit_count == 64u;
+					float4 shared_dir = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+					if (whole && MODE == AO_UNIFORM)
+						shared_dir = OCRT_COLD_PTR(const float4 *, ao_table)[dir0 + (base >> 6)];
+					// the interval of the walk array this packet has to walk (entry_kernel): the one of its table direction,
+					// or the tile's.  Two words, made scalar by hand like every load through a re-read pointer.
+					uint32_t entry_begin, entry_end;
+					{
+						const uint32_t stride = OCRT_COLD_U32(P.entry_stride);  // (1: this frame keeps the tiles' own intervals only)
+						const uint32_t which = (whole && MODE == AO_UNIFORM && stride > 1u) ? 1u + dir0 + (base >> 6) : 0u;
+						const uint2 range = OCRT_COLD_PTR(const uint2 *, tile_entry)[(size_t) tile * stride + which];
+						entry_begin = (uint32_t) __builtin_amdgcn_readfirstlane((int) range.x);
+						entry_end = (uint32_t) __builtin_amdgcn_readfirstlane((int) range.y);
 					}
-					take_from_cursor();  // (fixed shares: the cursor holds nothing)
-					} while (total != 0u);
+					if (alive)
+						setup_ray(base + lane, whole, shared_dir);
+					const bool exact = !scene_fast || (!tame && wave_ballot(alive && !ray_is_selectable(ray, OCRT_COLD_F32(P.origin_limit))) != 0ull);
 #ifdef OCRT_STAMPS
-					if (fresh_lane() == 0u && job_exact) {
-						atomicAdd(&A.counters->stamp[63], (unsigned long long) job_exact);  // packets that took the exact form
-						atomicAdd(&A.counters->stamp[64], (__builtin_amdgcn_s_memrealtime() - t_frames));  // ... and the time of the jobs holding them
-					}
+					job_exact += exact ? 1u : 0u;
 #endif
+					if (exact)
+						shared_walk_any_hit<true>(OCRT_COLD_PTR(const float4 *, nodes_ptr), walk_ptr, tris_ptr, count, ray, sh.frame, h,
+						                          OCRT_COLD_F32(P.ao_max_distance), A.P.ao_below, 0.0f, alive, false, &sh.occluded[h], sh.batch,
+						                          A.P.batch_below, walk_prof);
+					else
+						shared_walk_any_hit<false, PREFETCH>(nullptr, walk_ptr, tris_ptr, count, ray, sh.frame, h,
+						                           0.0f, A.P.ao_below, OCRT_COLD_F32(P.walk_scale), alive, tame, &sh.occluded[h], sh.batch,
+						                           A.P.batch_below, walk_prof, entry_begin, entry_end, OCRT_COLD_U32(P.walk_ce_bytes));
 				}
+				take_from_cursor();  // (fixed shares: the cursor holds nothing)
+				} while (total != 0u);
+#ifdef OCRT_STAMPS
+				if (fresh_lane() == 0u && job_exact) {
+					atomicAdd(&A.counters->stamp[63], (unsigned long long) job_exact);  // packets that took the exact form
+					atomicAdd(&A.counters->stamp[64], (__builtin_amdgcn_s_memrealtime() - t_frames));  // ... and the time of the jobs holding them
+				}
+#endif
 				wave_lds_sync();
 				OCRT_STAMP(t_walked);
 				OCRT_STAMP_ADD(2, t_walked - t_frames);
@@ -559,11 +498,11 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 #endif
 }
 
-template <int MODE, bool SHARED, bool PREFETCH = false>
+template <int MODE, bool PREFETCH = false>
 __global__ __launch_bounds__(64 * AO_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void ao_kernel(FrameArgs A) {
 	__shared__ TileShared shared_tiles[AO_WAVES];
 	__shared__ unsigned int wg_claim[8];
-	ao_pass<MODE, SHARED, PREFETCH>(A, shared_tiles, wg_claim);
+	ao_pass<MODE, PREFETCH>(A, shared_tiles, wg_claim);
 }
 
 }  // namespace ocrt

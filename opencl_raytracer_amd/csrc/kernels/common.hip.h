@@ -422,8 +422,5 @@ __device__ __forceinline__ SceneViews make_views(const float4 *nodes_ptr, const 
 	scene.tris = __builtin_amdgcn_make_buffer_rsrc((void *) tris_ptr, 0, (int) (tri_count * LEAF_BYTES), 0x00020000);
 	return scene;
 }
-__device__ __forceinline__ SceneViews make_views(const float4 *nodes_ptr, const float4 *tris_ptr, const KernelParams &P) {
-	return make_views(nodes_ptr, tris_ptr, P.node_count, P.tri_count);
-}
 
 }  // namespace ocrt

@@ -1,4 +1,4 @@
-// kernels/primary.hip.h -- pass 1: primary rays (closest hit, smooth normal, head-light term) and the ordering step in its tail
+// kernels/primary.hip.h -- pass 1: primary rays (closest hit, smooth normal, head-light term)
 // (part of the one translation unit kernels.hip; see its head for the passes and the arithmetic contract)
 #pragma once
 #include "walk.hip.h"
@@ -68,8 +68,6 @@ using AoArgs = FrameArgs;
 constexpr uint32_t PENDING_TAG = 0xFFC00000u;
 __device__ __forceinline__ bool is_pending(uint32_t bits) { return (bits & 0xFFFFFFC0u) == PENDING_TAG; }
 
-// SHARED: the shared walk.  (The A/B build also instantiates the first generation, SHARED = false; two instantiations,
-// so that its per-lane state stays out of the default path's register budget.)
 // One tile of the primary pass, one wave.
 // `cb`: this wave's LDS slice for the leaves it tests 64 pairs at a time.
 // `part`: WHOLE_TILE, or 0..3 -- one QUARTER of the tile (4 x 4 sub-pixels), the other three being cast by the other waves of
@@ -96,7 +94,7 @@ __device__ __forceinline__ Ray posed_origin(Ray r) {
 	}
 	return r;
 }
-template <bool SHARED, bool POSED = false>
+template <bool POSED = false>
 __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &cb, uint32_t tile_x, uint32_t local_row, uint32_t part = WHOLE_TILE,
                                              unsigned long long *quarter_hits = nullptr) {
 	// What the tile needs of the launch constants is READ HERE, by loads the compiler can neither hoist nor merge (cold_u32):
@@ -106,9 +104,6 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 		uint32_t tiles_x, width, height, node_count, tri_count, fast_walk, batch_below;
 		float a, half_w, half_h, origin_limit, primary_below;
 		Partition part;
-#ifdef OCRT_DEBUG_KNOBS
-		uint32_t scene_regular, leaf_min;
-#endif
 	} P;
 	P.tiles_x = OCRT_PCOLD_U32(P.tiles_x); P.width = OCRT_PCOLD_U32(P.width); P.height = OCRT_PCOLD_U32(P.height);
 	P.node_count = OCRT_PCOLD_U32(P.node_count); P.tri_count = OCRT_PCOLD_U32(P.tri_count); P.fast_walk = OCRT_PCOLD_U32(P.fast_walk);
@@ -116,11 +111,8 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 	P.a = OCRT_COLD_F32(P.a); P.half_w = OCRT_COLD_F32(P.half_w); P.half_h = OCRT_COLD_F32(P.half_h);
 	P.origin_limit = OCRT_COLD_F32(P.origin_limit); P.primary_below = OCRT_COLD_F32(P.primary_below);
 	P.part.rank = OCRT_PCOLD_U32(P.part.rank); P.part.nranks = OCRT_PCOLD_U32(P.part.nranks); P.part.band_tile_rows = OCRT_PCOLD_U32(P.part.band_tile_rows);
-#ifdef OCRT_DEBUG_KNOBS
-	P.scene_regular = OCRT_PCOLD_U32(P.scene_regular); P.leaf_min = OCRT_PCOLD_U32(P.leaf_min);
-#endif
 	const float4 *__restrict__ const walk_ptr = A.walk_ptr, *__restrict__ const tris_ptr = A.tris_ptr;
-	const float4 *__restrict__ const nodes_ptr = OCRT_PCOLD_PTR(const float4 *, nodes_ptr);  // (exact form and first-generation walk only)
+	const float4 *__restrict__ const nodes_ptr = OCRT_PCOLD_PTR(const float4 *, nodes_ptr);  // (exact form only)
 	const uint32_t lane = threadIdx.x & 63u;
 	const SceneViews scene = make_views(nodes_ptr, tris_ptr, P.node_count, P.tri_count);
 	const uint32_t tile = local_row * P.tiles_x + tile_x;
@@ -155,161 +147,129 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 	best.px = best.py = best.pz = 0.0f;
 	bool hit = false;
 	uint32_t leaf_stops = 0u;  // leaves the tile's shared walk stopped at: how dense the geometry is along these rays
-	if (SHARED) {
-		const bool exact = !P.fast_walk || wave_ballot(active && !ray_is_selectable(ray, P.origin_limit)) != 0ull;
-		// the exact form's leaf step (exact_walk): closest hit = minimum of (distance, reference leaf), see nearer();
-		// reference :106-112
-		auto leaf_test = [&](uint32_t leaf, bool box) {
-			const float4 *tri = tris_ptr + LEAF_F4 * leaf + LEAF_TRI_F4;
-			const float4 q0 = tri[0], q1 = tri[1], q2 = tri[2], q3 = tri[3];
-			if (box) {
-				const TriResult tr = tri_eval<true>(q0, q1, q2, q3, posed_origin<POSED>(ray));
-				if (tr.accepted) {
-					hit = true;
-					if (nearer(tr.distance, leaf, best))
-						take(best, tr, leaf);
-				}
+	const bool exact = !P.fast_walk || wave_ballot(active && !ray_is_selectable(ray, P.origin_limit)) != 0ull;
+	// the exact form's leaf step (exact_walk): closest hit = minimum of (distance, reference leaf), see nearer();
+	// reference :106-112
+	auto leaf_test = [&](uint32_t leaf, bool box) {
+		const float4 *tri = tris_ptr + LEAF_F4 * leaf + LEAF_TRI_F4;
+		const float4 q0 = tri[0], q1 = tri[1], q2 = tri[2], q3 = tri[3];
+		if (box) {
+			const TriResult tr = tri_eval<true>(q0, q1, q2, q3, posed_origin<POSED>(ray));
+			if (tr.accepted) {
+				hit = true;
+				if (nearer(tr.distance, leaf, best))
+					take(best, tr, leaf);
 			}
-			++leaf_stops;
-			return false;  // (closest hit: nobody leaves the walk)
-		};
-		if (!exact) {
-			// Leaves hit by few lanes are collected and tested 64 pairs at a time (see ClosestBatch).
-			cb.best_key[lane] = KEY_NONE;
-			if (lane < 2u)
-				cb.hit_bits[lane] = 0u;
-			unsigned long long my_key = KEY_NONE;  // from the leaves tested on the spot
-			uint32_t waiting = 0u;
-			auto key_of = [](float distance, uint32_t leaf) {
-				return ((unsigned long long) __float_as_uint(distance) << 32) | leaf;
-			};
-			auto run_batch = [&](uint32_t n) {
-				wave_lds_sync();
-				const uint32_t pair = cb.entry[lane < n ? lane : 0u];
-				const int owner = (int) (pair >> 26);
-				Ray theirs = posed_origin<POSED>(ray);  // (all primary rays start at the eye)
-				theirs.dx = __shfl(ray.dx, owner); theirs.dy = __shfl(ray.dy, owner); theirs.dz = __shfl(ray.dz, owner);
-				theirs.ix = __shfl(ray.ix, owner); theirs.iy = __shfl(ray.iy, owner); theirs.iz = __shfl(ray.iz, owner);
-				if (lane < n) {
-					// a candidate of the padded walk: the leaf's own box decides whether the reference tests it (:189)
-					const uint32_t leaf = pair & 0x03FFFFFFu;
-					const float4 lo = load_f4(scene.tris, leaf * LEAF_BYTES), hi = load_f4(scene.tris, leaf * LEAF_BYTES + 16u);
-					if (exact_leaf_gate(lo, hi, theirs, P.primary_below)) {
-						const uint32_t at = leaf * LEAF_BYTES + LEAF_TRI_OFFSET;
-						const Candidate tr = tri_candidate(load_f4(scene.tris, at), load_f4(scene.tris, at + 16u), load_f4(scene.tris, at + 32u),
-						                                   load_f4(scene.tris, at + 48u), hi.w, theirs);
-						if (tr.accepted) {
-							atomicMin(&cb.best_key[owner], key_of(tr.distance, leaf));
-							atomicOr(&cb.hit_bits[owner >> 5], 1u << (owner & 31));
-						}
-					}
-				}
-			};
-			const unsigned long long alive_mask = wave_ballot(active);
-			const SignMasks sign = sign_masks(ray);
-			const uint32_t variant = walk_variant(sign, alive_mask);
-			const uint32_t first = 0u;  // (the plane-form records)
-			const WalkRay walk_ray = make_walk_ray(ray, 1.0f);
-			const uint32_t list_lds_address = (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) (uintptr_t) &cb.entry[0]);  // (low half of the flat address; scalar)
-			const uint32_t end = first + OCRT_PCOLD_U32(P.primary_walk_bytes);
-			uint32_t at = first;  // byte offset
-			// What the reference does not do and no result can show: a lane that has a hit does not enter boxes that begin
-			// BEHIND it.  The reference walks every box its ray meets below 100000 and keeps the minimum of (distance, leaf);
-			// a triangle whose leaf box begins more than `prune_margin` + 1e-5 of the distance behind the nearest hit so far
-			// cannot bring a distance that is smaller or equal (the margin: how far outside its box the reference's slack of
-			// 1e-5 on s and t lets a hit lie -- scene_pack.cc -- and the rounding of the two distances).  `far_limit` is the
-			// node test's upper limit, per lane; it costs the loop nothing (the operand was a scalar register).
-			float far_limit = P.primary_below;
-			{
-				const float margin = OCRT_COLD_F32(P.prune_margin);
-				const uint32_t unpruned = OCRT_PCOLD_U32(P.unpruned_bytes);
-				if (lane == 0u) {
-					cb.prune_margin = margin;
-					cb.unpruned_bytes = unpruned;
-				}
-			}
-			while (alive_mask != 0ull && at < end) {
-				uint32_t leaf = 0u;
-				unsigned long long hit_mask = 0ull;
-				const uint32_t status = walk_collect<false>(variant, walk_ptr, at, walk_ray, sign, far_limit, alive_mask, hit_mask,
-				                                            leaf, waiting, leaf_stops, list_lds_address, lane << 26, P.batch_below);
-				if (status == 0u)
-					break;
-				if (status == 1u) {
-					const float4 *rec = tris_ptr + LEAF_F4 * leaf;
-					const float4 lo = rec[0], hi = rec[1], q0 = rec[2], q1 = rec[3], q2 = rec[4], q3 = rec[5];
-					const Ray here = posed_origin<POSED>(ray);
-					if (((hit_mask >> lane) & 1ull) && exact_leaf_gate(lo, hi, here, P.primary_below)) {
-						const Candidate tr = tri_candidate(q0, q1, q2, q3, hi.w, here);
-						if (tr.accepted) {
-							hit = true;
-							const unsigned long long key = key_of(tr.distance, leaf);
-							my_key = key < my_key ? key : my_key;
-							// (not while the walk is among the faces no box promises anything about -- make_walk_array: they
-							// lie at the head of the records --; afterwards the lane's nearest hit so far counts, theirs included)
-							if (at >= (uint32_t) __float_as_uint(lane_value(__uint_as_float(cb.unpruned_bytes))))
-								far_limit = fminf(far_limit, __uint_as_float((uint32_t) (my_key >> 32)) * 1.00001f + lane_value(cb.prune_margin));
-						}
-					}
-				} else {
-					run_batch(64u);
-					waiting -= 64u;
-					if (lane < waiting)  // the pairs beyond the batch move to the front
-						cb.entry[lane] = cb.entry[64u + lane];
-					wave_lds_sync();
-					const uint32_t nearest = (uint32_t) (cb.best_key[lane] >> 32);  // (distance bits; KEY_NONE: all ones)
-					if (nearest < INF_BITS && at >= (uint32_t) __float_as_uint(lane_value(__uint_as_float(cb.unpruned_bytes))))
-						far_limit = fminf(far_limit, __uint_as_float(nearest) * 1.00001f + lane_value(cb.prune_margin));
-				}
-				at += 32u;
-			}
-			if (waiting != 0u)
-				run_batch(waiting);
-			wave_lds_sync();
-			const unsigned long long batched = cb.best_key[lane];
-			const unsigned long long key = batched < my_key ? batched : my_key;
-			hit = hit || ((cb.hit_bits[lane >> 5] >> (lane & 31u)) & 1u);
-			// the nearest hit's barycentrics and position: the same test once more, on the ray's own lane.  (A
-			// distance of +inf or NaN never satisfies the reference's `best.distance > distance`: `best` stays as it is.)
-			if (hit && (uint32_t) (key >> 32) < INF_BITS) {
-				const uint32_t leaf = (uint32_t) key;
-				take(best, tri_test<true>(scene.tris, leaf, posed_origin<POSED>(ray)), leaf);
-			}
-		} else {
-			const Ray exact_ray = posed_origin<POSED>(ray);  // (no hand-scheduled loop here: the eye may stay in registers)
-			exact_walk(nodes_ptr, count, exact_ray, 100000.0f, active, leaf_test);
 		}
-	}
-#ifdef OCRT_DEBUG_KNOBS
-	if (!SHARED) {
-		const bool regular = P.scene_regular && ray_is_regular(ray);
-		uint32_t i = active ? 0u : count;
-		Pending pending = { NONE, NONE };
-		for (;;) {
-			const unsigned long long walking = wave_ballot(can_walk(pending, i, count));
-			const unsigned long long leaves = wave_ballot(pending.first != NONE);
-			if (leaves != 0ull && ((uint32_t) __popcll(leaves) >= P.leaf_min || walking == 0ull)) {
-				if (pending.first != NONE) {
-					const TriResult tr = tri_test<true>(scene.tris, pending.first, ray);
-					// closest hit = minimum of (distance, reference leaf), see nearer(); reference :106-112
+		++leaf_stops;
+		return false;  // (closest hit: nobody leaves the walk)
+	};
+	if (!exact) {
+		// Leaves hit by few lanes are collected and tested 64 pairs at a time (see ClosestBatch).
+		cb.best_key[lane] = KEY_NONE;
+		if (lane < 2u)
+			cb.hit_bits[lane] = 0u;
+		unsigned long long my_key = KEY_NONE;  // from the leaves tested on the spot
+		uint32_t waiting = 0u;
+		auto key_of = [](float distance, uint32_t leaf) {
+			return ((unsigned long long) __float_as_uint(distance) << 32) | leaf;
+		};
+		auto run_batch = [&](uint32_t n) {
+			wave_lds_sync();
+			const uint32_t pair = cb.entry[lane < n ? lane : 0u];
+			const int owner = (int) (pair >> 26);
+			Ray theirs = posed_origin<POSED>(ray);  // (all primary rays start at the eye)
+			theirs.dx = __shfl(ray.dx, owner); theirs.dy = __shfl(ray.dy, owner); theirs.dz = __shfl(ray.dz, owner);
+			theirs.ix = __shfl(ray.ix, owner); theirs.iy = __shfl(ray.iy, owner); theirs.iz = __shfl(ray.iz, owner);
+			if (lane < n) {
+				// a candidate of the padded walk: the leaf's own box decides whether the reference tests it (:189)
+				const uint32_t leaf = pair & 0x03FFFFFFu;
+				const float4 lo = load_f4(scene.tris, leaf * LEAF_BYTES), hi = load_f4(scene.tris, leaf * LEAF_BYTES + 16u);
+				if (exact_leaf_gate(lo, hi, theirs, P.primary_below)) {
+					const uint32_t at = leaf * LEAF_BYTES + LEAF_TRI_OFFSET;
+					const Candidate tr = tri_candidate(load_f4(scene.tris, at), load_f4(scene.tris, at + 16u), load_f4(scene.tris, at + 32u),
+					                                   load_f4(scene.tris, at + 48u), hi.w, theirs);
+					if (tr.accepted) {
+						atomicMin(&cb.best_key[owner], key_of(tr.distance, leaf));
+						atomicOr(&cb.hit_bits[owner >> 5], 1u << (owner & 31));
+					}
+				}
+			}
+		};
+		const unsigned long long alive_mask = wave_ballot(active);
+		const SignMasks sign = sign_masks(ray);
+		const uint32_t variant = walk_variant(sign, alive_mask);
+		const uint32_t first = 0u;  // (the plane-form records)
+		const WalkRay walk_ray = make_walk_ray(ray, 1.0f);
+		const uint32_t list_lds_address = (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) (uintptr_t) &cb.entry[0]);  // (low half of the flat address; scalar)
+		const uint32_t end = first + OCRT_PCOLD_U32(P.primary_walk_bytes);
+		uint32_t at = first;  // byte offset
+		// What the reference does not do and no result can show: a lane that has a hit does not enter boxes that begin
+		// BEHIND it.  The reference walks every box its ray meets below 100000 and keeps the minimum of (distance, leaf);
+		// a triangle whose leaf box begins more than `prune_margin` + 1e-5 of the distance behind the nearest hit so far
+		// cannot bring a distance that is smaller or equal (the margin: how far outside its box the reference's slack of
+		// 1e-5 on s and t lets a hit lie -- scene_pack.cc -- and the rounding of the two distances).  `far_limit` is the
+		// node test's upper limit, per lane; it costs the loop nothing (the operand was a scalar register).
+		float far_limit = P.primary_below;
+		{
+			const float margin = OCRT_COLD_F32(P.prune_margin);
+			const uint32_t unpruned = OCRT_PCOLD_U32(P.unpruned_bytes);
+			if (lane == 0u) {
+				cb.prune_margin = margin;
+				cb.unpruned_bytes = unpruned;
+			}
+		}
+		while (alive_mask != 0ull && at < end) {
+			uint32_t leaf = 0u;
+			unsigned long long hit_mask = 0ull;
+			const uint32_t status = walk_collect<false>(variant, walk_ptr, at, walk_ray, sign, far_limit, alive_mask, hit_mask,
+			                                            leaf, waiting, leaf_stops, list_lds_address, lane << 26, P.batch_below);
+			if (status == 0u)
+				break;
+			if (status == 1u) {
+				const float4 *rec = tris_ptr + LEAF_F4 * leaf;
+				const float4 lo = rec[0], hi = rec[1], q0 = rec[2], q1 = rec[3], q2 = rec[4], q3 = rec[5];
+				const Ray here = posed_origin<POSED>(ray);
+				if (((hit_mask >> lane) & 1ull) && exact_leaf_gate(lo, hi, here, P.primary_below)) {
+					const Candidate tr = tri_candidate(q0, q1, q2, q3, hi.w, here);
 					if (tr.accepted) {
 						hit = true;
-						if (nearer(tr.distance, pending.first, best))
-							take(best, tr, pending.first);
+						const unsigned long long key = key_of(tr.distance, leaf);
+						my_key = key < my_key ? key : my_key;
+						// (not while the walk is among the faces no box promises anything about -- make_walk_array: they
+						// lie at the head of the records --; afterwards the lane's nearest hit so far counts, theirs included)
+						if (at >= (uint32_t) __float_as_uint(lane_value(__uint_as_float(cb.unpruned_bytes))))
+							far_limit = fminf(far_limit, __uint_as_float((uint32_t) (my_key >> 32)) * 1.00001f + lane_value(cb.prune_margin));
 					}
-					pending.first = pending.second;
-					pending.second = NONE;
 				}
-				continue;
+			} else {
+				run_batch(64u);
+				waiting -= 64u;
+				if (lane < waiting)  // the pairs beyond the batch move to the front
+					cb.entry[lane] = cb.entry[64u + lane];
+				wave_lds_sync();
+				const uint32_t nearest = (uint32_t) (cb.best_key[lane] >> 32);  // (distance bits; KEY_NONE: all ones)
+				if (nearest < INF_BITS && at >= (uint32_t) __float_as_uint(lane_value(__uint_as_float(cb.unpruned_bytes))))
+					far_limit = fminf(far_limit, __uint_as_float(nearest) * 1.00001f + lane_value(cb.prune_margin));
 			}
-			if (walking == 0ull)
-				break;
-			advance_walkers(scene, ray, regular, 100000.0f, P.primary_below, count, i, pending);
-			if ((uint32_t) __popcll(wave_ballot(pending.first != NONE)) < P.leaf_min)
-				advance_walkers(scene, ray, regular, 100000.0f, P.primary_below, count, i, pending);
+			at += 32u;
 		}
+		if (waiting != 0u)
+			run_batch(waiting);
+		wave_lds_sync();
+		const unsigned long long batched = cb.best_key[lane];
+		const unsigned long long key = batched < my_key ? batched : my_key;
+		hit = hit || ((cb.hit_bits[lane >> 5] >> (lane & 31u)) & 1u);
+		// the nearest hit's barycentrics and position: the same test once more, on the ray's own lane.  (A
+		// distance of +inf or NaN never satisfies the reference's `best.distance > distance`: `best` stays as it is.)
+		if (hit && (uint32_t) (key >> 32) < INF_BITS) {
+			const uint32_t leaf = (uint32_t) key;
+			take(best, tri_test<true>(scene.tris, leaf, posed_origin<POSED>(ray)), leaf);
+		}
+	} else {
+		const Ray exact_ray = posed_origin<POSED>(ray);  // (no hand-scheduled loop here: the eye may stay in registers)
+		exact_walk(nodes_ptr, count, exact_ray, 100000.0f, active, leaf_test);
 	}
-#endif
 
 	// smooth normal and head-light term, reference :296-304
 	float value = 0.0f;
@@ -339,7 +299,7 @@ __device__ __forceinline__ void primary_tile(const FrameArgs &A, ClosestBatch &c
 		// walk about as far as the primary packet did (correlation 0.8-0.9, tools/analysis/packet_union.cc).
 		// The hit count does not predict the cost at all: a sparse tile's packets mix several directions
 		// and walk as many nodes as a full tile's.
-		uint32_t cost = SHARED ? leaf_stops : hit_count;
+		uint32_t cost = leaf_stops;
 		cost = cost < 1u ? 1u : cost;
 		cost = cost > 64u ? 64u : cost;
 		OCRT_PCOLD_PTR(uint32_t *, tile_hits)[tile] = hit_count | (hit_count ? cost << 8 : 0u);
@@ -377,7 +337,7 @@ constexpr uint32_t PRIMARY_ROWS = PRIMARY_WAVES / 2u;
 constexpr uint32_t PRIMARY_NO_ENTRY = 0xFFFFFFFFu;  // (an empty place in primary_kernel's list)
 
 // (the body of the pass; POSED: primary_tile's.  Two kernels below, so that the default one keeps its name and its ISA.)
-template <bool SHARED, bool POSED>
+template <bool POSED>
 __device__ __forceinline__ void primary_pass(const PrimaryArgs &A) {
 	__shared__ ClosestBatch closest_batches[PRIMARY_WAVES];
 	const uint32_t wave = threadIdx.x >> 6;
@@ -433,7 +393,7 @@ __device__ __forceinline__ void primary_pass(const PrimaryArgs &A) {
 	}
 #endif
 	if (there)
-		primary_tile<SHARED, POSED>(A, closest_batches[wave], tile_x, local_row, part, quarter_hits);
+		primary_tile<POSED>(A, closest_batches[wave], tile_x, local_row, part, quarter_hits);
 #ifdef OCRT_PRIMARY_TICKS
 	uint32_t *const ticks_out = *(uint32_t *const volatile *) ((const char *) __builtin_amdgcn_kernarg_segment_ptr() + offsetof(FrameArgs, tile_cost));
 	if (ticks_out && (threadIdx.x & 63u) == 0u && tick0[threadIdx.x >> 6][1] != 0xFFFFFFFFu)
@@ -441,14 +401,12 @@ __device__ __forceinline__ void primary_pass(const PrimaryArgs &A) {
 #endif
 }
 
-template <bool SHARED>
 __global__ __launch_bounds__(64 * PRIMARY_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void primary_kernel(PrimaryArgs A) {
-	primary_pass<SHARED, false>(A);
+	primary_pass<false>(A);
 }
 // ... for a host with a camera pose (DeviceRenderer::setCamera): the same pass, eye and basis read from the launch constants
-template <bool SHARED>
 __global__ __launch_bounds__(64 * PRIMARY_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void primary_posed_kernel(PrimaryArgs A) {
-	primary_pass<SHARED, true>(A);
+	primary_pass<true>(A);
 }
 
 }  // namespace ocrt

@@ -9,8 +9,8 @@ namespace ocrt {
 // Shared walk.  The 64 rays of a wave visit the union of their nodes together:
 // one wave-uniform node index `at`, so a node (and a leaf's triangle) arrives by
 // scalar loads and the box is tested out of SGPRs; no per-lane index, no gathers,
-// no scheduling.  Needs sibling subtrees to tile their parent's index range (KernelParams::shared_walk;
-// checked at upload for the uploaded binary tree and again for the rebuilt, possibly wider one).
+// no scheduling.  Needs sibling subtrees to tile their parent's index range (pack_scene: an upload that is
+// no full binary tree is refused, and the rebuilt, possibly wider tree is checked again).
 //
 // Fast form (`exact` false: regular scene with nested boxes, regular rays): every
 // live lane tests every visited box.  A lane that missed an ancestor also misses

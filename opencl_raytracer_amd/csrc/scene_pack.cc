@@ -105,7 +105,6 @@ PackedScene pack_scene(const std::vector<uint32_t> &faces, const std::vector<uin
 	if (leaf != tri_count)
 		throw std::invalid_argument("upload: leaf count differs from triangle count");
 	// children of inner node i are i+1 and i+1+skip(i+1)
-	out.binary_tree = true;
 	out.nested = true;
 	for (size_t i = 0; i < count; ++i) {
 		const NodeRec &p = out.nodes[i];
@@ -671,9 +670,6 @@ uint32_t local_tile_rows_for(uint32_t total_height, const Partition &part) {
 
 SceneFacts scene_facts(const PackedScene &scene, const WalkArray &walk) {
 	SceneFacts f;
-	f.regular = scene.regular;
-	f.nested = scene.nested;
-	f.binary_tree = scene.binary_tree;
 	f.has_walk = !walk.nodes.empty();
 	f.origin_limit = walk.origin_limit;
 	f.ao_scale = walk.ao_scale;
@@ -721,13 +717,7 @@ KernelParams make_kernel_params(const RayTracer &rt, uint32_t node_count, uint32
 	                walk_scale_usable(facts->ao_scale, facts->origin_limit) &&
 	                !debug_knob("OCRT_NO_SCALED_WALK")) ? facts->ao_scale : 0.0f;  // (debug knob)
 	p.fast_walk = (facts && facts->has_walk && !debug_knob("OCRT_FORCE_EXACT_WALK")) ? 1 : 0;  // (debug knob)
-	p.scene_regular = (facts && facts->regular) ? 1 : 0;
-	p.scene_nested = (facts && facts->nested && !debug_knob("OCRT_FORCE_EXACT_WALK")) ? 1 : 0;  // (debug knob)
-	p.shared_walk = (facts && facts->binary_tree && !debug_knob("OCRT_NO_SHARED_WALK")) ? 1 : 0;  // (debug knob)
 	p.debug_no_sort = debug_knob("OCRT_NO_SORT") ? 1 : 0;
-	const char *refill_min = debug_knob("OCRT_REFILL_MIN"), *leaf_min = debug_knob("OCRT_LEAF_MIN");
-	p.refill_min = refill_min ? (uint32_t) std::atoi(refill_min) : 16u;
-	p.leaf_min = leaf_min ? (uint32_t) std::atoi(leaf_min) : 16u;
 	const char *guide = debug_knob("OCRT_AO_GUIDE");  // debug knob
 	p.ao_guide = guide && std::atoi(guide) > 0 ? (uint32_t) std::atoi(guide) : 0u;  // (0: claims never shrink, the default)
 	const char *claim_max = debug_knob("OCRT_AO_CLAIM_MAX");  // debug knob

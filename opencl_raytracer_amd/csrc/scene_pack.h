@@ -41,10 +41,10 @@ struct PackedScene {
 	std::vector<ShadeRec> shade;
 	// The flags describe `nodes` as the kernels will walk it -- the uploaded array, or (rebuilt = true) the
 	// cheaper tree over the same leaves that pack_scene put in its place and re-validated.
-	bool regular = false;  // all boxes finite, |coord| <= 1e37, lo <= hi (see kernels.hip slab_hit_regular)
-	bool binary_tree = false;  // sibling subtrees tile their parent's index range (the UPLOADED array must be a full
-	                           // binary tree, what the reference's triangle counter assumes; a rebuilt one may have
-	                           // inner nodes with more children: the skip list and the shared walk do not care)
+	// Sibling subtrees always tile their parent's index range: the UPLOADED array must be a full binary tree (what the
+	// reference's triangle counter assumes; pack_scene throws otherwise), a rebuilt one may have inner nodes with more
+	// children -- the skip list and the shared walk do not care.
+	bool regular = false;  // all boxes finite, |coord| <= 1e37, lo <= hi
 	bool nested = false;       // ... and every node's box contains its children's boxes (true for any tree built by
 	                           // uniting child boxes; arbitrary uploaded arrays need not be)
 	bool rebuilt = false;      // `nodes` is the rebuilt tree, not the uploaded one
@@ -114,7 +114,6 @@ uint32_t local_tile_rows_for(uint32_t total_height, const Partition &part);
 
 // What the launch constants need to know of an uploaded scene (the arrays themselves stay on the device).
 struct SceneFacts {
-	bool regular = false, nested = false, binary_tree = false;  // PackedScene's flags
 	bool has_walk = false;                                       // the padded walk array exists
 	float origin_limit = 0.0f, ao_scale = 0.0f;                  // WalkArray's
 	float prune_margin = 0.0f;                                   // WalkArray's

@@ -134,7 +134,7 @@ std::vector<uint32_t> DeviceRenderer::orderByMeasuredCost(const std::vector<floa
 	// (half-tile claims end where the LDS cursor says, and the pass takes the cursor form below 0x8000 directions only --
 	// its word holds end << 16 | next --: from there on fixed shares would run up to three units past a half, into the
 	// next claim's, and those rays would be cast and counted twice.  No tile is split then.)
-	if (split && order_policy.split_above > 0.0f && kp.shared_walk && (kp.ao_dirs & 1u) == 0u && kp.ao_dirs >= 2u && kp.ao_dirs < 0x8000u) {
+	if (split && order_policy.split_above > 0.0f && (kp.ao_dirs & 1u) == 0u && kp.ao_dirs >= 2u && kp.ao_dirs < 0x8000u) {
 		double total = 0.0;
 		for (float c : cost)
 			total += c;

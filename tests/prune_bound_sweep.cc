@@ -454,7 +454,7 @@ void sweep_stream(int stream, unsigned long long triangles, double factor, Tally
 				one.nodes[0].skip = 1;
 				one.nodes[0].leaf = 0;
 				one.tris.push_back(t);
-				one.regular = one.nested = one.binary_tree = true;
+				one.regular = one.nested = true;
 				const WalkArray w = make_walk_array(one, 0.0f, true, eye);
 				++tally.compared;
 				bool same = !w.nodes.empty() && w.eye_covered && std::memcmp(&w.prune_margin, &leaf.margin, sizeof(float)) == 0 &&

@@ -9,13 +9,12 @@ would otherwise turn into silent scratch traffic in the hottest loop.
 
     check_kernel_resources.py <remarks.txt> [--table out.txt] [--isa kernels.s] [--report-only]
 
-Hot kernels (must have VGPR spill 0, scratch 0, occupancy 8): the default path, i.e. the
-shared-walk instantiations primary_kernel<true>, its posed form primary_posed_kernel<true> (a host with a camera
-pose: the same pass, eye and basis read from the launch constants) and ao_kernel<1, true> (1 = UNIFORM).  The build
+Hot kernels (must have VGPR spill 0, scratch 0, occupancy 8): the default path, i.e.
+primary_kernel, its posed form primary_posed_kernel (a host with a camera
+pose: the same pass, eye and basis read from the launch constants) and ao_kernel<1, ..> (1 = UNIFORM).  The build
 fails, too, when one of the two primary kernels is not found in the remarks at all: the kernels are matched by the prefix
-of their demangled names, and a gate that matches nothing guards nothing.  The
-first-generation instantiations (<.., false>, debug knob OCRT_NO_SHARED_WALK) and the RANDOM
-mode (ao_kernel<2, ..>, outside the bit-exact contract) must keep the occupancy; their
+of their demangled names, and a gate that matches nothing guards nothing.  The RANDOM
+mode (ao_kernel<2, ..>, outside the bit-exact contract) must keep the occupancy; its
 spills are reported, not fatal.  The ray-query kernels (query_kernel<true> / <false>, query_key_kernel,
 query_scatter_kernel, query_scan_kernel: kernels/query.hip.h) must be present, with VGPR spill 0 and scratch 0; they do
 not use walk_collect's fixed registers (their walk is the exact form, plain C++ around one scalar load per node), so no
@@ -35,10 +34,10 @@ import sys
 LANE_OPS_PER_WALK_TURN = 10  # v_readlane / v_writelane per turn of the loop around walk_collect, i.e. per leaf stop or batch (measured: 6 primary;
                              # 9 AO: four in the batch block, five single reloads on paths that exclude each other)
 LANE_OPS_PER_PACKET = 40     # ... in the per-packet code around that loop (measured: 38 of ~700 vector instructions)
-# ... and for the posed form of the primary pass (primary_posed_kernel<true>), which holds more launch constants around the walk
+# ... and for the posed form of the primary pass (primary_posed_kernel), which holds more launch constants around the walk
 POSED_LANE_OPS_PER_WALK_TURN = 4  # (measured: 2 -- the eye is read again at every leaf stop instead of being held, kernels/primary.hip.h)
 POSED_LANE_OPS_PER_PACKET = 8     # (measured: 5 of ~700 vector instructions)
-HOT_PRIMARY = ("primary_kernel<true>", "primary_posed_kernel<true>")
+HOT_PRIMARY = ("primary_kernel", "primary_posed_kernel")
 
 FIELDS = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill",
           "VGPRs Spill", "LDS Size [bytes/block]")
@@ -128,9 +127,9 @@ def main():
                f"{k.get('ScratchSize [bytes/lane]', '?'):>8s} {k.get('Occupancy [waves/SIMD]', '?'):>10s} "
                f"{k.get('SGPRs Spill', '?'):>10s} {k.get('VGPRs Spill', '?'):>10s} {k.get('LDS Size [bytes/block]', '?'):>7s}")
         lines.append(row)
-        # hot: the default path = shared-walk instantiations of the primary pass and of the UNIFORM ambient-occlusion pass
-        hot = name.startswith(HOT_PRIMARY) or name.startswith("ao_kernel<1, true")
-        walker = hot or name.startswith("ao_kernel<") or name.startswith("primary_kernel<") or name.startswith("primary_posed_kernel<")
+        # hot: the default path = the primary pass's two kernels and the UNIFORM ambient-occlusion pass
+        hot = name.startswith(HOT_PRIMARY) or name.startswith("ao_kernel<1, ")
+        walker = hot or name.startswith("ao_kernel<")
         if walker and k.get("Occupancy [waves/SIMD]") != "8":
             errors.append(f"{name}: occupancy {k.get('Occupancy [waves/SIMD]')} waves/SIMD, the walk is scheduled for 8")
         if hot and (k.get("VGPRs Spill") != "0" or k.get("ScratchSize [bytes/lane]") != "0"):
@@ -159,9 +158,9 @@ def main():
         for kname, p in places.items():
             short = kname.replace("ocrt::", "").replace("void ", "")
             lines.append(f"{short:44s} {p['total']:5d} {p['in_node_loop']:5d} {p['walk_turn']:5d} {p['per_packet']:5d}   {p['depths']}")
-            if not (short.startswith(HOT_PRIMARY) or short.startswith("ao_kernel<1, true")):
+            if not (short.startswith(HOT_PRIMARY) or short.startswith("ao_kernel<1, ")):
                 continue
-            posed = short.startswith("primary_posed_kernel<true>")
+            posed = short.startswith("primary_posed_kernel")
             turn_limit = POSED_LANE_OPS_PER_WALK_TURN if posed else LANE_OPS_PER_WALK_TURN
             packet_limit = POSED_LANE_OPS_PER_PACKET if posed else LANE_OPS_PER_PACKET
             if p["in_node_loop"]:

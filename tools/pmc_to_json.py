@@ -71,7 +71,7 @@ def main():
         entry = {
             "kernel": names[0],
             "valu_insts": c.get("SQ_INSTS_VALU"), "salu_insts": c.get("SQ_INSTS_SALU"), "smem_insts": c.get("SQ_INSTS_SMEM"),
-            # every kernel of a frame together (primary pass with the ordering step, ambient-occlusion pass, finishing kernel)
+            # every kernel of a frame together (primary pass, ambient-occlusion pass, finishing kernel)
             "frame_valu_insts": sum(kernels[name].get("SQ_INSTS_VALU", 0.0) for name in kernels_of_a_frame(kernels)),
             "vmem_rd_insts": c.get("SQ_INSTS_VMEM_RD"), "lds_insts": c.get("SQ_INSTS_LDS"), "branch_insts": c.get("SQ_INSTS_BRANCH"),
             "waves": c.get("SQ_WAVES"), "wave_quad_cycles": c.get("SQ_WAVE_CYCLES"), "busy_cycles": c.get("SQ_BUSY_CYCLES"),
