@@ -104,6 +104,14 @@ int rt_debug_prune_facts(rt_host *h, float *prune_margin, uint32_t *unpruned_byt
  * leaned on what the one before it left there could never be seen without this.  Waits for the host's frames first. */
 int rt_debug_poison_hit_list(rt_host *h);
 
+/* Multi-view rendering (rt_hip_views.h).  rt_debug_set_views_chunk: a views call works through at most `max_views` views
+ * per chunk (0, the default: as many as fit) -- so that a test can make several chunks of a few small views; results never
+ * depend on it.  rt_debug_last_views: what the host's last views call did -- the views it rendered, the chunks it took,
+ * and the points its ambient-occlusion step ran over: the sub-pixels that were hit, over all the views (0 for a call
+ * without that step).  Zeros before the first call; out pointers may be NULL.  RT_E_STATE on the hosts of a frame ring. */
+int rt_debug_set_views_chunk(rt_host *h, uint32_t max_views);
+int rt_debug_last_views(rt_host *h, uint32_t *views, uint32_t *chunks, uint64_t *ao_points);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@ raises.
 """
 from .api import (  # noqa: F401
     LAYER_OUTPUTS,
+    VIEW_OUTPUTS,
     Camera,
     FrameRing,
     Host,

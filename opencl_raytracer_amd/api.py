@@ -217,6 +217,8 @@ _SIGNATURES = {
     "rt_debug_split_tiles": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_debug_prune_facts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_poison_hit_list": (C.c_int, [C.c_void_p]),
+    "rt_debug_set_views_chunk": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_debug_last_views": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     # include/rt_hip_query.h
     "rt_trace_closest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
     "rt_trace_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
@@ -237,6 +239,9 @@ _SIGNATURES = {
     # include/rt_hip_layers.h
     "rt_render_layers": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_render_layers_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    # include/rt_hip_views.h
+    "rt_render_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rt_render_views_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     # include/rt_hip_camera.h
     "rt_camera_default": (None, [C.POINTER(Camera)]),
     "rt_camera_look_at": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Camera)]),
@@ -263,12 +268,18 @@ class _LayerArrays(C.Structure):
     _fields_ = _HitArrays._fields_ + [("direction", C.c_void_p), ("shade", C.c_void_p), ("ao", C.c_void_p), ("value", C.c_void_p)]
 
 
+class _ViewArrays(C.Structure):
+    """rt_view_arrays (include/rt_hip_views.h)."""
+    _fields_ = [("layers", _LayerArrays), ("image", C.c_void_p)]
+
+
 RT_QUERY_NO_SORT = 1
 RT_MULTIHIT_MAX_K = 16
 MULTIHIT_OUTPUTS = ("count", "distance", "leaf", "barycentric", "position", "normal")
 QUERY_OUTPUTS = ("hit", "distance", "leaf", "barycentric", "position", "normal")
 AO_OUTPUTS = ("ao", "occluded")
 LAYER_OUTPUTS = QUERY_OUTPUTS + ("direction", "shade", "ao", "value")
+VIEW_OUTPUTS = LAYER_OUTPUTS + ("image",)
 # per output of any query: numpy dtype, values per record.  The first four are one value per ray or point; the others are
 # the fields of a hit record: one record per ray (closest hit) or k of them (multi-hit).
 _OUTPUT_LAYOUT = {"hit": (np.uint8, 1), "count": (np.uint32, 1), "ao": (np.float32, 1), "occluded": (np.uint32, 1),
@@ -841,6 +852,68 @@ class Host:
         arrays = _LayerArrays(*[out[name].ctypes.data if name in out else None for name in LAYER_OUTPUTS])
         _check(lib.rt_render_layers(self._h, C.byref(arrays)))
         return out
+
+    # ---- multi-view rendering (include/rt_hip_views.h) ----
+    def render_views(self, cameras, outputs=("value",), as_torch: bool = False) -> dict:
+        """The frame layers and the finished 8-bit image of V poses against the uploaded scene, in one call and without a
+        new upload: {output name: (V, H, W) or (V, H, W, 3) array} with H x W = total_height x total_width, and "image":
+        (V, height, width) uint8 (those named in `outputs`, from VIEW_OUTPUTS).  View v's block of a layer is what
+        render_layers returns on a host that was given cameras[v] with set_camera before its upload; "image" is what its
+        download_u8() returns after render().  `cameras`: a sequence of Camera, or a (V, 4, 3) float32 array (eye, right,
+        up, forward per view, used as given).  The host's own pose plays no part.  numpy out (blocking), or with
+        as_torch=True torch tensors on the host's GPU, enqueued on torch.cuda.current_stream() (the rules are
+        render_layers')."""
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in VIEW_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {VIEW_OUTPUTS}")
+        if isinstance(cameras, np.ndarray):
+            if cameras.dtype != np.float32 or cameras.ndim != 3 or cameras.shape[1:] != (4, 3):
+                raise ValueError("cameras: expected a float32 array of shape (V, 4, 3), or a sequence of Camera")
+            poses = np.ascontiguousarray(cameras)
+        else:
+            cameras = list(cameras)
+            if not all(isinstance(c, Camera) for c in cameras):
+                raise ValueError("cameras: expected a sequence of Camera, or a float32 array of shape (V, 4, 3)")
+            poses = np.array([c.as_array() for c in cameras], dtype=np.float32).reshape(-1, 4, 3)
+        views = int(poses.shape[0])
+        h, w = self.options.total_height, self.options.total_width
+        shapes = {name: (views, self.options.height, self.options.width) if name == "image" else
+                  (views, h, w) + ((_OUTPUT_LAYOUT[name][1],) if _OUTPUT_LAYOUT[name][1] > 1 else ()) for name in outputs}
+        dtypes = {name: np.uint8 if name == "image" else _OUTPUT_LAYOUT[name][0] for name in outputs}
+        lib = load_library()
+        if as_torch:
+            import torch
+
+            index = getattr(self, "_device", -1)
+            device = torch.device("cuda", index if index >= 0 else int(os.environ.get("OCRT_DEVICE", "0")))
+            out = {name: torch.empty(shape, dtype=getattr(torch, np.dtype(dtypes[name]).name), device=device)
+                   for name, shape in shapes.items()}
+            address = lambda t: t.data_ptr()
+        else:
+            out = {name: np.empty(shape, dtype=dtypes[name]) for name, shape in shapes.items()}
+            address = lambda a: a.ctypes.data
+        # (an array that holds nothing is not named: V = 0 asks for nothing)
+        pointers = [address(out[name]) if name in out and views else None for name in VIEW_OUTPUTS]
+        arrays = _ViewArrays(_LayerArrays(*pointers[:-1]), pointers[-1])
+        if as_torch:
+            _check(lib.rt_render_views_device(self._h, poses.ctypes.data, views, C.byref(arrays),
+                                              torch.cuda.current_stream(device).cuda_stream))
+        else:
+            _check(lib.rt_render_views(self._h, poses.ctypes.data, views, C.byref(arrays)))
+        return out
+
+    def set_views_chunk(self, max_views: int) -> None:
+        """Test aid (include/rt_hip_debug.h, rt_debug_set_views_chunk): at most `max_views` views per chunk of a
+        render_views call; 0: as many as fit.  Same results."""
+        _check(load_library().rt_debug_set_views_chunk(self._h, int(max_views)))
+
+    def last_views(self) -> dict:
+        """What the last render_views call did (include/rt_hip_debug.h, rt_debug_last_views): {"views", "chunks",
+        "ao_points": the sub-pixels its ambient-occlusion step ran over -- the hit ones}."""
+        views, chunks, points = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        _check(load_library().rt_debug_last_views(self._h, C.byref(views), C.byref(chunks), C.byref(points)))
+        return {"views": views.value, "chunks": chunks.value, "ao_points": points.value}
 
     def vertex_ao(self, scene: "Scene") -> np.ndarray:
         """Per-vertex AO baking: ambient_occlusion(scene.vertices, scene.vnormals)["ao"], one value per vertex of the file, in

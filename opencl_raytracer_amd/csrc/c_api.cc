@@ -1,5 +1,5 @@
 // c_api.cc -- the extern "C" boundary declared in include/rt_hip.h (the seam), rt_hip_ring.h (streams of frames, several GPUs), rt_hip_debug.h,
-// rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h, rt_hip_layers.h and rt_hip_camera.h.
+// rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h, rt_hip_layers.h, rt_hip_views.h and rt_hip_camera.h.
 #include "../../include/rt_hip.h"
 #include "../../include/rt_hip_ao.h"
 #include "../../include/rt_hip_camera.h"
@@ -7,6 +7,7 @@
 #include "../../include/rt_hip_debug.h"
 #include "../../include/rt_hip_multihit.h"
 #include "../../include/rt_hip_query.h"
+#include "../../include/rt_hip_views.h"
 
 #include <algorithm>
 #include <hip/hip_runtime.h>
@@ -1032,6 +1033,71 @@ int rt_render_layers_device(rt_host *h, const rt_layer_arrays *out, void *hip_st
 	if (!(records_aligned(q) && aligned({ q.direction, q.shade, q.ao, q.value }, 4)))
 		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
 	return guarded([&] { queries_of(h).layersDevice(q, hip_stream); });
+}
+
+// ---- rt_hip_views.h ----
+namespace {
+
+// What both views entry points check before they touch the device (include/rt_hip_views.h, "Errors"); the limits that
+// depend on the host's options are RayQueries::requireViews'.
+int views_precheck(const rt_host *h, const rt_camera *cameras, uint32_t views, const rt_view_arrays *out) {
+	const int rc = host_precheck(h, "multi-view");
+	if (rc != RT_OK)
+		return rc;
+	if (!out)
+		return fail(RT_E_INVALID, "null view arrays");
+	if (views > 0 && !cameras)
+		return fail(RT_E_INVALID, "null cameras");
+	return RT_OK;
+}
+
+ocrt::ViewOutputs view_outputs(const rt_view_arrays &from) {
+	ocrt::ViewOutputs q;
+	static_cast<ocrt::LayerOutputs &>(q) = layer_outputs(from.layers);
+	q.image = from.image;
+	return q;
+}
+
+}  // namespace
+
+int rt_render_views(rt_host *h, const rt_camera *cameras, uint32_t views, const rt_view_arrays *out) {
+	const int rc = views_precheck(h, cameras, views, out);
+	if (rc != RT_OK)
+		return rc;
+	return guarded([&] { queries_of(h).viewsHost(reinterpret_cast<const ocrt::CameraPose *>(cameras), views, view_outputs(*out)); });
+}
+
+int rt_render_views_device(rt_host *h, const rt_camera *cameras, uint32_t views, const rt_view_arrays *out, void *hip_stream) {
+	const int rc = views_precheck(h, cameras, views, out);
+	if (rc != RT_OK)
+		return rc;
+	const ocrt::ViewOutputs q = view_outputs(*out);
+	if (!(records_aligned(q) && aligned({ q.direction, q.shade, q.ao, q.value }, 4)))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).viewsDevice(reinterpret_cast<const ocrt::CameraPose *>(cameras), views, q, hip_stream); });
+}
+
+int rt_debug_set_views_chunk(rt_host *h, uint32_t max_views) {
+	if (!h)
+		return fail(RT_E_INVALID, "null host");
+	if (!h->owned)
+		return fail(RT_E_STATE, "multi-view queries are not available on the hosts of a frame ring");
+	return guarded([&] { queries_of(h).setViewsChunk(max_views); });
+}
+
+int rt_debug_last_views(rt_host *h, uint32_t *views, uint32_t *chunks, uint64_t *ao_points) {
+	if (!h)
+		return fail(RT_E_INVALID, "null host");
+	if (!h->owned)
+		return fail(RT_E_STATE, "multi-view queries are not available on the hosts of a frame ring");
+	const ocrt::RayQueries::ViewsDone done = h->queries ? h->queries->lastViews() : ocrt::RayQueries::ViewsDone();
+	if (views)
+		*views = done.views;
+	if (chunks)
+		*chunks = done.chunks;
+	if (ao_points)
+		*ao_points = done.ao_points;
+	return RT_OK;
 }
 
 float rt_last_query_ms(const rt_host *h) {

@@ -194,6 +194,23 @@ struct LayerOutputs : QueryOutputs {
 	bool any() const { return hit || anySlot() || direction || shade || ao || value; }
 };
 
+// Multi-view rendering (include/rt_hip_views.h): the layers of `views` poses, view v's block of a layer behind view v - 1's,
+// and their 8-bit images, by view, output row and output column.
+struct ViewOutputs : LayerOutputs {
+	unsigned char *image = nullptr;
+	bool any() const { return LayerOutputs::any() || image; }
+};
+// The hit sub-pixels of a chunk of views, listed for the ambient-occlusion step (kernels/views.hip.h): device pointers;
+// m = the chunk's sub-pixels.
+struct ViewList {
+	unsigned char *flags;    // [m] 1 = hit
+	void *points, *normals;  // [m] float4 each, written where flagged; normal.w: the head-light term
+	uint32_t *seeds;         // [m] the sub-pixel's index within its view
+	uint32_t *sums;          // [m / 1024 rounded up] the flags set per block of 1024 sub-pixels, then their prefix sums
+	uint32_t *order;         // [m] the j-th hit sub-pixel in index order
+	uint32_t *listed;        // their number
+};
+
 // Waves per workgroup of the ambient-occlusion pass: they take consecutive parts of a claim (kernels.hip), which is
 // why the host deals the UNIFORM direction table to that many groups (device_renderer.cc).
 constexpr uint32_t AO_WORKGROUP_WAVES = 4;

@@ -37,6 +37,10 @@
 //                   layers_kernel<POSED> casts the frame's own rays, a wave per tile, and writes every sub-pixel's record, direction
 //                   and head-light term, layers_combine_kernel their product with the ambient-occlusion factors
 //                   (kernels/layers.hip.h, include/rt_hip_layers.h).
+//                   views_kernel does the same for every pose of a chunk of views, a wave per (view, tile), and lists the hit
+//                   sub-pixels for ao_query_kernel (views_count_kernel, views_scan_sums_kernel, views_order_kernel: their number
+//                   and order); views_scatter_kernel writes their factors and products, views_resize_kernel every view's
+//                   8-bit image (kernels/views.hip.h, include/rt_hip_views.h).
 //   (on demand)     entry_kernel: the walk intervals, once per upload; occluded_sum_kernel: the frame's occlusion
 //                   total when the statistics are asked for; resize_kernel: a box filter on its own.
 // Why not one fused launch (it was, see profiles/r01_notes.md): cost per tile
@@ -73,6 +77,7 @@
 #include "kernels/ao_query.hip.h"
 #include "kernels/multihit.hip.h"
 #include "kernels/layers.hip.h"
+#include "kernels/views.hip.h"
 
 
 namespace ocrt {
@@ -417,30 +422,36 @@ void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void 
 
 // Frame layers (kernels/layers.hip.h).  `points`, `normals`: n = width * height float4 of scratch each, or null -- no
 // ambient-occlusion step follows; `value`: where the head-light term goes once more (a host without ambient occlusion).
-void launch_layers(const SceneBuffers &scene, const KernelParams &P, const CameraPose &pose, bool posed, const LayerOutputs &out,
-                   float *value, void *points, void *normals, void *stream) {
-	const uint32_t tiles_x = (P.width + TILE_W - 1u) / TILE_W, tiles = tiles_x * ((P.height + TILE_H - 1u) / TILE_H);
-	if (tiles == 0)
-		return;
+// (what layers_kernel and views_kernel are launched with alike)
+static LayersArgs layers_args(const SceneBuffers &scene, const KernelParams &P, const LayerOutputs &out, float *value) {
 	LayersArgs a{};
 	a.nodes_ptr = (const float4 *) scene.nodes;
 	a.tris_ptr = (const float4 *) scene.tris;
 	a.shade_recs = (const float4 *) scene.shade;
 	a.width = P.width;
 	a.height = P.height;
-	a.tiles_x = tiles_x;
-	a.tiles = tiles;
+	a.tiles_x = (P.width + TILE_W - 1u) / TILE_W;
+	a.tiles = a.tiles_x * ((P.height + TILE_H - 1u) / TILE_H);
 	a.node_count = P.node_count;
 	a.shading = P.shading;
 	a.a = P.a;
 	a.half_w = P.half_w;
 	a.half_h = P.half_h;
-	a.pose = pose;
 	a.hit = out.hit;
 	a.out = out;
 	a.direction = out.direction;
 	a.shade = out.shade;
 	a.value = value;
+	return a;
+}
+
+void launch_layers(const SceneBuffers &scene, const KernelParams &P, const CameraPose &pose, bool posed, const LayerOutputs &out,
+                   float *value, void *points, void *normals, void *stream) {
+	LayersArgs a = layers_args(scene, P, out, value);
+	const uint32_t tiles = a.tiles;
+	if (tiles == 0)
+		return;
+	a.pose = pose;
 	a.points = (float4 *) points;
 	a.normals = (float4 *) normals;
 	const dim3 blocks((tiles + LAYERS_WAVES - 1u) / LAYERS_WAVES), lanes(64 * LAYERS_WAVES);
@@ -456,6 +467,58 @@ void launch_layers_combine(const void *points, const void *normals, const float 
 		return;
 	hipLaunchKernelGGL(layers_combine_kernel, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t) stream, (const float4 *) points,
 	                   (const float4 *) normals, factor, ao, value, n);
+}
+
+// Multi-view rendering (kernels/views.hip.h).  `out`: the blocks of the chunk's first view; `poses`: the chunk's `views`
+// poses on the device; `value`: where the head-light term goes once more (no ambient-occlusion step) or null.  With that
+// step: `list` gets the hit sub-pixels -- flags, entries, order and, in *list->listed, their number -- and
+// `ao`, `product` the missed sub-pixels' 1 and 0.
+void launch_views(const SceneBuffers &scene, const KernelParams &P, const void *poses, uint32_t views, const LayerOutputs &out,
+                  float *value, float *ao, float *product, const ViewList *list, void *stream) {
+	ViewsArgs v{};
+	v.layers = layers_args(scene, P, out, value);
+	const uint64_t waves = (uint64_t) views * v.layers.tiles;
+	if (waves == 0)
+		return;
+	hipStream_t s = (hipStream_t) stream;
+	v.poses = (const CameraPose *) poses;
+	v.views = views;
+	v.n = P.width * P.height;
+	if (list) {
+		v.ao = ao;
+		v.product = product;
+		v.flags = list->flags;
+		v.points = (float4 *) list->points;
+		v.normals = (float4 *) list->normals;
+		v.seeds = list->seeds;
+	}
+	hipLaunchKernelGGL(views_kernel, dim3((uint32_t) ((waves + LAYERS_WAVES - 1u) / LAYERS_WAVES)), dim3(64 * LAYERS_WAVES), 0, s, v);
+	if (!list)
+		return;
+	const uint32_t m = views * v.n, blocks = (m + VIEWS_SCAN - 1u) / VIEWS_SCAN;  // (m <= RT_QUERY_MAX_RAYS: RayQueries::viewsPerChunk)
+	hipLaunchKernelGGL(views_count_kernel, dim3(blocks), dim3(VIEWS_SCAN), 0, s, (const uint8_t *) list->flags, list->sums, m);
+	hipLaunchKernelGGL(views_scan_sums_kernel, dim3(1), dim3(VIEWS_SUMS), 0, s, list->sums, blocks, list->listed);
+	hipLaunchKernelGGL(views_order_kernel, dim3(blocks), dim3(VIEWS_SCAN), 0, s, (const uint8_t *) list->flags, (const uint32_t *) list->sums,
+	                   list->order, m);
+}
+
+// ... the factors of the `listed` hit sub-pixels, from the ambient-occlusion step's counts, to where they belong
+// (`ao`, `product`: either may be null) ...
+void launch_views_scatter(const ViewList &list, const uint32_t *count, uint32_t divisor, float *ao, float *product, uint32_t listed,
+                          void *stream) {
+	if (listed == 0 || (!ao && !product))
+		return;
+	hipLaunchKernelGGL(views_scatter_kernel, dim3((listed + 255u) / 256u), dim3(256), 0, (hipStream_t) stream, (const float4 *) list.normals,
+	                   count, (const uint32_t *) list.order, ao, product, listed, divisor ? divisor : 1u);
+}
+
+// ... and the 8-bit images of `views` float images that lie back to back at `value`, n x n sub-pixels per pixel.
+void launch_views_resize(const float *value, unsigned char *image, const KernelParams &P, uint32_t out_width, uint32_t out_height,
+                         uint32_t n, uint32_t views, void *stream) {
+	if (views == 0 || out_width == 0 || out_height == 0 || n == 0)
+		return;
+	hipLaunchKernelGGL(views_resize_kernel, dim3((out_width + 255u) / 256u, out_height, views), dim3(256), 0, (hipStream_t) stream, value,
+	                   image, out_width, out_height, P.width, n, P.width * P.height);
 }
 
 }  // namespace ocrt

@@ -1,8 +1,10 @@
-// ray_query.cc -- ray queries, multi-hit queries, ambient-occlusion queries and frame layers on a render host's uploaded scene
-// (ray_query.h).
+// ray_query.cc -- ray queries, multi-hit queries, ambient-occlusion queries, frame layers and multi-view rendering on a render
+// host's uploaded scene (ray_query.h).
 #include "ray_query.h"
 
+#include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 
@@ -21,7 +23,11 @@ enum { RAY_ORIGINS, RAY_DIRECTIONS, RAY_FIRST, RAY_RECORDS, RAY_PIECES = RAY_REC
 enum { AO_POINTS, AO_NORMALS, AO_COUNTS, AO_SEEDS, AO_VALUES, AO_PIECES };
 // Frame layers: the hit flags, the five record arrays, then the four layers of their own.
 enum { LAYER_HIT, LAYER_RECORDS, LAYER_DIRECTION = LAYER_RECORDS + 5, LAYER_SHADE, LAYER_AO, LAYER_VALUE, LAYER_PIECES };
+// Multi-view rendering: the layers' pieces, then the 8-bit images.
+enum { VIEW_IMAGE = LAYER_PIECES, VIEW_PIECES };
 constexpr uint32_t QUERY_MAX_RAYS = 1u << 27;  // include/rt_hip_query.h
+constexpr uint32_t VIEWS_MAX_CHUNK = 65535u;   // views_resize_kernel: a grid's third dimension
+constexpr size_t PINNED_HEAD = 16u;            // viewsDevice: the read-back word in front of the poses
 }  // namespace
 
 RayQueries::RayQueries(DeviceRenderer &renderer) : dev(renderer) {
@@ -35,8 +41,10 @@ RayQueries::~RayQueries() {
 		return;
 	if (timed)
 		(void) hipEventSynchronize((hipEvent_t) ev_stop);
-	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &list, &layers })
+	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &list, &layers, &views })
 		device_free(scratch->ptr);
+	if (pinned)
+		(void) hipHostFree(pinned);
 	(void) hipEventDestroy((hipEvent_t) ev_start);
 	(void) hipEventDestroy((hipEvent_t) ev_stop);
 }
@@ -277,15 +285,18 @@ void RayQueries::aoHost(const float *points4, const float *normals4, const uint3
 
 // What a layers call may ask of this host; returns whether it needs the ambient-occlusion step (`ao`, or `value` on a host
 // whose options have ambient occlusion on).
-bool RayQueries::requireLayers(const LayerOutputs &out) const {
+bool RayQueries::requireLayers(const LayerOutputs &out) const { return requireFrameRays(out.ao != nullptr, out.ao || out.value); }
+
+// ... `ao`: that layer is asked for; `product`: something made of it -- or, without it, of the head-light term alone -- is.
+bool RayQueries::requireFrameRays(bool ao, bool product) const {
 	requireScene("frame layers");
 	const KernelParams &kp = dev.params();
 	if (kp.part.nranks > 1)
 		throw std::logic_error("frame layers on a band-partitioned host: it renders a part of the image only");
 	const uint32_t per_point = aoRaysPerPoint(dev);
-	if (out.ao && per_point == 0)
+	if (ao && per_point == 0)
 		throw std::logic_error("the ao layer on a host whose options have ambient occlusion off");
-	const bool with_ao = per_point != 0 && (out.ao || out.value);
+	const bool with_ao = per_point != 0 && product;
 	const uint64_t n = (uint64_t) kp.width * kp.height;
 	if (n > QUERY_MAX_RAYS || (with_ao && n > QUERY_MAX_RAYS / per_point))
 		throw std::invalid_argument(with_ao ? "more sub-pixels than RT_QUERY_MAX_RAYS / rays per point: ask for neither ao nor value"
@@ -340,6 +351,171 @@ void RayQueries::layersHost(const LayerOutputs &host) {
 	out.value = (float *) p[LAYER_VALUE].device;
 	layersDevice(out, s);
 	stageOut(p, LAYER_PIECES, s);
+}
+
+// What a views call may ask of this host: what a layers call may, with the image counted among the layers made of `value`.
+bool RayQueries::requireViews(const ViewOutputs &out) const { return requireFrameRays(out.ao != nullptr, out.ao || out.value || out.image); }
+
+// Views per chunk: as many as keep a chunk's sub-pixels -- with the ambient-occlusion step: their rays, were all of them
+// hit -- within what one query takes (requireViews: one view does), or the debug limit.
+uint32_t RayQueries::viewsPerChunk(bool with_ao) const {
+	const KernelParams &kp = dev.params();
+	const uint64_t n = (uint64_t) kp.width * kp.height, most = with_ao ? QUERY_MAX_RAYS / aoRaysPerPoint(dev) : QUERY_MAX_RAYS;
+	const uint32_t fit = (uint32_t) std::min<uint64_t>(std::max<uint64_t>(most / (n ? n : 1u), 1u), VIEWS_MAX_CHUNK);
+	return views_chunk ? std::min(views_chunk, fit) : fit;
+}
+
+// `out` from view `view` on.
+ViewOutputs RayQueries::viewsFrom(const ViewOutputs &out, size_t view, const KernelParams &kp, size_t image_bytes) {
+	const size_t first = view * (size_t) kp.width * kp.height;
+	ViewOutputs at = out;
+	auto advance = [](auto *&p, size_t by) {
+		if (p)
+			p += by;
+	};
+	advance(at.hit, first);
+	advance(at.distance, first);
+	advance(at.leaf, first);
+	advance(at.barycentric, 3u * first);
+	advance(at.position, 3u * first);
+	advance(at.normal, 3u * first);
+	advance(at.direction, 3u * first);
+	advance(at.shade, first);
+	advance(at.ao, first);
+	advance(at.value, first);
+	advance(at.image, view * image_bytes);
+	return at;
+}
+
+void RayQueries::viewsDevice(const CameraPose *cameras, uint32_t views, const ViewOutputs &out, void *stream) {
+	const bool with_ao = requireViews(out);
+	const KernelParams &kp = dev.params();
+	const RayTracer &rt = dev.rayTracer();
+	const uint32_t n = kp.width * kp.height, grid = RayTracer::gridSize(rt.options.nSuperSamples);
+	if (views == 0 || n == 0 || !out.any())
+		return;
+	const uint32_t per_chunk = std::min(viewsPerChunk(with_ao), views);
+	const size_t most = (size_t) per_chunk * n, image_bytes = (size_t) rt.options.width * rt.options.height;
+	// the poses: into host memory of this host's own that the copies may read after the call has returned -- once the
+	// call before, which may still be reading it, is over
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	if (timed)
+		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
+	const size_t pose_bytes = (size_t) views * sizeof(CameraPose);
+	if (PINNED_HEAD + pose_bytes > pinned_bytes) {
+		if (pinned)
+			(void) hipHostFree(pinned);
+		pinned = nullptr;
+		pinned_bytes = 0;
+		OCRT_HIP(hipHostMalloc(&pinned, PINNED_HEAD + pose_bytes, hipHostMallocDefault));
+		pinned_bytes = PINNED_HEAD + pose_bytes;
+	}
+	uint32_t *const listed_host = (uint32_t *) pinned;
+	const CameraPose *const poses_host = (const CameraPose *) ((char *) pinned + PINNED_HEAD);
+	std::memcpy((char *) pinned + PINNED_HEAD, cameras, pose_bytes);
+	// a chunk's scratch: its poses, the number of hit sub-pixels, then -- as far as the call needs them -- their list (by
+	// sub-pixel: flags, points, normals, seeds, order; by block of 1024: the sums) and the chunk's float images where the
+	// caller has no `value` array for them
+	const bool own_product = out.image && !out.value;
+	const size_t listable = with_ao ? most : 0u;
+	size_t at = 0;
+	auto piece = [&](size_t bytes) {
+		const size_t here = at;
+		at += round16(bytes);
+		return here;
+	};
+	const size_t poses_at = piece(per_chunk * sizeof(CameraPose)), listed_at = piece(sizeof(uint32_t));
+	const size_t points_at = piece(listable * 16u), normals_at = piece(listable * 16u), seeds_at = piece(listable * 4u);
+	const size_t order_at = piece(listable * 4u), flags_at = piece(listable), sums_at = piece((listable + 1023u) / 1024u * 4u);
+	const size_t product_at = piece(own_product ? most * 4u : 0u);
+	const Enqueue q = begin(stream, nullptr, nullptr, n, n, QUERY_NO_SORT,
+	                        { Need{ &this->views, at }, Need{ with_ao ? &ao_hits : nullptr, listable * sizeof(uint32_t) } });
+	char *const base = (char *) this->views.ptr;
+	ViewList list{};
+	list.flags = (unsigned char *) (base + flags_at);
+	list.points = base + points_at;
+	list.normals = base + normals_at;
+	list.seeds = (uint32_t *) (base + seeds_at);
+	list.sums = (uint32_t *) (base + sums_at);
+	list.order = (uint32_t *) (base + order_at);
+	list.listed = (uint32_t *) (base + listed_at);
+	hipStream_t s = (hipStream_t) q.stream;
+	ViewsDone done;
+	done.views = views;
+	for (uint32_t first = 0; first < views; first += per_chunk, ++done.chunks) {
+		const uint32_t chunk = std::min(per_chunk, views - first);
+		const ViewOutputs to = viewsFrom(out, first, kp, image_bytes);
+		// (`product`: the chunk's float images -- the caller's `value`, or scratch for the 8-bit images alone)
+		float *const product = own_product ? (float *) (base + product_at) : to.value;
+		OCRT_HIP(hipMemcpyAsync(base + poses_at, poses_host + first, (size_t) chunk * sizeof(CameraPose), hipMemcpyHostToDevice, s));
+		// (without the ambient-occlusion step `value` is the head-light term itself)
+		launch_views(dev.deviceScene()->buffers(), kp, base + poses_at, chunk, to, with_ao ? nullptr : product, to.ao, product,
+		             with_ao ? &list : nullptr, s);
+		if (with_ao) {
+			// (the step's counts go by sub-pixel: all the chunk's are cleared -- while the host waits --, the hit ones are
+			// counted into)
+			uint32_t *const count = (uint32_t *) ao_hits.ptr;
+			OCRT_HIP(hipMemsetAsync(count, 0, (size_t) chunk * n * sizeof(uint32_t), s));
+			// the reference's ambient_occlusion(position, normal, index) of the hit sub-pixels alone, in index order:
+			// how many there are sizes the launch
+			OCRT_HIP(hipMemcpyAsync(listed_host, list.listed, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+			OCRT_HIP(hipStreamSynchronize(s));
+			const uint32_t listed = *listed_host;
+			if (listed > (size_t) chunk * n)
+				throw DeviceError("multi-view rendering: more sub-pixels listed than the chunk holds");
+			launch_ao_query(dev.deviceScene()->buffers(), kp.node_count, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, list.points,
+			                list.normals, list.seeds, list.order, listed, count, nullptr, s);
+			launch_views_scatter(list, count, kp.ao_divisor, to.ao, product, listed, s);
+			done.ao_points += listed;
+		}
+		if (to.image)
+			launch_views_resize(product, to.image, kp, rt.options.width, rt.options.height, grid, chunk, s);
+	}
+	end(q);
+	last_views = done;
+}
+
+void RayQueries::viewsHost(const CameraPose *cameras, uint32_t views, const ViewOutputs &host) {
+	const bool with_ao = requireViews(host);
+	const KernelParams &kp = dev.params();
+	const RayTracer &rt = dev.rayTracer();
+	const size_t n = (size_t) kp.width * kp.height, image_bytes = (size_t) rt.options.width * rt.options.height;
+	if (views == 0 || n == 0 || !host.any())
+		return;
+	// chunk by chunk through the staging buffer, so that it holds one chunk's outputs, not the call's
+	const uint32_t per_chunk = std::min(viewsPerChunk(with_ao), views);
+	ViewsDone done;
+	float ms = 0.0f;
+	for (uint32_t first = 0; first < views; first += per_chunk) {
+		const size_t chunk = std::min(per_chunk, views - first), m = chunk * n;
+		const ViewOutputs to = viewsFrom(host, first, kp, image_bytes);
+		Staged p[VIEW_PIECES];
+		p[LAYER_HIT] = output(to.hit, m);
+		recordPieces(p + LAYER_RECORDS, to, m);
+		p[LAYER_DIRECTION] = output(to.direction, m * 12u);
+		p[LAYER_SHADE] = output(to.shade, m * 4u);
+		p[LAYER_AO] = output(to.ao, m * 4u);
+		p[LAYER_VALUE] = output(to.value, m * 4u);
+		p[VIEW_IMAGE] = output(to.image, chunk * image_bytes);
+		void *s = stageIn(p, VIEW_PIECES);
+		ViewOutputs out;
+		out.hit = (unsigned char *) p[LAYER_HIT].device;
+		recordDevice(p + LAYER_RECORDS, out);
+		out.direction = (float *) p[LAYER_DIRECTION].device;
+		out.shade = (float *) p[LAYER_SHADE].device;
+		out.ao = (float *) p[LAYER_AO].device;
+		out.value = (float *) p[LAYER_VALUE].device;
+		out.image = (unsigned char *) p[VIEW_IMAGE].device;
+		viewsDevice(cameras + first, (uint32_t) chunk, out, s);
+		stageOut(p, VIEW_PIECES, s);
+		ms += lastMs();
+		done.views += last_views.views;
+		done.chunks += last_views.chunks;
+		done.ao_points += last_views.ao_points;
+	}
+	last_views = done;
+	last_ms = ms;  // (every chunk's events have been read: the call's time is their sum)
+	have_ms = true;
 }
 
 float RayQueries::lastMs() {

@@ -1,6 +1,7 @@
-// ray_query.h -- ray queries, multi-hit queries, ambient-occlusion queries and frame layers on a render host's uploaded scene
-// (include/rt_hip_query.h, include/rt_hip_multihit.h, include/rt_hip_ao.h, include/rt_hip_layers.h; kernels/query.hip.h,
-// kernels/multihit.hip.h, kernels/ao_query.hip.h, kernels/layers.hip.h).
+// ray_query.h -- ray queries, multi-hit queries, ambient-occlusion queries, frame layers and multi-view rendering on a render
+// host's uploaded scene (include/rt_hip_query.h, include/rt_hip_multihit.h, include/rt_hip_ao.h, include/rt_hip_layers.h,
+// include/rt_hip_views.h; kernels/query.hip.h, kernels/multihit.hip.h, kernels/ao_query.hip.h, kernels/layers.hip.h,
+// kernels/views.hip.h).
 #pragma once
 #include <cstdint>
 #include <initializer_list>
@@ -55,6 +56,22 @@ class RayQueries {
 		void layersDevice(const LayerOutputs &out, void *stream);
 		// Host memory, blocking.
 		void layersHost(const LayerOutputs &out);
+		// Multi-view rendering (include/rt_hip_views.h): the layers and the 8-bit image of `views` poses -- `cameras`, host
+		// memory, copied before the call returns -- against the uploaded scene, whatever pose the host itself has; view v's
+		// block of every array lies behind view v - 1's.  Worked through in chunks of viewsPerChunk() views, scratch for one
+		// chunk.  Errors as for the layers; std::invalid_argument where ONE view exceeds what a layers call takes.
+		// Device memory, enqueued on `stream` (null: the renderer's).  With the ambient-occlusion step the call waits, per
+		// chunk, for the chunk's own rays: how many sub-pixels they hit sizes that step.
+		void viewsDevice(const CameraPose *cameras, uint32_t views, const ViewOutputs &out, void *stream);
+		// Host memory, blocking: staged chunk by chunk.
+		void viewsHost(const CameraPose *cameras, uint32_t views, const ViewOutputs &out);
+		// (include/rt_hip_debug.h) at most `max_views` views per chunk, 0: as many as fit; and what the last views call did
+		void setViewsChunk(uint32_t max_views) { views_chunk = max_views; }
+		struct ViewsDone {
+			uint32_t views = 0, chunks = 0;
+			uint64_t ao_points = 0;  // sub-pixels the ambient-occlusion step ran over: the hit ones
+		};
+		ViewsDone lastViews() const { return last_views; }
 		float lastMs();  // the last query of any kind
 
 	private:
@@ -90,6 +107,10 @@ class RayQueries {
 		void requireSlots(uint32_t k) const;
 		void requireAo() const;
 		bool requireLayers(const LayerOutputs &out) const;  // true: the call needs the ambient-occlusion step
+		bool requireViews(const ViewOutputs &out) const;    // the same for a views call
+		bool requireFrameRays(bool ao, bool product) const;
+		uint32_t viewsPerChunk(bool with_ao) const;
+		static ViewOutputs viewsFrom(const ViewOutputs &out, size_t view, const KernelParams &kp, size_t image_bytes);
 		void grow(Scratch &scratch, size_t bytes);
 		void sceneBox(const DeviceScene &scene, float lo[3], float scale[3]);
 		Enqueue begin(void *stream, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags,
@@ -108,6 +129,12 @@ class RayQueries {
 		Scratch list;          // multihitDevice: the rays' key lists, n * k * 8 bytes
 		Scratch layers;        // layersDevice with ambient occlusion: the sub-pixels' points and normals (float4 each), and
 		                       // their factors where the caller gave no `ao` array
+		Scratch views;         // viewsDevice: a chunk's poses, its list of hit sub-pixels (ViewList), its float images where the
+		                       // caller gave no `value` array
+		void *pinned = nullptr;  // viewsDevice, host memory: the list's size as read back, then the call's poses
+		size_t pinned_bytes = 0;
+		uint32_t views_chunk = 0;
+		ViewsDone last_views;
 		void *ev_start = nullptr, *ev_stop = nullptr;
 		bool timed = false, have_ms = false;
 		float last_ms = 0.0f;
@@ -127,6 +154,12 @@ void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode
                      uint32_t *count, float *ao, void *stream);
 void launch_layers(const SceneBuffers &scene, const KernelParams &P, const CameraPose &pose, bool posed, const LayerOutputs &out,
                    float *value, void *points, void *normals, void *stream);
+void launch_views(const SceneBuffers &scene, const KernelParams &P, const void *poses, uint32_t views, const LayerOutputs &out,
+                  float *value, float *ao, float *product, const ViewList *list, void *stream);
+void launch_views_scatter(const ViewList &list, const uint32_t *count, uint32_t divisor, float *ao, float *product, uint32_t listed,
+                          void *stream);
+void launch_views_resize(const float *value, unsigned char *image, const KernelParams &P, uint32_t out_width, uint32_t out_height,
+                         uint32_t n, uint32_t views, void *stream);
 void launch_layers_combine(const void *points, const void *normals, const float *factor, float *ao, float *value, uint32_t n, void *stream);
 
 }  // namespace ocrt
