@@ -34,13 +34,12 @@
 //                   ao_query_finish_kernel writes their 1 - hits / n (kernels/ao_query.hip.h, include/rt_hip_ao.h).
 //                   multihit_walk_kernel<K> counts every triangle a caller-supplied ray's walk accepts and keeps the first K,
 //                   multihit_resolve_kernel writes their records (kernels/multihit.hip.h, include/rt_hip_multihit.h).
-//                   layers_kernel<POSED> casts the frame's own rays, a wave per tile, and writes every sub-pixel's record, direction
-//                   and head-light term, layers_combine_kernel their product with the ambient-occlusion factors
-//                   (kernels/layers.hip.h, include/rt_hip_layers.h).
-//                   views_kernel does the same for every pose of a chunk of views, a wave per (view, tile), and lists the hit
-//                   sub-pixels for ao_query_kernel (views_count_kernel, views_scan_sums_kernel, views_order_kernel: their number
-//                   and order); views_scatter_kernel writes their factors and products, views_resize_kernel every view's
-//                   8-bit image (kernels/views.hip.h, include/rt_hip_views.h).
+//                   layers_kernel<POSED, ARRAY> casts the frame's own rays for one pose or for every pose of a chunk of views, a wave
+//                   per (view, tile), and writes every sub-pixel's record, direction and head-light term (kernels/layers.hip.h,
+//                   include/rt_hip_layers.h, include/rt_hip_views.h).  ao_query_kernel runs over its points -- all of them
+//                   (a layers call) or the hit ones, listed (a views call: views_count_kernel, views_scan_sums_kernel,
+//                   views_order_kernel make their number and order) --, views_scatter_kernel writes their factors and
+//                   products, views_resize_kernel every view's 8-bit image (kernels/views.hip.h).
 //   (on demand)     entry_kernel: the walk intervals, once per upload; occluded_sum_kernel: the frame's occlusion
 //                   total when the statistics are asked for; resize_kernel: a box filter on its own.
 // Why not one fused launch (it was, see profiles/r01_notes.md): cost per tile
@@ -420,10 +419,14 @@ void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void 
 		hipLaunchKernelGGL(multihit_resolve_kernel, dim3((n * k + 255u) / 256u), dim3(256), 0, s, a);
 }
 
-// Frame layers (kernels/layers.hip.h).  `points`, `normals`: n = width * height float4 of scratch each, or null -- no
-// ambient-occlusion step follows; `value`: where the head-light term goes once more (a host without ambient occlusion).
-// (what layers_kernel and views_kernel are launched with alike)
-static LayersArgs layers_args(const SceneBuffers &scene, const KernelParams &P, const LayerOutputs &out, float *value) {
+// Frame layers and multi-view rendering (kernels/layers.hip.h, kernels/views.hip.h): the frame's own rays of `views`
+// views.  `out`: the blocks of the first view.  The poses: `poses`, on the device, or -- null -- `pose` for every view (a
+// layers call: one view), which only a `posed` host reads: without a pose the kernel holds the reference's camera as
+// constants.  `value`: where the head-light term goes once more (no ambient-occlusion step) or null.  `list`: null = no
+// such step follows; else its points and normals get the step's entries, and with list->flags -- listing -- only the hit
+// sub-pixels do: their flags, seeds, order and, in *list->listed, their number, and `ao`, `product` the missed ones' 1 and 0.
+void launch_layers(const SceneBuffers &scene, const KernelParams &P, const void *poses, const CameraPose &pose, bool posed, uint32_t views,
+                   const LayerOutputs &out, float *value, float *ao, float *product, const ViewList *list, void *stream) {
 	LayersArgs a{};
 	a.nodes_ptr = (const float4 *) scene.nodes;
 	a.tris_ptr = (const float4 *) scene.tris;
@@ -437,73 +440,43 @@ static LayersArgs layers_args(const SceneBuffers &scene, const KernelParams &P, 
 	a.a = P.a;
 	a.half_w = P.half_w;
 	a.half_h = P.half_h;
+	a.pose = pose;
+	a.poses = (const CameraPose *) poses;
+	a.n = P.width * P.height;
 	a.hit = out.hit;
 	a.out = out;
 	a.direction = out.direction;
 	a.shade = out.shade;
 	a.value = value;
-	return a;
-}
-
-void launch_layers(const SceneBuffers &scene, const KernelParams &P, const CameraPose &pose, bool posed, const LayerOutputs &out,
-                   float *value, void *points, void *normals, void *stream) {
-	LayersArgs a = layers_args(scene, P, out, value);
-	const uint32_t tiles = a.tiles;
-	if (tiles == 0)
-		return;
-	a.pose = pose;
-	a.points = (float4 *) points;
-	a.normals = (float4 *) normals;
-	const dim3 blocks((tiles + LAYERS_WAVES - 1u) / LAYERS_WAVES), lanes(64 * LAYERS_WAVES);
-	if (posed)
-		hipLaunchKernelGGL(layers_kernel<true>, blocks, lanes, 0, (hipStream_t) stream, a);
-	else
-		hipLaunchKernelGGL(layers_kernel<false>, blocks, lanes, 0, (hipStream_t) stream, a);
-}
-
-// ... and their last step: `ao` and `value` (either may be null) from the n factors at `factor`.
-void launch_layers_combine(const void *points, const void *normals, const float *factor, float *ao, float *value, uint32_t n, void *stream) {
-	if (n == 0 || (!ao && !value))
-		return;
-	hipLaunchKernelGGL(layers_combine_kernel, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t) stream, (const float4 *) points,
-	                   (const float4 *) normals, factor, ao, value, n);
-}
-
-// Multi-view rendering (kernels/views.hip.h).  `out`: the blocks of the chunk's first view; `poses`: the chunk's `views`
-// poses on the device; `value`: where the head-light term goes once more (no ambient-occlusion step) or null.  With that
-// step: `list` gets the hit sub-pixels -- flags, entries, order and, in *list->listed, their number -- and
-// `ao`, `product` the missed sub-pixels' 1 and 0.
-void launch_views(const SceneBuffers &scene, const KernelParams &P, const void *poses, uint32_t views, const LayerOutputs &out,
-                  float *value, float *ao, float *product, const ViewList *list, void *stream) {
-	ViewsArgs v{};
-	v.layers = layers_args(scene, P, out, value);
-	const uint64_t waves = (uint64_t) views * v.layers.tiles;
-	if (waves == 0)
+	if (views == 0 || a.tiles == 0)
 		return;
 	hipStream_t s = (hipStream_t) stream;
-	v.poses = (const CameraPose *) poses;
-	v.views = views;
-	v.n = P.width * P.height;
 	if (list) {
-		v.ao = ao;
-		v.product = product;
-		v.flags = list->flags;
-		v.points = (float4 *) list->points;
-		v.normals = (float4 *) list->normals;
-		v.seeds = list->seeds;
+		a.points = (float4 *) list->points;
+		a.normals = (float4 *) list->normals;
+		a.flags = list->flags;
+		a.seeds = list->seeds;
+		a.ao = ao;
+		a.product = product;
 	}
-	hipLaunchKernelGGL(views_kernel, dim3((uint32_t) ((waves + LAYERS_WAVES - 1u) / LAYERS_WAVES)), dim3(64 * LAYERS_WAVES), 0, s, v);
-	if (!list)
+	const dim3 blocks((a.tiles + LAYERS_WAVES - 1u) / LAYERS_WAVES, views), lanes(64 * LAYERS_WAVES);  // (views <= 65535: RayQueries::viewsPerChunk)
+	if (poses)
+		hipLaunchKernelGGL((layers_kernel<true, true>), blocks, lanes, 0, s, a);
+	else if (posed)
+		hipLaunchKernelGGL((layers_kernel<true, false>), blocks, lanes, 0, s, a);
+	else
+		hipLaunchKernelGGL((layers_kernel<false, false>), blocks, lanes, 0, s, a);
+	if (!list || !list->flags)
 		return;
-	const uint32_t m = views * v.n, blocks = (m + VIEWS_SCAN - 1u) / VIEWS_SCAN;  // (m <= RT_QUERY_MAX_RAYS: RayQueries::viewsPerChunk)
-	hipLaunchKernelGGL(views_count_kernel, dim3(blocks), dim3(VIEWS_SCAN), 0, s, (const uint8_t *) list->flags, list->sums, m);
-	hipLaunchKernelGGL(views_scan_sums_kernel, dim3(1), dim3(VIEWS_SUMS), 0, s, list->sums, blocks, list->listed);
-	hipLaunchKernelGGL(views_order_kernel, dim3(blocks), dim3(VIEWS_SCAN), 0, s, (const uint8_t *) list->flags, (const uint32_t *) list->sums,
+	const uint32_t m = views * a.n, scans = (m + VIEWS_SCAN - 1u) / VIEWS_SCAN;  // (m <= RT_QUERY_MAX_RAYS: RayQueries::viewsPerChunk)
+	hipLaunchKernelGGL(views_count_kernel, dim3(scans), dim3(VIEWS_SCAN), 0, s, (const uint8_t *) list->flags, list->sums, m);
+	hipLaunchKernelGGL(views_scan_sums_kernel, dim3(1), dim3(VIEWS_SUMS), 0, s, list->sums, scans, list->listed);
+	hipLaunchKernelGGL(views_order_kernel, dim3(scans), dim3(VIEWS_SCAN), 0, s, (const uint8_t *) list->flags, (const uint32_t *) list->sums,
 	                   list->order, m);
 }
 
-// ... the factors of the `listed` hit sub-pixels, from the ambient-occlusion step's counts, to where they belong
-// (`ao`, `product`: either may be null) ...
+// ... the factors of the step's `listed` entries, from its counts, to where they belong: list.order[j], or sub-pixel j
+// itself where there is no order (`ao`, `product`: either may be null) ...
 void launch_views_scatter(const ViewList &list, const uint32_t *count, uint32_t divisor, float *ao, float *product, uint32_t listed,
                           void *stream) {
 	if (listed == 0 || (!ao && !product))

@@ -1,21 +1,29 @@
-// kernels/layers.hip.h -- frame layers: the closest-hit record of every sub-pixel's own ray and what the frame makes of
-// it (include/rt_hip_layers.h)
+// kernels/layers.hip.h -- the frame's own rays: the closest-hit record of every sub-pixel of one pose or of many, and what
+// the frame makes of it (include/rt_hip_layers.h, include/rt_hip_views.h)
 // (part of the one translation unit kernels.hip; see its head for the passes and the arithmetic contract)
 //
-// layers_kernel<POSED> packs its rays as the primary pass does -- one wave per 8 x 8 tile of sub-pixels, lane & 7 across,
+// layers_kernel<POSED, ARRAY> packs its rays as the primary pass does -- one wave per 8 x 8 tile of sub-pixels, lane & 7 across,
 // lane >> 3 down, four waves per workgroup -- and makes each ray in registers with the primary pass's arithmetic
 // (camera_ray below restates primary_tile's lines: a helper of its own, so that the frame kernels' code, registers and
-// hand-scheduled loop stay exactly as they are); no ray array exists.  From there on it is query_kernel<true>: the
-// EXACT form of the shared walk (walk.hip.h, exact_walk) over the uploaded scene's exact node records with the frame's
-// max_distance, tri_eval<true>, nearer, take, and store_record for the record -- so the answer is the query contract's
-// for any pose, non-finite eyes and eyes the fast walk's margins do not cover included.  The epilogue adds the ray's
-// direction and the head-light term (the primary epilogue's dot3, max and min).
+// hand-scheduled loop stay exactly as they are); no ray array exists.  The grid is tiles by views -- blockIdx.y is the
+// view, so no wave divides to find it --: a wave's view is a scalar, and its pose comes by scalar loads from the call's array of poses on the device or, where there is none (a
+// layers call: one view), from the kernel arguments.  From there on it is query_kernel<true>: the EXACT form of the
+// shared walk (walk.hip.h, exact_walk) over the uploaded scene's exact node records with the frame's max_distance,
+// tri_eval<true>, nearer and take at a leaf, and closest_entry and closest_store (kernels/query.hip.h) for the record --
+// so the answer is the query contract's for any pose, non-finite eyes and eyes the fast walk's margins do not cover included.  The epilogue adds the
+// ray's direction and the head-light term (the primary epilogue's dot3, max and min).  Everything is written into view
+// v's block of every layer, at view * N + index.
 //
-// With ambient occlusion asked for, the kernel also leaves every sub-pixel's point and normal as float4 in scratch
-// (point.w: the hit flag, normal.w: the head-light term) for ao_query_kernel to run over in index order -- point i gets
-// seed i = y * W + x, the reference's `index` --, and layers_combine_kernel writes `ao` and `value` from its factors.  A
-// sub-pixel without a hit leaves a NaN point: its ambient-occlusion rays fail the slab test at the root and walk
-// nothing, and the combine step writes ao = 1, value = 0 for it whatever the factor says.
+// With the ambient-occlusion step to follow, the kernel leaves a sub-pixel's point and normal as float4 (normal.w: the
+// head-light term) at the sub-pixel's index, for ao_query_kernel to run over and views_scatter_kernel (kernels/views.hip.h)
+// to write `ao` and `value` from.  Two modes, a uniform branch on `flags`:
+//   not listing (a layers call)  every live lane writes its entry, and the step runs over all N sub-pixels in index order
+//       -- point i gets seed i = y * W + x, the reference's `index`.  A sub-pixel without a hit leaves a NaN point and a
+//       zero normal: its ambient-occlusion rays fail the slab test at the root and walk nothing, so its count stays 0 and
+//       the tail's own arithmetic gives ao = 1 - 0 / n = 1 and value = 0 * 1 = +0.  Nothing is read back: the call only enqueues.
+//   listing (a views call)  the sub-pixels that were HIT -- and only they -- are listed for the step.  Every live lane leaves
+//       its hit flag, a hit one also its entry and the reference's `index` of the sub-pixel WITHIN ITS VIEW (the RANDOM
+//       sampler's seed); a missed one gets its ao = 1, value = 0 here.  kernels/views.hip.h makes the list's order.
 #pragma once
 #include "query.hip.h"
 
@@ -26,17 +34,22 @@ struct LayersArgs {
 	const float4 *tris_ptr;   // TriRec by leaf
 	const float4 *shade_recs; // ShadeRec by leaf
 	uint32_t width, height;   // sub-pixels
-	uint32_t tiles_x, tiles;  // tiles per row, tiles in all
+	uint32_t tiles_x, tiles;  // tiles per row, tiles per view
 	uint32_t node_count;
 	int32_t shading;
 	float a, half_w, half_h;  // KernelParams: the camera-space terms of a sub-pixel
-	CameraPose pose;          // (POSED only)
-	uint8_t *hit;             // by sub-pixel index; every output: null = not written
+	CameraPose pose;          // (POSED, not ARRAY) the pose of the one view
+	const CameraPose *poses;  // (ARRAY) [views] on the device
+	uint32_t n;               // sub-pixels per view
+	uint8_t *hit;             // by sub-pixel index, the first view's block; every output: null = not written
 	RecordOutputs out;
-	float *direction;         // float[3 n]
+	float *direction;         // float[3 n] per view
 	float *shade;             // float[n]: the head-light term
 	float *value;             // float[n]: the same once more -- `value` of a host without ambient occlusion
-	float4 *points, *normals; // float4[n] scratch for the ambient-occlusion step, or null
+	float4 *points, *normals; // [views * n] the entries of the ambient-occlusion step; null: no such step follows
+	uint8_t *flags;           // [views * n] 1 = hit: listed; null: not listing
+	uint32_t *seeds;          // [views * n] (listing)
+	float *ao, *product;      // [views * n] or null (listing): the missed sub-pixels' 1.0f and 0.0f
 };
 
 constexpr uint32_t LAYERS_WAVES = 4u;
@@ -62,22 +75,24 @@ __device__ __forceinline__ Ray camera_ray(const LayersArgs &a, uint32_t x, uint3
 	return POSED ? make_ray(a.pose.eye[0], a.pose.eye[1], a.pose.eye[2], dx, dy, dz) : make_ray(0.0f, 0.0f, 2.0f, dx, dy, dz);
 }
 
-template <bool POSED>
+// POSED: a pose is read at all; ARRAY: from `poses` (then POSED), else from the arguments.  Where the pose comes from is a
+// template parameter because as a run-time branch it cost the posed layers call 1 to 1.5 %.
+template <bool POSED, bool ARRAY>
 __global__ __launch_bounds__(64 * LAYERS_WAVES) void layers_kernel(LayersArgs a) {
-	const uint32_t tile = blockIdx.x * LAYERS_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-	if (tile >= a.tiles)  // (the last workgroup's spare waves)
+	// (wave-uniform by construction; read through the first lane so that the compiler keeps the tile in SGPRs, as the view is)
+	const uint32_t tile = (uint32_t) __builtin_amdgcn_readfirstlane((int) (blockIdx.x * LAYERS_WAVES + (threadIdx.x >> 6)));
+	const uint32_t view = blockIdx.y, lane = threadIdx.x & 63u;
+	if (tile >= a.tiles)  // (the spare waves of a view's last workgroup)
 		return;
+	if (ARRAY)
+		a.pose = a.poses[view];
 	const uint32_t tile_y = tile / a.tiles_x, tile_x = tile - tile_y * a.tiles_x;
 	const uint32_t x = tile_x * TILE_W + (lane & 7u), y = tile_y * TILE_H + (lane >> 3);
 	// (a partial tile on the right or bottom edge: its lanes outside the image walk nothing and write nothing)
 	const bool live = x < a.width && y < a.height;
 	const Ray ray = camera_ray<POSED>(a, x, y);
 	bool hit = false;
-	Hit best;
-	best.distance = __builtin_inff();
-	best.leaf = 0u;
-	best.s = best.t = 0.0f;
-	best.px = best.py = best.pz = 0.0f;
+	Hit best = closest_entry();
 	exact_walk(a.nodes_ptr, a.node_count, ray, LAYERS_MAX_DISTANCE, live, [&](uint32_t leaf, bool box) {
 		const float4 *tri = a.tris_ptr + LEAF_F4 * leaf + LEAF_TRI_F4;
 		const float4 q0 = tri[0], q1 = tri[1], q2 = tri[2], q3 = tri[3];
@@ -93,18 +108,9 @@ __global__ __launch_bounds__(64 * LAYERS_WAVES) void layers_kernel(LayersArgs a)
 	});
 	if (!live)
 		return;
-	const size_t idx = (size_t) y * a.width + x;
-	// the record, as query_kernel<true> writes it
-	if (a.hit)
-		a.hit[idx] = hit ? 1u : 0u;
-	const bool kept = hit && best.distance < __builtin_inff();  // (the record was replaced at least once)
-	const float b0 = kept ? 1.0f - best.s - best.t : 0.0f, b1 = kept ? best.s : 0.0f, b2 = kept ? best.t : 0.0f;
-	const float px = kept ? best.px : 0.0f, py = kept ? best.py : 0.0f, pz = kept ? best.pz : 0.0f;
-	if (a.out.distance)
-		a.out.distance[idx] = best.distance;
-	if (a.out.leaf)
-		a.out.leaf[idx] = hit ? best.leaf : NONE;
-	store_record(a.out, idx, a.shade_recs, best.leaf, hit, b0, b1, b2, px, py, pz);
+	const uint32_t seed = y * a.width + x;          // the sub-pixel's index within its view
+	const size_t idx = (size_t) view * a.n + seed;  // ... and within the launch: view v's block of every layer
+	const ClosestRecord rec = closest_store(a.hit, a.out, idx, a.shade_recs, hit, best);
 	if (a.direction) {
 		a.direction[3u * idx + 0u] = ray.dx;
 		a.direction[3u * idx + 1u] = ray.dy;
@@ -116,7 +122,7 @@ __global__ __launch_bounds__(64 * LAYERS_WAVES) void layers_kernel(LayersArgs a)
 	float value = 0.0f;
 	float nx = 0.0f, ny = 0.0f, nz = 0.0f;
 	if (hit) {
-		smooth_normal(a.shade_recs, best.leaf, b0, b1, b2, nx, ny, nz);
+		smooth_normal(a.shade_recs, best.leaf, rec.b0, rec.b1, rec.b2, nx, ny, nz);
 		value = 1.0f;
 		if (a.shading)
 			value = fminf(fmaxf(-dot3(nx, ny, nz, ray.dx, ray.dy, ray.dz), 0.0f), 1.0f);
@@ -125,26 +131,26 @@ __global__ __launch_bounds__(64 * LAYERS_WAVES) void layers_kernel(LayersArgs a)
 		a.shade[idx] = value;
 	if (a.value)
 		a.value[idx] = value;
-	if (a.points) {
+	if (!a.points)
+		return;
+	// the ambient-occlusion step follows
+	if (a.flags) {
+		// listing: a missed sub-pixel is final, a hit one goes onto the list
+		if (!hit) {
+			if (a.ao)
+				a.ao[idx] = 1.0f;
+			if (a.product)
+				a.product[idx] = 0.0f;
+		}
+		a.flags[idx] = hit ? 1u : 0u;
+		if (hit)
+			a.seeds[idx] = seed;
+	}
+	if (hit || !a.flags) {
 		const float none = __builtin_nanf("");
-		a.points[idx] = hit ? make_float4(px, py, pz, 1.0f) : make_float4(none, none, none, 0.0f);
+		a.points[idx] = hit ? make_float4(rec.px, rec.py, rec.pz, 1.0f) : make_float4(none, none, none, 0.0f);
 		a.normals[idx] = make_float4(nx, ny, nz, value);
 	}
-}
-
-// ao[i] and value[i] = shade * ao of sub-pixel i from the factors of the ambient-occlusion step over layers_kernel's
-// points (`factor` may be `ao` itself); without a hit: ao = 1, value = 0.  The product is the frame's finishing sweep's.
-__global__ __launch_bounds__(256) void layers_combine_kernel(const float4 *__restrict__ points, const float4 *__restrict__ normals,
-                                                             const float *factor, float *ao, float *value, uint32_t n) {
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n)
-		return;
-	const bool hit = points[i].w != 0.0f;
-	const float f = hit ? factor[i] : 1.0f;
-	if (ao)
-		ao[i] = f;
-	if (value)
-		value[i] = hit ? normals[i].w * f : 0.0f;
 }
 
 }  // namespace ocrt

@@ -185,12 +185,55 @@ __device__ __forceinline__ void store_record(const RecordOutputs &out, size_t sl
 	}
 }
 
+// The closest-hit record of one ray, CLOSEST's contract below, for the kernels that make their own rays (layers_kernel).
+// closest_entry: its state on entry to the walk -- isect.distance = INFINITY, the other fields 0, as the CPU oracle starts them.
+__device__ __forceinline__ Hit closest_entry() {
+	Hit best;
+	best.distance = __builtin_inff();
+	best.leaf = 0u;
+	best.s = best.t = 0.0f;
+	best.px = best.py = best.pz = 0.0f;
+	return best;
+}
+
+// What closest_store wrote of the record where it was kept (zeros otherwise), for the epilogues that go on from it.
+struct ClosestRecord {
+	float b0, b1, b2, px, py, pz;
+};
+
+// closest_store: the boolean and the record into `slot` of the arrays that were asked for.  Where some triangle is accepted
+// but none replaces the record (a distance of +inf or NaN) the record keeps its entry values -- leaf 0, barycentrics and
+// point 0, distance +inf.  The smooth normal is the reference's get_smooth_normal for that record (smooth_normal, as the
+// primary pass computes it).
+__device__ __forceinline__ ClosestRecord closest_store(uint8_t *hit_flags, const RecordOutputs &out, size_t slot, const float4 *shade, bool hit,
+                                                       const Hit &best) {
+	if (hit_flags)
+		hit_flags[slot] = hit ? 1u : 0u;
+	const bool kept = hit && best.distance < __builtin_inff();  // (the record was replaced at least once)
+	ClosestRecord r;
+	r.b0 = kept ? 1.0f - best.s - best.t : 0.0f;
+	r.b1 = kept ? best.s : 0.0f;
+	r.b2 = kept ? best.t : 0.0f;
+	r.px = kept ? best.px : 0.0f;
+	r.py = kept ? best.py : 0.0f;
+	r.pz = kept ? best.pz : 0.0f;
+	if (out.distance)
+		out.distance[slot] = best.distance;
+	if (out.leaf)
+		out.leaf[slot] = hit ? best.leaf : NONE;
+	store_record(out, slot, shade, best.leaf, hit, r.b0, r.b1, r.b2, r.px, r.py, r.pz);
+	return r;
+}
+
 // CLOSEST: the reference's scene_intersect with isect.distance = INFINITY on entry (the other fields 0, as the CPU oracle
 // starts them): the boolean, and the record of the nearest accepted triangle with the lowest leaf index among equal
 // distances (nearer()); where some triangle is accepted but none replaces the record (a distance of +inf or NaN) the
 // record keeps its entry values -- leaf 0, barycentrics and point 0, distance +inf.  The smooth normal is the reference's
 // get_smooth_normal for that record (smooth_normal, as the primary pass computes it).
 // ANY: the same boolean; a lane leaves the walk at its first accepted triangle.
+// (query_kernel keeps lines of its own for the entry state and the store: written through the helpers above, the compiler
+// schedules query_kernel<true> differently -- 499 instructions for 494 -- and that kernel is not to move.  The leaf step
+// stays in each kernel's own lambda: as a function of its own it costs the walk loop three scalar instructions a turn.)
 template <bool CLOSEST>
 __global__ __launch_bounds__(64 * QUERY_WAVES) void query_kernel(QueryArgs a) {
 	bool live;

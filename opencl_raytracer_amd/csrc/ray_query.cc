@@ -26,7 +26,7 @@ enum { LAYER_HIT, LAYER_RECORDS, LAYER_DIRECTION = LAYER_RECORDS + 5, LAYER_SHAD
 // Multi-view rendering: the layers' pieces, then the 8-bit images.
 enum { VIEW_IMAGE = LAYER_PIECES, VIEW_PIECES };
 constexpr uint32_t QUERY_MAX_RAYS = 1u << 27;  // include/rt_hip_query.h
-constexpr uint32_t VIEWS_MAX_CHUNK = 65535u;   // views_resize_kernel: a grid's third dimension
+constexpr uint32_t VIEWS_MAX_CHUNK = 65535u;   // layers_kernel, views_resize_kernel: a grid's second and third dimension
 constexpr size_t PINNED_HEAD = 16u;            // viewsDevice: the read-back word in front of the poses
 }  // namespace
 
@@ -41,7 +41,7 @@ RayQueries::~RayQueries() {
 		return;
 	if (timed)
 		(void) hipEventSynchronize((hipEvent_t) ev_stop);
-	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &list, &layers, &views })
+	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &list, &views })
 		device_free(scratch->ptr);
 	if (pinned)
 		(void) hipHostFree(pinned);
@@ -182,6 +182,24 @@ void RayQueries::recordDevice(const Staged *p, RecordOutputs &out) {
 	out.normal = (float *) p[4].device;
 }
 
+void RayQueries::layerPieces(Staged *p, const LayerOutputs &host, size_t records) {
+	p[LAYER_HIT] = output(host.hit, records);
+	recordPieces(p + LAYER_RECORDS, host, records);
+	p[LAYER_DIRECTION] = output(host.direction, records * 12u);
+	p[LAYER_SHADE] = output(host.shade, records * 4u);
+	p[LAYER_AO] = output(host.ao, records * 4u);
+	p[LAYER_VALUE] = output(host.value, records * 4u);
+}
+
+void RayQueries::layerDevice(const Staged *p, LayerOutputs &out) {
+	out.hit = (unsigned char *) p[LAYER_HIT].device;
+	recordDevice(p + LAYER_RECORDS, out);
+	out.direction = (float *) p[LAYER_DIRECTION].device;
+	out.shade = (float *) p[LAYER_SHADE].device;
+	out.ao = (float *) p[LAYER_AO].device;
+	out.value = (float *) p[LAYER_VALUE].device;
+}
+
 void RayQueries::traceDevice(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
                              uint32_t flags, const QueryOutputs &out, void *stream) {
 	requireScene("ray query");
@@ -258,15 +276,15 @@ void RayQueries::aoDevice(const float *points4, const float *normals4, const uin
 	// the POINTS are ordered (key: point and normal) from as many on as make RT_QUERY_SORT_MIN rays
 	const Enqueue q = begin(stream, points4, normals4, n, (uint64_t) n * kp.ao_dirs, flags,
 	                        { Need{ occluded ? nullptr : &ao_hits, (size_t) n * sizeof(uint32_t) } });
-	aoEnqueue(q, points4, normals4, seeds, n, occluded ? occluded : (uint32_t *) ao_hits.ptr, ao);
+	aoEnqueue(q, points4, normals4, seeds, q.order, n, occluded ? occluded : (uint32_t *) ao_hits.ptr, ao);
 	end(q);
 }
 
-void RayQueries::aoEnqueue(const Enqueue &q, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n,
-                           uint32_t *count, float *ao) {
+void RayQueries::aoEnqueue(const Enqueue &q, const float *points4, const float *normals4, const uint32_t *seeds, const void *order,
+                           uint32_t n, uint32_t *count, float *ao) {
 	const KernelParams &kp = dev.params();
 	launch_ao_query(dev.deviceScene()->buffers(), kp.node_count, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4,
-	                normals4, seeds, q.order, n, count, ao, q.stream);
+	                normals4, seeds, order, n, count, ao, q.stream);
 }
 
 void RayQueries::aoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
@@ -304,27 +322,81 @@ bool RayQueries::requireFrameRays(bool ao, bool product) const {
 	return with_ao;
 }
 
+// (a piece that is not needed has no bytes; with nothing needed, `bytes` is 0)
+RayQueries::ChunkScratch RayQueries::chunkScratch(size_t poses, size_t entries, bool listing, size_t products) {
+	ChunkScratch c{};
+	auto piece = [&c](size_t bytes) {
+		const size_t here = c.bytes;
+		c.bytes += round16(bytes);
+		return here;
+	};
+	const size_t listable = listing ? entries : 0u;
+	c.poses = piece(poses * sizeof(CameraPose));
+	c.listed = piece(listing ? sizeof(uint32_t) : 0u);
+	c.points = piece(entries * 16u);
+	c.normals = piece(entries * 16u);
+	c.seeds = piece(listable * 4u);
+	c.order = piece(listable * 4u);
+	c.flags = piece(listable);
+	c.sums = piece((listable + 1023u) / 1024u * 4u);
+	c.product = piece(products * 4u);
+	return c;
+}
+
+uint32_t RayQueries::castChunk(const Enqueue &q, const ChunkScratch &at, bool listing, const void *poses, uint32_t views,
+                               const LayerOutputs &to, float *product, bool with_ao) {
+	const KernelParams &kp = dev.params();
+	hipStream_t s = (hipStream_t) q.stream;
+	char *const base = (char *) this->views.ptr;
+	ViewList list{};
+	if (with_ao) {
+		list.points = base + at.points;
+		list.normals = base + at.normals;
+	}
+	if (with_ao && listing) {
+		list.flags = (unsigned char *) (base + at.flags);
+		list.seeds = (uint32_t *) (base + at.seeds);
+		list.sums = (uint32_t *) (base + at.sums);
+		list.order = (uint32_t *) (base + at.order);
+		list.listed = (uint32_t *) (base + at.listed);
+	}
+	// (without the ambient-occlusion step `value` is the head-light term itself)
+	launch_layers(dev.deviceScene()->buffers(), kp, poses, dev.camera(), dev.cameraIsSet(), views, to, with_ao ? nullptr : product, to.ao,
+	              product, with_ao ? &list : nullptr, s);
+	if (!with_ao)
+		return 0u;
+	// the reference's ambient_occlusion(position, normal, index) in index order: of every sub-pixel -- seed i for point i --
+	// or of the hit ones alone, whose number then sizes the launch
+	uint32_t *const count = (uint32_t *) ao_hits.ptr;
+	uint32_t entries = views * kp.width * kp.height;
+	if (listing) {
+		// (the step's counts go by sub-pixel: all the chunk's are cleared -- while the host waits --, the hit ones are
+		// counted into)
+		uint32_t *const listed_host = (uint32_t *) pinned;
+		OCRT_HIP(hipMemsetAsync(count, 0, (size_t) entries * sizeof(uint32_t), s));
+		OCRT_HIP(hipMemcpyAsync(listed_host, list.listed, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+		OCRT_HIP(hipStreamSynchronize(s));
+		if (*listed_host > entries)
+			throw DeviceError("multi-view rendering: more sub-pixels listed than the chunk holds");
+		entries = *listed_host;
+	}
+	aoEnqueue(q, (const float *) list.points, (const float *) list.normals, list.seeds, list.order, entries, count, nullptr);
+	launch_views_scatter(list, count, kp.ao_divisor, to.ao, product, entries, s);
+	return entries;
+}
+
 void RayQueries::layersDevice(const LayerOutputs &out, void *stream) {
 	const bool with_ao = requireLayers(out);
 	const KernelParams &kp = dev.params();
 	const uint32_t n = kp.width * kp.height;
 	if (n == 0 || !out.any())
 		return;
-	// (ambient occlusion: the points and normals, then -- without an `ao` array to hold them -- the factors)
-	const size_t vectors = (size_t) n * 16u;
+	// one view, the host's own pose: with the ambient-occlusion step every sub-pixel is an entry of it -- nothing is
+	// listed, nothing read back, the call only enqueues
+	const ChunkScratch at = chunkScratch(0u, with_ao ? n : 0u, false, 0u);
 	const Enqueue q = begin(stream, nullptr, nullptr, n, n, QUERY_NO_SORT,
-	                        { Need{ with_ao ? &layers : nullptr, 2u * vectors + (out.ao ? 0u : (size_t) n * sizeof(float)) },
-	                          Need{ with_ao ? &ao_hits : nullptr, (size_t) n * sizeof(uint32_t) } });
-	char *const points = with_ao ? (char *) layers.ptr : nullptr, *const normals = with_ao ? points + vectors : nullptr;
-	// (without that step `value` is the head-light term itself)
-	launch_layers(dev.deviceScene()->buffers(), kp, dev.camera(), dev.cameraIsSet(), out, with_ao ? nullptr : out.value, points, normals,
-	              q.stream);
-	if (with_ao) {
-		// the reference's ambient_occlusion(position, normal, index) of every sub-pixel, in index order: seed i for point i
-		float *const factor = out.ao ? out.ao : (float *) (normals + vectors);
-		aoEnqueue(q, (const float *) points, (const float *) normals, nullptr, n, (uint32_t *) ao_hits.ptr, factor);
-		launch_layers_combine(points, normals, factor, out.ao, out.value, n, q.stream);
-	}
+	                        { Need{ with_ao ? &views : nullptr, at.bytes }, Need{ with_ao ? &ao_hits : nullptr, (size_t) n * sizeof(uint32_t) } });
+	(void) castChunk(q, at, false, nullptr, 1u, out, out.value, with_ao);
 	end(q);
 }
 
@@ -335,20 +407,10 @@ void RayQueries::layersHost(const LayerOutputs &host) {
 	if (n == 0 || !host.any())
 		return;
 	Staged p[LAYER_PIECES];
-	p[LAYER_HIT] = output(host.hit, n);
-	recordPieces(p + LAYER_RECORDS, host, n);
-	p[LAYER_DIRECTION] = output(host.direction, n * 12u);
-	p[LAYER_SHADE] = output(host.shade, n * 4u);
-	p[LAYER_AO] = output(host.ao, n * 4u);
-	p[LAYER_VALUE] = output(host.value, n * 4u);
+	layerPieces(p, host, n);
 	void *s = stageIn(p, LAYER_PIECES);
 	LayerOutputs out;
-	out.hit = (unsigned char *) p[LAYER_HIT].device;
-	recordDevice(p + LAYER_RECORDS, out);
-	out.direction = (float *) p[LAYER_DIRECTION].device;
-	out.shade = (float *) p[LAYER_SHADE].device;
-	out.ao = (float *) p[LAYER_AO].device;
-	out.value = (float *) p[LAYER_VALUE].device;
+	layerDevice(p, out);
 	layersDevice(out, s);
 	stageOut(p, LAYER_PIECES, s);
 }
@@ -410,35 +472,15 @@ void RayQueries::viewsDevice(const CameraPose *cameras, uint32_t views, const Vi
 		OCRT_HIP(hipHostMalloc(&pinned, PINNED_HEAD + pose_bytes, hipHostMallocDefault));
 		pinned_bytes = PINNED_HEAD + pose_bytes;
 	}
-	uint32_t *const listed_host = (uint32_t *) pinned;
 	const CameraPose *const poses_host = (const CameraPose *) ((char *) pinned + PINNED_HEAD);
 	std::memcpy((char *) pinned + PINNED_HEAD, cameras, pose_bytes);
-	// a chunk's scratch: its poses, the number of hit sub-pixels, then -- as far as the call needs them -- their list (by
-	// sub-pixel: flags, points, normals, seeds, order; by block of 1024: the sums) and the chunk's float images where the
-	// caller has no `value` array for them
+	// a chunk's scratch: its poses, then -- as far as the call needs them -- the list of its hit sub-pixels and the chunk's
+	// float images where the caller has no `value` array for them
 	const bool own_product = out.image && !out.value;
-	const size_t listable = with_ao ? most : 0u;
-	size_t at = 0;
-	auto piece = [&](size_t bytes) {
-		const size_t here = at;
-		at += round16(bytes);
-		return here;
-	};
-	const size_t poses_at = piece(per_chunk * sizeof(CameraPose)), listed_at = piece(sizeof(uint32_t));
-	const size_t points_at = piece(listable * 16u), normals_at = piece(listable * 16u), seeds_at = piece(listable * 4u);
-	const size_t order_at = piece(listable * 4u), flags_at = piece(listable), sums_at = piece((listable + 1023u) / 1024u * 4u);
-	const size_t product_at = piece(own_product ? most * 4u : 0u);
+	const ChunkScratch at = chunkScratch(per_chunk, with_ao ? most : 0u, true, own_product ? most : 0u);
 	const Enqueue q = begin(stream, nullptr, nullptr, n, n, QUERY_NO_SORT,
-	                        { Need{ &this->views, at }, Need{ with_ao ? &ao_hits : nullptr, listable * sizeof(uint32_t) } });
+	                        { Need{ &this->views, at.bytes }, Need{ with_ao ? &ao_hits : nullptr, most * sizeof(uint32_t) } });
 	char *const base = (char *) this->views.ptr;
-	ViewList list{};
-	list.flags = (unsigned char *) (base + flags_at);
-	list.points = base + points_at;
-	list.normals = base + normals_at;
-	list.seeds = (uint32_t *) (base + seeds_at);
-	list.sums = (uint32_t *) (base + sums_at);
-	list.order = (uint32_t *) (base + order_at);
-	list.listed = (uint32_t *) (base + listed_at);
 	hipStream_t s = (hipStream_t) q.stream;
 	ViewsDone done;
 	done.views = views;
@@ -446,28 +488,9 @@ void RayQueries::viewsDevice(const CameraPose *cameras, uint32_t views, const Vi
 		const uint32_t chunk = std::min(per_chunk, views - first);
 		const ViewOutputs to = viewsFrom(out, first, kp, image_bytes);
 		// (`product`: the chunk's float images -- the caller's `value`, or scratch for the 8-bit images alone)
-		float *const product = own_product ? (float *) (base + product_at) : to.value;
-		OCRT_HIP(hipMemcpyAsync(base + poses_at, poses_host + first, (size_t) chunk * sizeof(CameraPose), hipMemcpyHostToDevice, s));
-		// (without the ambient-occlusion step `value` is the head-light term itself)
-		launch_views(dev.deviceScene()->buffers(), kp, base + poses_at, chunk, to, with_ao ? nullptr : product, to.ao, product,
-		             with_ao ? &list : nullptr, s);
-		if (with_ao) {
-			// (the step's counts go by sub-pixel: all the chunk's are cleared -- while the host waits --, the hit ones are
-			// counted into)
-			uint32_t *const count = (uint32_t *) ao_hits.ptr;
-			OCRT_HIP(hipMemsetAsync(count, 0, (size_t) chunk * n * sizeof(uint32_t), s));
-			// the reference's ambient_occlusion(position, normal, index) of the hit sub-pixels alone, in index order:
-			// how many there are sizes the launch
-			OCRT_HIP(hipMemcpyAsync(listed_host, list.listed, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-			OCRT_HIP(hipStreamSynchronize(s));
-			const uint32_t listed = *listed_host;
-			if (listed > (size_t) chunk * n)
-				throw DeviceError("multi-view rendering: more sub-pixels listed than the chunk holds");
-			launch_ao_query(dev.deviceScene()->buffers(), kp.node_count, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, list.points,
-			                list.normals, list.seeds, list.order, listed, count, nullptr, s);
-			launch_views_scatter(list, count, kp.ao_divisor, to.ao, product, listed, s);
-			done.ao_points += listed;
-		}
+		float *const product = own_product ? (float *) (base + at.product) : to.value;
+		OCRT_HIP(hipMemcpyAsync(base + at.poses, poses_host + first, (size_t) chunk * sizeof(CameraPose), hipMemcpyHostToDevice, s));
+		done.ao_points += castChunk(q, at, true, base + at.poses, chunk, to, product, with_ao);
 		if (to.image)
 			launch_views_resize(product, to.image, kp, rt.options.width, rt.options.height, grid, chunk, s);
 	}
@@ -490,21 +513,11 @@ void RayQueries::viewsHost(const CameraPose *cameras, uint32_t views, const View
 		const size_t chunk = std::min(per_chunk, views - first), m = chunk * n;
 		const ViewOutputs to = viewsFrom(host, first, kp, image_bytes);
 		Staged p[VIEW_PIECES];
-		p[LAYER_HIT] = output(to.hit, m);
-		recordPieces(p + LAYER_RECORDS, to, m);
-		p[LAYER_DIRECTION] = output(to.direction, m * 12u);
-		p[LAYER_SHADE] = output(to.shade, m * 4u);
-		p[LAYER_AO] = output(to.ao, m * 4u);
-		p[LAYER_VALUE] = output(to.value, m * 4u);
+		layerPieces(p, to, m);
 		p[VIEW_IMAGE] = output(to.image, chunk * image_bytes);
 		void *s = stageIn(p, VIEW_PIECES);
 		ViewOutputs out;
-		out.hit = (unsigned char *) p[LAYER_HIT].device;
-		recordDevice(p + LAYER_RECORDS, out);
-		out.direction = (float *) p[LAYER_DIRECTION].device;
-		out.shade = (float *) p[LAYER_SHADE].device;
-		out.ao = (float *) p[LAYER_AO].device;
-		out.value = (float *) p[LAYER_VALUE].device;
+		layerDevice(p, out);
 		out.image = (unsigned char *) p[VIEW_IMAGE].device;
 		viewsDevice(cameras + first, (uint32_t) chunk, out, s);
 		stageOut(p, VIEW_PIECES, s);

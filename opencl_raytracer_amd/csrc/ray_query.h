@@ -94,6 +94,9 @@ class RayQueries {
 		// The five record arrays of `host`, `records` records each, as pieces p[0..4]; and those pieces' device pointers.
 		static void recordPieces(Staged *p, const RecordOutputs &host, size_t records);
 		static void recordDevice(const Staged *p, RecordOutputs &out);
+		// The same for the layers of `host`, `records` sub-pixels each: pieces p[LAYER_HIT .. LAYER_VALUE].
+		static void layerPieces(Staged *p, const LayerOutputs &host, size_t records);
+		static void layerDevice(const Staged *p, LayerOutputs &out);
 		struct Need {  // scratch of a family's own that begin() grows with the sort's
 			Scratch *scratch;  // (null: none)
 			size_t bytes;
@@ -110,15 +113,28 @@ class RayQueries {
 		bool requireViews(const ViewOutputs &out) const;    // the same for a views call
 		bool requireFrameRays(bool ao, bool product) const;
 		uint32_t viewsPerChunk(bool with_ao) const;
+		// Where the pieces of a chunk's scratch lie in `views`: `poses` poses, the ambient-occlusion step's `entries` points
+		// and normals, with `listing` the list of the hit ones (ViewList), and `products` floats of the chunk's own.
+		struct ChunkScratch {
+			size_t poses, listed, points, normals, seeds, order, flags, sums, product, bytes;
+		};
+		static ChunkScratch chunkScratch(size_t poses, size_t entries, bool listing, size_t products);
+		// A layers or views call between begin() and end(): the frame's own rays of `views` views -- `poses` on the device, or
+		// null: the host's own pose, one view -- into `to`, the blocks of the first view, then where `with_ao` the
+		// ambient-occlusion step and its tail into to.ao and `product`.  `listing`: the step runs over the hit sub-pixels
+		// alone, and the call waits for their number, which it returns; else over all of them, enqueued like the rest.
+		uint32_t castChunk(const Enqueue &q, const ChunkScratch &at, bool listing, const void *poses, uint32_t views, const LayerOutputs &to,
+		                   float *product, bool with_ao);
 		static ViewOutputs viewsFrom(const ViewOutputs &out, size_t view, const KernelParams &kp, size_t image_bytes);
 		void grow(Scratch &scratch, size_t bytes);
 		void sceneBox(const DeviceScene &scene, float lo[3], float scale[3]);
 		Enqueue begin(void *stream, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags,
 		              std::initializer_list<Need> needs = {});
 		void end(const Enqueue &q);
-		// aoDevice between begin() and end(): `count` holds n words (the caller's `occluded` or ao_hits).
-		void aoEnqueue(const Enqueue &q, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t *count,
-		               float *ao);
+		// The ambient-occlusion step between begin() and end(): n entries -- point order[j], or j where `order` is null --,
+		// counted into `count` by point index (the caller's `occluded` or ao_hits).
+		void aoEnqueue(const Enqueue &q, const float *points4, const float *normals4, const uint32_t *seeds, const void *order, uint32_t n,
+		               uint32_t *count, float *ao);
 		void *stageIn(Staged *pieces, size_t n);  // returns the stream
 		void stageOut(const Staged *pieces, size_t n, void *stream);
 
@@ -127,10 +143,9 @@ class RayQueries {
 		Scratch stage;         // the host-memory forms' inputs and outputs
 		Scratch ao_hits;       // aoDevice without an `occluded` array: the points' counts
 		Scratch list;          // multihitDevice: the rays' key lists, n * k * 8 bytes
-		Scratch layers;        // layersDevice with ambient occlusion: the sub-pixels' points and normals (float4 each), and
-		                       // their factors where the caller gave no `ao` array
-		Scratch views;         // viewsDevice: a chunk's poses, its list of hit sub-pixels (ViewList), its float images where the
-		                       // caller gave no `value` array
+		Scratch views;         // layersDevice, viewsDevice (ChunkScratch): a chunk's poses, the points and normals of its
+		                       // ambient-occlusion step, the list of the hit ones (ViewList), its float images where the caller
+		                       // gave no `value` array
 		void *pinned = nullptr;  // viewsDevice, host memory: the list's size as read back, then the call's poses
 		size_t pinned_bytes = 0;
 		uint32_t views_chunk = 0;
@@ -152,14 +167,11 @@ void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void 
 void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
                      float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
                      uint32_t *count, float *ao, void *stream);
-void launch_layers(const SceneBuffers &scene, const KernelParams &P, const CameraPose &pose, bool posed, const LayerOutputs &out,
-                   float *value, void *points, void *normals, void *stream);
-void launch_views(const SceneBuffers &scene, const KernelParams &P, const void *poses, uint32_t views, const LayerOutputs &out,
-                  float *value, float *ao, float *product, const ViewList *list, void *stream);
+void launch_layers(const SceneBuffers &scene, const KernelParams &P, const void *poses, const CameraPose &pose, bool posed, uint32_t views,
+                   const LayerOutputs &out, float *value, float *ao, float *product, const ViewList *list, void *stream);
 void launch_views_scatter(const ViewList &list, const uint32_t *count, uint32_t divisor, float *ao, float *product, uint32_t listed,
                           void *stream);
 void launch_views_resize(const float *value, unsigned char *image, const KernelParams &P, uint32_t out_width, uint32_t out_height,
                          uint32_t n, uint32_t views, void *stream);
-void launch_layers_combine(const void *points, const void *normals, const float *factor, float *ao, float *value, uint32_t n, void *stream);
 
 }  // namespace ocrt

@@ -1,6 +1,7 @@
 """Child process of tests/test_views_gpu.py::test_torch_path_equals_numpy_path: torch's HIP runtime comes up first, then
 the library; Host.render_views(as_torch=True) under a stream of the caller's -- in one chunk and in several -- must equal
-the numpy path."""
+the numpy path; so must a layers call with the ambient-occlusion step enqueued behind them on that stream, which leaves
+rt_debug_last_views as the views calls left it."""
 import os
 import sys
 
@@ -43,7 +44,17 @@ def main():
         chunked = host.render_views(cams, rt.VIEW_OUTPUTS, as_torch=True)
         assert host.last_views() == {"views": 5, "chunks": 3, "ao_points": hits}
         host.set_views_chunk(0)
+        # a layers call with the ambient-occlusion step behind them on the same stream: enqueued like the rest, and no
+        # views call -- what the last one did stays on the books
+        done = host.last_views()
+        layers = host.render_layers(("hit", "ao", "value"), as_torch=True)
+        assert host.last_views() == done
     side.synchronize()
+    layers_want = host.render_layers(("hit", "ao", "value"))
+    assert host.last_views() == done
+    for name in ("hit", "ao", "value"):
+        assert layers[name].device.type == "cuda" and layers[name].cpu().numpy().view(np.uint8).tobytes() == layers_want[name].view(np.uint8).tobytes(), name
+    assert layers_want["hit"].any() and not layers_want["hit"].all()
     assert host.last_query_ms > 0.0
     for name in rt.VIEW_OUTPUTS:
         for t in (got[name], chunked[name]):

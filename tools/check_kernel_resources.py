@@ -17,7 +17,7 @@ of their demangled names, and a gate that matches nothing guards nothing.  The R
 mode (ao_kernel<2, ..>, outside the bit-exact contract) must keep the occupancy; its
 spills are reported, not fatal.  The ray-query kernels (query_kernel<true> / <false>, query_key_kernel,
 query_scatter_kernel, query_scan_kernel: kernels/query.hip.h; and the kernels beside them: multi-hit, ambient-occlusion
-queries, multi-view rendering) must be present, with VGPR spill 0 and scratch 0; they do
+queries, frame layers and multi-view rendering) must be present, with VGPR spill 0 and scratch 0; they do
 not use walk_collect's fixed registers (their walk is the exact form, plain C++ around one scalar load per node), so no
 occupancy is pinned for them -- a spill there would still be memory traffic on every node of every query.  SGPR spills go to VGPR lanes (v_writelane / v_readlane), not
 to memory -- but those are vector instructions, the very resource the walk is bound by, so
@@ -139,7 +139,7 @@ def main():
     queries = ("query_kernel<true>", "query_kernel<false>", "query_key_kernel", "query_scatter_kernel", "query_scan_kernel",
                "multihit_walk_kernel<0", "multihit_walk_kernel<1u", "multihit_walk_kernel<2", "multihit_walk_kernel<4",
                "multihit_walk_kernel<8", "multihit_walk_kernel<16", "multihit_resolve_kernel", "ao_query_kernel<1",
-               "ao_query_kernel<2", "ao_query_finish_kernel", "views_kernel", "views_count_kernel", "views_scan_sums_kernel", "views_order_kernel",
+               "ao_query_kernel<2", "ao_query_finish_kernel", "layers_kernel<false, false>", "layers_kernel<true, false>", "layers_kernel<true, true>", "views_count_kernel", "views_scan_sums_kernel", "views_order_kernel",
                "views_scatter_kernel", "views_resize_kernel")
     names = [k["name"].replace("ocrt::", "").replace("void ", "") for k in kernels]
     for p in HOT_PRIMARY:
