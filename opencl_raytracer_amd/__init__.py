@@ -8,6 +8,7 @@ if the shared library is missing, importing :mod:`opencl_raytracer_amd.api`
 raises.
 """
 from .api import (  # noqa: F401
+    DIRECTIONAL_OUTPUTS,
     LAYER_OUTPUTS,
     VIEW_OUTPUTS,
     Camera,
@@ -24,4 +25,5 @@ from .api import (  # noqa: F401
     rccl_available,
     rccl_unique_id,
     resize_cpu,
+    unpack_ao_mask,
 )

@@ -1,5 +1,5 @@
-"""ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h, rt_hip_query.h, rt_hip_layers.h and rt_hip_camera.h (see those headers
-for the contract)."""
+"""ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h, rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h,
+rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h and rt_hip_camera.h (see those headers for the contract)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -236,6 +236,13 @@ _SIGNATURES = {
     "rt_trace_ao": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_trace_ao_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    # include/rt_hip_directional.h
+    "rt_ao_mask_words": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "rt_trace_ao_directional": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_trace_ao_directional_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                 C.c_void_p]),
+    "rt_ao_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_ao_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     # include/rt_hip_layers.h
     "rt_render_layers": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_render_layers_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -263,6 +270,11 @@ class _MultiHitArrays(C.Structure):
                 ("position", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class _DirectionalArrays(C.Structure):
+    """rt_ao_directional_arrays (include/rt_hip_directional.h)."""
+    _fields_ = [("ao", C.c_void_p), ("occluded", C.c_void_p), ("mask", C.c_void_p), ("bent", C.c_void_p)]
+
+
 class _LayerArrays(C.Structure):
     """rt_layer_arrays (include/rt_hip_layers.h)."""
     _fields_ = _HitArrays._fields_ + [("direction", C.c_void_p), ("shade", C.c_void_p), ("ao", C.c_void_p), ("value", C.c_void_p)]
@@ -278,13 +290,15 @@ RT_MULTIHIT_MAX_K = 16
 MULTIHIT_OUTPUTS = ("count", "distance", "leaf", "barycentric", "position", "normal")
 QUERY_OUTPUTS = ("hit", "distance", "leaf", "barycentric", "position", "normal")
 AO_OUTPUTS = ("ao", "occluded")
+DIRECTIONAL_OUTPUTS = ("ao", "occluded", "mask", "bent")
 LAYER_OUTPUTS = QUERY_OUTPUTS + ("direction", "shade", "ao", "value")
 VIEW_OUTPUTS = LAYER_OUTPUTS + ("image",)
 # per output of any query: numpy dtype, values per record.  The first four are one value per ray or point; the others are
 # the fields of a hit record: one record per ray (closest hit) or k of them (multi-hit).
 _OUTPUT_LAYOUT = {"hit": (np.uint8, 1), "count": (np.uint32, 1), "ao": (np.float32, 1), "occluded": (np.uint32, 1),
                   "distance": (np.float32, 1), "leaf": (np.uint32, 1), "barycentric": (np.float32, 3), "position": (np.float32, 3),
-                  "normal": (np.float32, 3), "direction": (np.float32, 3), "shade": (np.float32, 1), "value": (np.float32, 1)}
+                  "normal": (np.float32, 3), "direction": (np.float32, 3), "shade": (np.float32, 1), "value": (np.float32, 1),
+                  "bent": (np.float32, 3)}
 _RECORD_FIELDS = ("distance", "leaf", "barycentric", "position", "normal")
 
 
@@ -359,13 +373,17 @@ class _QueryArrays:
             raise ValueError("seeds: expected a uint32 array of shape (N,)")
         return np.ascontiguousarray(seeds)
 
-    def outputs(self, names, k=None) -> dict:
-        """{name: (N,) or (N, 3)}; with k the fields of a hit record are (N, k) or (N, k, 3)."""
+    def outputs(self, names, k=None, shapes=None) -> dict:
+        """{name: (N,) or (N, 3)}; with k the fields of a hit record are (N, k) or (N, k, 3).  `shapes`: {name: (dtype, what
+        follows N in the shape)} for outputs whose layout depends on the host's options."""
         out = {}
         for name in names:
-            dtype, per = _OUTPUT_LAYOUT[name]
-            slots = (k,) if k is not None and name in _RECORD_FIELDS else ()
-            shape = (self.n,) + slots + ((per,) if per > 1 else ())
+            if shapes and name in shapes:
+                dtype, shape = shapes[name][0], (self.n,) + tuple(shapes[name][1])
+            else:
+                dtype, per = _OUTPUT_LAYOUT[name]
+                slots = (k,) if k is not None and name in _RECORD_FIELDS else ()
+                shape = (self.n,) + slots + ((per,) if per > 1 else ())
             if self.torch:
                 import torch
 
@@ -387,6 +405,25 @@ class _QueryArrays:
         _check(getattr(load_library(), function + self.suffix)(h, self.ptr(self.a), self.ptr(self.b), *args, *self.stream))
         for t in self.padded:  # (the padded copies must live until the kernels have read them)
             t.record_stream(self.current)
+
+
+def unpack_ao_mask(mask, rays: int):
+    """The (N, W) uint32 mask rows of directional_occlusion as booleans: (N, rays), [i, k] True iff ray k of point i was
+    blocked.  numpy in, numpy out; torch in, torch out on the same device."""
+    rays = int(rays)
+    if mask.ndim != 2 or rays < 0 or rays > 32 * int(mask.shape[1]):
+        raise ValueError("mask: expected (N, W) rows with W >= ceil(rays / 32)")
+    k = np.arange(rays)
+    if _is_torch(mask):
+        import torch
+
+        if mask.dtype not in (torch.uint32, torch.int32):
+            raise ValueError("mask: expected uint32 words")
+        words = mask.view(torch.int32)[:, torch.from_numpy(k >> 5).to(mask.device)]
+        return ((words >> torch.from_numpy((k & 31).astype(np.int32)).to(mask.device)) & 1).to(torch.bool)
+    if not isinstance(mask, np.ndarray) or mask.dtype != np.uint32:
+        raise ValueError("mask: expected uint32 words")
+    return ((mask[:, k >> 5] >> (k & 31).astype(np.uint32)) & np.uint32(1)).astype(bool)
 
 
 def load_library() -> C.CDLL:
@@ -821,6 +858,54 @@ class Host:
         io.call(self._h, "rt_trace_ao", io.ptr(seeds) if seeds is not None and io.n else None, io.n,
                 0 if sort else RT_QUERY_NO_SORT, *io.pointers(out, AO_OUTPUTS))
         return out
+
+    # ---- directional occlusion queries (include/rt_hip_directional.h) ----
+    @property
+    def ao_mask_words(self) -> int:
+        """W: the uint32 words of a point's mask row, ceil(rays per point / 32)."""
+        words = C.c_uint32()
+        _check(load_library().rt_ao_mask_words(self._h, C.byref(words)))
+        return int(words.value)
+
+    def directional_occlusion(self, points, normals, seeds=None, outputs=DIRECTIONAL_OUTPUTS, sort: bool = True) -> dict:
+        """Which of every point's ambient-occlusion rays were blocked, and what follows from that: {"mask": uint32 (N, W) --
+        bit k & 31 of word k >> 5 is 1 iff ray k of the point was blocked (unpack_ao_mask makes booleans of it) --,
+        "occluded": uint32 (N,), the row's popcount, "ao": float32 (N,) -- both as ambient_occlusion returns them --,
+        "bent": float32 (N, 3), the sum of the directions of the point's open rays, added in ray order and not normalised}
+        (those named in `outputs`).  Ray k is the k-th ray the reference's ambient_occlusion() casts; ao_rays returns
+        the rays themselves.  Inputs, seeds, sorting and the numpy / torch forms are ambient_occlusion's."""
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in DIRECTIONAL_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {DIRECTIONAL_OUTPUTS}")
+        io = _QueryArrays(points, normals, ("points", "normals", "seeds"), "points", also=seeds)
+        if seeds is not None:
+            seeds = io.seeds(seeds)
+        out = io.outputs(outputs, shapes={"mask": (np.uint32, (self.ao_mask_words,))} if "mask" in outputs else None)
+        arrays = _DirectionalArrays(*io.pointers(out, DIRECTIONAL_OUTPUTS))
+        io.call(self._h, "rt_trace_ao_directional", io.ptr(seeds) if seeds is not None and io.n else None, io.n,
+                0 if sort else RT_QUERY_NO_SORT, C.byref(arrays))
+        return out
+
+    def ao_rays(self, points, normals, seeds=None) -> dict:
+        """The rays ambient_occlusion and directional_occlusion cast: {"origins": float32 (N, 4), "directions": float32
+        (N, R, 4)}, direction k of point i at [i, k], the fourth component 0; R = ao_rays_per_point[0].  The directions are
+        as cast: not normalised where the reference does not normalise them.  No ray is walked.  Inputs, seeds and the
+        numpy / torch forms are ambient_occlusion's."""
+        io = _QueryArrays(points, normals, ("points", "normals", "seeds"), "points", also=seeds)
+        if seeds is not None:
+            seeds = io.seeds(seeds)
+        rays = self.ao_rays_per_point[0]
+        out = io.outputs(("origins", "directions"), shapes={"origins": (np.float32, (4,)), "directions": (np.float32, (rays, 4))})
+        io.call(self._h, "rt_ao_rays", io.ptr(seeds) if seeds is not None and io.n else None, io.n,
+                *io.pointers(out, ("origins", "directions")))
+        return out
+
+    def vertex_bent_normals(self, scene: "Scene") -> np.ndarray:
+        """Per-vertex bent-normal baking: directional_occlusion(scene.vertices, scene.vnormals)["bent"], the raw sum of the
+        open rays' directions per vertex of the file, in its order (as vertex_ao is for "ao"); normalise, or divide by the
+        number of open rays, as the use demands.  A vertex with a zero normal gets what the arithmetic gives: not a number."""
+        return self.directional_occlusion(scene.vertices, scene.vnormals, outputs=("bent",))["bent"]
 
     # ---- frame layers (include/rt_hip_layers.h) ----
     def render_layers(self, outputs=LAYER_OUTPUTS, as_torch: bool = False) -> dict:

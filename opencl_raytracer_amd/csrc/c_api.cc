@@ -1,8 +1,9 @@
 // c_api.cc -- the extern "C" boundary declared in include/rt_hip.h (the seam), rt_hip_ring.h (streams of frames, several GPUs), rt_hip_debug.h,
-// rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h, rt_hip_layers.h, rt_hip_views.h and rt_hip_camera.h.
+// rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h and rt_hip_camera.h.
 #include "../../include/rt_hip.h"
 #include "../../include/rt_hip_ao.h"
 #include "../../include/rt_hip_camera.h"
+#include "../../include/rt_hip_directional.h"
 #include "../../include/rt_hip_layers.h"
 #include "../../include/rt_hip_debug.h"
 #include "../../include/rt_hip_multihit.h"
@@ -989,6 +990,72 @@ int rt_trace_ao_device(rt_host *h, const float *points4, const float *normals4, 
 	if (!aligned({ seeds, ao, occluded }, 4))
 		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
 	return guarded([&] { queries_of(h).aoDevice(points4, normals4, seeds, n, flags, ao, occluded, hip_stream); });
+}
+
+// ---- rt_hip_directional.h ----
+namespace {
+
+ocrt::RayQueries::DirectionalOutputs directional_outputs(const rt_ao_directional_arrays *from) {
+	ocrt::RayQueries::DirectionalOutputs q;
+	if (!from)
+		return q;
+	q.ao = from->ao;
+	q.occluded = from->occluded;
+	q.mask = from->mask;
+	q.bent = from->bent;
+	return q;
+}
+
+}  // namespace
+
+int rt_ao_mask_words(const rt_host *h, uint32_t *words) {
+	uint32_t per_point = 0;
+	const int rc = ao_precheck(h, nullptr, nullptr, 0, false, &per_point);
+	if (rc != RT_OK)
+		return rc;
+	if (words)
+		*words = (per_point + 31u) / 32u;
+	return RT_OK;
+}
+
+int rt_trace_ao_directional(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
+                            const rt_ao_directional_arrays *out) {
+	const int rc = ao_precheck(h, points4, normals4, n, false, nullptr);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	const ocrt::RayQueries::DirectionalOutputs q = directional_outputs(out);
+	return guarded([&] { queries_of(h).directionalHost(points4, normals4, seeds, n, flags, q); });
+}
+
+int rt_trace_ao_directional_device(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n,
+                                   uint32_t flags, const rt_ao_directional_arrays *out, void *hip_stream) {
+	const int rc = ao_precheck(h, points4, normals4, n, true, nullptr);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	const ocrt::RayQueries::DirectionalOutputs q = directional_outputs(out);
+	if (!aligned({ seeds, q.ao, q.occluded, q.mask, q.bent }, 4))
+		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).directionalDevice(points4, normals4, seeds, n, flags, q, hip_stream); });
+}
+
+int rt_ao_rays(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4,
+               float *directions4) {
+	const int rc = ao_precheck(h, points4, normals4, n, false, nullptr);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	return guarded([&] { queries_of(h).aoRaysHost(points4, normals4, seeds, n, origins4, directions4); });
+}
+
+int rt_ao_rays_device(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4,
+                      float *directions4, void *hip_stream) {
+	const int rc = ao_precheck(h, points4, normals4, n, true, nullptr);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	if (!aligned({ origins4, directions4 }, 16))
+		return fail(RT_E_INVALID, "device origin and direction arrays must be 16-byte aligned");
+	if (!aligned({ seeds }, 4))
+		return fail(RT_E_INVALID, "device seeds must be 4-byte aligned");
+	return guarded([&] { queries_of(h).aoRaysDevice(points4, normals4, seeds, n, origins4, directions4, hip_stream); });
 }
 
 // ---- rt_hip_layers.h ----

@@ -32,6 +32,9 @@
 //                   key, query_kernel<CLOSEST> casts them (kernels/query.hip.h, include/rt_hip_query.h): not part of a frame.
 //                   ao_query_kernel<MODE> makes, casts and counts the ambient-occlusion rays of caller-supplied points,
 //                   ao_query_finish_kernel writes their 1 - hits / n (kernels/ao_query.hip.h, include/rt_hip_ao.h).
+//                   ao_mask_kernel<MODE> casts the same rays and keeps their hit flags apart, a bit per ray,
+//                   ao_directional_finish_kernel<MODE> writes a point's count, value and the sum of its open rays' directions,
+//                   ao_rays_kernel<MODE> the rays themselves (kernels/directional.hip.h, include/rt_hip_directional.h).
 //                   multihit_walk_kernel<K> counts every triangle a caller-supplied ray's walk accepts and keeps the first K,
 //                   multihit_resolve_kernel writes their records (kernels/multihit.hip.h, include/rt_hip_multihit.h).
 //                   layers_kernel<POSED, ARRAY> casts the frame's own rays for one pose or for every pose of a chunk of views, a wave
@@ -74,6 +77,7 @@
 #include "kernels/finish.hip.h"
 #include "kernels/query.hip.h"
 #include "kernels/ao_query.hip.h"
+#include "kernels/directional.hip.h"
 #include "kernels/multihit.hip.h"
 #include "kernels/layers.hip.h"
 #include "kernels/views.hip.h"
@@ -387,6 +391,79 @@ void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode
 	if (ao)
 		hipLaunchKernelGGL(ao_query_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, (const uint32_t *) count, ao, n,
 		                   divisor ? divisor : 1u);
+}
+
+// Directional occlusion queries (kernels/directional.hip.h).  `mask`: n rows of ceil(rays_per_point / 32) words on the
+// device (the caller's array or scratch), zeroed here on the stream; `order`: launch_query_sort's order of the POINTS or
+// null; `occluded`, `ao`, `bent`: null = not written -- with all three null the resolve is not launched.
+void launch_ao_directional(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
+                           float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
+                           uint32_t *mask, uint32_t *occluded, float *ao, float *bent, void *stream) {
+	if (n == 0 || rays_per_point == 0)
+		return;
+	hipStream_t s = (hipStream_t) stream;
+	AoMaskArgs a{};
+	a.nodes_ptr = (const float4 *) scene.nodes;
+	a.tris_ptr = (const float4 *) scene.tris;
+	a.ao_table = (const float4 *) scene.ao_table;
+	a.points = (const float4 *) points;
+	a.normals = (const float4 *) normals;
+	a.seeds = seeds;
+	a.order = (const uint32_t *) order;
+	a.mask = mask;
+	a.n = n;
+	a.rays = rays_per_point;
+	a.words = (rays_per_point + 31u) / 32u;
+	a.total = n * rays_per_point;  // (<= RT_QUERY_MAX_RAYS: checked at the boundary)
+	a.node_count = node_count;
+	a.max_distance = max_distance;
+	(void) hipMemsetAsync(mask, 0, (size_t) n * a.words * sizeof(uint32_t), s);
+	const uint32_t blocks = (a.total + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
+	if (ao_mode == AO_RANDOM)
+		hipLaunchKernelGGL(ao_mask_kernel<AO_RANDOM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+	else
+		hipLaunchKernelGGL(ao_mask_kernel<AO_UNIFORM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+	if (!occluded && !ao && !bent)
+		return;
+	AoResolveArgs f{};
+	f.mask = mask;
+	f.ao_table = a.ao_table;
+	f.points = a.points;
+	f.normals = a.normals;
+	f.seeds = seeds;
+	f.occluded = occluded;
+	f.ao = ao;
+	f.bent = bent;
+	f.n = n;
+	f.rays = rays_per_point;
+	f.words = a.words;
+	f.ao_divisor = divisor ? divisor : 1u;
+	if (ao_mode == AO_RANDOM)
+		hipLaunchKernelGGL(ao_directional_finish_kernel<AO_RANDOM>, dim3((n + 255u) / 256u), dim3(256), 0, s, f);
+	else
+		hipLaunchKernelGGL(ao_directional_finish_kernel<AO_UNIFORM>, dim3((n + 255u) / 256u), dim3(256), 0, s, f);
+}
+
+// The rays of an ambient-occlusion query, written out (kernels/directional.hip.h): `origins` float4[n], `directions`
+// float4[n * rays_per_point]; null = not written.
+void launch_ao_rays(const SceneBuffers &scene, int ao_mode, uint32_t rays_per_point, const void *points, const void *normals,
+                    const uint32_t *seeds, uint32_t n, void *origins, void *directions, void *stream) {
+	if (n == 0 || rays_per_point == 0 || (!origins && !directions))
+		return;
+	AoRaysArgs a{};
+	a.ao_table = (const float4 *) scene.ao_table;
+	a.points = (const float4 *) points;
+	a.normals = (const float4 *) normals;
+	a.seeds = seeds;
+	a.origins = (float4 *) origins;
+	a.directions = (float4 *) directions;
+	a.rays = rays_per_point;
+	a.total = n * rays_per_point;  // (<= RT_QUERY_MAX_RAYS: checked at the boundary)
+	const uint32_t blocks = (a.total + 255u) / 256u;
+	if (ao_mode == AO_RANDOM)
+		hipLaunchKernelGGL(ao_rays_kernel<AO_RANDOM>, dim3(blocks), dim3(256), 0, (hipStream_t) stream, a);
+	else
+		hipLaunchKernelGGL(ao_rays_kernel<AO_UNIFORM>, dim3(blocks), dim3(256), 0, (hipStream_t) stream, a);
 }
 
 // Multi-hit queries (kernels/multihit.hip.h).  `k` <= MULTIHIT_MAX_K slots per ray (0: the count alone); `list`: n * k

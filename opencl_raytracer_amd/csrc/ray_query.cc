@@ -21,6 +21,10 @@ size_t round16(size_t bytes) { return (bytes + 15u) & ~(size_t) 15u; }
 // then the five record arrays.  Ambient occlusion: the counts come third, so that they are placed as they always were.
 enum { RAY_ORIGINS, RAY_DIRECTIONS, RAY_FIRST, RAY_RECORDS, RAY_PIECES = RAY_RECORDS + 5 };
 enum { AO_POINTS, AO_NORMALS, AO_COUNTS, AO_SEEDS, AO_VALUES, AO_PIECES };
+// Directional occlusion: the inputs, the rows (staged whether they are copied back or not), then the outputs made of them;
+// the rays of the points: the inputs and the two ray arrays.
+enum { DIR_POINTS, DIR_NORMALS, DIR_SEEDS, DIR_ROWS, DIR_COUNTS, DIR_VALUES, DIR_BENT, DIR_PIECES };
+enum { AORAY_POINTS, AORAY_NORMALS, AORAY_SEEDS, AORAY_ORIGINS, AORAY_DIRECTIONS, AORAY_PIECES };
 // Frame layers: the hit flags, the five record arrays, then the four layers of their own.
 enum { LAYER_HIT, LAYER_RECORDS, LAYER_DIRECTION = LAYER_RECORDS + 5, LAYER_SHADE, LAYER_AO, LAYER_VALUE, LAYER_PIECES };
 // Multi-view rendering: the layers' pieces, then the 8-bit images.
@@ -41,7 +45,7 @@ RayQueries::~RayQueries() {
 		return;
 	if (timed)
 		(void) hipEventSynchronize((hipEvent_t) ev_stop);
-	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &list, &views })
+	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &ao_rows, &list, &views })
 		device_free(scratch->ptr);
 	if (pinned)
 		(void) hipHostFree(pinned);
@@ -299,6 +303,66 @@ void RayQueries::aoHost(const float *points4, const float *normals4, const uint3
 	aoDevice((const float *) p[AO_POINTS].device, (const float *) p[AO_NORMALS].device, (const uint32_t *) p[AO_SEEDS].device, n, flags,
 	         (float *) p[AO_VALUES].device, (uint32_t *) p[AO_COUNTS].device, s);
 	stageOut(p, AO_PIECES, s);
+}
+
+void RayQueries::directionalDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
+                                   const DirectionalOutputs &out, void *stream) {
+	requireAo();
+	if (n == 0 || !out.any())
+		return;
+	const KernelParams &kp = dev.params();
+	const size_t row_bytes = (size_t) aoMaskWords(dev) * sizeof(uint32_t);
+	// the POINTS are ordered as for aoDevice; the rows are the caller's, or scratch where only what is made of them is wanted
+	const Enqueue q = begin(stream, points4, normals4, n, (uint64_t) n * kp.ao_dirs, flags,
+	                        { Need{ out.mask ? nullptr : &ao_rows, (size_t) n * row_bytes } });
+	launch_ao_directional(dev.deviceScene()->buffers(), kp.node_count, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4,
+	                      normals4, seeds, q.order, n, out.mask ? out.mask : (uint32_t *) ao_rows.ptr, out.occluded, out.ao, out.bent,
+	                      q.stream);
+	end(q);
+}
+
+void RayQueries::directionalHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
+                                 const DirectionalOutputs &host) {
+	requireAo();
+	if (n == 0 || !host.any())
+		return;
+	const size_t row_bytes = (size_t) aoMaskWords(dev) * sizeof(uint32_t);
+	Staged p[DIR_PIECES] = { input(points4, (size_t) n * 16u), input(normals4, (size_t) n * 16u), input(seeds, (size_t) n * 4u),
+		                     scratch(host.mask, (size_t) n * row_bytes), output(host.occluded, (size_t) n * 4u),
+		                     output(host.ao, (size_t) n * 4u), output(host.bent, (size_t) n * 12u) };
+	void *s = stageIn(p, DIR_PIECES);
+	DirectionalOutputs out;
+	out.mask = (uint32_t *) p[DIR_ROWS].device;
+	out.occluded = (uint32_t *) p[DIR_COUNTS].device;
+	out.ao = (float *) p[DIR_VALUES].device;
+	out.bent = (float *) p[DIR_BENT].device;
+	directionalDevice((const float *) p[DIR_POINTS].device, (const float *) p[DIR_NORMALS].device, (const uint32_t *) p[DIR_SEEDS].device, n,
+	                  flags, out, s);
+	stageOut(p, DIR_PIECES, s);
+}
+
+void RayQueries::aoRaysDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4,
+                              float *directions4, void *stream) {
+	requireAo();
+	if (n == 0 || (!origins4 && !directions4))
+		return;
+	const KernelParams &kp = dev.params();
+	const Enqueue q = begin(stream, nullptr, nullptr, n, (uint64_t) n * kp.ao_dirs, QUERY_NO_SORT);  // (nothing is walked: no order)
+	launch_ao_rays(dev.deviceScene()->buffers(), kp.ao_mode, kp.ao_dirs, points4, normals4, seeds, n, origins4, directions4, q.stream);
+	end(q);
+}
+
+void RayQueries::aoRaysHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4,
+                            float *directions4) {
+	requireAo();
+	if (n == 0 || (!origins4 && !directions4))
+		return;
+	Staged p[AORAY_PIECES] = { input(points4, (size_t) n * 16u), input(normals4, (size_t) n * 16u), input(seeds, (size_t) n * 4u),
+		                       output(origins4, (size_t) n * 16u), output(directions4, (size_t) n * aoRaysPerPoint(dev) * 16u) };
+	void *s = stageIn(p, AORAY_PIECES);
+	aoRaysDevice((const float *) p[AORAY_POINTS].device, (const float *) p[AORAY_NORMALS].device, (const uint32_t *) p[AORAY_SEEDS].device, n,
+	             (float *) p[AORAY_ORIGINS].device, (float *) p[AORAY_DIRECTIONS].device, s);
+	stageOut(p, AORAY_PIECES, s);
 }
 
 // What a layers call may ask of this host; returns whether it needs the ambient-occlusion step (`ao`, or `value` on a host

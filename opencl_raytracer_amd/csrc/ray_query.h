@@ -1,7 +1,7 @@
 // ray_query.h -- ray queries, multi-hit queries, ambient-occlusion queries, frame layers and multi-view rendering on a render
-// host's uploaded scene (include/rt_hip_query.h, include/rt_hip_multihit.h, include/rt_hip_ao.h, include/rt_hip_layers.h,
-// include/rt_hip_views.h; kernels/query.hip.h, kernels/multihit.hip.h, kernels/ao_query.hip.h, kernels/layers.hip.h,
-// kernels/views.hip.h).
+// host's uploaded scene (include/rt_hip_query.h, include/rt_hip_multihit.h, include/rt_hip_ao.h, include/rt_hip_directional.h,
+// include/rt_hip_layers.h, include/rt_hip_views.h; kernels/query.hip.h, kernels/multihit.hip.h, kernels/ao_query.hip.h,
+// kernels/directional.hip.h, kernels/layers.hip.h, kernels/views.hip.h).
 #pragma once
 #include <cstdint>
 #include <initializer_list>
@@ -48,6 +48,26 @@ class RayQueries {
 		// Host memory, blocking.
 		void aoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
 		            uint32_t *occluded);
+		// Directional occlusion queries (include/rt_hip_directional.h): the same rays, their hit flags a bit each in `mask`
+		// (aoMaskWords() words per point), the count and value made of a point's row, and the ordered sum of its open rays'
+		// directions.  Any output may be null; errors as for aoDevice.
+		struct DirectionalOutputs {
+			float *ao = nullptr;
+			uint32_t *occluded = nullptr, *mask = nullptr;
+			float *bent = nullptr;
+			bool any() const { return ao || occluded || mask || bent; }
+		};
+		static uint32_t aoMaskWords(const DeviceRenderer &renderer) { return (aoRaysPerPoint(renderer) + 31u) / 32u; }
+		// Device memory, enqueued on `stream` (null: the renderer's).
+		void directionalDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
+		                       const DirectionalOutputs &out, void *stream);
+		// Host memory, blocking.
+		void directionalHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
+		                     const DirectionalOutputs &out);
+		// The rays themselves: origins4 float4[n], directions4 float4[n * rays per point]; either may be null; no walk is run.
+		void aoRaysDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4, float *directions4,
+		                  void *stream);
+		void aoRaysHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4, float *directions4);
 		// Frame layers (include/rt_hip_layers.h): the closest-hit record of every sub-pixel's own ray -- the host's pose,
 		// DeviceRenderer::camera() / cameraIsSet() --, its direction, head-light term, ambient-occlusion factor and their
 		// product.  std::logic_error on a band-partitioned host and for out.ao where the options have ambient occlusion
@@ -142,7 +162,8 @@ class RayQueries {
 		Scratch count, order;  // the sort's histogram and the order it makes
 		Scratch stage;         // the host-memory forms' inputs and outputs
 		Scratch ao_hits;       // aoDevice without an `occluded` array: the points' counts
-		Scratch list;          // multihitDevice: the rays' key lists, n * k * 8 bytes
+		Scratch ao_rows;       // directionalDevice without a `mask` array: the points' rows
+	Scratch list;          // multihitDevice: the rays' key lists, n * k * 8 bytes
 		Scratch views;         // layersDevice, viewsDevice (ChunkScratch): a chunk's poses, the points and normals of its
 		                       // ambient-occlusion step, the list of the hit ones (ViewList), its float images where the caller
 		                       // gave no `value` array
@@ -167,6 +188,11 @@ void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void 
 void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
                      float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
                      uint32_t *count, float *ao, void *stream);
+void launch_ao_directional(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
+                           float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
+                           uint32_t *mask, uint32_t *occluded, float *ao, float *bent, void *stream);
+void launch_ao_rays(const SceneBuffers &scene, int ao_mode, uint32_t rays_per_point, const void *points, const void *normals,
+                    const uint32_t *seeds, uint32_t n, void *origins, void *directions, void *stream);
 void launch_layers(const SceneBuffers &scene, const KernelParams &P, const void *poses, const CameraPose &pose, bool posed, uint32_t views,
                    const LayerOutputs &out, float *value, float *ao, float *product, const ViewList *list, void *stream);
 void launch_views_scatter(const ViewList &list, const uint32_t *count, uint32_t divisor, float *ao, float *product, uint32_t listed,

@@ -17,7 +17,8 @@ of their demangled names, and a gate that matches nothing guards nothing.  The R
 mode (ao_kernel<2, ..>, outside the bit-exact contract) must keep the occupancy; its
 spills are reported, not fatal.  The ray-query kernels (query_kernel<true> / <false>, query_key_kernel,
 query_scatter_kernel, query_scan_kernel: kernels/query.hip.h; and the kernels beside them: multi-hit, ambient-occlusion
-queries, frame layers and multi-view rendering) must be present, with VGPR spill 0 and scratch 0; they do
+queries, directional occlusion queries, frame layers and multi-view rendering) must be present, with VGPR spill 0 and scratch 0
+(the directional kernels: no SGPR spill either, and their walk, ao_mask_kernel, at 8 waves per SIMD); they do
 not use walk_collect's fixed registers (their walk is the exact form, plain C++ around one scalar load per node), so no
 occupancy is pinned for them -- a spill there would still be memory traffic on every node of every query.  SGPR spills go to VGPR lanes (v_writelane / v_readlane), not
 to memory -- but those are vector instructions, the very resource the walk is bound by, so
@@ -140,7 +141,11 @@ def main():
                "multihit_walk_kernel<0", "multihit_walk_kernel<1u", "multihit_walk_kernel<2", "multihit_walk_kernel<4",
                "multihit_walk_kernel<8", "multihit_walk_kernel<16", "multihit_resolve_kernel", "ao_query_kernel<1",
                "ao_query_kernel<2", "ao_query_finish_kernel", "layers_kernel<false, false>", "layers_kernel<true, false>", "layers_kernel<true, true>", "views_count_kernel", "views_scan_sums_kernel", "views_order_kernel",
-               "views_scatter_kernel", "views_resize_kernel")
+               "views_scatter_kernel", "views_resize_kernel", "ao_mask_kernel<1", "ao_mask_kernel<2", "ao_directional_finish_kernel<1",
+               "ao_directional_finish_kernel<2", "ao_rays_kernel<1", "ao_rays_kernel<2")
+    # the directional occlusion queries' walk is ao_query_kernel's with another tail (kernels/directional.hip.h): it must keep
+    # that kernel's occupancy, 8 waves per SIMD -- a tail that needs more live state than the old one shows here
+    full_occupancy = ("ao_mask_kernel<1", "ao_mask_kernel<2")
     names = [k["name"].replace("ocrt::", "").replace("void ", "") for k in kernels]
     for p in HOT_PRIMARY:
         if not any(n.startswith(p) for n in names):
@@ -152,6 +157,10 @@ def main():
         for k in found:
             if k.get("VGPRs Spill") != "0" or k.get("ScratchSize [bytes/lane]") != "0":
                 errors.append(f"{q}: VGPR spill {k.get('VGPRs Spill')}, scratch {k.get('ScratchSize [bytes/lane]')} B/lane in a ray-query kernel")
+            if k.get("SGPRs Spill") != "0" and q.startswith(("ao_mask_kernel", "ao_directional_finish_kernel", "ao_rays_kernel")):
+                errors.append(f"{q}: SGPR spill {k.get('SGPRs Spill')} in a directional-occlusion kernel")
+            if q in full_occupancy and k.get("Occupancy [waves/SIMD]") != "8":
+                errors.append(f"{q}: occupancy {k.get('Occupancy [waves/SIMD]')} waves/SIMD, ao_query_kernel's walk runs at 8")
     if "--isa" in sys.argv:
         places = lane_ops_by_place(open(sys.argv[sys.argv.index("--isa") + 1]).read())
         lines.append("")
