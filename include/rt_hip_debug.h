@@ -112,6 +112,27 @@ int rt_debug_poison_hit_list(rt_host *h);
 int rt_debug_set_views_chunk(rt_host *h, uint32_t max_views);
 int rt_debug_last_views(rt_host *h, uint32_t *views, uint32_t *chunks, uint64_t *ao_points);
 
+/* Vertex updates (rt_hip_update.h).  The inner boxes are refitted bottom-up by a schedule made on the host: the inner nodes
+ * cut into groups of at most S, a workgroup per group, a launch per pass.  rt_debug_set_refit_group: S for this host's
+ * updates (0, the default: 256; at most 1024) -- so that a small mesh can take several passes; results never depend on it.
+ * rt_debug_refit_schedule: the schedule for a CPU-side scene's tree (`packed_tree` 0: its own node array; 1: the tree an
+ * upload puts on the device, which may be a cheaper one over the same leaves whose inner nodes have more than two
+ * children).  counts6: nodes, scheduled entries, child references, groups, passes, S as used; the arrays (any may be NULL;
+ * call once with NULLs for the counts): `skips` (a word per node: subtree size, 1 = leaf), `entries` (4 words each: node,
+ * first child reference, children, round within the group; in group order, by round within a group), `children` (a node
+ * index, or 0x80000000 | the entry's position within its own group), `groups` (4 words each: first entry, entries, rounds,
+ * pass from 1; in pass order).
+ * rt_debug_record_counts / rt_debug_download_records: the scene on the device as every query walks it -- how many node
+ * records (32 bytes: lo[3], skip, hi[3], leaf) and leaf records it has, and copies of the node records, the leaf records
+ * (96 bytes: lo[3], pad, hi[3], inv_d, ta[3], u[3], v[3], n[3], uu, uv, vv, D) and the shading records (48 bytes: three
+ * normals of four floats), taken once everything enqueued has finished; any pointer may be NULL.  RT_E_STATE without a
+ * scene and on the hosts of a frame ring. */
+int rt_debug_set_refit_group(rt_host *h, uint32_t nodes);
+int rt_debug_refit_schedule(const rt_scene *s, uint32_t group_nodes, int packed_tree, uint32_t counts6[6], uint32_t *skips, uint32_t *entries,
+                            uint32_t *children, uint32_t *groups);
+int rt_debug_record_counts(const rt_host *h, uint32_t *nodes, uint32_t *leaves);
+int rt_debug_download_records(rt_host *h, void *nodes_out, void *tris_out, void *shade_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 """ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h, rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h,
-rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h and rt_hip_camera.h (see those headers for the contract)."""
+rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers for the contract)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -249,6 +249,16 @@ _SIGNATURES = {
     # include/rt_hip_views.h
     "rt_render_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rt_render_views_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    # include/rt_hip_update.h
+    "rt_update_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rt_update_vertices_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rt_scene_refit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rt_last_update_ms": (C.c_float, [C.c_void_p]),
+    "rt_debug_set_refit_group": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_debug_refit_schedule": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "rt_debug_record_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rt_debug_download_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # include/rt_hip_camera.h
     "rt_camera_default": (None, [C.POINTER(Camera)]),
     "rt_camera_look_at": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Camera)]),
@@ -286,6 +296,13 @@ class _ViewArrays(C.Structure):
 
 
 RT_QUERY_NO_SORT = 1
+# the records of a scene on the device (csrc/device_types.h: NodeRec, TriRec, ShadeRec), as Host.records() returns them
+NODE_RECORD = np.dtype([("lo", np.float32, 3), ("skip", np.uint32), ("hi", np.float32, 3), ("leaf", np.uint32)])
+TRI_RECORD = np.dtype([("lo", np.float32, 3), ("pad0", np.float32), ("hi", np.float32, 3), ("inv_d", np.float32), ("ta", np.float32, 3),
+                       ("u", np.float32, 3), ("v", np.float32, 3), ("n", np.float32, 3), ("uu", np.float32), ("uv", np.float32),
+                       ("vv", np.float32), ("D", np.float32)])
+SHADE_RECORD = np.dtype([("n0", np.float32, 4), ("n1", np.float32, 4), ("n2", np.float32, 4)])
+assert (NODE_RECORD.itemsize, TRI_RECORD.itemsize, SHADE_RECORD.itemsize) == (32, 96, 48)
 RT_MULTIHIT_MAX_K = 16
 MULTIHIT_OUTPUTS = ("count", "distance", "leaf", "barycentric", "position", "normal")
 QUERY_OUTPUTS = ("hit", "distance", "leaf", "barycentric", "position", "normal")
@@ -561,6 +578,28 @@ class Scene:
     @property
     def sorted_faces(self) -> np.ndarray:
         return self._arr("rt_scene_sorted_faces", 3 * self.num_faces if self.num_nodes else 0, np.uint32)
+
+    def refit(self, vertices) -> "Scene":
+        """New vertex positions for the same faces (include/rt_hip_update.h, rt_scene_refit): `vertices` (V, 3) or (V, 4)
+        float32 replaces every position, `vnormals` is recomputed, `aabbs` is refitted by the refit rule; nodes, triangles,
+        faces and sorted_faces stay.  RtError -1 for another vertex count and for coordinates that are not finite or
+        exceed 1e37.  What Host.update_vertices does to the scene on the device, on the CPU arrays."""
+        v = _rays4_numpy(np.asarray(vertices), "vertices")
+        _check(load_library().rt_scene_refit(self._h, v.ctypes.data, v.shape[0]))
+        return self
+
+    def refit_schedule(self, group_nodes: int = 0, packed_tree: bool = False) -> dict:
+        """The schedule by which an update refits the inner boxes (include/rt_hip_debug.h, rt_debug_refit_schedule):
+        {"skips": (N,), "entries": (E, 4) node / first child reference / children / round, "children": (C,), "groups":
+        (G, 4) first entry / entries / rounds / pass, "passes", "group_nodes": S as used}, all uint32."""
+        lib, counts = load_library(), (C.c_uint32 * 6)()
+        _check(lib.rt_debug_refit_schedule(self._h, int(group_nodes), int(packed_tree), counts, None, None, None, None))
+        skips, entries = np.zeros(counts[0], np.uint32), np.zeros((counts[1], 4), np.uint32)
+        children, groups = np.zeros(counts[2], np.uint32), np.zeros((counts[3], 4), np.uint32)
+        _check(lib.rt_debug_refit_schedule(self._h, int(group_nodes), int(packed_tree), counts, skips.ctypes.data, entries.ctypes.data,
+                                           children.ctypes.data, groups.ctypes.data))
+        return {"skips": skips, "entries": entries, "children": children, "groups": groups, "passes": int(counts[4]),
+                "group_nodes": int(counts[5])}
 
     def face_of_leaf(self, leaf=None) -> np.ndarray:
         """The file-order face a query's `leaf` index stands for (rt_scene_triangles, include/rt_hip_query.h); without an
@@ -999,6 +1038,57 @@ class Host:
         views, chunks, points = C.c_uint32(), C.c_uint32(), C.c_uint64()
         _check(load_library().rt_debug_last_views(self._h, C.byref(views), C.byref(chunks), C.byref(points)))
         return {"views": views.value, "chunks": chunks.value, "ao_points": points.value}
+
+    # ---- vertex updates (include/rt_hip_update.h) ----
+    def update_vertices(self, vertices, vnormals=None) -> None:
+        """Refits the uploaded scene on the device to new vertex positions, without a new upload (rt_update_vertices):
+        `vertices` (V, 3) or (V, 4) float32 replaces every position -- V must be the upload's --, `vnormals` the shading
+        normals (None: they stay as uploaded; Scene.refit recomputes them on the CPU).  numpy arrays (blocking; refuses
+        coordinates that are not finite or exceed 1e37), or torch tensors on the host's GPU, enqueued on
+        torch.cuda.current_stream() without waiting (the rules are the queries').  Every query, render_layers and
+        render_views see the update; render() raises RtError -4 until the next upload."""
+        given = [vertices] + ([] if vnormals is None else [vnormals])
+        on_device = any(_is_torch(x) for x in given)
+        if on_device and not all(_is_torch(x) for x in given):
+            raise ValueError("vertices and vnormals must both be torch tensors or both numpy arrays")
+        pad = _rays4_torch if on_device else _rays4_numpy
+        v = pad(vertices, "vertices")
+        n = None if vnormals is None else pad(vnormals, "vnormals")
+        if n is not None and (n.shape[0] != v.shape[0] or (on_device and n.device != v.device)):
+            raise ValueError("vertices and vnormals must hold the same number of vertices" + (" on the same device" if on_device else ""))
+        lib = load_library()
+        if on_device:
+            import torch
+
+            current = torch.cuda.current_stream(v.device)
+            _check(lib.rt_update_vertices_device(self._h, v.data_ptr(), None if n is None else n.data_ptr(), int(v.shape[0]),
+                                                 current.cuda_stream))
+            for t, was in ((v, vertices), (n, vnormals)):  # (the padded copies must live until the kernels have read them)
+                if t is not None and t is not was:
+                    t.record_stream(current)
+        else:
+            _check(lib.rt_update_vertices(self._h, v.ctypes.data, None if n is None else n.ctypes.data, int(v.shape[0])))
+
+    @property
+    def last_update_ms(self) -> float:
+        """HIP-event time of the last update_vertices' kernels, ms (0.0 before the first)."""
+        return float(load_library().rt_last_update_ms(self._h))
+
+    def set_refit_group(self, nodes: int) -> None:
+        """Test aid (include/rt_hip_debug.h, rt_debug_set_refit_group): at most `nodes` inner nodes per group of an update's
+        schedule; 0: the default.  Same results."""
+        _check(load_library().rt_debug_set_refit_group(self._h, int(nodes)))
+
+    def records(self) -> dict:
+        """The scene on the device as every query walks it (include/rt_hip_debug.h, rt_debug_download_records): {"nodes":
+        NODE_RECORD (N,), "tris": TRI_RECORD (T,), "shade": SHADE_RECORD (T,)} structured arrays, taken once everything
+        enqueued has finished."""
+        lib, nodes, leaves = load_library(), C.c_uint32(), C.c_uint32()
+        _check(lib.rt_debug_record_counts(self._h, C.byref(nodes), C.byref(leaves)))
+        out = {"nodes": np.zeros(nodes.value, NODE_RECORD), "tris": np.zeros(leaves.value, TRI_RECORD),
+               "shade": np.zeros(leaves.value, SHADE_RECORD)}
+        _check(lib.rt_debug_download_records(self._h, out["nodes"].ctypes.data, out["tris"].ctypes.data, out["shade"].ctypes.data))
+        return out
 
     def vertex_ao(self, scene: "Scene") -> np.ndarray:
         """Per-vertex AO baking: ambient_occlusion(scene.vertices, scene.vnormals)["ao"], one value per vertex of the file, in

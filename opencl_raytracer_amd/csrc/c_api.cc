@@ -1,5 +1,5 @@
 // c_api.cc -- the extern "C" boundary declared in include/rt_hip.h (the seam), rt_hip_ring.h (streams of frames, several GPUs), rt_hip_debug.h,
-// rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h and rt_hip_camera.h.
+// rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h.
 #include "../../include/rt_hip.h"
 #include "../../include/rt_hip_ao.h"
 #include "../../include/rt_hip_camera.h"
@@ -9,10 +9,12 @@
 #include "../../include/rt_hip_multihit.h"
 #include "../../include/rt_hip_query.h"
 #include "../../include/rt_hip_views.h"
+#include "../../include/rt_hip_update.h"
 
 #include <algorithm>
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <initializer_list>
 #include <memory>
@@ -28,6 +30,7 @@
 #include "mesh.h"
 #include "ray_query.h"
 #include "ray_tracer.h"
+#include "refit.h"
 #include "scene_pack.h"
 
 struct rt_scene {
@@ -1165,6 +1168,126 @@ int rt_debug_last_views(rt_host *h, uint32_t *views, uint32_t *chunks, uint64_t 
 	if (ao_points)
 		*ao_points = done.ao_points;
 	return RT_OK;
+}
+
+// ---- rt_hip_update.h ----
+namespace {
+
+int update_precheck(const rt_host *h, const float *vertices4) {
+	if (!h)
+		return fail(RT_E_INVALID, "null host");
+	if (!h->owned)
+		return fail(RT_E_STATE, "vertex updates are not available on the hosts of a frame ring: their scene on the device is shared (one copy, many readers)");
+	if (!h->dev->sceneReady())
+		return fail(RT_E_STATE, "vertex update before a scene was uploaded");
+	if (!vertices4)
+		return fail(RT_E_INVALID, "null vertex array");
+	return RT_OK;
+}
+
+}  // namespace
+
+int rt_update_vertices(rt_host *h, const float *vertices4, const float *vnormals4, uint32_t num_vertices) {
+	const int rc = update_precheck(h, vertices4);
+	if (rc != RT_OK)
+		return rc;
+	return guarded([&] { queries_of(h).updateHost(vertices4, vnormals4, num_vertices); });
+}
+
+int rt_update_vertices_device(rt_host *h, const float *vertices4, const float *vnormals4, uint32_t num_vertices, void *hip_stream) {
+	const int rc = update_precheck(h, vertices4);
+	if (rc != RT_OK)
+		return rc;
+	if (!aligned({ vertices4, vnormals4 }, 16))
+		return fail(RT_E_INVALID, "device vertex and normal arrays must be 16-byte aligned");
+	return guarded([&] { queries_of(h).updateDevice(vertices4, vnormals4, num_vertices, hip_stream); });
+}
+
+int rt_scene_refit(rt_scene *s, const float *vertices4, uint32_t num_vertices) {
+	if (!s || !vertices4)
+		return fail(RT_E_INVALID, "null argument");
+	if (num_vertices != s->mesh.vertices.size())
+		return fail(RT_E_INVALID, "refit: the number of vertices differs from the scene's (the topology stays: every position is replaced)");
+	for (size_t i = 0; i < (size_t) num_vertices; ++i)
+		for (unsigned k = 0; k < 3; ++k)
+			if (!(std::fabs(vertices4[4 * i + k]) <= 1.0e37f))
+				return fail(RT_E_INVALID, "refit: a coordinate is not finite or exceeds 1e37 (nothing was written)");
+	return guarded([&] {
+		for (uint32_t i = 0; i < num_vertices; ++i)
+			s->mesh.vertices[i] = Vec3f(vertices4[4 * i], vertices4[4 * i + 1], vertices4[4 * i + 2]);
+		compute_vertex_normals(&s->mesh);
+		if (s->built)
+			ocrt::refit_boxes(s->bvh.nodes, s->sorted_faces, s->mesh.vertices, s->bvh.aabbs);
+	});
+}
+
+float rt_last_update_ms(const rt_host *h) {
+	if (!h || !h->queries)
+		return 0.0f;
+	try {
+		return h->queries->lastUpdateMs();
+	} catch (...) {
+		fail_from_exception();
+		return 0.0f;
+	}
+}
+
+int rt_debug_set_refit_group(rt_host *h, uint32_t nodes) {
+	if (!h)
+		return fail(RT_E_INVALID, "null host");
+	h->dev->setRefitGroup(nodes);
+	return RT_OK;
+}
+
+int rt_debug_download_records(rt_host *h, void *nodes_out, void *tris_out, void *shade_out) {
+	const int rc = host_precheck(h, "record");
+	if (rc != RT_OK)
+		return rc;
+	return guarded([&] { queries_of(h).downloadRecords(nodes_out, tris_out, shade_out); });
+}
+
+int rt_debug_record_counts(const rt_host *h, uint32_t *nodes, uint32_t *leaves) {
+	if (!h)
+		return fail(RT_E_INVALID, "null host");
+	if (!h->dev->sceneReady() || !h->dev->deviceScene())
+		return fail(RT_E_STATE, "no scene on the device");
+	if (nodes)
+		*nodes = h->dev->deviceScene()->nodeCount();
+	if (leaves)
+		*leaves = h->dev->deviceScene()->triCount();
+	return RT_OK;
+}
+
+int rt_debug_refit_schedule(const rt_scene *s, uint32_t group_nodes, int packed_tree, uint32_t counts6[6], uint32_t *skips_out, uint32_t *entries_out,
+                            uint32_t *children_out, uint32_t *groups_out) {
+	if (!s || !counts6)
+		return fail(RT_E_INVALID, "null argument");
+	if (!s->built)
+		return fail(RT_E_STATE, "scene has no BVH yet (call rt_scene_build_bvh)");
+	return guarded([&] {
+		std::vector<uint32_t> skips = s->bvh.nodes;
+		if (packed_tree) {  // the tree an upload puts on the device: the uploaded one, or the cheaper one pack_scene made of its leaves
+			const ocrt::PackedScene packed = ocrt::pack_scene(s->sorted_faces, s->bvh.nodes, s->bvh.aabbs, s->mesh.vertices, s->mesh.vnormals);
+			skips.resize(packed.nodes.size());
+			for (size_t i = 0; i < packed.nodes.size(); ++i)
+				skips[i] = packed.nodes[i].skip;
+		}
+		const ocrt::RefitSchedule schedule = ocrt::make_refit_schedule(skips, group_nodes);
+		counts6[0] = (uint32_t) skips.size();
+		counts6[1] = (uint32_t) (schedule.entries.size() / 4);
+		counts6[2] = (uint32_t) schedule.children.size();
+		counts6[3] = (uint32_t) (schedule.groups.size() / 4);
+		counts6[4] = schedule.passes();
+		counts6[5] = schedule.group_nodes;
+		if (skips_out)
+			std::copy(skips.begin(), skips.end(), skips_out);
+		if (entries_out)
+			std::copy(schedule.entries.begin(), schedule.entries.end(), entries_out);
+		if (children_out)
+			std::copy(schedule.children.begin(), schedule.children.end(), children_out);
+		if (groups_out)
+			std::copy(schedule.groups.begin(), schedule.groups.end(), groups_out);
+	});
 }
 
 float rt_last_query_ms(const rt_host *h) {

@@ -192,7 +192,28 @@ void DeviceRenderer::useDevice() const { OCRT_HIP(hipSetDevice(device)); }
 
 void DeviceRenderer::freeScene() {
 	scene_on_device.reset();  // (the arrays go when the last renderer lets go of them)
+	scene_of_my_own.reset();
+	scene_updated = false;
 	scene_ready = false;
+}
+
+DeviceScene *DeviceRenderer::updatableScene(const char **why) {
+	if (!scene_ready || !scene_on_device) {
+		*why = "vertex update before a scene was uploaded";
+		return nullptr;
+	}
+	// (two owners: scene_on_device and scene_of_my_own)
+	if (!scene_of_my_own || scene_of_my_own.get() != scene_on_device.get() || scene_of_my_own.use_count() != 2) {
+		*why = "vertex update on a host whose scene on the device is shared with other hosts (one copy, many readers: upload a scene of the host's own)";
+		return nullptr;
+	}
+	return scene_of_my_own.get();
+}
+
+void DeviceRenderer::requireFramePath(const char *what) const {
+	if (scene_updated)
+		throw std::logic_error(std::string(what) + " after a vertex update: the walk array, the hit list and the claim orders are the old positions' until the "
+		                                           "next upload (render_layers and render_views draw an updated scene)");
 }
 
 std::string DeviceRenderer::deviceName() const {
@@ -206,9 +227,11 @@ size_t DeviceRenderer::upload(const PackedScene &scene) {
 	useDevice();
 	synchronize();
 	freeScene();
-	std::shared_ptr<const DeviceScene> made = DeviceScene::create(device, scene, opts, expected_frames >= FRAMES_WORTH_INTERVALS, pose_set ? pose.eye : nullptr);
+	std::shared_ptr<DeviceScene> made = DeviceScene::create(device, scene, opts, expected_frames >= FRAMES_WORTH_INTERVALS, pose_set ? pose.eye : nullptr);
 	const size_t scene_bytes = made->bytes();
-	return scene_bytes + adopt(std::move(made));
+	const size_t own_bytes = adopt(made);
+	scene_of_my_own = std::move(made);  // (this renderer made it: it may refit it while nobody else holds it)
+	return scene_bytes + own_bytes;
 }
 
 size_t DeviceRenderer::adopt(std::shared_ptr<const DeviceScene> scene, const DeviceRenderer *layout_from) {
@@ -499,12 +522,16 @@ DeviceRenderer::WalkEntries DeviceRenderer::walkEntries() const {
 
 void DeviceRenderer::expectFrames(uint64_t frames) {
 	const bool before = expected_frames >= FRAMES_WORTH_INTERVALS, after = frames >= FRAMES_WORTH_INTERVALS;
+	if (before != after && scene_ready)
+		requireFramePath("expectFrames");
 	expected_frames = frames;
 	if (before == after || !scene_ready)
 		return;
 	// the scene is on the device already: lay the hit list out again, with or without the table (adopt() decides)
 	std::shared_ptr<const DeviceScene> scene = scene_on_device;
+	std::shared_ptr<DeviceScene> mine = scene_of_my_own;
 	adopt(std::move(scene));
+	scene_of_my_own = std::move(mine);
 }
 
 void DeviceRenderer::setAoPrefetch(bool on) {
@@ -517,6 +544,7 @@ void DeviceRenderer::setAoPrefetch(bool on) {
 bool DeviceRenderer::calibrateAoPrefetch(float *ms_without, float *ms_with) {
 	if (!scene_ready)
 		throw std::logic_error("calibration before upload");
+	requireFramePath("calibration");
 	const bool has_ao = kp.ao_mode == AO_UNIFORM && kp.ao_dirs > 0 && tile_count > 0 && kp.fast_walk && kp.walk_scale > 0.0f;
 	float median[2] = { 0.0f, 0.0f };
 	if (has_ao) {
@@ -550,6 +578,7 @@ bool DeviceRenderer::calibrateAoPrefetch(float *ms_without, float *ms_with) {
 void DeviceRenderer::enqueueRender() {
 	if (!scene_ready)
 		throw std::logic_error("render called before upload");
+	requireFramePath("render");
 	useDevice();
 	FrameEvents ev = takeEvents();
 	hipStream_t s = (hipStream_t) stream;
@@ -632,6 +661,7 @@ const DeviceRenderer::FrameGraph *DeviceRenderer::frameGraphFor(void *dst) {
 void DeviceRenderer::prepareFrame(void *device_u8) {
 	if (!scene_ready)
 		throw std::logic_error("prepare called before upload");
+	requireFramePath("prepare");
 	useDevice();
 	if (graph_mode)
 		(void) frameGraphFor(device_u8 ? device_u8 : d_u8);
@@ -640,6 +670,7 @@ void DeviceRenderer::prepareFrame(void *device_u8) {
 void DeviceRenderer::enqueueFrame(void *device_u8) {
 	if (!scene_ready)
 		throw std::logic_error("render called before upload");
+	requireFramePath("render");
 	useDevice();
 	void *dst = device_u8 ? device_u8 : d_u8;
 	const bool has_ao = kp.ao_mode != AO_NONE && kp.ao_dirs > 0 && tile_count > 0;

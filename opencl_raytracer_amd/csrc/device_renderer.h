@@ -42,8 +42,10 @@ class DeviceScene {
 		// (`for_a_stream`: make_walk_array's -- what only pays over many frames of the scene)
 		// (`eye`: make_walk_array's -- where the primary rays of the renderers that will adopt the scene start; nullptr: the
 		// reference's camera.  The walk array is made for that eye: servesEye() says whether a renderer's agrees.)
-		static std::shared_ptr<const DeviceScene> create(int device, const PackedScene &scene, const RayTracer::Options &options, bool for_a_stream = true,
-		                                                 const float *eye = nullptr);
+		// (Returned non-const: the renderer that made the scene and shares it with nobody may refit it -- updateVertices below.
+		// Everybody it is handed on to gets a pointer to const.)
+		static std::shared_ptr<DeviceScene> create(int device, const PackedScene &scene, const RayTracer::Options &options, bool for_a_stream = true,
+		                                           const float *eye = nullptr);
 		// A scene's arrays live in ONE device allocation.  A front end that knows the size of what is coming before it has
 		// the arrays (the triangle count of a mesh file's header) can have that allocation made ahead of time -- on the
 		// thread that brings the device up -- and create() takes it over if it is large enough (else it is dropped).
@@ -64,8 +66,32 @@ class DeviceScene {
 		uint32_t aoDirs() const { return ao_dirs; }
 		const SceneFacts &facts() const { return scene_facts_; }
 
+		// Vertex updates (include/rt_hip_update.h; kernels/refit.hip.h).  The records of `nodes`, `tris` and `shade` are made
+		// again on the device from `vertices4` (float4 per vertex, vertexCount() of them) and, where given, `vnormals4`;
+		// enqueued on `stream`, nothing is waited for.  What the launches need beside the records -- the leaf-ordered faces,
+		// the leaf -> node map, the schedule of the inner boxes -- is kept on the HOST from the upload on and goes to the
+		// device, into an allocation of its own, with the first update: bytes(), bytesFor() and the arena are an upload's as
+		// they always were.  `group_nodes`: RefitSchedule's (0: the default); the schedule is made again when it changes.
+		// The padded walk array is NOT remade: it stays the old positions'.
+		uint32_t vertexCount() const { return vertex_count; }
+		void updateVertices(const float *vertices4, const float *vnormals4, uint32_t group_nodes, void *stream);
+		uint32_t refitPasses() const { return (uint32_t) (refit_pass_first.empty() ? 0 : refit_pass_first.size() - 1); }
+		size_t refitBytes() const { return refit_bytes; }  // the allocation of the first update (0 before it)
+
 	private:
 		DeviceScene() = default;
+		// host side of the vertex updates: kept from the upload on
+		std::shared_ptr<const std::vector<uint32_t>> leaf_faces;  // three vertex ids per leaf
+		std::vector<uint32_t> node_skips, leaf_nodes;             // the tree's shape; the node of every leaf
+		uint32_t vertex_count = 0;
+		// device side: made by the first update
+		void *refit_arena = nullptr;
+		void *d_faces = nullptr, *d_leaf_nodes = nullptr, *d_entries = nullptr, *d_children = nullptr, *d_groups = nullptr;
+		size_t refit_bytes = 0, schedule_capacity = 0;
+		void *d_schedule = nullptr;  // entries, children, groups of the schedule in use (one allocation, remade with group_nodes)
+		uint32_t refit_group_nodes = 0;  // the schedule on the device was made for this (0: none yet)
+		std::vector<uint32_t> refit_pass_first;
+		void prepareRefit(uint32_t group_nodes);
 		int device_index = 0;
 		void *arena = nullptr;  // the one allocation the five arrays below point into
 		void *d_nodes = nullptr, *d_walk = nullptr, *d_tris = nullptr, *d_shade = nullptr, *d_ao = nullptr;
@@ -101,6 +127,19 @@ class DeviceRenderer {
 		// host): the hit list's layout is copied from it instead of being counted again.
 		size_t adopt(std::shared_ptr<const DeviceScene> scene, const DeviceRenderer *layout_from = nullptr);
 		const std::shared_ptr<const DeviceScene> &deviceScene() const { return scene_on_device; }
+		// Vertex updates (include/rt_hip_update.h): the scene this renderer uploaded ITSELF and shares with nobody, for
+		// writing -- null where there is none, `why` then says which of the two it is.  A scene that was adopted, or that
+		// another renderer has adopted from this one, stays one copy with many readers.
+		DeviceScene *updatableScene(const char **why);
+		// After an update the frame path is closed until the next upload: the padded walk array, the hit list's size, the
+		// claim orders and the walk intervals were all made for the old positions (enqueueRender, enqueueFrame,
+		// prepareFrame, the calibrations and expectFrames throw std::logic_error).  The queries, layers and views walk
+		// the exact records and go on.
+		void markSceneUpdated() { scene_updated = true; }
+		bool sceneUpdated() const { return scene_updated; }
+		// (include/rt_hip_debug.h) the schedule's group size for this renderer's updates; 0: the default
+		void setRefitGroup(uint32_t nodes) { refit_group = nodes; }
+		uint32_t refitGroup() const { return refit_group; }
 		// The camera pose (device_types.h: CameraPose): where this renderer's primary rays start and the basis their
 		// directions are made in, used as given.  BEFORE the upload only (std::logic_error afterwards): the walk array, the
 		// hit list's size, the tile order and the walk intervals are all made once per upload, for one view.  A renderer
@@ -253,6 +292,10 @@ class DeviceRenderer {
 		uint32_t local_out_rows;
 		void *own_stream, *stream;
 		std::shared_ptr<const DeviceScene> scene_on_device;
+		std::shared_ptr<DeviceScene> scene_of_my_own;  // the same scene for writing, where upload() made it (null after adopt() alone)
+		bool scene_updated = false;
+		uint32_t refit_group = 0;
+		void requireFramePath(const char *what) const;
 		void *d_image, *d_u8, *d_hits, *d_occluded, *d_tile_hits, *d_tile_base, *d_tile_entry, *d_order, *d_counters;
 		size_t hit_slots;     // slots of the hit list: the scene's hit sub-pixels in this rank's bands (sizeHitList)
 		size_t entryBytes() const { return (size_t) tile_count * kp.entry_stride * 2 * sizeof(uint32_t); }  // the tiles' walk intervals (entry_kernel)
@@ -340,5 +383,9 @@ void launch_finish(float *image, const void *hits, const void *occluded_of, cons
 void launch_occluded_sum(const void *occluded_of, size_t slots, void *counters, void *stream);
 void launch_resize(const float *tmp, unsigned char *out, const KernelParams &P, uint32_t out_width, uint32_t n,
                    uint32_t local_out_rows, void *stream);
+void launch_refit_leaves(const void *faces, const void *leaf_nodes, const void *vertices4, const void *vnormals4, void *tris, void *shade,
+                         void *nodes, uint32_t leaves, void *stream);
+void launch_refit_inner(const void *entries, const void *children, const void *groups, void *nodes, uint32_t first_group, uint32_t groups_in_pass,
+                        void *stream);
 
 }  // namespace ocrt

@@ -3,6 +3,7 @@
 #include <mutex>
 
 #include "device_internal.h"
+#include "refit.h"
 
 namespace ocrt {
 
@@ -16,8 +17,8 @@ int reserved_device = -1;
 size_t round_up(size_t bytes) { return (bytes + 255) & ~(size_t) 255; }
 }  // namespace
 
-std::shared_ptr<const DeviceScene> DeviceScene::create(int device, const PackedScene &scene, const RayTracer::Options &opts, bool for_a_stream,
-                                                       const float *eye) {
+std::shared_ptr<DeviceScene> DeviceScene::create(int device, const PackedScene &scene, const RayTracer::Options &opts, bool for_a_stream,
+                                                 const float *eye) {
 	UploadClock clock;
 	OCRT_HIP(hipSetDevice(device));
 	std::shared_ptr<DeviceScene> out(new DeviceScene());
@@ -110,6 +111,18 @@ std::shared_ptr<const DeviceScene> DeviceScene::create(int device, const PackedS
 #endif
 	clock.mark("copies of walk array, nodes, leaf records, normals, table");
 	out->device_bytes = nodes_bytes + walk_bytes + tris_bytes + shade_bytes + ao_bytes;
+	// What a vertex update will need, kept on the host (one sweep over the node records; the faces are shared, not copied):
+	// nothing of it goes to the device before the first update.
+	out->leaf_faces = scene.leaf_faces;
+	out->vertex_count = scene.vertex_count;
+	out->node_skips.resize(scene.nodes.size());
+	out->leaf_nodes.assign(scene.tris.size(), 0u);
+	for (size_t i = 0; i < scene.nodes.size(); ++i) {
+		out->node_skips[i] = scene.nodes[i].skip;
+		if (scene.nodes[i].skip == 1 && scene.nodes[i].leaf < out->leaf_nodes.size())
+			out->leaf_nodes[scene.nodes[i].leaf] = (uint32_t) i;
+	}
+	clock.mark("tree shape kept for vertex updates");
 	return out;
 }
 
@@ -117,6 +130,57 @@ DeviceScene::~DeviceScene() {
 	if (hipSetDevice(device_index) != hipSuccess)
 		return;
 	device_free(arena);
+	device_free(refit_arena);
+	device_free(d_schedule);
+}
+
+// The first update's uploads (faces, leaf -> node map) and the schedule for `group_nodes`, blocking: they are made once.
+void DeviceScene::prepareRefit(uint32_t group_nodes) {
+	if (!leaf_faces || leaf_faces->size() != (size_t) tri_count * 3 || leaf_nodes.size() != tri_count || node_skips.size() != node_count)
+		throw std::logic_error("vertex update: the scene was uploaded without its faces");
+	const uint32_t wanted = group_nodes == 0 ? REFIT_DEFAULT_GROUP : group_nodes < REFIT_MAX_GROUP ? group_nodes : REFIT_MAX_GROUP;
+	if (!refit_arena) {
+		const size_t faces_bytes = leaf_faces->size() * sizeof(uint32_t), map_bytes = leaf_nodes.size() * sizeof(uint32_t);
+		refit_arena = device_alloc(round_up(faces_bytes) + round_up(map_bytes));
+		d_faces = refit_arena;
+		d_leaf_nodes = (char *) refit_arena + round_up(faces_bytes);
+		OCRT_HIP(hipMemcpy(d_faces, leaf_faces->data(), faces_bytes, hipMemcpyHostToDevice));
+		OCRT_HIP(hipMemcpy(d_leaf_nodes, leaf_nodes.data(), map_bytes, hipMemcpyHostToDevice));
+		refit_bytes = faces_bytes + map_bytes;
+	}
+	if (refit_group_nodes == wanted)
+		return;
+	const RefitSchedule schedule = make_refit_schedule(node_skips, wanted);
+	const size_t entries_bytes = schedule.entries.size() * sizeof(uint32_t), children_bytes = schedule.children.size() * sizeof(uint32_t),
+	             groups_bytes = schedule.groups.size() * sizeof(uint32_t);
+	const size_t need = round_up(entries_bytes) + round_up(children_bytes) + round_up(groups_bytes);
+	OCRT_HIP(hipDeviceSynchronize());  // (an update by the old schedule may still be running)
+	if (need > schedule_capacity || !d_schedule) {
+		device_free(d_schedule);
+		schedule_capacity = 0;
+		d_schedule = device_alloc(need);
+		schedule_capacity = need;
+	}
+	d_entries = d_schedule;
+	d_children = (char *) d_schedule + round_up(entries_bytes);
+	d_groups = (char *) d_children + round_up(children_bytes);
+	if (entries_bytes)
+		OCRT_HIP(hipMemcpy(d_entries, schedule.entries.data(), entries_bytes, hipMemcpyHostToDevice));
+	if (children_bytes)
+		OCRT_HIP(hipMemcpy(d_children, schedule.children.data(), children_bytes, hipMemcpyHostToDevice));
+	if (groups_bytes)
+		OCRT_HIP(hipMemcpy(d_groups, schedule.groups.data(), groups_bytes, hipMemcpyHostToDevice));
+	refit_pass_first = schedule.pass_first;
+	refit_group_nodes = wanted;
+}
+
+void DeviceScene::updateVertices(const float *vertices4, const float *vnormals4, uint32_t group_nodes, void *stream) {
+	OCRT_HIP(hipSetDevice(device_index));
+	prepareRefit(group_nodes);
+	launch_refit_leaves(d_faces, d_leaf_nodes, vertices4, vnormals4, d_tris, d_shade, d_nodes, tri_count, stream);
+	for (size_t p = 0; p + 1 < refit_pass_first.size(); ++p)
+		launch_refit_inner(d_entries, d_children, d_groups, d_nodes, refit_pass_first[p], refit_pass_first[p + 1] - refit_pass_first[p], stream);
+	OCRT_HIP(hipGetLastError());
 }
 
 void DeviceScene::reserve(int device, size_t bytes) {

@@ -81,6 +81,7 @@
 #include "kernels/multihit.hip.h"
 #include "kernels/layers.hip.h"
 #include "kernels/views.hip.h"
+#include "kernels/refit.hip.h"
 
 
 namespace ocrt {
@@ -569,6 +570,39 @@ void launch_views_resize(const float *value, unsigned char *image, const KernelP
 		return;
 	hipLaunchKernelGGL(views_resize_kernel, dim3((out_width + 255u) / 256u, out_height, views), dim3(256), 0, (hipStream_t) stream, value,
 	                   image, out_width, out_height, P.width, n, P.width * P.height);
+}
+
+// Vertex updates (kernels/refit.hip.h, include/rt_hip_update.h): the leaf records and leaf boxes of `leaves` leaves from
+// the new positions (`vnormals4` null: the ShadeRecs stay) ...
+void launch_refit_leaves(const void *faces, const void *leaf_nodes, const void *vertices4, const void *vnormals4, void *tris, void *shade,
+                         void *nodes, uint32_t leaves, void *stream) {
+	if (leaves == 0)
+		return;
+	RefitLeafArgs a{};
+	a.faces = (const uint32_t *) faces;
+	a.leaf_node = (const uint32_t *) leaf_nodes;
+	a.vertices = (const float4 *) vertices4;
+	a.vnormals = (const float4 *) vnormals4;
+	a.tris = (float4 *) tris;
+	a.shade = (float4 *) shade;
+	a.nodes = (float *) nodes;
+	a.leaves = leaves;
+	hipLaunchKernelGGL(refit_leaves_kernel, dim3((leaves + REFIT_LEAF_LANES - 1u) / REFIT_LEAF_LANES), dim3(REFIT_LEAF_LANES), 0,
+	                   (hipStream_t) stream, a);
+}
+
+// ... and one pass of the inner boxes: the schedule's groups first_group ... first_group + groups_in_pass - 1, a workgroup each.
+void launch_refit_inner(const void *entries, const void *children, const void *groups, void *nodes, uint32_t first_group, uint32_t groups_in_pass,
+                        void *stream) {
+	if (groups_in_pass == 0)
+		return;
+	RefitInnerArgs a{};
+	a.entries = (const uint4 *) entries;
+	a.children = (const uint32_t *) children;
+	a.groups = (const uint4 *) groups;
+	a.nodes = (float *) nodes;
+	a.first_group = first_group;
+	hipLaunchKernelGGL(refit_inner_kernel, dim3(groups_in_pass), dim3(REFIT_INNER_LANES), 0, (hipStream_t) stream, a);
 }
 
 }  // namespace ocrt

@@ -38,6 +38,9 @@ RayQueries::RayQueries(DeviceRenderer &renderer) : dev(renderer) {
 	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
 	OCRT_HIP(hipEventCreate((hipEvent_t *) &ev_start));
 	OCRT_HIP(hipEventCreate((hipEvent_t *) &ev_stop));
+	OCRT_HIP(hipEventCreate((hipEvent_t *) &ev_update_start));
+	OCRT_HIP(hipEventCreate((hipEvent_t *) &ev_update_stop));
+	OCRT_HIP(hipEventCreateWithFlags((hipEvent_t *) &ev_frames, hipEventDisableTiming));
 }
 
 RayQueries::~RayQueries() {
@@ -51,6 +54,9 @@ RayQueries::~RayQueries() {
 		(void) hipHostFree(pinned);
 	(void) hipEventDestroy((hipEvent_t) ev_start);
 	(void) hipEventDestroy((hipEvent_t) ev_stop);
+	(void) hipEventDestroy((hipEvent_t) ev_update_start);
+	(void) hipEventDestroy((hipEvent_t) ev_update_stop);
+	(void) hipEventDestroy((hipEvent_t) ev_frames);
 }
 
 // (hipFree waits for the device: a query still running on the old buffer finishes first)
@@ -86,6 +92,9 @@ void RayQueries::sceneBox(const DeviceScene &scene, float lo[3], float scale[3])
 	const std::shared_ptr<const DeviceScene> current = dev.deviceScene();
 	if (boxed.lock() != current) {
 		NodeRec root{};
+		// (the copy below is ordered against no stream: an update still on its way to the root is waited for first)
+		if (timed)
+			OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
 		if (scene.nodeCount() > 0)
 			OCRT_HIP(hipMemcpy(&root, scene.buffers().nodes, sizeof root, hipMemcpyDeviceToHost));
 		for (int k = 0; k < 3; ++k) {
@@ -593,6 +602,88 @@ void RayQueries::viewsHost(const CameraPose *cameras, uint32_t views, const View
 	last_views = done;
 	last_ms = ms;  // (every chunk's events have been read: the call's time is their sum)
 	have_ms = true;
+}
+
+// The update is a query as far as ordering goes: it waits for the one before it by ev_stop and leaves ev_stop behind for the
+// one after it -- whatever streams they run on.  The frames of the renderer's own stream read the records too: the update
+// waits for that stream's tail on the device (an event of its own; nothing blocks the host).
+void RayQueries::updateDevice(const float *vertices4, const float *vnormals4, uint32_t num_vertices, void *stream) {
+	const char *why = "";
+	DeviceScene *const scene = dev.updatableScene(&why);
+	if (!scene)
+		throw std::logic_error(why);
+	if (num_vertices != scene->vertexCount())
+		throw std::invalid_argument("vertex update: the number of vertices differs from the upload's (the topology stays: every position is replaced)");
+	if (!vertices4)
+		throw std::invalid_argument("vertex update: null vertex array");
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
+	if (timed)
+		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	if (s != (hipStream_t) dev.streamHandle()) {
+		OCRT_HIP(hipEventRecord((hipEvent_t) ev_frames, (hipStream_t) dev.streamHandle()));
+		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_frames, 0));
+	}
+	// (from here on the records are the new positions' as far as the host is concerned, whether the launches below succeed
+	// or not: no frame may lean on the old walk array again, and the sort's box is read afresh)
+	dev.markSceneUpdated();
+	boxed.reset();
+	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
+	OCRT_HIP(hipEventRecord((hipEvent_t) ev_update_start, s));
+	scene->updateVertices(vertices4, vnormals4, dev.refitGroup(), s);
+	OCRT_HIP(hipEventRecord((hipEvent_t) ev_update_stop, s));
+	update_timed = true;
+	have_update_ms = false;
+	end(Enqueue{ s, nullptr });
+}
+
+void RayQueries::updateHost(const float *vertices4, const float *vnormals4, uint32_t num_vertices) {
+	const char *why = "";
+	DeviceScene *const scene = dev.updatableScene(&why);
+	if (!scene)
+		throw std::logic_error(why);
+	if (num_vertices != scene->vertexCount())
+		throw std::invalid_argument("vertex update: the number of vertices differs from the upload's (the topology stays: every position is replaced)");
+	if (!vertices4)
+		throw std::invalid_argument("vertex update: null vertex array");
+	for (size_t i = 0; i < (size_t) num_vertices; ++i)
+		for (unsigned k = 0; k < 3; ++k)
+			if (!(std::fabs(vertices4[4 * i + k]) <= 1.0e37f))  // (false for a NaN too)
+				throw std::invalid_argument("vertex update: a coordinate is not finite or exceeds 1e37 (nothing was written)");
+	if (num_vertices == 0)
+		return;
+	Staged p[2] = { input(vertices4, (size_t) num_vertices * 16u), input(vnormals4, (size_t) num_vertices * 16u) };
+	void *s = stageIn(p, 2);
+	updateDevice((const float *) p[0].device, (const float *) p[1].device, num_vertices, s);
+	stageOut(p, 2, s);
+}
+
+float RayQueries::lastUpdateMs() {
+	if (!update_timed)
+		return 0.0f;
+	if (!have_update_ms) {
+		OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_update_stop));
+		OCRT_HIP(hipEventElapsedTime(&last_update_ms, (hipEvent_t) ev_update_start, (hipEvent_t) ev_update_stop));
+		have_update_ms = true;
+	}
+	return last_update_ms;
+}
+
+void RayQueries::downloadRecords(void *nodes_out, void *tris_out, void *shade_out) {
+	requireScene("record download");
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	if (timed)
+		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
+	OCRT_HIP(hipStreamSynchronize((hipStream_t) dev.streamHandle()));
+	const DeviceScene &scene = *dev.deviceScene();
+	const SceneBuffers b = scene.buffers();
+	if (nodes_out && scene.nodeCount())
+		OCRT_HIP(hipMemcpy(nodes_out, b.nodes, (size_t) scene.nodeCount() * sizeof(NodeRec), hipMemcpyDeviceToHost));
+	if (tris_out && scene.triCount())
+		OCRT_HIP(hipMemcpy(tris_out, b.tris, (size_t) scene.triCount() * sizeof(TriRec), hipMemcpyDeviceToHost));
+	if (shade_out && scene.triCount())
+		OCRT_HIP(hipMemcpy(shade_out, b.shade, (size_t) scene.triCount() * sizeof(ShadeRec), hipMemcpyDeviceToHost));
 }
 
 float RayQueries::lastMs() {

@@ -93,6 +93,18 @@ class RayQueries {
 		};
 		ViewsDone lastViews() const { return last_views; }
 		float lastMs();  // the last query of any kind
+		// Vertex updates (include/rt_hip_update.h): the renderer's own scene refitted on the device from `vertices4` (and
+		// `vnormals4`, or null: the shading normals stay) -- serialised with this host's queries by the event they use among
+		// themselves, and behind whatever the renderer's frame stream holds; a later query sees the whole update.  Closes
+		// the renderer's frame path until its next upload (DeviceRenderer::markSceneUpdated) and drops the cached root box.
+		// std::logic_error before an upload and on a shared scene, std::invalid_argument for another vertex count.
+		// Device memory, enqueued on `stream` (null: the renderer's).
+		void updateDevice(const float *vertices4, const float *vnormals4, uint32_t num_vertices, void *stream);
+		// Host memory, blocking; refuses coordinates that are not finite or beyond 1e37 before anything is written.
+		void updateHost(const float *vertices4, const float *vnormals4, uint32_t num_vertices);
+		float lastUpdateMs();  // HIP-event time of the last update's launches (0: none yet)
+		// (include/rt_hip_debug.h) the three record arrays as they are on the device, once everything enqueued has finished
+		void downloadRecords(void *nodes_out, void *tris_out, void *shade_out);
 
 	private:
 		struct Scratch {  // device memory of this host's own, grown on demand
@@ -174,6 +186,9 @@ class RayQueries {
 		void *ev_start = nullptr, *ev_stop = nullptr;
 		bool timed = false, have_ms = false;
 		float last_ms = 0.0f;
+		void *ev_update_start = nullptr, *ev_update_stop = nullptr, *ev_frames = nullptr;  // an update's own times; the frame stream's tail
+		bool update_timed = false, have_update_ms = false;
+		float last_update_ms = 0.0f;
 		std::weak_ptr<const DeviceScene> boxed;  // the scene box_lo / box_scale were read from
 		float box_lo[3] = { 0, 0, 0 }, box_scale[3] = { 0, 0, 0 };
 };

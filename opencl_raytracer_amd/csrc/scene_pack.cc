@@ -229,6 +229,8 @@ PackedScene pack_scene(const std::vector<uint32_t> &faces, const std::vector<uin
 			out.rebuilt = true;
 		}
 	}
+	out.leaf_faces = std::make_shared<const std::vector<uint32_t>>(faces);
+	out.vertex_count = (uint32_t) vertices.size();
 	// the leaf's own box, exactly as uploaded, next to its triangle (leaf indices are the same in either tree)
 	for (const NodeRec &n : out.nodes)
 		if (n.skip == 1)

@@ -48,6 +48,11 @@ struct PackedScene {
 	bool nested = false;       // ... and every node's box contains its children's boxes (true for any tree built by
 	                           // uniting child boxes; arbitrary uploaded arrays need not be)
 	bool rebuilt = false;      // `nodes` is the rebuilt tree, not the uploaded one
+	// What a vertex update needs beside the records (include/rt_hip_update.h; TriRec replaced the face indices): the
+	// leaf-ordered faces as uploaded, shared so that the scene on the device keeps them without a copy, and how many
+	// vertices they index.
+	std::shared_ptr<const std::vector<uint32_t>> leaf_faces;
+	uint32_t vertex_count = 0;
 	// Optional: the walk array made ahead of the upload (prepare_walk_array) for this AO_MAX_DISTANCE -- CPU work that a
 	// caller can do before it has a device; DeviceRenderer::upload makes its own when this one is absent or was made for
 	// another distance.

@@ -289,6 +289,7 @@ extern void *primary_ticks_probe;  // (kernels.hip)
 bool DeviceRenderer::measureTileCosts(unsigned frames) {
 	if (!scene_ready)
 		throw std::logic_error("measurement before upload");
+	requireFramePath("measurement");
 	const bool has_ao = kp.ao_mode != AO_NONE && kp.ao_dirs > 0 && tile_count > 0 && tile_words.size() == tile_count;
 	if (!has_ao || frames == 0)
 		return false;

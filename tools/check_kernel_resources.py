@@ -142,7 +142,8 @@ def main():
                "multihit_walk_kernel<8", "multihit_walk_kernel<16", "multihit_resolve_kernel", "ao_query_kernel<1",
                "ao_query_kernel<2", "ao_query_finish_kernel", "layers_kernel<false, false>", "layers_kernel<true, false>", "layers_kernel<true, true>", "views_count_kernel", "views_scan_sums_kernel", "views_order_kernel",
                "views_scatter_kernel", "views_resize_kernel", "ao_mask_kernel<1", "ao_mask_kernel<2", "ao_directional_finish_kernel<1",
-               "ao_directional_finish_kernel<2", "ao_rays_kernel<1", "ao_rays_kernel<2")
+               "ao_directional_finish_kernel<2", "ao_rays_kernel<1", "ao_rays_kernel<2",
+               "refit_leaves_kernel", "refit_inner_kernel")  # vertex updates (kernels/refit.hip.h): a spill there is memory traffic per record
     # the directional occlusion queries' walk is ao_query_kernel's with another tail (kernels/directional.hip.h): it must keep
     # that kernel's occupancy, 8 waves per SIMD -- a tail that needs more live state than the old one shows here
     full_occupancy = ("ao_mask_kernel<1", "ao_mask_kernel<2")
