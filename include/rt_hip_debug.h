@@ -133,6 +133,11 @@ int rt_debug_refit_schedule(const rt_scene *s, uint32_t group_nodes, int packed_
 int rt_debug_record_counts(const rt_host *h, uint32_t *nodes, uint32_t *leaves);
 int rt_debug_download_records(rt_host *h, void *nodes_out, void *tris_out, void *shade_out);
 
+/* Device-side builds (rt_hip_build.h): where the last build's time went, in ms -- the topology's kernels (keys, sort, shape,
+ * layout; HIP events), the records' and boxes' kernels (HIP events), and the host's step between them: the schedule of the
+ * inner boxes made from the downloaded skips and copied to the device (wall clock).  Zeros before the first build. */
+int rt_debug_last_build_times(rt_host *h, float ms3[3]);
+
 #ifdef __cplusplus
 }
 #endif

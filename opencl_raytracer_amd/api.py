@@ -254,6 +254,13 @@ _SIGNATURES = {
     "rt_update_vertices_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rt_scene_refit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "rt_last_update_ms": (C.c_float, [C.c_void_p]),
+    # include/rt_hip_build.h
+    "rt_build_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "rt_build_scene_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rt_built_faces": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_scene_build_lbvh": (C.c_int, [C.c_void_p]),
+    "rt_last_build_ms": (C.c_float, [C.c_void_p]),
+    "rt_debug_last_build_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "rt_debug_set_refit_group": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rt_debug_refit_schedule": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
@@ -534,6 +541,13 @@ class Scene:
 
     def build_bvh(self, method: int = 0) -> "Scene":
         _check(load_library().rt_scene_build_bvh(self._h, int(method)))
+        return self
+
+    def build_lbvh(self) -> "Scene":
+        """The tree a device-side build makes (include/rt_hip_build.h, rt_scene_build_lbvh), on the CPU: Morton keys of the
+        leaf boxes' centres, the stable order by key, the binary radix tree over them in pre-order, boxes by the refit rule.
+        nodes, aabbs, triangles and sorted_faces as build_bvh leaves them; upload_scene takes the scene like any other."""
+        _check(load_library().rt_scene_build_lbvh(self._h))
         return self
 
     @property
@@ -1073,6 +1087,71 @@ class Host:
     def last_update_ms(self) -> float:
         """HIP-event time of the last update_vertices' kernels, ms (0.0 before the first)."""
         return float(load_library().rt_last_update_ms(self._h))
+
+    # ---- device-side builds (include/rt_hip_build.h) ----
+    def build_scene(self, vertices, faces, vnormals=None) -> None:
+        """Builds the scene ON the device from triangles (rt_build_scene): `vertices` (V, 3) or (V, 4) float32, `faces`
+        (F, 3) vertex ids, `vnormals` like vertices.  The new scene replaces the host's (or comes first); every query,
+        render_layers, render_views and update_vertices work on it, render() raises RtError -4 until the next upload;
+        `leaf` indices count in the build's order: face_of_leaf.  numpy arrays (blocking; vnormals None: computed on the CPU
+        as Scene.from_arrays does; refuses a face index >= V and coordinates that are not finite or exceed 1e37), or torch
+        tensors on the host's GPU (faces int32 or int64; vnormals required), enqueued on torch.cuda.current_stream() -- the
+        call waits for it once; a face index out of range is found on the device: RtError -1, the previous scene stays."""
+        given = [vertices, faces] + ([] if vnormals is None else [vnormals])
+        on_device = any(_is_torch(x) for x in given)
+        if on_device and not all(_is_torch(x) for x in given):
+            raise ValueError("vertices, faces and vnormals must all be torch tensors or all numpy arrays")
+        pad = _rays4_torch if on_device else _rays4_numpy
+        v = pad(vertices, "vertices")
+        n = None if vnormals is None else pad(vnormals, "vnormals")
+        if n is not None and (n.shape[0] != v.shape[0] or (on_device and n.device != v.device)):
+            raise ValueError("vertices and vnormals must hold the same number of vertices" + (" on the same device" if on_device else ""))
+        lib = load_library()
+        if on_device:
+            import torch
+
+            if n is None:
+                raise RtError(RT_E_INVALID, "build_scene: the device form needs vnormals (the device does not compute vertex normals)")
+            if faces.dtype not in (torch.int32, torch.int64) or faces.device != v.device:
+                raise ValueError("faces: expected an int32 or int64 tensor on the vertices' device")
+            f = faces.reshape(-1).to(torch.int32).contiguous()  # (the bits of a uint32 id below 2^31)
+            if f.numel() % 3:
+                raise ValueError("faces must hold 3 vertex ids per triangle")
+            current = torch.cuda.current_stream(v.device)
+            _check(lib.rt_build_scene_device(self._h, v.data_ptr(), n.data_ptr(), int(v.shape[0]), f.data_ptr(), f.numel() // 3,
+                                             current.cuda_stream))
+        else:
+            f = np.ascontiguousarray(faces, dtype=np.uint32).reshape(-1)
+            if f.size % 3:
+                raise ValueError("faces must hold 3 vertex ids per triangle")
+            _check(lib.rt_build_scene(self._h, v.ctypes.data, None if n is None else n.ctypes.data, int(v.shape[0]), f.ctypes.data,
+                                      f.size // 3))
+
+    def face_of_leaf(self, leaf=None) -> np.ndarray:
+        """Scene.face_of_leaf for the scene this host built (rt_built_faces): the file-order face a query's `leaf` index
+        stands for; without an argument the whole map.  Leaves of 0xFFFFFFFF (no hit) map to 0xFFFFFFFF.  RtError -4 where
+        the host's scene was uploaded, not built."""
+        lib, leaves = load_library(), C.c_uint32()
+        _check(lib.rt_debug_record_counts(self._h, None, C.byref(leaves)))
+        faces = np.zeros(leaves.value, np.uint32)
+        _check(lib.rt_built_faces(self._h, faces.ctypes.data))
+        if leaf is None:
+            return faces
+        leaf = np.asarray(leaf, dtype=np.uint32)
+        miss = leaf == 0xFFFFFFFF
+        return np.where(miss, np.uint32(0xFFFFFFFF), faces[np.where(miss, 0, leaf)]).astype(np.uint32)
+
+    @property
+    def last_build_ms(self) -> float:
+        """HIP-event time of the last build_scene's kernels, ms (0.0 before the first)."""
+        return float(load_library().rt_last_build_ms(self._h))
+
+    def last_build_times(self) -> dict:
+        """Where the last build's time went (include/rt_hip_debug.h, rt_debug_last_build_times), ms: the topology's kernels,
+        the records' kernels, the host's schedule step between them."""
+        ms = (C.c_float * 3)()
+        _check(load_library().rt_debug_last_build_times(self._h, ms))
+        return {"topology_ms": float(ms[0]), "records_ms": float(ms[1]), "schedule_host_ms": float(ms[2])}
 
     def set_refit_group(self, nodes: int) -> None:
         """Test aid (include/rt_hip_debug.h, rt_debug_set_refit_group): at most `nodes` inner nodes per group of an update's

@@ -1,5 +1,6 @@
 // c_api.cc -- the extern "C" boundary declared in include/rt_hip.h (the seam), rt_hip_ring.h (streams of frames, several GPUs), rt_hip_debug.h,
-// rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h.
+// rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h, rt_hip_build.h and
+// rt_hip_camera.h.
 #include "../../include/rt_hip.h"
 #include "../../include/rt_hip_ao.h"
 #include "../../include/rt_hip_camera.h"
@@ -10,6 +11,7 @@
 #include "../../include/rt_hip_query.h"
 #include "../../include/rt_hip_views.h"
 #include "../../include/rt_hip_update.h"
+#include "../../include/rt_hip_build.h"
 
 #include <algorithm>
 #include <hip/hip_runtime.h>
@@ -27,6 +29,7 @@
 #include "device_renderer.h"
 #include "frame_ring.h"
 #include "hip_host.h"
+#include "lbvh.h"
 #include "mesh.h"
 #include "ray_query.h"
 #include "ray_tracer.h"
@@ -1230,6 +1233,106 @@ float rt_last_update_ms(const rt_host *h) {
 		fail_from_exception();
 		return 0.0f;
 	}
+}
+
+// ---- rt_hip_build.h ----
+namespace {
+
+int build_precheck(const rt_host *h, const float *vertices4, const uint32_t *faces, uint32_t num_vertices, uint32_t num_faces) {
+	if (!h)
+		return fail(RT_E_INVALID, "null host");
+	if (!h->owned)
+		return fail(RT_E_STATE, "builds are not available on the hosts of a frame ring: their scene on the device is shared (one copy, many readers)");
+	if (!vertices4 || !faces)
+		return fail(RT_E_INVALID, "build: null vertex or face array");
+	if (num_faces == 0 || num_vertices == 0)
+		return fail(RT_E_INVALID, "build: no faces, or no vertices");
+	if (num_faces >= (1u << 25))
+		return fail(RT_E_INVALID, "build: scene too large for 32-bit device offsets");
+	return RT_OK;
+}
+
+}  // namespace
+
+int rt_build_scene(rt_host *h, const float *vertices4, const float *vnormals4, uint32_t num_vertices, const uint32_t *faces, uint32_t num_faces) {
+	const int rc = build_precheck(h, vertices4, faces, num_vertices, num_faces);
+	if (rc != RT_OK)
+		return rc;
+	return guarded([&] {
+		Mesh mesh;  // (without normals: the CPU's routine over the same faces, as rt_scene_from_arrays)
+		if (!vnormals4) {
+			for (size_t i = 0; i < (size_t) num_faces * 3; ++i)
+				if (faces[i] >= num_vertices)
+					throw std::invalid_argument("build: face references a vertex out of range (nothing was written)");
+			mesh.vertices.resize(num_vertices);
+			for (uint32_t i = 0; i < num_vertices; ++i)
+				mesh.vertices[i] = Vec3f(vertices4[4 * i], vertices4[4 * i + 1], vertices4[4 * i + 2]);
+			mesh.faces.assign(faces, faces + 3 * (size_t) num_faces);
+			compute_vertex_normals(&mesh);
+		}
+		queries_of(h).buildHost(vertices4, vnormals4 ? vnormals4 : &mesh.vnormals.data()->x, num_vertices, faces, num_faces);
+	});
+}
+
+int rt_build_scene_device(rt_host *h, const float *vertices4, const float *vnormals4, uint32_t num_vertices, const uint32_t *faces,
+                          uint32_t num_faces, void *hip_stream) {
+	const int rc = build_precheck(h, vertices4, faces, num_vertices, num_faces);
+	if (rc != RT_OK)
+		return rc;
+	if (!vnormals4)
+		return fail(RT_E_INVALID, "build: null normal array (the device does not compute vertex normals: rt_hip_build.h)");
+	if (!aligned({ vertices4, vnormals4 }, 16) || !aligned({ faces }, 4))
+		return fail(RT_E_INVALID, "device vertex and normal arrays must be 16-byte aligned, the face array 4-byte aligned");
+	return guarded([&] { queries_of(h).buildDevice(vertices4, vnormals4, num_vertices, faces, num_faces, hip_stream); });
+}
+
+int rt_built_faces(const rt_host *h, uint32_t *face_of_leaf) {
+	if (!h || !face_of_leaf)
+		return fail(RT_E_INVALID, "null argument");
+	if (!h->dev->sceneReady() || !h->dev->deviceScene() || h->dev->deviceScene()->builtFaces().empty())
+		return fail(RT_E_STATE, "the host's scene was not built on the device (an uploaded scene's leaf order is rt_scene_triangles)");
+	const std::vector<uint32_t> &faces = h->dev->deviceScene()->builtFaces();
+	std::copy(faces.begin(), faces.end(), face_of_leaf);
+	return RT_OK;
+}
+
+int rt_scene_build_lbvh(rt_scene *s) {
+	if (!s)
+		return fail(RT_E_INVALID, "null scene");
+	return guarded([&] {
+		s->built = false;
+		// The tree of rt_hip_build.h, steps 1-6: leaf boxes by the refit rule, the root box over them, 30-bit Morton keys of the
+		// boxes' centres, the stable order by key, the binary radix tree over key << 32 | leaf, laid out in pre-order (lbvh.h) --
+		// and step 8: every box by the refit rule.
+		ocrt::LbvhTree tree = ocrt::lbvh_build(s->mesh.faces, s->mesh.vertices);
+		s->bvh = BVH();
+		s->bvh.nodes = std::move(tree.nodes);
+		s->bvh.triangles = std::move(tree.triangles);
+		s->bvh.aabbs.assign(2 * s->bvh.nodes.size(), Vec3f());
+		s->sorted_faces = sort_faces_by_leaf_order(s->mesh, s->bvh);
+		ocrt::refit_boxes(s->bvh.nodes, s->sorted_faces, s->mesh.vertices, s->bvh.aabbs);
+		s->built = true;
+	});
+}
+
+float rt_last_build_ms(const rt_host *h) {
+	if (!h || !h->queries)
+		return 0.0f;
+	try {
+		return h->queries->lastBuildMs();
+	} catch (...) {
+		fail_from_exception();
+		return 0.0f;
+	}
+}
+
+int rt_debug_last_build_times(rt_host *h, float ms3[3]) {
+	if (!h || !ms3)
+		return fail(RT_E_INVALID, "null argument");
+	ms3[0] = ms3[1] = ms3[2] = 0.0f;
+	if (!h->queries)
+		return RT_OK;
+	return guarded([&] { h->queries->lastBuildTimes(ms3); });
 }
 
 int rt_debug_set_refit_group(rt_host *h, uint32_t nodes) {

@@ -212,8 +212,33 @@ DeviceScene *DeviceRenderer::updatableScene(const char **why) {
 
 void DeviceRenderer::requireFramePath(const char *what) const {
 	if (scene_updated)
-		throw std::logic_error(std::string(what) + " after a vertex update: the walk array, the hit list and the claim orders are the old positions' until the "
-		                                           "next upload (render_layers and render_views draw an updated scene)");
+		throw std::logic_error(std::string(what) + " after a vertex update or a device-side build: the walk array, the hit list and the claim orders are "
+		                                           "the last upload's until the next one (render_layers and render_views draw an updated or built scene)");
+}
+
+bool DeviceRenderer::sceneIsShared() const {
+	if (!scene_on_device)
+		return false;
+	return !scene_of_my_own || scene_of_my_own.get() != scene_on_device.get() || scene_of_my_own.use_count() != 2;
+}
+
+void DeviceRenderer::adoptBuilt(std::shared_ptr<DeviceScene> scene) {
+	if (!scene || scene->device() != device)
+		throw std::invalid_argument("the scene lives on another device than the renderer");
+	if (!scene->servesOptions(opts))
+		throw std::invalid_argument("the scene on the device was made for other ambient-occlusion options than the renderer's");
+	useDevice();
+	synchronize();
+	freeScene();
+	kp = make_kernel_params(rt, scene->nodeCount(), scene->triCount(), scene->aoDirs(), part, &scene->facts(), pose_set ? &pose : nullptr);
+	kp.shared_device = device_share > 1u ? 1 : 0;
+	kp.entry_stride = 1u;
+	scene_beyond_caches = scene->bytes() > BIG_SCENE_BYTES;
+	scene_on_device = scene;
+	scene_of_my_own = std::move(scene);
+	scene_ready = true;
+	scene_updated = true;  // (nothing was prepared for the frame path: closed until the next upload)
+	++scene_version;
 }
 
 std::string DeviceRenderer::deviceName() const {

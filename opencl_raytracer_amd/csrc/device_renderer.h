@@ -78,8 +78,28 @@ class DeviceScene {
 		uint32_t refitPasses() const { return (uint32_t) (refit_pass_first.empty() ? 0 : refit_pass_first.size() - 1); }
 		size_t refitBytes() const { return refit_bytes; }  // the allocation of the first update (0 before it)
 
+		// Device-side builds (include/rt_hip_build.h; kernels/build.hip.h, build_sort.hip, lbvh.h): a scene made ON the device
+		// from `num_faces` faces (three vertex ids each) over `num_vertices` vertices and normals (float4 each), all in device
+		// memory -- the exact node records, the leaf records, the shading normals and the options' direction table; no padded
+		// walk array.  Enqueued on `stream`, which is waited for ONCE: the skips come back to the host (4 bytes per node) for
+		// the schedule of the inner boxes, and with them the flag a face index out of range raised (std::invalid_argument
+		// then; nothing was read out of bounds) and the face of every leaf.  The scene keeps the leaf-ordered faces, the
+		// leaf -> node map and the schedule: its first updateVertices prepares nothing.  `scratch`: buildScratchBytes(num_faces)
+		// bytes of the caller's, free again when `stream` has run.  `events`: four events recorded around the two runs of
+		// launches, before and after the wait; `host_ms`: what the download and the schedule took on the host.
+		static size_t buildScratchBytes(uint32_t num_faces);
+		static std::shared_ptr<DeviceScene> build(int device, const RayTracer::Options &options, const float *vertices4, const float *vnormals4,
+		                                          uint32_t num_vertices, const uint32_t *faces, uint32_t num_faces, uint32_t group_nodes,
+		                                          void *scratch, void *stream, void *const events[4], float *host_ms);
+		// the file-order face of every leaf of a built scene (empty: the scene was uploaded)
+		const std::vector<uint32_t> &builtFaces() const { return built_faces; }
+
 	private:
 		DeviceScene() = default;
+		std::vector<float> takeOptions(const RayTracer::Options &options);  // what of the options a scene holds; returns the direction table
+		void finishTable(const RayTracer::Options &options, size_t table_bytes);
+		void uploadSchedule(uint32_t wanted);
+		std::vector<uint32_t> built_faces;
 		// host side of the vertex updates: kept from the upload on
 		std::shared_ptr<const std::vector<uint32_t>> leaf_faces;  // three vertex ids per leaf
 		std::vector<uint32_t> node_skips, leaf_nodes;             // the tree's shape; the node of every leaf
@@ -137,6 +157,13 @@ class DeviceRenderer {
 		// the exact records and go on.
 		void markSceneUpdated() { scene_updated = true; }
 		bool sceneUpdated() const { return scene_updated; }
+		// Device-side builds (include/rt_hip_build.h): `scene`, made by DeviceScene::build on this renderer's device for its
+		// options, takes the place of whatever scene the renderer had -- its own, for writing.  It has no padded walk array and
+		// nothing an upload prepares for the renderer's one view: the frame path is closed as after an update, until the
+		// next upload.  sceneIsShared(): the renderer's scene has other readers (a ring's hosts): no build may replace it.
+		void adoptBuilt(std::shared_ptr<DeviceScene> scene);
+		bool sceneIsShared() const;
+		const RayTracer::Options &options() const { return opts; }
 		// (include/rt_hip_debug.h) the schedule's group size for this renderer's updates; 0: the default
 		void setRefitGroup(uint32_t nodes) { refit_group = nodes; }
 		uint32_t refitGroup() const { return refit_group; }
@@ -387,5 +414,13 @@ void launch_refit_leaves(const void *faces, const void *leaf_nodes, const void *
                          void *nodes, uint32_t leaves, void *stream);
 void launch_refit_inner(const void *entries, const void *children, const void *groups, void *nodes, uint32_t first_group, uint32_t groups_in_pass,
                         void *stream);
+// Device-side builds (kernels/build.hip.h; BuildBuffers: device_types.h)
+uint32_t build_partials(uint32_t faces);
+void launch_build_keys(const BuildBuffers &b, void *stream);
+void launch_build_tree(const BuildBuffers &b, void *stream);
+// build_sort.hip
+size_t build_sort_bytes(uint32_t pairs);
+void launch_build_sort(void *temporary, size_t temporary_bytes, const void *keys_in, void *keys_out, const void *ids_in, void *ids_out,
+                       uint32_t pairs, void *stream);
 
 }  // namespace ocrt

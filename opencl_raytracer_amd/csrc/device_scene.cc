@@ -1,5 +1,6 @@
 // device_scene.cc -- ocrt::DeviceScene (device_renderer.h): one uploaded scene on one GPU, shared by every render host of
 // that GPU.
+#include <limits>
 #include <mutex>
 
 #include "device_internal.h"
@@ -17,32 +18,49 @@ int reserved_device = -1;
 size_t round_up(size_t bytes) { return (bytes + 255) & ~(size_t) 255; }
 }  // namespace
 
-std::shared_ptr<DeviceScene> DeviceScene::create(int device, const PackedScene &scene, const RayTracer::Options &opts, bool for_a_stream,
-                                                 const float *eye) {
-	UploadClock clock;
-	OCRT_HIP(hipSetDevice(device));
-	std::shared_ptr<DeviceScene> out(new DeviceScene());
-	out->device_index = device;
+std::vector<float> DeviceScene::takeOptions(const RayTracer::Options &opts) {
 	std::vector<float> table;
-	out->ao_on = opts.enableAO && opts.aoNumSamples > 0;
-	out->ao_method = (int) opts.aoMethod;
-	out->ao_samples = opts.aoNumSamples;
-	out->ao_alpha_min = opts.aoAlphaMin;
-	out->ao_alpha_max = opts.aoAlphaMax;
-	if (out->ao_on) {
+	ao_on = opts.enableAO && opts.aoNumSamples > 0;
+	ao_method = (int) opts.aoMethod;
+	ao_samples = opts.aoNumSamples;
+	ao_alpha_min = opts.aoAlphaMin;
+	ao_alpha_max = opts.aoAlphaMax;
+	if (ao_on) {
 		if (opts.aoMethod == RayTracer::AmbientOcclusionMethod::UNIFORM) {
 			// The reference's order, ring by ring.  (The occlusion count of a hit is a sum over the directions, so the order is
 			// free: while a workgroup's four waves took FIXED quarters of a tile's directions the table was dealt round-robin
 			// to the quarters so that they cost about the same; with the claim's cursor -- kernels.hip, ao_kernel -- the waves
 			// balance themselves, and neighbouring directions cast at the same time are worth 0.5-2 %.)
 			table = uniform_ao_table(opts.aoNumSamples, opts.aoAlphaMin, opts.aoAlphaMax);
-			out->ao_dirs = (uint32_t) (table.size() / 4);
+			ao_dirs = (uint32_t) (table.size() / 4);
 		} else {
 			// RANDOM casts the normal ray plus AO_NUM_SAMPLES + 1 random ones (reference :260-275)
-			out->ao_dirs = opts.aoNumSamples + 2;
+			ao_dirs = opts.aoNumSamples + 2;
 		}
 	}
-	out->walk_distance = out->ao_on ? kernel_float(opts.aoMaxDistance) : 0.0f;
+	walk_distance = ao_on ? kernel_float(opts.aoMaxDistance) : 0.0f;
+	return table;
+}
+
+void DeviceScene::finishTable(const RayTracer::Options &opts, size_t table_bytes) {
+#ifdef OCRT_OCML_BUILTINS
+	// (test-only build: the table as the reference kernel's own float trigonometry makes it on this device, kernels.hip)
+	if (table_bytes && opts.aoMethod == RayTracer::AmbientOcclusionMethod::UNIFORM &&
+	    ocml_ao_table(d_ao, opts.aoNumSamples, opts.aoAlphaMin, opts.aoAlphaMax, ao_dirs) != ao_dirs)
+		throw DeviceError("the device's trigonometry counts another number of ambient-occlusion directions than the host's");
+#else
+	(void) opts;
+	(void) table_bytes;
+#endif
+}
+
+std::shared_ptr<DeviceScene> DeviceScene::create(int device, const PackedScene &scene, const RayTracer::Options &opts, bool for_a_stream,
+                                                 const float *eye) {
+	UploadClock clock;
+	OCRT_HIP(hipSetDevice(device));
+	std::shared_ptr<DeviceScene> out(new DeviceScene());
+	out->device_index = device;
+	const std::vector<float> table = out->takeOptions(opts);
 	if (eye)
 		for (unsigned k = 0; k < 3; ++k)
 			out->walk_eye[k] = eye[k];
@@ -103,12 +121,7 @@ std::shared_ptr<DeviceScene> DeviceScene::create(int device, const PackedScene &
 	if (ao_bytes)
 		OCRT_HIP(hipMemcpy(out->d_ao, table.data(), ao_bytes, hipMemcpyHostToDevice));
 	OCRT_HIP(hipDeviceSynchronize());
-#ifdef OCRT_OCML_BUILTINS
-	// (test-only build: the table as the reference kernel's own float trigonometry makes it on this device, kernels.hip)
-	if (ao_bytes && opts.aoMethod == RayTracer::AmbientOcclusionMethod::UNIFORM &&
-	    ocml_ao_table(out->d_ao, opts.aoNumSamples, opts.aoAlphaMin, opts.aoAlphaMax, out->ao_dirs) != out->ao_dirs)
-		throw DeviceError("the device's trigonometry counts another number of ambient-occlusion directions than the host's");
-#endif
+	out->finishTable(opts, ao_bytes);
 	clock.mark("copies of walk array, nodes, leaf records, normals, table");
 	out->device_bytes = nodes_bytes + walk_bytes + tris_bytes + shade_bytes + ao_bytes;
 	// What a vertex update will need, kept on the host (one sweep over the node records; the faces are shared, not copied):
@@ -136,7 +149,9 @@ DeviceScene::~DeviceScene() {
 
 // The first update's uploads (faces, leaf -> node map) and the schedule for `group_nodes`, blocking: they are made once.
 void DeviceScene::prepareRefit(uint32_t group_nodes) {
-	if (!leaf_faces || leaf_faces->size() != (size_t) tri_count * 3 || leaf_nodes.size() != tri_count || node_skips.size() != node_count)
+	// (a scene built on the device has faces and map there from the start, and nothing of them on the host)
+	if (node_skips.size() != node_count ||
+	    (!refit_arena && (!leaf_faces || leaf_faces->size() != (size_t) tri_count * 3 || leaf_nodes.size() != tri_count)))
 		throw std::logic_error("vertex update: the scene was uploaded without its faces");
 	const uint32_t wanted = group_nodes == 0 ? REFIT_DEFAULT_GROUP : group_nodes < REFIT_MAX_GROUP ? group_nodes : REFIT_MAX_GROUP;
 	if (!refit_arena) {
@@ -150,6 +165,11 @@ void DeviceScene::prepareRefit(uint32_t group_nodes) {
 	}
 	if (refit_group_nodes == wanted)
 		return;
+	uploadSchedule(wanted);
+}
+
+// The schedule for groups of `wanted` nodes, made of node_skips and copied to the device (blocking).
+void DeviceScene::uploadSchedule(uint32_t wanted) {
 	const RefitSchedule schedule = make_refit_schedule(node_skips, wanted);
 	const size_t entries_bytes = schedule.entries.size() * sizeof(uint32_t), children_bytes = schedule.children.size() * sizeof(uint32_t),
 	             groups_bytes = schedule.groups.size() * sizeof(uint32_t);
@@ -172,6 +192,139 @@ void DeviceScene::prepareRefit(uint32_t group_nodes) {
 		OCRT_HIP(hipMemcpy(d_groups, schedule.groups.data(), groups_bytes, hipMemcpyHostToDevice));
 	refit_pass_first = schedule.pass_first;
 	refit_group_nodes = wanted;
+}
+
+namespace {
+// Where the pieces of a build's scratch lie (each on a 256-byte boundary).
+struct BuildScratch {
+	size_t centres, partials, root, flag, keys, ids, sorted_keys, sorted_ids, ranges, inner_links, leaf_links, skips, sort, sort_bytes, bytes;
+};
+BuildScratch build_scratch(uint32_t faces) {
+	BuildScratch at{};
+	size_t end = 0;
+	auto take = [&](size_t bytes) {
+		const size_t p = end;
+		end += round_up(bytes ? bytes : 1);
+		return p;
+	};
+	const size_t n = faces;
+	at.centres = take(n * 16);
+	at.partials = take((size_t) build_partials(faces) * 32);
+	at.root = take(32);
+	at.flag = take(4);
+	at.keys = take(n * 4);
+	at.ids = take(n * 4);
+	at.sorted_keys = take(n * 4);
+	at.sorted_ids = take(n * 4);
+	at.ranges = take(n * 8);
+	at.inner_links = take(n * 4);
+	at.leaf_links = take(n * 4);
+	at.skips = take(n * 8);
+	at.sort_bytes = build_sort_bytes(faces);
+	at.sort = take(at.sort_bytes);
+	at.bytes = end;
+	return at;
+}
+}  // namespace
+
+size_t DeviceScene::buildScratchBytes(uint32_t num_faces) { return build_scratch(num_faces).bytes; }
+
+std::shared_ptr<DeviceScene> DeviceScene::build(int device, const RayTracer::Options &opts, const float *vertices4, const float *vnormals4,
+                                                uint32_t num_vertices, const uint32_t *faces, uint32_t num_faces, uint32_t group_nodes, void *scratch,
+                                                void *stream, void *const events[4], float *host_ms) {
+	if (!vertices4 || !vnormals4 || !faces || !scratch)
+		throw std::invalid_argument("build: null vertex, normal or face array");
+	if (num_faces == 0 || num_vertices == 0)
+		throw std::invalid_argument("build: no faces, or no vertices");
+	if (num_faces >= (1u << 25))  // (pack_scene's bound: the kernels address leaf records with 32-bit byte offsets)
+		throw std::invalid_argument("build: scene too large for 32-bit device offsets");
+	OCRT_HIP(hipSetDevice(device));
+	hipStream_t s = (hipStream_t) stream;
+	std::shared_ptr<DeviceScene> out(new DeviceScene());
+	out->device_index = device;
+	const std::vector<float> table = out->takeOptions(opts);
+	out->scene_facts_ = SceneFacts{};  // (no padded walk array: every walk takes the exact form)
+	out->scene_facts_.prune_margin = std::numeric_limits<float>::infinity();
+	out->node_count = 2u * num_faces - 1u;
+	out->tri_count = num_faces;
+	out->vertex_count = num_vertices;
+	const size_t nodes_bytes = (size_t) out->node_count * sizeof(NodeRec), tris_bytes = (size_t) num_faces * sizeof(TriRec),
+	             shade_bytes = (size_t) num_faces * sizeof(ShadeRec), ao_bytes = table.size() * sizeof(float);
+	// one allocation for the four arrays, as an upload's (a zero record behind the nodes: the shared walk fetches a node with
+	// its successor), one for the leaf-ordered faces and the leaf -> node map, as a first update's
+	out->arena = device_alloc(round_up(nodes_bytes + sizeof(NodeRec)) + round_up(tris_bytes) + round_up(shade_bytes) + round_up(ao_bytes) + 256);
+	char *at = (char *) out->arena;
+	auto take = [&](size_t bytes) {
+		void *p = at;
+		at += round_up(bytes);
+		return p;
+	};
+	out->d_nodes = take(nodes_bytes + sizeof(NodeRec));
+	out->d_tris = take(tris_bytes);
+	out->d_shade = take(shade_bytes);
+	out->d_ao = take(ao_bytes ? ao_bytes : 1);
+	out->device_bytes = nodes_bytes + tris_bytes + shade_bytes + ao_bytes;
+	const size_t faces_bytes = (size_t) num_faces * 3 * sizeof(uint32_t), map_bytes = (size_t) num_faces * sizeof(uint32_t);
+	out->refit_arena = device_alloc(round_up(faces_bytes) + round_up(map_bytes));
+	out->d_faces = out->refit_arena;
+	out->d_leaf_nodes = (char *) out->refit_arena + round_up(faces_bytes);
+	out->refit_bytes = faces_bytes + map_bytes;
+
+	const BuildScratch where = build_scratch(num_faces);
+	char *const base = (char *) scratch;
+	BuildBuffers b{};
+	b.faces = faces;
+	b.vertices = vertices4;
+	b.num_faces = num_faces;
+	b.num_vertices = num_vertices;
+	b.centres = base + where.centres;
+	b.partials = base + where.partials;
+	b.root = base + where.root;
+	b.flag = base + where.flag;
+	b.keys = base + where.keys;
+	b.ids = base + where.ids;
+	b.sorted_keys = base + where.sorted_keys;
+	b.sorted_ids = base + where.sorted_ids;
+	b.leaf_faces = out->d_faces;
+	b.ranges = base + where.ranges;
+	b.inner_links = base + where.inner_links;
+	b.leaf_links = base + where.leaf_links;
+	b.nodes = out->d_nodes;
+	b.skips = base + where.skips;
+	b.leaf_node = out->d_leaf_nodes;
+	// the topology: keys, the sort, shape and layout
+	OCRT_HIP(hipEventRecord((hipEvent_t) events[0], s));
+	OCRT_HIP(hipMemsetAsync(b.flag, 0, sizeof(uint32_t), s));
+	OCRT_HIP(hipMemsetAsync(b.skips, 0, (size_t) out->node_count * sizeof(uint32_t), s));
+	OCRT_HIP(hipMemsetAsync((char *) out->d_nodes + nodes_bytes, 0, sizeof(NodeRec), s));
+	OCRT_HIP(hipMemsetAsync(out->d_leaf_nodes, 0, map_bytes, s));  // (every entry is written by the layout; no launch ever reads an unwritten one)
+	launch_build_keys(b, s);
+	launch_build_sort(base + where.sort, where.sort_bytes, b.keys, b.sorted_keys, b.ids, b.sorted_ids, num_faces, s);
+	launch_build_tree(b, s);
+	OCRT_HIP(hipGetLastError());
+	OCRT_HIP(hipEventRecord((hipEvent_t) events[1], s));
+	// the one wait: the skips for the schedule, the flag, the face of every leaf
+	uint32_t flag = 0;
+	out->node_skips.resize(out->node_count);
+	out->built_faces.resize(num_faces);
+	OCRT_HIP(hipMemcpyAsync(&flag, b.flag, sizeof flag, hipMemcpyDeviceToHost, s));
+	OCRT_HIP(hipMemcpyAsync(out->node_skips.data(), b.skips, (size_t) out->node_count * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+	OCRT_HIP(hipMemcpyAsync(out->built_faces.data(), b.sorted_ids, (size_t) num_faces * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+	if (ao_bytes)
+		OCRT_HIP(hipMemcpyAsync(out->d_ao, table.data(), ao_bytes, hipMemcpyHostToDevice, s));
+	OCRT_HIP(hipStreamSynchronize(s));
+	if (flag)
+		throw std::invalid_argument("build: a face references a vertex out of range (nothing was read through it; the host's scene stays as it was)");
+	const auto before = std::chrono::steady_clock::now();
+	out->uploadSchedule(group_nodes == 0 ? REFIT_DEFAULT_GROUP : group_nodes < REFIT_MAX_GROUP ? group_nodes : REFIT_MAX_GROUP);
+	if (host_ms)
+		*host_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - before).count();
+	out->finishTable(opts, ao_bytes);
+	// the records and the boxes, as an update makes them
+	OCRT_HIP(hipEventRecord((hipEvent_t) events[2], s));
+	out->updateVertices(vertices4, vnormals4, group_nodes, s);
+	OCRT_HIP(hipEventRecord((hipEvent_t) events[3], s));
+	return out;
 }
 
 void DeviceScene::updateVertices(const float *vertices4, const float *vnormals4, uint32_t group_nodes, void *stream) {

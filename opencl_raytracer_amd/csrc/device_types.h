@@ -173,6 +173,14 @@ struct SceneBuffers {  // device pointers of one uploaded scene
 	const void *ao_table;    // float4[ao_dirs] (UNIFORM)
 };
 
+// What the launches of a device-side build work on (kernels/build.hip.h, BuildArgs: every array's size is given there).
+struct BuildBuffers {
+	const void *faces, *vertices;
+	uint32_t num_faces, num_vertices;
+	void *centres, *partials, *root, *flag, *keys, *ids, *sorted_keys, *sorted_ids, *leaf_faces, *ranges, *inner_links, *leaf_links, *nodes,
+	    *skips, *leaf_node;
+};
+
 // Outputs of the ray queries (ray_query.h) as their launchers take them: device pointers, null = not written.
 // What a closest-hit query and a multi-hit query both write, by ray index or by ray and slot (slot j of ray i at i * k + j):
 struct RecordOutputs {

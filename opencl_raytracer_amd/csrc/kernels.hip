@@ -43,6 +43,10 @@
 //                   (a layers call) or the hit ones, listed (a views call: views_count_kernel, views_scan_sums_kernel,
 //                   views_order_kernel make their number and order) --, views_scatter_kernel writes their factors and
 //                   products, views_resize_kernel every view's 8-bit image (kernels/views.hip.h).
+//   (scenes)        refit_leaves_kernel / refit_inner_kernel make the records and boxes of a scene again from new positions
+//                   (kernels/refit.hip.h, include/rt_hip_update.h); build_boxes_kernel, build_root_kernel, build_keys_kernel,
+//                   build_tree_kernel and build_layout_kernel make a scene's tree from triangles, around a sort that lives in
+//                   build_sort.hip (kernels/build.hip.h, include/rt_hip_build.h).
 //   (on demand)     entry_kernel: the walk intervals, once per upload; occluded_sum_kernel: the frame's occlusion
 //                   total when the statistics are asked for; resize_kernel: a box filter on its own.
 // Why not one fused launch (it was, see profiles/r01_notes.md): cost per tile
@@ -67,6 +71,7 @@
 
 #include "device_types.h"
 #include "exact_reciprocal.h"
+#include "lbvh.h"
 #include "tri_predicate.h"
 
 #include "kernels/common.hip.h"
@@ -82,6 +87,7 @@
 #include "kernels/layers.hip.h"
 #include "kernels/views.hip.h"
 #include "kernels/refit.hip.h"
+#include "kernels/build.hip.h"
 
 
 namespace ocrt {
@@ -603,6 +609,57 @@ void launch_refit_inner(const void *entries, const void *children, const void *g
 	a.nodes = (float *) nodes;
 	a.first_group = first_group;
 	hipLaunchKernelGGL(refit_inner_kernel, dim3(groups_in_pass), dim3(REFIT_INNER_LANES), 0, (hipStream_t) stream, a);
+}
+
+// Device-side scene builds (kernels/build.hip.h, include/rt_hip_build.h): the keys of `b.num_faces` faces and their ids, the
+// pairs the sort takes (build_sort.hip) ...
+namespace {
+BuildArgs build_args(const BuildBuffers &b) {
+	BuildArgs a{};
+	a.faces = (const uint32_t *) b.faces;
+	a.vertices = (const float4 *) b.vertices;
+	a.num_faces = b.num_faces;
+	a.num_vertices = b.num_vertices;
+	a.centres = (float4 *) b.centres;
+	a.partials = (float4 *) b.partials;
+	a.root = (float4 *) b.root;
+	a.flag = (uint32_t *) b.flag;
+	a.keys = (uint32_t *) b.keys;
+	a.ids = (uint32_t *) b.ids;
+	a.sorted_keys = (const uint32_t *) b.sorted_keys;
+	a.sorted_ids = (const uint32_t *) b.sorted_ids;
+	a.leaf_faces = (uint32_t *) b.leaf_faces;
+	a.ranges = (uint2 *) b.ranges;
+	a.inner_links = (uint32_t *) b.inner_links;
+	a.leaf_links = (uint32_t *) b.leaf_links;
+	a.nodes = (uint4 *) b.nodes;
+	a.skips = (uint32_t *) b.skips;
+	a.leaf_node = (uint32_t *) b.leaf_node;
+	return a;
+}
+}  // namespace
+
+uint32_t build_partials(uint32_t faces) { return (faces + BUILD_LANES - 1u) / BUILD_LANES; }
+
+void launch_build_keys(const BuildBuffers &b, void *stream) {
+	if (b.num_faces == 0 || b.num_vertices == 0)
+		return;
+	const BuildArgs a = build_args(b);
+	const uint32_t groups = build_partials(b.num_faces);
+	hipLaunchKernelGGL(build_boxes_kernel, dim3(groups), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
+	hipLaunchKernelGGL(build_root_kernel, dim3(1), dim3(BUILD_LANES), 0, (hipStream_t) stream, a, groups);
+	hipLaunchKernelGGL(build_keys_kernel, dim3(groups), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
+}
+
+// ... and, of the sorted pairs, the faces in leaf order, the tree's shape and its pre-order layout: `skip` and `leaf` words of
+// every node record, the leaf -> node map, the skips alone.
+void launch_build_tree(const BuildBuffers &b, void *stream) {
+	if (b.num_faces == 0 || b.num_vertices == 0)
+		return;
+	const BuildArgs a = build_args(b);
+	hipLaunchKernelGGL(build_tree_kernel, dim3(build_partials(b.num_faces)), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
+	const uint32_t nodes = 2u * b.num_faces - 1u;
+	hipLaunchKernelGGL(build_layout_kernel, dim3((nodes + BUILD_LANES - 1u) / BUILD_LANES), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
 }
 
 }  // namespace ocrt

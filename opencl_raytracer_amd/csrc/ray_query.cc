@@ -41,6 +41,8 @@ RayQueries::RayQueries(DeviceRenderer &renderer) : dev(renderer) {
 	OCRT_HIP(hipEventCreate((hipEvent_t *) &ev_update_start));
 	OCRT_HIP(hipEventCreate((hipEvent_t *) &ev_update_stop));
 	OCRT_HIP(hipEventCreateWithFlags((hipEvent_t *) &ev_frames, hipEventDisableTiming));
+	for (void *&ev : ev_build)
+		OCRT_HIP(hipEventCreate((hipEvent_t *) &ev));
 }
 
 RayQueries::~RayQueries() {
@@ -48,8 +50,11 @@ RayQueries::~RayQueries() {
 		return;
 	if (timed)
 		(void) hipEventSynchronize((hipEvent_t) ev_stop);
-	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &ao_rows, &list, &views })
+	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &ao_rows, &list, &views, &build })
 		device_free(scratch->ptr);
+	for (void *ev : ev_build)
+		if (ev)
+			(void) hipEventDestroy((hipEvent_t) ev);
 	if (pinned)
 		(void) hipHostFree(pinned);
 	(void) hipEventDestroy((hipEvent_t) ev_start);
@@ -668,6 +673,83 @@ float RayQueries::lastUpdateMs() {
 		have_update_ms = true;
 	}
 	return last_update_ms;
+}
+
+// A build orders itself as an update does.  Its launches leave the renderer's scene alone -- they write scratch and the new
+// scene's own allocations --, so a refused build changes nothing; an accepted one replaces the scene once its records are
+// enqueued, and the queries after it wait for them by ev_stop.
+void RayQueries::buildDevice(const float *vertices4, const float *vnormals4, uint32_t num_vertices, const uint32_t *faces, uint32_t num_faces,
+                             void *stream) {
+	if (dev.sceneIsShared())
+		throw std::logic_error("build on a host whose scene on the device is shared with other hosts (one copy, many readers: upload a scene of the host's own)");
+	if (!vertices4 || !vnormals4 || !faces)
+		throw std::invalid_argument("build: null vertex, normal or face array (the device does not compute vertex normals)");
+	if (num_faces == 0 || num_vertices == 0)
+		throw std::invalid_argument("build: no faces, or no vertices");
+	if (num_faces >= (1u << 25))
+		throw std::invalid_argument("build: scene too large for 32-bit device offsets");
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
+	if (timed)
+		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	if (s != (hipStream_t) dev.streamHandle()) {
+		OCRT_HIP(hipEventRecord((hipEvent_t) ev_frames, (hipStream_t) dev.streamHandle()));
+		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_frames, 0));
+	}
+	grow(build, DeviceScene::buildScratchBytes(num_faces));
+	build_timed = false;
+	std::shared_ptr<DeviceScene> made = DeviceScene::build(dev.deviceIndex(), dev.options(), vertices4, vnormals4, num_vertices, faces, num_faces,
+	                                                       dev.refitGroup(), build.ptr, s, ev_build, &last_build_ms[2]);
+	build_timed = true;
+	have_build_ms = false;
+	dev.adoptBuilt(std::move(made));  // (waits for the renderer's own stream and lets the old scene go)
+	boxed.reset();
+	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
+	end(Enqueue{ s, nullptr });
+}
+
+void RayQueries::buildHost(const float *vertices4, const float *vnormals4, uint32_t num_vertices, const uint32_t *faces, uint32_t num_faces) {
+	if (dev.sceneIsShared())
+		throw std::logic_error("build on a host whose scene on the device is shared with other hosts (one copy, many readers: upload a scene of the host's own)");
+	if (!vertices4 || !vnormals4 || !faces)
+		throw std::invalid_argument("build: null vertex, normal or face array");
+	if (num_faces == 0 || num_vertices == 0)
+		throw std::invalid_argument("build: no faces, or no vertices");
+	if (num_faces >= (1u << 25))
+		throw std::invalid_argument("build: scene too large for 32-bit device offsets");
+	for (size_t i = 0; i < (size_t) num_faces * 3; ++i)
+		if (faces[i] >= num_vertices)
+			throw std::invalid_argument("build: face references a vertex out of range (nothing was written)");
+	for (size_t i = 0; i < (size_t) num_vertices; ++i)
+		for (unsigned k = 0; k < 3; ++k)
+			if (!(std::fabs(vertices4[4 * i + k]) <= 1.0e37f))  // (false for a NaN too)
+				throw std::invalid_argument("build: a coordinate is not finite or exceeds 1e37 (nothing was written)");
+	Staged p[3] = { input(vertices4, (size_t) num_vertices * 16u), input(vnormals4, (size_t) num_vertices * 16u),
+		            input(faces, (size_t) num_faces * 12u) };
+	void *s = stageIn(p, 3);
+	buildDevice((const float *) p[0].device, (const float *) p[1].device, num_vertices, (const uint32_t *) p[2].device, num_faces, s);
+	stageOut(p, 3, s);
+}
+
+void RayQueries::lastBuildTimes(float ms[3]) {
+	ms[0] = ms[1] = ms[2] = 0.0f;
+	if (!build_timed)
+		return;
+	if (!have_build_ms) {
+		OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_build[3]));
+		OCRT_HIP(hipEventElapsedTime(&last_build_ms[0], (hipEvent_t) ev_build[0], (hipEvent_t) ev_build[1]));
+		OCRT_HIP(hipEventElapsedTime(&last_build_ms[1], (hipEvent_t) ev_build[2], (hipEvent_t) ev_build[3]));
+		have_build_ms = true;
+	}
+	for (int k = 0; k < 3; ++k)
+		ms[k] = last_build_ms[k];
+}
+
+float RayQueries::lastBuildMs() {
+	float ms[3];
+	lastBuildTimes(ms);
+	return ms[0] + ms[1];
 }
 
 void RayQueries::downloadRecords(void *nodes_out, void *tris_out, void *shade_out) {

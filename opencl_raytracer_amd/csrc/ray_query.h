@@ -103,6 +103,20 @@ class RayQueries {
 		// Host memory, blocking; refuses coordinates that are not finite or beyond 1e37 before anything is written.
 		void updateHost(const float *vertices4, const float *vnormals4, uint32_t num_vertices);
 		float lastUpdateMs();  // HIP-event time of the last update's launches (0: none yet)
+		// Device-side builds (include/rt_hip_build.h): a scene made on the device from faces, vertices and normals
+		// (DeviceScene::build) takes the place of the renderer's own -- or comes first.  Ordered as an update is, and the sort's
+		// cached root box is dropped; the call waits once for its stream (the skips and the flag come back to the host).  Closes
+		// the frame path as an update does.  std::logic_error on a shared scene; std::invalid_argument for null arrays, no
+		// face, too many, and -- after the launches, the renderer's scene untouched -- for a face index out of range.
+		// Device memory, enqueued on `stream` (null: the renderer's).
+		void buildDevice(const float *vertices4, const float *vnormals4, uint32_t num_vertices, const uint32_t *faces, uint32_t num_faces,
+		                 void *stream);
+		// Host memory, blocking; refuses bad indices and what updateHost refuses of coordinates before anything is launched.
+		void buildHost(const float *vertices4, const float *vnormals4, uint32_t num_vertices, const uint32_t *faces, uint32_t num_faces);
+		float lastBuildMs();  // HIP-event time of the last build's launches, both runs (0: none yet)
+		// (include/rt_hip_debug.h) ... apart: the topology's launches, the records' launches, the host's download-to-schedule
+		// step between them (wall clock)
+		void lastBuildTimes(float ms[3]);
 		// (include/rt_hip_debug.h) the three record arrays as they are on the device, once everything enqueued has finished
 		void downloadRecords(void *nodes_out, void *tris_out, void *shade_out);
 
@@ -189,6 +203,10 @@ class RayQueries {
 		void *ev_update_start = nullptr, *ev_update_stop = nullptr, *ev_frames = nullptr;  // an update's own times; the frame stream's tail
 		bool update_timed = false, have_update_ms = false;
 		float last_update_ms = 0.0f;
+		Scratch build;  // buildDevice: DeviceScene::buildScratchBytes
+		void *ev_build[4] = { nullptr, nullptr, nullptr, nullptr };  // around a build's two runs of launches
+		bool build_timed = false, have_build_ms = false;
+		float last_build_ms[3] = { 0.0f, 0.0f, 0.0f };  // topology, records, the host's step between them
 		std::weak_ptr<const DeviceScene> boxed;  // the scene box_lo / box_scale were read from
 		float box_lo[3] = { 0, 0, 0 }, box_scale[3] = { 0, 0, 0 };
 };

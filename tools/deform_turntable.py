@@ -5,11 +5,13 @@ nothing is uploaded again --, and every step is drawn from `--views` poses by on
 view, <prefix>_s000_v000.pgm ..., in the format `render` writes.
 
     python3 tools/deform_turntable.py mesh.off out/bunny [-w 800 -h 600 -s 4 -a 3] [--steps 12] [--views 1] [--twist 1.5]
-                                      [--radius 2 --elevation 0.4] [--look-at x,y,z]
+                                      [--radius 2 --elevation 0.4] [--look-at x,y,z] [--rebuild N]
 
 The shading normals follow the deformation: Scene.refit recomputes them on the CPU for every step (the device keeps the
 uploaded ones when an update gives none).  The tree keeps its shape, so a strong twist is walked less well than a fresh
-upload of the twisted mesh would be; the images are the same.
+upload of the twisted mesh would be; the images are the same.  `--rebuild N` repairs that on the device: at every N-th step
+host.build_scene (include/rt_hip_build.h) makes the scene again from the step's own positions, tree included, instead of
+refitting the old one -- still nothing is uploaded, and the images are the same again.
 """
 import argparse
 import os
@@ -52,9 +54,10 @@ def main(argv=None):
     ap.add_argument("--radius", type=float, default=2.0)
     ap.add_argument("--elevation", type=float, default=0.4)
     ap.add_argument("--look-at", type=triple, default=(0.0, 0.0, 0.0))
+    ap.add_argument("--rebuild", type=int, default=0, help="build the scene again on the device at every N-th step (0: refit only)")
     args = ap.parse_args(argv)
-    if args.steps < 1 or args.views < 1:
-        ap.error("--steps and --views must be at least 1")
+    if args.steps < 1 or args.views < 1 or args.rebuild < 0:
+        ap.error("--steps and --views must be at least 1, --rebuild not negative")
     ao = args.ambient_occlusion_samples
     method = 0 if args.bvh_strategy == "longest" else 1
     opt = rt.Options.defaults(width=args.width, height=args.height, n_super_samples=args.supersamples, ao_num_samples=ao,
@@ -65,18 +68,26 @@ def main(argv=None):
     host.upload_scene(scene)  # the one upload
     cameras = orbit(args.views, args.radius, args.elevation, args.look_at)
     os.makedirs(os.path.dirname(os.path.abspath(args.prefix)), exist_ok=True)
-    update_ms = views_ms = 0.0
+    update_ms = views_ms = build_ms = 0.0
+    builds = 0
+    faces = scene.faces.reshape(-1, 3).copy()
     for step in range(args.steps):
         scene.refit(twisted(original, args.twist * step / max(args.steps - 1, 1)))  # positions, normals and boxes on the CPU
-        host.update_vertices(scene.vertices, scene.vnormals)                        # ... and the scene on the device
-        update_ms += host.last_update_ms
+        if args.rebuild and step and step % args.rebuild == 0:
+            host.build_scene(scene.vertices, faces, scene.vnormals)                 # ... a new tree around them, on the device
+            build_ms += host.last_build_ms
+            builds += 1
+        else:
+            host.update_vertices(scene.vertices, scene.vnormals)                    # ... and the scene on the device
+            update_ms += host.last_update_ms
         images = host.render_views(cameras, ("image",))["image"]
         views_ms += host.last_query_ms
         for v in range(args.views):
             with open(f"{args.prefix}_s{step:03d}_v{v:03d}.pgm", "wb") as f:
                 f.write(rt.pgm_bytes(images[v]))
     host.close()
-    print(f"{args.steps} steps x {args.views} views of {args.width}x{args.height} from one upload: {update_ms / args.steps:.3f} ms per update, "
+    print(f"{args.steps} steps x {args.views} views of {args.width}x{args.height} from one upload: {update_ms / max(args.steps - builds, 1):.3f} ms per update, "
+          + (f"{build_ms / builds:.3f} ms per build ({builds} of them), " if builds else "") +
           f"{views_ms / args.steps:.3f} ms per step's views on the device; wrote {args.prefix}_s000_v000.pgm ... "
           f"{args.prefix}_s{args.steps - 1:03d}_v{args.views - 1:03d}.pgm")
 
