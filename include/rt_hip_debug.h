@@ -138,6 +138,15 @@ int rt_debug_download_records(rt_host *h, void *nodes_out, void *tris_out, void 
  * inner boxes made from the downloaded skips and copied to the device (wall clock).  Zeros before the first build. */
 int rt_debug_last_build_times(rt_host *h, float ms3[3]);
 
+/* The any-hit walk's node test (kernels/walk.hip.h, OCRT_TEST_CE_SCALED: near and far of an axis from one packed fma, nine
+ * vector instructions) held against the twelve-instruction form it replaced (a v_fma_f32 per value), on the device and on the
+ * caller's data; needs no host and no scene.  records8: `boxes` records of the centre / half-extent copy of the walk array
+ * (8 words: c.xyz, skip, e.xyz, leaf; 1 ... 65536).  rays6: `rays` walk rays (ix, iy, iz, oix, oiy, oiz: the scaled
+ * reciprocals and -(o * i); a multiple of 64, 65536 at the most).  out9: nine words per (ray, record), ray-major -- near, far
+ * (bit patterns) and the decision (0 / 1) of the old form, of the new form in the registers of the loop's node `a`, and of
+ * the new form in those of node `b`. */
+int rt_debug_node_test_forms(int device, const float *records8, uint32_t boxes, const float *rays6, uint32_t rays, uint32_t *out9);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ from .api import (  # noqa: F401
     device_count,
     lib_path,
     load_library,
+    node_test_forms,
     partition_rows,
     pgm_bytes,
     rccl_available,

@@ -217,6 +217,7 @@ _SIGNATURES = {
     "rt_debug_split_tiles": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_debug_prune_facts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_poison_hit_list": (C.c_int, [C.c_void_p]),
+    "rt_debug_node_test_forms": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rt_debug_set_views_chunk": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rt_debug_last_views": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     # include/rt_hip_query.h
@@ -491,6 +492,21 @@ def _raise_last() -> None:
 
 def device_count() -> int:
     return load_library().rt_device_count()
+
+
+def node_test_forms(records: np.ndarray, rays: np.ndarray, device: int = 0) -> np.ndarray:
+    """The any-hit walk's node test in its two forms on the device (include/rt_hip_debug.h, rt_debug_node_test_forms):
+    `records` (B, 8) float32 centre / half-extent records, `rays` (R, 6) float32 walk rays, R a multiple of 64.  Returns
+    (R, B, 9) uint32: near, far (bit patterns) and the decision of the old form, of the new form on node a's registers, of
+    the new form on node b's."""
+    records = np.ascontiguousarray(records, dtype=np.float32)
+    rays = np.ascontiguousarray(rays, dtype=np.float32)
+    if records.ndim != 2 or records.shape[1] != 8 or rays.ndim != 2 or rays.shape[1] != 6:
+        raise ValueError("node_test_forms: expected (B, 8) records and (R, 6) rays")
+    out = np.empty((rays.shape[0], records.shape[0], 9), dtype=np.uint32)
+    _check(load_library().rt_debug_node_test_forms(int(device), records.ctypes.data, records.shape[0], rays.ctypes.data,
+                                                   rays.shape[0], out.ctypes.data))
+    return out
 
 
 def _view(ptr: int, count: int, dtype) -> np.ndarray:

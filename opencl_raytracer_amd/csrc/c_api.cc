@@ -26,6 +26,7 @@
 #include "bvh.h"
 #include "band_gather.h"
 #include "camera.h"
+#include "device_internal.h"
 #include "device_renderer.h"
 #include "frame_ring.h"
 #include "hip_host.h"
@@ -677,6 +678,36 @@ int rt_debug_poison_hit_list(rt_host *h) {
 	if (!h)
 		return fail(RT_E_INVALID, "null argument");
 	return guarded([&] { h->dev->poisonHitList(); });
+}
+
+int rt_debug_node_test_forms(int device, const float *records8, uint32_t boxes, const float *rays6, uint32_t rays, uint32_t *out9) {
+	if (!records8 || !rays6 || !out9)
+		return fail(RT_E_INVALID, "null argument");
+	if (boxes == 0 || boxes > 65536u || rays == 0 || rays > 65536u || rays % 64u != 0)
+		return fail(RT_E_INVALID, "1 ... 65536 records and a multiple of 64 rays, 65536 at the most");
+	const size_t record_bytes = (size_t) boxes * 32u, ray_bytes = (size_t) rays * 24u, out_bytes = (size_t) rays * boxes * 36u;
+	return guarded([&] {
+		OCRT_HIP(hipSetDevice(device));
+		void *d_records = nullptr, *d_rays = nullptr, *d_out = nullptr;
+		try {
+			d_records = ocrt::device_alloc(record_bytes);
+			d_rays = ocrt::device_alloc(ray_bytes);
+			d_out = ocrt::device_alloc(out_bytes);
+			OCRT_HIP(hipMemcpy(d_records, records8, record_bytes, hipMemcpyHostToDevice));
+			OCRT_HIP(hipMemcpy(d_rays, rays6, ray_bytes, hipMemcpyHostToDevice));
+			ocrt::launch_node_test_forms(d_records, boxes, d_rays, rays, d_out, nullptr);
+			OCRT_HIP(hipGetLastError());
+			OCRT_HIP(hipMemcpy(out9, d_out, out_bytes, hipMemcpyDeviceToHost));
+		} catch (...) {
+			ocrt::device_free(d_records);
+			ocrt::device_free(d_rays);
+			ocrt::device_free(d_out);
+			throw;
+		}
+		ocrt::device_free(d_records);
+		ocrt::device_free(d_rays);
+		ocrt::device_free(d_out);
+	});
 }
 
 uint32_t rt_ring_size(const rt_ring *r) { return r ? r->ring->size() : 0; }

@@ -414,6 +414,8 @@ void launch_refit_leaves(const void *faces, const void *leaf_nodes, const void *
                          void *nodes, uint32_t leaves, void *stream);
 void launch_refit_inner(const void *entries, const void *children, const void *groups, void *nodes, uint32_t first_group, uint32_t groups_in_pass,
                         void *stream);
+// Test aid: the any-hit node test in both forms (kernels/node_test_forms.hip.h)
+void launch_node_test_forms(const void *records, uint32_t boxes, const void *rays6, uint32_t rays, void *out, void *stream);
 // Device-side builds (kernels/build.hip.h; BuildBuffers: device_types.h)
 uint32_t build_partials(uint32_t faces);
 void launch_build_keys(const BuildBuffers &b, void *stream);

@@ -49,6 +49,8 @@
 //                   build_sort.hip (kernels/build.hip.h, include/rt_hip_build.h).
 //   (on demand)     entry_kernel: the walk intervals, once per upload; occluded_sum_kernel: the frame's occlusion
 //                   total when the statistics are asked for; resize_kernel: a box filter on its own.
+//   (tests)         node_test_forms_kernel: the any-hit node test against the form it replaced, on the caller's records and
+//                   rays (kernels/node_test_forms.hip.h, include/rt_hip_debug.h).
 // Why not one fused launch (it was, see profiles/r01_notes.md): cost per tile
 // varies 30x (background vs model, 29 rays per hit sub-pixel), so the frame used
 // to end on a long tail of half-empty CUs.  With the tiles' costs known from the
@@ -88,6 +90,7 @@
 #include "kernels/views.hip.h"
 #include "kernels/refit.hip.h"
 #include "kernels/build.hip.h"
+#include "kernels/node_test_forms.hip.h"
 
 
 namespace ocrt {
@@ -660,6 +663,15 @@ void launch_build_tree(const BuildBuffers &b, void *stream) {
 	hipLaunchKernelGGL(build_tree_kernel, dim3(build_partials(b.num_faces)), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
 	const uint32_t nodes = 2u * b.num_faces - 1u;
 	hipLaunchKernelGGL(build_layout_kernel, dim3((nodes + BUILD_LANES - 1u) / BUILD_LANES), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
+}
+
+// Test aid (kernels/node_test_forms.hip.h, include/rt_hip_debug.h): the any-hit node test in both forms, `rays` (a multiple of
+// 64) walk rays against `boxes` centre / half-extent records, nine words per pair into `out`.
+void launch_node_test_forms(const void *records, uint32_t boxes, const void *rays6, uint32_t rays, void *out, void *stream) {
+	if (boxes == 0 || rays == 0)
+		return;
+	hipLaunchKernelGGL(node_test_forms_kernel, dim3(rays / 64u), dim3(64), 0, (hipStream_t) stream, (const float4 *) records, boxes,
+	                   (const float *) rays6, (uint32_t *) out);
 }
 
 }  // namespace ocrt

@@ -104,11 +104,16 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 // 6 v_fma + max + min + max3 + min3 + cmp = 11 vector instructions; the loop exists once per sign octant
 // (OCRT_WALK_COHERENT).  Mixed packets select per lane with v_cndmask on the sign masks: 17 (the first generation of
 // this loop computed (b - o) * inv exactly: 23).  The any-hit rays of the ambient-occlusion pass, whose max_distance is
-// one number per frame, take the SCALED form of the test on centre / half-extent records: 12, one loop for every packet
-// (OCRT_TEST_CE_SCALED below).  What an instruction costs here (tools/microbench/
-// valu_rate_probe.hip, 8 waves per SIMD): ~2.3 cycles per SIMD for v_fma / v_mul / v_add / v_mov on registers, ~4.2
-// for everything else (min / max / max3 / cmp / cndmask, v_pk_fma_f32, and alone also an fma with a scalar operand):
-// the 11-instruction test runs at 35.7 cycles, the 9-instruction one at 28.3, a v_pk_fma_f32 version with 8 at 35.9.
+// one number per frame, take the SCALED form of the test on centre / half-extent records: 9, three of them packed fmas
+// that make near and far of an axis at once, one loop for every packet (OCRT_TEST_CE_SCALED below).  What an instruction
+// costs here (tools/microbench/valu_rate_probe.hip, 8 waves per SIMD): ~2.3 cycles per SIMD for v_fma / v_mul / v_add /
+// v_mov on registers, ~4.2 for everything else (min / max / max3 / cmp / cndmask, v_pk_fma_f32 -- with or without an
+// SGPR pair, op_sel, neg_lo --, and alone also an fma with a scalar operand; among other instructions such an fma
+// issues at ~3.1): the 11-instruction test runs at 35.7 cycles, the any-hit test at 30.5 (40.4 when every one of its six
+// near / far values had a v_fma_f32 of its own: a packed fma with a scalar operand costs 4.2, the two plain ones with a
+// scalar operand it replaces 6.1 -- on REGISTERS two plain fmas are the cheaper, which is why the rest of the device code
+// is compiled without SLP vectorisation), a v_pk_fma_f32 version of the plane form with 8 at 35.9
+// (profiles/node_test_packed_probe.txt).
 //
 // One 64-byte load fetches a node and its pre-order successor: after a hit on an inner node its first child is
 // tested straight from s[56:63].  The array ends in two END records whose infinite box every live lane "hits" and
@@ -166,25 +171,31 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 // It reads the CENTRE / HALF-EXTENT copy of the walk array (scene_pack.cc, ce_record: c in the lo fields, e in the hi
 // fields; the copy lies behind the plane form's records and their END records):
 // t_c = fma(c, inv, oi), near = fma(-e, |inv|, t_c), far = fma(e, |inv|, t_c) -- right for either sign of inv, so ONE loop
-// serves every any-hit packet: 9 v_fma + max3 + min3 + cmp = 12 vector instructions, nine of them of the fast class.
+// serves every any-hit packet: 3 v_fma + 3 v_pk_fma + max3 + min3 + cmp = 9 vector instructions.
 // (Rounds 2-3 walked the plane-form records here too: a loop per sign octant, 6 fma + max3 + min3 + cmp = 9 per node, and
 // a select form of 15 -- nine of them of the slow class -- for packets whose rays disagree on a sign, a third of the
 // bunny's model packets.  The one loop measures 1.3 ... 4.4 % faster per frame on every workload, although coherent
-// packets execute three instructions more per node: fast-class fmas, one array in the caches, a ninth of the code.)
+// packets executed three instructions more per node then: fast-class fmas, one array in the caches, a ninth of the code.)
 // Conservative like the plane form (the half-extent carries the rounding of t_c: proof at ce_record).
-#define OCRT_TEST_CE_SCALED(CX, CY, CZ, EX, EY, EZ)       \
-	"\tv_fma_f32 v56, " CX ", %[ix], %[oix]\n"           \
-	"\tv_fma_f32 v57, " CY ", %[iy], %[oiy]\n"           \
-	"\tv_fma_f32 v58, " CZ ", %[iz], %[oiz]\n"           \
-	"\tv_fma_f32 v59, -" EX ", |%[ix]|, v56\n"           \
-	"\tv_fma_f32 v56, " EX ", |%[ix]|, v56\n"            \
-	"\tv_fma_f32 v60, -" EY ", |%[iy]|, v57\n"           \
-	"\tv_fma_f32 v57, " EY ", |%[iy]|, v57\n"            \
-	"\tv_fma_f32 v61, -" EZ ", |%[iz]|, v58 clamp\n"     \
-	"\tv_fma_f32 v58, " EZ ", |%[iz]|, v58 clamp\n"      \
-	"\tv_max3_f32 v59, v59, v60, v61\n"                  \
-	"\tv_min3_f32 v56, v56, v57, v58\n"                  \
-	"\tv_cmp_lt_f32 vcc, v59, v56\n"
+// Near and far of an axis differ in the sign of e alone, so ONE v_pk_fma_f32 makes both: t_c goes to the low half of an
+// aligned pair, the packed fma reads it for both halves (op_sel / op_sel_hi 0 on src2) and negates e in the low half
+// (neg_lo on src0) -- (near, far) in (v56, v57), (v58, v59), (v60, v61).  E_XY = the aligned SGPR pair (e.x, e.y), of which
+// op_sel / op_sel_hi pick the half; E_ZW = (e.z, leaf).  VOP3P has no |...| modifier: %[axy] = (|ix|, |iy|) and
+// %[azw] = (|iz|, -) are register pairs made once per packet (walk_collect).  Each half is the fused multiply-add that
+// v_fma_f32 is on the same operands, the clamp applies to both halves -- the bits of near and far are those of the
+// twelve-instruction form, a v_fma_f32 per value (tests/test_node_test_forms_gpu.py holds the two against each other on the
+// device, kernels/node_test_forms.hip.h).  Against that form the any-hit pass issues 13.8 % fewer vector instructions and
+// the headline frame is 2 ... 6 % shorter (profiles/node_test_packed_notes.md).
+#define OCRT_TEST_CE_SCALED(CX, CY, CZ, E_XY, E_ZW)                                                                   \
+	"\tv_fma_f32 v56, " CX ", %[ix], %[oix]\n"                                                                        \
+	"\tv_fma_f32 v58, " CY ", %[iy], %[oiy]\n"                                                                        \
+	"\tv_fma_f32 v60, " CZ ", %[iz], %[oiz]\n"                                                                        \
+	"\tv_pk_fma_f32 v[56:57], " E_XY ", %[axy], v[56:57] op_sel:[0,0,0] op_sel_hi:[0,0,0] neg_lo:[1,0,0]\n"           \
+	"\tv_pk_fma_f32 v[58:59], " E_XY ", %[axy], v[58:59] op_sel:[1,1,0] op_sel_hi:[1,1,0] neg_lo:[1,0,0]\n"           \
+	"\tv_pk_fma_f32 v[60:61], " E_ZW ", %[azw], v[60:61] op_sel:[0,0,0] op_sel_hi:[0,0,0] neg_lo:[1,0,0] clamp\n"     \
+	"\tv_max3_f32 v56, v56, v58, v60\n"                                                                               \
+	"\tv_min3_f32 v57, v57, v59, v61\n"                                                                               \
+	"\tv_cmp_lt_f32 vcc, v56, v57\n"
 // (LEAF: the s-register holding the node's leaf field; NEXT: where the walk goes on after an append)
 #define OCRT_WALK_LEAF(LEAF, NOW, NEXT)                 \
 	"\ts_cmp_eq_u32 " LEAF ", -2\n"                     \
@@ -315,13 +326,13 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 	               [oiz] "v"(ray.oiz)                                                                                    \
 	             : OCRT_WALK_CLOBBERS)
 #define OCRT_WALK_MIXED_CE(TEST, PF)                                                                                      \
-	asm volatile(OCRT_WALK_ASM(OCRT_HEAD_END, TEST("s48", "s49", "s50", "s52", "s53", "s54"), TEST("s56", "s57", "s58", "s60", "s61", "s62"), PF) \
+	asm volatile(OCRT_WALK_ASM(OCRT_HEAD_END, TEST("s48", "s49", "s50", "s[52:53]", "s[54:55]"), TEST("s56", "s57", "s58", "s[60:61]", "s[62:63]"), PF) \
 	             : [at] "+s"(at), [waiting] "+s"(waiting), [stops] "+s"(leaf_stops), [hit] "=&s"(hit_mask),               \
 	               [leaf] "=&s"(leaf), [status] "=&s"(status)                                                            \
 	             : [base] "s"(walk_ptr), [alive] "s"(alive_mask), [end] "s"(walk_end), [batch_below] "s"(batch_below),    \
 	               [list] "s"(list_lds_address), [tag] "v"(lane_tag),                                                      \
 	               [ix] "v"(ray.ix), [iy] "v"(ray.iy), [iz] "v"(ray.iz), [oix] "v"(ray.oix), [oiy] "v"(ray.oiy),          \
-	               [oiz] "v"(ray.oiz)                                                                                    \
+	               [oiz] "v"(ray.oiz), [axy] "v"(abs_xy), [azw] "v"(abs_zw)                                               \
 	             : OCRT_WALK_CLOBBERS)
 #define OCRT_WALK_SWITCH(COHERENT_TEST, MIXED_TEST, PF)                 \
 	switch (variant) {                                                  \
@@ -339,6 +350,7 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 // `variant`: 0..7 = sign octant of a coherent packet (bit 0: x reciprocals >= 0, bit 1: y, bit 2: z), 8 = mixed.
 // SCALED: `ray` was made with the frame's walk_scale and `below` is not looked at (the limit is 1.0).
 constexpr uint32_t WALK_MIXED = 8u;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <bool SCALED, bool PREFETCH = false>
 __device__ __forceinline__ uint32_t walk_collect(uint32_t variant, const float4 *walk_ptr, uint32_t &at, const WalkRay &ray,
                                                  const SignMasks &sign, float below, unsigned long long alive_mask,
@@ -352,6 +364,9 @@ __device__ __forceinline__ uint32_t walk_collect(uint32_t variant, const float4 
 		// copy of the array)
 		(void) sign;
 		(void) variant;
+		// |inv| for the packed fmas, as two aligned register pairs (the high half of the second is not read)
+		const f32x2 abs_xy = { __builtin_fabsf(ray.ix), __builtin_fabsf(ray.iy) };
+		const f32x2 abs_zw = { __builtin_fabsf(ray.iz), __builtin_fabsf(ray.iz) };
 		if (PREFETCH) {
 			OCRT_WALK_MIXED_CE(OCRT_TEST_CE_SCALED, OCRT_PF_SUCCESSORS);
 		} else {

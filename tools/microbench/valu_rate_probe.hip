@@ -1,6 +1,7 @@
 // Probe (gfx950): sustained issue rate of single vector instructions, 8 waves per SIMD (8 workgroups of 4 waves per CU),
 // 32 instructions per loop turn on 8 destination registers.  Event-timed; the shader clock is read with s_memtime
-// against the 100 MHz wall clock.  hipcc --offload-arch=gfx950 -O2 -w -o valu_rate_probe tools/microbench/valu_rate_probe.hip   (output of one run: profiles/r02_valu_rate_probe.txt)
+// against the 100 MHz wall clock.  hipcc --offload-arch=gfx950 -O2 -w -o valu_rate_probe tools/microbench/valu_rate_probe.hip   (output of one run: profiles/r02_valu_rate_probe.txt;
+// with the packed node test: profiles/node_test_packed_probe.txt)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 typedef float f2v __attribute__((ext_vector_type(2)));
@@ -81,6 +82,17 @@ KERNEL(node_test_12, "v_fma_f32 v40, s20, v48, v49\n v_fma_f32 v41, s21, v48, v4
        "v_fma_f32 v43, -s23, |v48|, v40\n v_fma_f32 v40, s23, |v48|, v40", "v_fma_f32 v44, -s20, |v48|, v41\n v_fma_f32 v41, s20, |v48|, v41",
        "v_fma_f32 v45, -s21, |v48|, v42 clamp\n v_fma_f32 v42, s21, |v48|, v42 clamp", "v_max3_f32 v43, v43, v44, v45", "v_min3_f32 v40, v40, v41, v42",
        "v_cmp_lt_f32 vcc, v43, v40", "s_and_b64 s[24:25], vcc, exec")
+// ... and the same test with near and far of an axis from ONE packed fma (they differ in the sign of e alone): 3 v_fma (t_c
+// into the low halves of three aligned pairs) + 3 v_pk_fma_f32 + max3 + min3 + cmp = 9.  v[48:49] stands for (|ix|, |iy|),
+// v[50:51] for (|iz|, -), s[20:21] / s[22:23] for the half-extents (kernels/walk.hip.h, OCRT_TEST_CE_PACKED)
+KERNEL(node_test_12pk, "v_fma_f32 v40, s20, v52, v53\n v_fma_f32 v42, s21, v52, v53\n v_fma_f32 v44, s22, v52, v53",
+       "v_pk_fma_f32 v[40:41], s[20:21], v[48:49], v[40:41] op_sel:[0,0,0] op_sel_hi:[0,0,0] neg_lo:[1,0,0]",
+       "v_pk_fma_f32 v[42:43], s[20:21], v[48:49], v[42:43] op_sel:[1,1,0] op_sel_hi:[1,1,0] neg_lo:[1,0,0]",
+       "v_pk_fma_f32 v[44:45], s[22:23], v[50:51], v[44:45] op_sel:[0,0,0] op_sel_hi:[0,0,0] neg_lo:[1,0,0] clamp", "v_max3_f32 v40, v40, v42, v44",
+       "v_min3_f32 v41, v41, v43, v45", "v_cmp_lt_f32 vcc, v40, v41", "s_and_b64 s[24:25], vcc, exec")
+#define PKNEG(D, S) "v_pk_fma_f32 v[" D "], s[" S "], v[50:51], v[52:53] op_sel:[1,1,1] op_sel_hi:[1,1,1] neg_lo:[1,0,0]"
+KERNEL(pk_fma_svv_neg, PKNEG("40:41", "20:21"), PKNEG("42:43", "22:23"), PKNEG("44:45", "20:21"), PKNEG("46:47", "22:23"), PKNEG("40:41", "20:21"),
+       PKNEG("42:43", "22:23"), PKNEG("44:45", "20:21"), PKNEG("46:47", "22:23"))
 KERNEL1(fma_svv_clamp, "v_fma_f32", "s20, v49, v50 clamp")
 KERNEL(fma_svv_4regs, "v_fma_f32 v40, s20, v48, v49", "v_fma_f32 v41, s21, v48, v49", "v_fma_f32 v42, s22, v48, v49", "v_fma_f32 v43, s23, v48, v49",
        "v_fma_f32 v44, s20, v48, v49", "v_fma_f32 v45, s21, v48, v49", "v_fma_f32 v46, s22, v48, v49", "v_fma_f32 v47, s23, v48, v49")
@@ -93,7 +105,8 @@ int main() {
 	const Kind kinds[] = {K(fma_vvv), K(fma_self), K(fma_svv), K(fma_vsv), K(fma_vvs), K(mul_vv), K(mul_sv), K(add_vv), K(sub_sv), K(max_vv), K(max_sv), K(max_cv),
 	                      K(max3_vvv), K(min3_svv), K(med3_vvv), K(mov_v), K(mov_s), K(cndmask_vcc), K(cndmask_s), K(and_vv), K(add_u32), K(lshl_add), K(cmp_vcc), K(cmp_sgpr),
 	                      K(pk_fma_vvv), K(pk_fma_svv), K(pk_fma_svv_sel), K(pk_mul_vv), {"node_test_11 (4 tests per turn)", node_test_11, 44.0}, {"node_test_8 (4 tests per turn)", node_test_8, 32.0},
-	                      {"node_test_9 (4 tests per turn)", node_test_9, 36.0}, {"node_test_12 (4 tests per turn)", node_test_12, 48.0}, K(fma_svv_clamp),
+	                      {"node_test_9 (4 tests per turn)", node_test_9, 36.0}, {"node_test_12 (4 tests per turn)", node_test_12, 48.0}, {"node_test_12pk (4 tests per turn)", node_test_12pk, 36.0},
+	                      K(pk_fma_svv_neg), K(fma_svv_clamp),
 	                      K(fma_svv_4regs)};
 	const int iters = 10000;
 	for (const Kind &kind : kinds) {
@@ -108,8 +121,11 @@ int main() {
 			if (ms < best) { best = ms; ghz = (double)h[1] / (h[2] * 10.0); }
 		}
 		const double per_simd = kind.vector_per_turn * iters * 8;
-		printf("%-32s %.3f ms  %.3f instr/ns/SIMD  clock %.2f GHz  -> %.2f cycles per vector instruction per SIMD\n", kind.name, best, per_simd / (best * 1e6), ghz,
+		printf("%-32s %.3f ms  %.3f instr/ns/SIMD  clock %.2f GHz  -> %.2f cycles per vector instruction per SIMD", kind.name, best, per_simd / (best * 1e6), ghz,
 		       best * 1e6 * ghz / per_simd);
+		if (kind.vector_per_turn != 32.0 || kind.k == node_test_8)
+			printf("  = %.2f cycles per TEST", best * 1e6 * ghz / (4.0 * iters * 8));
+		printf("\n");
 	}
 	return 0;
 }
