@@ -112,6 +112,18 @@ int rt_debug_poison_hit_list(rt_host *h);
 int rt_debug_set_views_chunk(rt_host *h, uint32_t max_views);
 int rt_debug_last_views(rt_host *h, uint32_t *views, uint32_t *chunks, uint64_t *ao_points);
 
+/* Closest-point queries (rt_hip_nearest.h), for tools/distance_bench.py.  rt_debug_set_nearest_walk: how the host's later
+ * closest-point queries walk -- RT_DEBUG_NEAREST_NO_START: no lane descends for a starting bound; RT_DEBUG_NEAREST_NO_PRUNE:
+ * no box is passed by (every leaf is tested); RT_DEBUG_NEAREST_COUNT: the kernel counts its tests.  Results never depend
+ * on the flags.  Flags other than 0 are the A/B build's (-DOCRT_DEBUG_KNOBS): RT_E_STATE in the product library, whose
+ * queries always walk the one way.  rt_debug_last_nearest_counts: per-point box tests and triangle tests of the host's
+ * last counted query, summed over its points (waits for it; zeros without one).  RT_E_STATE on the hosts of a frame ring. */
+#define RT_DEBUG_NEAREST_NO_START 1u
+#define RT_DEBUG_NEAREST_NO_PRUNE 2u
+#define RT_DEBUG_NEAREST_COUNT 4u
+int rt_debug_set_nearest_walk(rt_host *h, uint32_t flags);
+int rt_debug_last_nearest_counts(rt_host *h, uint64_t *node_tests, uint64_t *triangle_tests);
+
 /* Vertex updates (rt_hip_update.h).  The inner boxes are refitted bottom-up by a schedule made on the host: the inner nodes
  * cut into groups of at most S, a workgroup per group, a launch per pass.  rt_debug_set_refit_group: S for this host's
  * updates (0, the default: 256; at most 1024) -- so that a small mesh can take several passes; results never depend on it.

@@ -10,6 +10,7 @@ raises.
 from .api import (  # noqa: F401
     DIRECTIONAL_OUTPUTS,
     LAYER_OUTPUTS,
+    NEAREST_OUTPUTS,
     VIEW_OUTPUTS,
     Camera,
     FrameRing,

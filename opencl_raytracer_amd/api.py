@@ -1,5 +1,6 @@
 """ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h, rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h,
-rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers for the contract)."""
+rt_hip_nearest.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers
+for the contract)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -228,8 +229,13 @@ _SIGNATURES = {
     "rt_trace_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
                                            C.c_void_p]),
     "rt_last_query_ms": (C.c_float, [C.c_void_p]),
+    # include/rt_hip_nearest.h
+    "rt_closest_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
+    "rt_closest_points_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_debug_set_nearest_walk": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_debug_last_nearest_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     # include/rt_hip_multihit.h
-    "rt_trace_multihit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_trace_multihit":(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p]),
     "rt_trace_multihit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32,
                                            C.c_void_p, C.c_void_p]),
     # include/rt_hip_ao.h
@@ -314,6 +320,7 @@ assert (NODE_RECORD.itemsize, TRI_RECORD.itemsize, SHADE_RECORD.itemsize) == (32
 RT_MULTIHIT_MAX_K = 16
 MULTIHIT_OUTPUTS = ("count", "distance", "leaf", "barycentric", "position", "normal")
 QUERY_OUTPUTS = ("hit", "distance", "leaf", "barycentric", "position", "normal")
+NEAREST_OUTPUTS = QUERY_OUTPUTS  # closest-point queries: "hit" is `found`
 AO_OUTPUTS = ("ao", "occluded")
 DIRECTIONAL_OUTPUTS = ("ao", "occluded", "mask", "bent")
 LAYER_OUTPUTS = QUERY_OUTPUTS + ("direction", "shade", "ao", "value")
@@ -362,13 +369,15 @@ class _QueryArrays:
     without waiting.  The inputs a, b (and `also`, if given) must be of one kind."""
 
     def __init__(self, a, b, names, items: str, also=None):
-        given = [a, b] + ([] if also is None else [also])
+        given = [a] + ([] if b is None else [b]) + ([] if also is None else [also])
         self.torch = any(_is_torch(x) for x in given)
         if self.torch and not all(_is_torch(x) for x in given):
             both = "all" if len(names) > 2 else "both"
             raise ValueError(f"{', '.join(names[:-1])} and {names[-1]} must {both} be torch tensors or {both} numpy arrays")
         pad = _rays4_torch if self.torch else _rays4_numpy
-        self.a, self.b = pad(a, names[0]), pad(b, names[1])
+        self.a = pad(a, names[0])
+        self.b = self.a if b is None else pad(b, names[1])  # (b None: a query of points alone, closest_points)
+        self.inputs = (self.a,) if b is None else (self.a, self.b)
         if self.a.shape[0] != self.b.shape[0] or (self.torch and self.a.device != self.b.device):
             raise ValueError(f"{names[0]} and {names[1]} must hold the same number of {items}"
                              + (" on the same device" if self.torch else ""))
@@ -379,7 +388,7 @@ class _QueryArrays:
 
             self.current = torch.cuda.current_stream(self.a.device)
             self.suffix, self.stream = "_device", (self.current.cuda_stream,)
-            self.padded = [t for t, was in ((self.a, a), (self.b, b)) if t is not was]
+            self.padded = [t for t, was in ((self.a, a), (self.b, b)) if was is not None and t is not was]
 
     def ptr(self, x) -> int:
         return x.data_ptr() if self.torch else x.ctypes.data
@@ -426,8 +435,8 @@ class _QueryArrays:
         return [self.ptr(out[name]) if name in out and self.n else None for name in names]
 
     def call(self, h, function: str, *args) -> None:
-        """function(h, the two inputs, *args) -- or function_device(..., the current stream)."""
-        _check(getattr(load_library(), function + self.suffix)(h, self.ptr(self.a), self.ptr(self.b), *args, *self.stream))
+        """function(h, the two inputs -- or the one --, *args) -- or function_device(..., the current stream)."""
+        _check(getattr(load_library(), function + self.suffix)(h, *(self.ptr(x) for x in self.inputs), *args, *self.stream))
         for t in self.padded:  # (the padded copies must live until the kernels have read them)
             t.record_stream(self.current)
 
@@ -867,6 +876,33 @@ class Host:
         else:
             io.call(self._h, "rt_trace_occluded", *args, *io.pointers(out, ("hit",)))
         return out
+
+    # ---- closest-point queries (include/rt_hip_nearest.h) ----
+    def closest_points(self, points, max_distance: float = float("inf"), outputs=NEAREST_OUTPUTS, sort: bool = True) -> dict:
+        """The nearest point of the surface for every point: {"hit": uint8 (N,), 1 iff the surface lies within max_distance;
+        "distance": float32 (N,); "leaf": uint32 (N,); "barycentric", "position", "normal": float32 (N, 3)} (those named in
+        `outputs`); without one: +inf, 0xFFFFFFFF, zeros.  points: (N, 3) / (N, 4) float32.  numpy in, numpy out (blocking);
+        a torch tensor on the host's GPU in, torch tensors out, enqueued on torch.cuda.current_stream() without waiting (as
+        for trace_closest)."""
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in NEAREST_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {NEAREST_OUTPUTS}")
+        io = _QueryArrays(points, None, ("points",), "points")
+        out = io.outputs(outputs)
+        io.call(self._h, "rt_closest_points", io.n, float(max_distance), 0 if sort else RT_QUERY_NO_SORT,
+                C.byref(_HitArrays(*io.pointers(out, NEAREST_OUTPUTS))))
+        return out
+
+    def set_nearest_walk(self, no_start: bool = False, no_prune: bool = False, count: bool = False) -> None:
+        """(rt_debug_set_nearest_walk) How later closest_points calls walk; anything but the default needs the A/B build."""
+        _check(load_library().rt_debug_set_nearest_walk(self._h, (1 if no_start else 0) | (2 if no_prune else 0) | (4 if count else 0)))
+
+    def last_nearest_counts(self) -> tuple:
+        """(rt_debug_last_nearest_counts) (box tests, triangle tests) of the last counted closest_points call, over its points."""
+        nodes, tris = C.c_uint64(), C.c_uint64()
+        _check(load_library().rt_debug_last_nearest_counts(self._h, C.byref(nodes), C.byref(tris)))
+        return int(nodes.value), int(tris.value)
 
     # ---- multi-hit queries (include/rt_hip_multihit.h) ----
     def trace_multihit(self, origins, directions, max_distance: float = 100000.0, k: int = 4, outputs=MULTIHIT_OUTPUTS,

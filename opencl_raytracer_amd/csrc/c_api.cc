@@ -8,6 +8,7 @@
 #include "../../include/rt_hip_layers.h"
 #include "../../include/rt_hip_debug.h"
 #include "../../include/rt_hip_multihit.h"
+#include "../../include/rt_hip_nearest.h"
 #include "../../include/rt_hip_query.h"
 #include "../../include/rt_hip_views.h"
 #include "../../include/rt_hip_update.h"
@@ -956,6 +957,65 @@ int rt_trace_occluded_device(rt_host *h, const float *origins4, const float *dir
 	ocrt::QueryOutputs q;
 	q.hit = occluded;
 	return guarded([&] { queries_of(h).traceDevice(false, origins4, directions4, n, max_distance, flags, q, hip_stream); });
+}
+
+// ---- rt_hip_nearest.h ----
+namespace {
+
+// The checks of include/rt_hip_nearest.h ("Errors").
+int nearest_precheck(rt_host *h, const float *points4, uint32_t n, bool device) {
+	const int rc = host_precheck(h, "closest-point");
+	if (rc != RT_OK)
+		return rc;
+	if (n > RT_QUERY_MAX_RAYS)
+		return fail(RT_E_INVALID, "more points than RT_QUERY_MAX_RAYS in one call");
+	if (n > 0 && !points4)
+		return fail(RT_E_INVALID, "null point array");
+	if (device && n > 0 && !aligned({ points4 }, 16))
+		return fail(RT_E_INVALID, "the device point array must be 16-byte aligned");
+	return RT_OK;
+}
+
+}  // namespace
+
+int rt_closest_points(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags, const rt_hit_arrays *out) {
+	const int rc = nearest_precheck(h, points4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	return guarded([&] { queries_of(h).nearestHost(points4, n, max_distance, flags, hit_outputs(out)); });
+}
+
+int rt_closest_points_device(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags, const rt_hit_arrays *out,
+                             void *hip_stream) {
+	const int rc = nearest_precheck(h, points4, n, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	const ocrt::QueryOutputs q = hit_outputs(out);
+	if (!records_aligned(q))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).nearestDevice(points4, n, max_distance, flags, q, hip_stream); });
+}
+
+int rt_debug_set_nearest_walk(rt_host *h, uint32_t flags) {
+	if (!h)
+		return fail(RT_E_INVALID, "null host");
+	if (!h->owned)
+		return fail(RT_E_STATE, "closest-point queries are not available on the hosts of a frame ring");
+	return guarded([&] { queries_of(h).setNearestWalk(flags); });
+}
+
+int rt_debug_last_nearest_counts(rt_host *h, uint64_t *node_tests, uint64_t *triangle_tests) {
+	if (!h)
+		return fail(RT_E_INVALID, "null host");
+	if (!h->owned)
+		return fail(RT_E_STATE, "closest-point queries are not available on the hosts of a frame ring");
+	uint64_t counts[2] = { 0u, 0u };
+	const int rc = h->queries ? guarded([&] { h->queries->lastNearestCounts(counts); }) : RT_OK;
+	if (node_tests)
+		*node_tests = counts[0];
+	if (triangle_tests)
+		*triangle_tests = counts[1];
+	return rc;
 }
 
 // ---- rt_hip_multihit.h ----

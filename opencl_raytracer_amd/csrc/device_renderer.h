@@ -65,6 +65,10 @@ class DeviceScene {
 		uint32_t triCount() const { return tri_count; }
 		uint32_t aoDirs() const { return ao_dirs; }
 		const SceneFacts &facts() const { return scene_facts_; }
+		// Every box holds the triangles beneath it: the packer checked the uploaded arrays (PackedScene::enclosing), or the boxes
+		// are the refit rule's -- after an update or a device-side build, whose coordinates the host may not have seen: the
+		// closest-point queries hold a flag on the device against those (RayQueries::updateDevice).
+		bool boxesEnclose() const { return scene_facts_.boxes_enclose; }
 
 		// Vertex updates (include/rt_hip_update.h; kernels/refit.hip.h).  The records of `nodes`, `tris` and `shade` are made
 		// again on the device from `vertices4` (float4 per vertex, vertexCount() of them) and, where given, `vnormals4`;

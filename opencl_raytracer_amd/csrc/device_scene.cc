@@ -245,6 +245,7 @@ std::shared_ptr<DeviceScene> DeviceScene::build(int device, const RayTracer::Opt
 	const std::vector<float> table = out->takeOptions(opts);
 	out->scene_facts_ = SceneFacts{};  // (no padded walk array: every walk takes the exact form)
 	out->scene_facts_.prune_margin = std::numeric_limits<float>::infinity();
+	out->scene_facts_.boxes_enclose = true;  // (the refit rule's boxes)
 	out->node_count = 2u * num_faces - 1u;
 	out->tri_count = num_faces;
 	out->vertex_count = num_vertices;
@@ -334,6 +335,8 @@ void DeviceScene::updateVertices(const float *vertices4, const float *vnormals4,
 	for (size_t p = 0; p + 1 < refit_pass_first.size(); ++p)
 		launch_refit_inner(d_entries, d_children, d_groups, d_nodes, refit_pass_first[p], refit_pass_first[p + 1] - refit_pass_first[p], stream);
 	OCRT_HIP(hipGetLastError());
+	// (every box is the refit rule's now, whatever was uploaded: they hold their triangles wherever the coordinates are numbers)
+	scene_facts_.boxes_enclose = true;
 }
 
 void DeviceScene::reserve(int device, size_t bytes) {

@@ -37,6 +37,8 @@
 //                   ao_rays_kernel<MODE> the rays themselves (kernels/directional.hip.h, include/rt_hip_directional.h).
 //                   multihit_walk_kernel<K> counts every triangle a caller-supplied ray's walk accepts and keeps the first K,
 //                   multihit_resolve_kernel writes their records (kernels/multihit.hip.h, include/rt_hip_multihit.h).
+//                   nearest_key_kernel / nearest_scatter_kernel order caller-supplied POINTS by position, nearest_kernel finds
+//                   the nearest point of the surface for each (kernels/nearest.hip.h, include/rt_hip_nearest.h).
 //                   layers_kernel<POSED, ARRAY> casts the frame's own rays for one pose or for every pose of a chunk of views, a wave
 //                   per (view, tile), and writes every sub-pixel's record, direction and head-light term (kernels/layers.hip.h,
 //                   include/rt_hip_layers.h, include/rt_hip_views.h).  ao_query_kernel runs over its points -- all of them
@@ -74,6 +76,7 @@
 #include "device_types.h"
 #include "exact_reciprocal.h"
 #include "lbvh.h"
+#include "nearest_point.h"
 #include "tri_predicate.h"
 
 #include "kernels/common.hip.h"
@@ -91,6 +94,7 @@
 #include "kernels/refit.hip.h"
 #include "kernels/build.hip.h"
 #include "kernels/node_test_forms.hip.h"
+#include "kernels/nearest.hip.h"
 
 
 namespace ocrt {
@@ -367,6 +371,67 @@ void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, 
 		hipLaunchKernelGGL(query_kernel<true>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
 	} else {
 		hipLaunchKernelGGL(query_kernel<false>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
+	}
+}
+
+// Closest-point queries (kernels/nearest.hip.h).  The sort: launch_query_sort's with a key of the position alone.
+void launch_nearest_sort(const void *points, uint32_t n, const float lo[3], const float scale[3], void *count, void *order, void *stream) {
+	if (n == 0)
+		return;
+	hipStream_t s = (hipStream_t) stream;
+	NearestKeyArgs a{};
+	a.points = (const float4 *) points;
+	a.count = (uint32_t *) count;
+	a.order = (uint32_t *) order;
+	a.n = n;
+	for (int k = 0; k < 3; ++k) {
+		a.lo[k] = lo[k];
+		a.scale[k] = scale[k];
+	}
+	(void) hipMemsetAsync(count, 0, QUERY_BUCKETS * sizeof(uint32_t), s);
+	const uint32_t blocks = (n + 255u) / 256u;
+	hipLaunchKernelGGL(nearest_key_kernel, dim3(blocks), dim3(256), 0, s, a);
+	hipLaunchKernelGGL(query_scan_kernel, dim3(1), dim3(QUERY_SCAN_THREADS), 0, s, (uint32_t *) count);
+	hipLaunchKernelGGL(nearest_scatter_kernel, dim3(blocks), dim3(256), 0, s, a);
+}
+
+// `flag`: one word on the device, set to 1 where a coordinate of `vertices4` (float4 each) is no number or beyond 1e37.
+void launch_nearest_coordinates(const void *vertices4, uint32_t num_vertices, void *flag, void *stream) {
+	(void) hipMemsetAsync(flag, 0, sizeof(uint32_t), (hipStream_t) stream);
+	if (num_vertices == 0)
+		return;
+	hipLaunchKernelGGL(nearest_coordinates_kernel, dim3((num_vertices + 255u) / 256u), dim3(256), 0, (hipStream_t) stream,
+	                   (const float4 *) vertices4, num_vertices, (uint32_t *) flag);
+}
+
+// `walk`: NEAREST_START | NEAREST_PRUNE as far as the scene allows them (ray_query.cc); `coords_flag`: that word, or null:
+// the host has seen the scene's coordinates; `counts`: two 64-bit words on the device, zeroed here on the stream, for the
+// counted form -- or null: the product's form.
+void launch_nearest(const SceneBuffers &scene, uint32_t node_count, uint32_t tri_count, const void *points, const void *order, uint32_t n,
+                    float max_distance, uint32_t walk, const QueryOutputs &out, const void *coords_flag, void *counts, void *stream) {
+	if (n == 0)
+		return;
+	NearestArgs a{};
+	a.coords_flag = (const uint32_t *) coords_flag;
+	a.nodes_ptr = (const float4 *) scene.nodes;
+	a.tris_ptr = (const float4 *) scene.tris;
+	a.shade = (const float4 *) scene.shade;
+	a.points = (const float4 *) points;
+	a.order = (const uint32_t *) order;
+	a.n = n;
+	a.node_count = node_count;
+	a.tri_count = tri_count;
+	a.max_distance = max_distance;
+	a.walk = walk;
+	a.out = out;
+	a.hit = out.hit;
+	a.counts = (unsigned long long *) counts;
+	const uint32_t blocks = (n + 64u * NEAREST_WAVES - 1u) / (64u * NEAREST_WAVES);
+	if (counts) {
+		(void) hipMemsetAsync(counts, 0, 2u * sizeof(unsigned long long), (hipStream_t) stream);
+		hipLaunchKernelGGL(nearest_kernel<true>, dim3(blocks), dim3(64 * NEAREST_WAVES), 0, (hipStream_t) stream, a);
+	} else {
+		hipLaunchKernelGGL(nearest_kernel<false>, dim3(blocks), dim3(64 * NEAREST_WAVES), 0, (hipStream_t) stream, a);
 	}
 }
 

@@ -50,7 +50,7 @@ RayQueries::~RayQueries() {
 		return;
 	if (timed)
 		(void) hipEventSynchronize((hipEvent_t) ev_stop);
-	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &ao_rows, &list, &views, &build })
+	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &ao_rows, &list, &views, &build, &coords_flag, &nearest_counts })
 		device_free(scratch->ptr);
 	for (void *ev : ev_build)
 		if (ev)
@@ -141,8 +141,10 @@ RayQueries::Enqueue RayQueries::begin(void *stream, const float *keys_a4, const 
 	if (sort)
 		sceneBox(*dev.deviceScene(), lo, scale);
 	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
-	if (sort)
+	if (sort && keys_b4)
 		launch_query_sort(keys_a4, keys_b4, n, lo, scale, count.ptr, order.ptr, s);
+	else if (sort)  // (points without a direction: the key of the position alone)
+		launch_nearest_sort(keys_a4, n, lo, scale, count.ptr, order.ptr, s);
 	return Enqueue{ s, sort ? order.ptr : nullptr };
 }
 
@@ -246,6 +248,67 @@ void RayQueries::traceHost(bool closest, const float *origins4, const float *dir
 	recordDevice(p + RAY_RECORDS, out);
 	traceDevice(closest, (const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, max_distance, flags, out, s);
 	stageOut(p, RAY_PIECES, s);
+}
+
+// What the closest-point walk may do follows from the scene: where every box holds the triangles beneath it -- an upload the
+// packer found so, the refit rule's boxes after an update or a build -- each lane descends for a starting bound and boxes are
+// passed by (kernels/nearest.hip.h); otherwise (damaged arrays) every leaf is tested.  After an update or a build whose
+// coordinates only the device has seen, the word they left (checkCoordinates) decides it once more, in the kernel.
+void RayQueries::nearestDevice(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, void *stream) {
+	requireScene("closest-point query");
+	if (n == 0)
+		return;
+	const std::shared_ptr<const DeviceScene> scene = dev.deviceScene();
+	uint32_t walk = scene->boxesEnclose() ? 3u : 0u;  // NEAREST_START | NEAREST_PRUNE
+	if (nearest_debug & 1u)
+		walk &= ~1u;
+	if (nearest_debug & 2u)
+		walk = 0u;
+	const bool counting = (nearest_debug & 4u) != 0u;
+	const Enqueue q = begin(stream, points4, nullptr, n, n, flags, { Need{ counting ? &nearest_counts : nullptr, 2u * sizeof(uint64_t) } });
+	launch_nearest(scene->buffers(), scene->nodeCount(), scene->triCount(), points4, q.order, n, max_distance, walk, out,
+	               flagged.lock() == scene ? coords_flag.ptr : nullptr, counting ? nearest_counts.ptr : nullptr, q.stream);
+	nearest_counted = counting;
+	end(q);
+}
+
+void RayQueries::nearestHost(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &host) {
+	requireScene("closest-point query");
+	if (n == 0)
+		return;
+	// (the second piece stays empty: the points have no directions)
+	Staged p[RAY_PIECES] = { input(points4, (size_t) n * 16u), input(nullptr, 0u), output(host.hit, n) };
+	recordPieces(p + RAY_RECORDS, host, n);
+	void *s = stageIn(p, RAY_PIECES);
+	QueryOutputs out;
+	out.hit = (unsigned char *) p[RAY_FIRST].device;
+	recordDevice(p + RAY_RECORDS, out);
+	nearestDevice((const float *) p[RAY_ORIGINS].device, n, max_distance, flags, out, s);
+	stageOut(p, RAY_PIECES, s);
+}
+
+void RayQueries::setNearestWalk(uint32_t debug_flags) {
+#ifndef OCRT_DEBUG_KNOBS
+	if (debug_flags != 0u)
+		throw std::logic_error("the closest-point walk's switches and counters are the A/B build's (-DOCRT_DEBUG_KNOBS)");
+#endif
+	nearest_debug = debug_flags & 7u;
+}
+
+void RayQueries::lastNearestCounts(uint64_t counts[2]) {
+	counts[0] = counts[1] = 0u;
+	if (!nearest_counted || !nearest_counts.ptr)
+		return;
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	if (timed)
+		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
+	OCRT_HIP(hipMemcpy(counts, nearest_counts.ptr, 2u * sizeof(uint64_t), hipMemcpyDeviceToHost));
+}
+
+// Behind an update's or a build's own launches, on their stream: the word the closest-point queries of `scene` read.
+void RayQueries::checkCoordinates(const std::shared_ptr<const DeviceScene> &scene, const float *vertices4, uint32_t num_vertices, void *stream) {
+	launch_nearest_coordinates(vertices4, num_vertices, coords_flag.ptr, stream);
+	flagged = scene;
 }
 
 void RayQueries::multihitDevice(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
@@ -633,10 +696,12 @@ void RayQueries::updateDevice(const float *vertices4, const float *vnormals4, ui
 	// or not: no frame may lean on the old walk array again, and the sort's box is read afresh)
 	dev.markSceneUpdated();
 	boxed.reset();
+	grow(coords_flag, sizeof(uint32_t));
 	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
 	OCRT_HIP(hipEventRecord((hipEvent_t) ev_update_start, s));
 	scene->updateVertices(vertices4, vnormals4, dev.refitGroup(), s);
 	OCRT_HIP(hipEventRecord((hipEvent_t) ev_update_stop, s));
+	checkCoordinates(dev.deviceScene(), vertices4, num_vertices, s);  // (for the closest-point queries; not part of the update's own time)
 	update_timed = true;
 	have_update_ms = false;
 	end(Enqueue{ s, nullptr });
@@ -697,6 +762,7 @@ void RayQueries::buildDevice(const float *vertices4, const float *vnormals4, uin
 		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_frames, 0));
 	}
 	grow(build, DeviceScene::buildScratchBytes(num_faces));
+	grow(coords_flag, sizeof(uint32_t));
 	build_timed = false;
 	std::shared_ptr<DeviceScene> made = DeviceScene::build(dev.deviceIndex(), dev.options(), vertices4, vnormals4, num_vertices, faces, num_faces,
 	                                                       dev.refitGroup(), build.ptr, s, ev_build, &last_build_ms[2]);
@@ -704,6 +770,7 @@ void RayQueries::buildDevice(const float *vertices4, const float *vnormals4, uin
 	have_build_ms = false;
 	dev.adoptBuilt(std::move(made));  // (waits for the renderer's own stream and lets the old scene go)
 	boxed.reset();
+	checkCoordinates(dev.deviceScene(), vertices4, num_vertices, s);
 	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
 	end(Enqueue{ s, nullptr });
 }

@@ -36,6 +36,15 @@ class RayQueries {
 		// Host memory, blocking.
 		void multihitHost(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
 		                  const MultiHitOutputs &out);
+		// Closest-point queries (include/rt_hip_nearest.h): the nearest point of the surface for each of n points, the record
+		// of a closest hit (out.hit: `found`).  Device memory, enqueued on `stream` (null: the renderer's).
+		void nearestDevice(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, void *stream);
+		// Host memory, blocking.
+		void nearestHost(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out);
+		// (include/rt_hip_debug.h) how the later closest-point queries walk (RT_DEBUG_NEAREST_*; the A/B build's: std::logic_error
+		// for a flag in the product library), and the counts of the last counted one (waits for it)
+		void setNearestWalk(uint32_t debug_flags);
+		void lastNearestCounts(uint64_t counts[2]);
 		// Ambient-occlusion queries (include/rt_hip_ao.h): the reference's ambient_occlusion() of n points with the options
 		// the scene was uploaded for -- table, mode, rays per point, divisor and reach come from the renderer's launch
 		// constants and its DeviceScene.  std::logic_error where those options have ambient occlusion off.
@@ -207,6 +216,15 @@ class RayQueries {
 		void *ev_build[4] = { nullptr, nullptr, nullptr, nullptr };  // around a build's two runs of launches
 		bool build_timed = false, have_build_ms = false;
 		float last_build_ms[3] = { 0.0f, 0.0f, 0.0f };  // topology, records, the host's step between them
+		// Closest-point queries.  coords_flag: one word on the device, non-zero where the last update or build through this
+		// object was given a coordinate that is no number or beyond 1e37 (checked on the device, behind the update's own
+		// launches: the device-memory forms cannot look) -- the boxes of `flagged` then promise nothing and its closest-point
+		// walks pass no box by.  nearest_counts: the counted form's two words.
+		void checkCoordinates(const std::shared_ptr<const DeviceScene> &scene, const float *vertices4, uint32_t num_vertices, void *stream);
+		Scratch coords_flag, nearest_counts;
+		std::weak_ptr<const DeviceScene> flagged;  // the scene coords_flag speaks of
+		uint32_t nearest_debug = 0;
+		bool nearest_counted = false;
 		std::weak_ptr<const DeviceScene> boxed;  // the scene box_lo / box_scale were read from
 		float box_lo[3] = { 0, 0, 0 }, box_scale[3] = { 0, 0, 0 };
 };
@@ -216,6 +234,10 @@ void launch_query_sort(const void *origins, const void *directions, uint32_t n, 
                        void *order, void *stream);
 void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *origins, const void *directions,
                   const void *order, uint32_t n, float max_distance, const QueryOutputs &out, void *stream);
+void launch_nearest_sort(const void *points, uint32_t n, const float lo[3], const float scale[3], void *count, void *order, void *stream);
+void launch_nearest(const SceneBuffers &scene, uint32_t node_count, uint32_t tri_count, const void *points, const void *order, uint32_t n,
+                    float max_distance, uint32_t walk, const QueryOutputs &out, const void *coords_flag, void *counts, void *stream);
+void launch_nearest_coordinates(const void *vertices4, uint32_t num_vertices, void *flag, void *stream);
 void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void *origins, const void *directions, const void *order,
                      uint32_t n, float max_distance, uint32_t k, void *list, const MultiHitOutputs &out, void *stream);
 void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,

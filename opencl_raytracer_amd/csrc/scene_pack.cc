@@ -238,6 +238,15 @@ PackedScene pack_scene(const std::vector<uint32_t> &faces, const std::vector<uin
 				out.tris[n.leaf].lo[k] = n.lo[k];
 				out.tris[n.leaf].hi[k] = n.hi[k];
 			}
+	// ... and whether that box holds its triangle (negated comparisons: a NaN holds nothing)
+	out.enclosing = out.regular && out.nested;
+	for (size_t t = 0; out.enclosing && t < tri_count; ++t)
+		for (unsigned c = 0; c < 3; ++c)
+			for (unsigned k = 0; k < 3; ++k) {
+				const float x = vertices[faces[3 * t + c]][k];
+				if (!(out.tris[t].lo[k] <= x) || !(x <= out.tris[t].hi[k]))
+					out.enclosing = false;
+			}
 	return out;
 }
 
@@ -679,6 +688,7 @@ SceneFacts scene_facts(const PackedScene &scene, const WalkArray &walk) {
 	f.unpruned_bytes = walk.unpruned_bytes;
 	f.primary_bytes = walk.primary_bytes;
 	f.ce_offset = walk.ce_offset;
+	f.boxes_enclose = scene.enclosing;
 	return f;
 }
 

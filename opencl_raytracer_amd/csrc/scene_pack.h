@@ -48,6 +48,8 @@ struct PackedScene {
 	bool nested = false;       // ... and every node's box contains its children's boxes (true for any tree built by
 	                           // uniting child boxes; arbitrary uploaded arrays need not be)
 	bool rebuilt = false;      // `nodes` is the rebuilt tree, not the uploaded one
+	bool enclosing = false;    // regular, nested, and every leaf's box holds the three vertices of its triangle: a box then
+	                           // holds every triangle beneath it, what the closest-point walk prunes by (kernels/nearest.hip.h)
 	// What a vertex update needs beside the records (include/rt_hip_update.h; TriRec replaced the face indices): the
 	// leaf-ordered faces as uploaded, shared so that the scene on the device keeps them without a copy, and how many
 	// vertices they index.
@@ -123,6 +125,7 @@ struct SceneFacts {
 	float origin_limit = 0.0f, ao_scale = 0.0f;                  // WalkArray's
 	float prune_margin = 0.0f;                                   // WalkArray's
 	uint32_t unpruned_bytes = 0, primary_bytes = 0, ce_offset = 0;
+	bool boxes_enclose = false;                                  // PackedScene::enclosing
 };
 SceneFacts scene_facts(const PackedScene &scene, const WalkArray &walk);
 // `pose`: the host's camera pose (nullptr: none was given -- KernelParams::posed = 0, the reference's camera).
