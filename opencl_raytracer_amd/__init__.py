@@ -11,7 +11,10 @@ from .api import (  # noqa: F401
     DIRECTIONAL_OUTPUTS,
     LAYER_OUTPUTS,
     NEAREST_OUTPUTS,
+    SEGMENT_INTERVAL,
+    SEGMENT_OUTPUTS,
     VIEW_OUTPUTS,
+    VISIBILITY_OUTPUTS,
     Camera,
     FrameRing,
     Host,
@@ -28,4 +31,5 @@ from .api import (  # noqa: F401
     rccl_unique_id,
     resize_cpu,
     unpack_ao_mask,
+    unpack_visibility_mask,
 )

@@ -1,5 +1,5 @@
 """ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h, rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h,
-rt_hip_nearest.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers
+rt_hip_nearest.h, rt_hip_segment.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers
 for the contract)."""
 from __future__ import annotations
 
@@ -229,6 +229,17 @@ _SIGNATURES = {
     "rt_trace_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
                                            C.c_void_p]),
     "rt_last_query_ms": (C.c_float, [C.c_void_p]),
+    # include/rt_hip_segment.h
+    "rt_segments_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_void_p]),
+    "rt_segments_closest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_void_p]),
+    "rt_segments_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32,
+                                              C.c_void_p, C.c_void_p]),
+    "rt_segments_closest_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32,
+                                             C.c_void_p, C.c_void_p]),
+    "rt_visibility_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32,
+                                      C.c_void_p]),
+    "rt_visibility_masks_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_float,
+                                             C.c_uint32, C.c_void_p, C.c_void_p]),
     # include/rt_hip_nearest.h
     "rt_closest_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
     "rt_closest_points_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
@@ -299,6 +310,11 @@ class _DirectionalArrays(C.Structure):
     _fields_ = [("ao", C.c_void_p), ("occluded", C.c_void_p), ("mask", C.c_void_p), ("bent", C.c_void_p)]
 
 
+class _VisibilityArrays(C.Structure):
+    """rt_visibility_arrays (include/rt_hip_segment.h)."""
+    _fields_ = [("mask", C.c_void_p), ("count", C.c_void_p)]
+
+
 class _LayerArrays(C.Structure):
     """rt_layer_arrays (include/rt_hip_layers.h)."""
     _fields_ = _HitArrays._fields_ + [("direction", C.c_void_p), ("shade", C.c_void_p), ("ao", C.c_void_p), ("value", C.c_void_p)]
@@ -321,6 +337,9 @@ RT_MULTIHIT_MAX_K = 16
 MULTIHIT_OUTPUTS = ("count", "distance", "leaf", "barycentric", "position", "normal")
 QUERY_OUTPUTS = ("hit", "distance", "leaf", "barycentric", "position", "normal")
 NEAREST_OUTPUTS = QUERY_OUTPUTS  # closest-point queries: "hit" is `found`
+SEGMENT_OUTPUTS = QUERY_OUTPUTS  # segment queries, the closest form: "hit" is "the segment has a blocker"
+VISIBILITY_OUTPUTS = ("mask", "count")
+SEGMENT_INTERVAL = (1e-4, 1 - 1e-4)  # the default (t_lo, t_hi) of the segment queries, fractions of the segment
 AO_OUTPUTS = ("ao", "occluded")
 DIRECTIONAL_OUTPUTS = ("ao", "occluded", "mask", "bent")
 LAYER_OUTPUTS = QUERY_OUTPUTS + ("direction", "shade", "ao", "value")
@@ -458,6 +477,12 @@ def unpack_ao_mask(mask, rays: int):
     if not isinstance(mask, np.ndarray) or mask.dtype != np.uint32:
         raise ValueError("mask: expected uint32 words")
     return ((mask[:, k >> 5] >> (k & 31).astype(np.uint32)) & np.uint32(1)).astype(bool)
+
+
+def unpack_visibility_mask(mask, targets: int):
+    """The (P, W) uint32 mask rows of Host.visibility as booleans: (P, targets), [i, j] True iff the segment from point i to
+    target j is OCCLUDED.  numpy in, numpy out; torch in, torch out on the same device."""
+    return unpack_ao_mask(mask, targets)  # (the same layout: bit j & 31 of word j >> 5)
 
 
 def load_library() -> C.CDLL:
@@ -875,6 +900,65 @@ class Host:
             io.call(self._h, "rt_trace_closest", *args, C.byref(_HitArrays(*io.pointers(out, QUERY_OUTPUTS))))
         else:
             io.call(self._h, "rt_trace_occluded", *args, *io.pointers(out, ("hit",)))
+        return out
+
+    # ---- segment queries (include/rt_hip_segment.h) ----
+    def segments_occluded(self, a, b, interval=SEGMENT_INTERVAL, sort: bool = True):
+        """Line of sight: uint8 (N,), 1 iff something blocks the segment from a[i] to b[i] at a fraction r of it with
+        interval[0] < r < interval[1].  a, b: (N, 3) / (N, 4) float32.  numpy in, numpy out (blocking); torch tensors on the
+        host's GPU in, a torch tensor out, enqueued on torch.cuda.current_stream() without waiting (as for trace_occluded)."""
+        return self._segments(False, a, b, interval, ("hit",), sort)["hit"]
+
+    def segments_closest(self, a, b, interval=SEGMENT_INTERVAL, outputs=SEGMENT_OUTPUTS, sort: bool = True) -> dict:
+        """The first blocker of every segment, the record of trace_closest: {"hit": uint8 (N,), "distance": float32 (N,) --
+        a length from a[i], not a fraction --, "leaf", "barycentric", "position", "normal"} (those named in `outputs`);
+        without a blocker: +inf, 0xFFFFFFFF, zeros.  Inputs and forms as for segments_occluded."""
+        return self._segments(True, a, b, interval, tuple(outputs), sort)
+
+    def _segments(self, closest: bool, a, b, interval, outputs: tuple, sort: bool) -> dict:
+        unknown = [o for o in outputs if o not in SEGMENT_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {SEGMENT_OUTPUTS}")
+        t_lo, t_hi = interval
+        io = _QueryArrays(a, b, ("a", "b"), "points")
+        out = io.outputs(outputs)
+        args = (io.n, float(t_lo), float(t_hi), 0 if sort else RT_QUERY_NO_SORT)
+        if closest:
+            io.call(self._h, "rt_segments_closest", *args, C.byref(_HitArrays(*io.pointers(out, SEGMENT_OUTPUTS))))
+        else:
+            io.call(self._h, "rt_segments_occluded", *args, *io.pointers(out, ("hit",)))
+        return out
+
+    def visibility(self, points, targets, interval=SEGMENT_INTERVAL, outputs=VISIBILITY_OUTPUTS, sort: bool = True) -> dict:
+        """Every point against every target: {"mask": uint32 (P, W), W = ceil(T / 32) -- bit j & 31 of word j >> 5 of row i
+        is 1 iff the segment from points[i] to targets[j] is occluded, padding bits 0 (unpack_visibility_mask makes booleans
+        of it) --, "count": uint32 (P,), the row's popcount: the targets point i does NOT see} (those named in `outputs`).
+        points: (P, 3) / (P, 4), targets: (T, 3) / (T, 4) float32, P T <= 2^27; the P x T rays are never written out.
+        numpy / torch forms as for segments_occluded."""
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in VISIBILITY_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {VISIBILITY_OUTPUTS}")
+        t_lo, t_hi = interval
+        both = _is_torch(points), _is_torch(targets)
+        if both[0] != both[1]:
+            raise ValueError("points and targets must both be torch tensors or both numpy arrays")
+        io = _QueryArrays(points, None, ("points",), "points")
+        pad = _rays4_torch if io.torch else _rays4_numpy
+        targets4 = pad(targets, "targets")
+        if io.torch and targets4.device != io.a.device:
+            raise ValueError("points and targets must be on the same device")
+        nt = int(targets4.shape[0])
+        words = (nt + 31) // 32
+        out = io.outputs(outputs, shapes={"mask": (np.uint32, (words,))})
+        pointers = [io.ptr(out[name]) if name in out and io.n and nt else None for name in VISIBILITY_OUTPUTS]
+        if io.n and nt == 0:  # (nothing is launched: the rows have no words, every count is 0)
+            for name in out:
+                out[name][...] = 0
+        io.call(self._h, "rt_visibility_masks", io.n, io.ptr(targets4) if nt else None, nt, float(t_lo), float(t_hi),
+                0 if sort else RT_QUERY_NO_SORT, C.byref(_VisibilityArrays(*pointers)))
+        if io.torch and targets4 is not targets:  # (the padded copy must live until the kernels have read it)
+            targets4.record_stream(io.current)
         return out
 
     # ---- closest-point queries (include/rt_hip_nearest.h) ----

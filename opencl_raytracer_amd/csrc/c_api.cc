@@ -10,6 +10,7 @@
 #include "../../include/rt_hip_multihit.h"
 #include "../../include/rt_hip_nearest.h"
 #include "../../include/rt_hip_query.h"
+#include "../../include/rt_hip_segment.h"
 #include "../../include/rt_hip_views.h"
 #include "../../include/rt_hip_update.h"
 #include "../../include/rt_hip_build.h"
@@ -957,6 +958,95 @@ int rt_trace_occluded_device(rt_host *h, const float *origins4, const float *dir
 	ocrt::QueryOutputs q;
 	q.hit = occluded;
 	return guarded([&] { queries_of(h).traceDevice(false, origins4, directions4, n, max_distance, flags, q, hip_stream); });
+}
+
+// ---- rt_hip_segment.h ----
+namespace {
+
+// The checks of include/rt_hip_segment.h ("Errors"): `items` segments -- or pairs of a mask -- between the points of two arrays.
+int segment_precheck(rt_host *h, const float *a4, const float *b4, uint64_t items, bool device) {
+	const int rc = host_precheck(h, "segment");
+	if (rc != RT_OK)
+		return rc;
+	if (items > RT_QUERY_MAX_RAYS)
+		return fail(RT_E_INVALID, "more segments than RT_QUERY_MAX_RAYS in one call");
+	if (items > 0 && (!a4 || !b4))
+		return fail(RT_E_INVALID, "null point arrays");
+	if (device && items > 0 && !aligned({ a4, b4 }, 16))
+		return fail(RT_E_INVALID, "device point arrays must be 16-byte aligned");
+	return RT_OK;
+}
+
+ocrt::RayQueries::VisibilityOutputs visibility_outputs(const rt_visibility_arrays *from) {
+	ocrt::RayQueries::VisibilityOutputs q;
+	if (!from)
+		return q;
+	q.mask = from->mask;
+	q.count = from->count;
+	return q;
+}
+
+}  // namespace
+
+int rt_segments_closest(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+                        const rt_hit_arrays *out) {
+	const int rc = segment_precheck(h, from4, to4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	return guarded([&] { queries_of(h).segmentsHost(true, from4, to4, n, t_lo, t_hi, flags, hit_outputs(out)); });
+}
+
+int rt_segments_occluded(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+                         uint8_t *occluded) {
+	const int rc = segment_precheck(h, from4, to4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	ocrt::QueryOutputs q;
+	q.hit = occluded;
+	return guarded([&] { queries_of(h).segmentsHost(false, from4, to4, n, t_lo, t_hi, flags, q); });
+}
+
+int rt_segments_closest_device(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+                               const rt_hit_arrays *out, void *hip_stream) {
+	const int rc = segment_precheck(h, from4, to4, n, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	const ocrt::QueryOutputs q = hit_outputs(out);
+	if (!records_aligned(q))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).segmentsDevice(true, from4, to4, n, t_lo, t_hi, flags, q, hip_stream); });
+}
+
+int rt_segments_occluded_device(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+                                uint8_t *occluded, void *hip_stream) {
+	const int rc = segment_precheck(h, from4, to4, n, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	ocrt::QueryOutputs q;
+	q.hit = occluded;
+	return guarded([&] { queries_of(h).segmentsDevice(false, from4, to4, n, t_lo, t_hi, flags, q, hip_stream); });
+}
+
+int rt_visibility_masks(rt_host *h, const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
+                        uint32_t flags, const rt_visibility_arrays *out) {
+	const uint64_t pairs = (uint64_t) np * nt;
+	const int rc = segment_precheck(h, points4, targets4, pairs, false);
+	if (rc != RT_OK || pairs == 0)
+		return rc;
+	const ocrt::RayQueries::VisibilityOutputs q = visibility_outputs(out);
+	return guarded([&] { queries_of(h).visibilityHost(points4, np, targets4, nt, t_lo, t_hi, flags, q); });
+}
+
+int rt_visibility_masks_device(rt_host *h, const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo,
+                               float t_hi, uint32_t flags, const rt_visibility_arrays *out, void *hip_stream) {
+	const uint64_t pairs = (uint64_t) np * nt;
+	const int rc = segment_precheck(h, points4, targets4, pairs, true);
+	if (rc != RT_OK || pairs == 0)
+		return rc;
+	const ocrt::RayQueries::VisibilityOutputs q = visibility_outputs(out);
+	if (!aligned({ q.mask, q.count }, 4))
+		return fail(RT_E_INVALID, "device uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).visibilityDevice(points4, np, targets4, nt, t_lo, t_hi, flags, q, hip_stream); });
 }
 
 // ---- rt_hip_nearest.h ----

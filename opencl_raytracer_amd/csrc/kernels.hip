@@ -39,6 +39,10 @@
 //                   multihit_resolve_kernel writes their records (kernels/multihit.hip.h, include/rt_hip_multihit.h).
 //                   nearest_key_kernel / nearest_scatter_kernel order caller-supplied POINTS by position, nearest_kernel finds
 //                   the nearest point of the surface for each (kernels/nearest.hip.h, include/rt_hip_nearest.h).
+//                   segment_kernel<CLOSEST> answers whether the line between two caller-supplied points is free, or where it is
+//                   blocked first (segment_key_kernel / segment_scatter_kernel order the segments), visibility_mask_kernel
+//                   does so for P points against T targets, a bit per pair, visibility_count_kernel counts a point's bits
+//                   (kernels/segment.hip.h, include/rt_hip_segment.h).
 //                   layers_kernel<POSED, ARRAY> casts the frame's own rays for one pose or for every pose of a chunk of views, a wave
 //                   per (view, tile), and writes every sub-pixel's record, direction and head-light term (kernels/layers.hip.h,
 //                   include/rt_hip_layers.h, include/rt_hip_views.h).  ao_query_kernel runs over its points -- all of them
@@ -95,6 +99,7 @@
 #include "kernels/build.hip.h"
 #include "kernels/node_test_forms.hip.h"
 #include "kernels/nearest.hip.h"
+#include "kernels/segment.hip.h"
 
 
 namespace ocrt {
@@ -322,8 +327,9 @@ void launch_resize(const float *tmp, unsigned char *out, const KernelParams &P, 
 }
 
 // Ray queries (kernels/query.hip.h).  `count`: QUERY_BUCKETS words of scratch, `order`: n words; both on the device.
+// `segments`: the two arrays are the ends (a, b) of segments, keyed as the rays (a, b - a) (kernels/segment.hip.h).
 void launch_query_sort(const void *origins, const void *directions, uint32_t n, const float lo[3], const float scale[3], void *count,
-                       void *order, void *stream) {
+                       void *order, void *stream, bool segments) {
 	if (n == 0)
 		return;
 	hipStream_t s = (hipStream_t) stream;
@@ -339,9 +345,11 @@ void launch_query_sort(const void *origins, const void *directions, uint32_t n, 
 	}
 	(void) hipMemsetAsync(count, 0, QUERY_BUCKETS * sizeof(uint32_t), s);
 	const uint32_t blocks = (n + 255u) / 256u;
-	hipLaunchKernelGGL(query_key_kernel, dim3(blocks), dim3(256), 0, s, a);
+	const auto key_kernel = segments ? segment_key_kernel : query_key_kernel;
+	const auto scatter_kernel = segments ? segment_scatter_kernel : query_scatter_kernel;
+	hipLaunchKernelGGL(key_kernel, dim3(blocks), dim3(256), 0, s, a);
 	hipLaunchKernelGGL(query_scan_kernel, dim3(1), dim3(QUERY_SCAN_THREADS), 0, s, (uint32_t *) count);
-	hipLaunchKernelGGL(query_scatter_kernel, dim3(blocks), dim3(256), 0, s, a);
+	hipLaunchKernelGGL(scatter_kernel, dim3(blocks), dim3(256), 0, s, a);
 }
 
 // (what query_kernel and the multi-hit kernels are launched with alike)
@@ -433,6 +441,62 @@ void launch_nearest(const SceneBuffers &scene, uint32_t node_count, uint32_t tri
 	} else {
 		hipLaunchKernelGGL(nearest_kernel<false>, dim3(blocks), dim3(64 * NEAREST_WAVES), 0, (hipStream_t) stream, a);
 	}
+}
+
+// Segment queries (kernels/segment.hip.h); their sort is launch_query_sort's with `segments`.
+// `closest` false: occlusion into out.hit alone.
+void launch_segments(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *from, const void *to, const void *order,
+                     uint32_t n, float t_lo, float t_hi, const QueryOutputs &out, void *stream) {
+	if (n == 0)
+		return;
+	SegmentArgs a{};
+	a.nodes_ptr = (const float4 *) scene.nodes;
+	a.tris_ptr = (const float4 *) scene.tris;
+	a.shade = (const float4 *) scene.shade;
+	a.from = (const float4 *) from;
+	a.to = (const float4 *) to;
+	a.order = (const uint32_t *) order;
+	a.n = n;
+	a.node_count = node_count;
+	a.t_lo = t_lo;
+	a.t_hi = t_hi;
+	a.out = out;
+	a.hit = out.hit;
+	const uint32_t blocks = (n + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
+	if (closest) {
+		hipLaunchKernelGGL(segment_kernel<true>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
+	} else {
+		hipLaunchKernelGGL(segment_kernel<false>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
+	}
+}
+
+// The many-to-many form.  `mask`: np rows of ceil(nt / 32) words on the device (the caller's array or scratch), zeroed here
+// on the stream; `order`: launch_nearest_sort's order of the POINTS or null; `count`: null = not written.
+void launch_visibility(const SceneBuffers &scene, uint32_t node_count, const void *points, uint32_t np, const void *targets, uint32_t nt,
+                       const void *order, float t_lo, float t_hi, uint32_t *mask, uint32_t *count, void *stream) {
+	if (np == 0 || nt == 0)
+		return;
+	hipStream_t s = (hipStream_t) stream;
+	VisibilityArgs a{};
+	a.nodes_ptr = (const float4 *) scene.nodes;
+	a.tris_ptr = (const float4 *) scene.tris;
+	a.points = (const float4 *) points;
+	a.targets = (const float4 *) targets;
+	a.order = (const uint32_t *) order;
+	a.mask = mask;
+	a.np = np;
+	a.nt = nt;
+	a.words = (nt + 31u) / 32u;
+	a.total = np * nt;  // (<= RT_QUERY_MAX_RAYS: checked at the boundary)
+	visibility_divisor(nt, a.magic, a.shift);
+	a.node_count = node_count;
+	a.t_lo = t_lo;
+	a.t_hi = t_hi;
+	(void) hipMemsetAsync(mask, 0, (size_t) np * a.words * sizeof(uint32_t), s);
+	const uint32_t blocks = (a.total + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
+	hipLaunchKernelGGL(visibility_mask_kernel, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+	if (count)
+		hipLaunchKernelGGL(visibility_count_kernel, dim3((np + 255u) / 256u), dim3(256), 0, s, (const uint32_t *) mask, count, np, a.words);
 }
 
 // Ambient-occlusion queries (kernels/ao_query.hip.h).  `count`: n words on the device (the caller's `occluded` array or

@@ -1,4 +1,4 @@
-// ray_query.cc -- ray queries, multi-hit queries, ambient-occlusion queries, frame layers and multi-view rendering on a render
+// ray_query.cc -- ray queries, segment queries, multi-hit queries, ambient-occlusion queries, frame layers and multi-view rendering on a render
 // host's uploaded scene (ray_query.h).
 #include "ray_query.h"
 
@@ -25,6 +25,8 @@ enum { AO_POINTS, AO_NORMALS, AO_COUNTS, AO_SEEDS, AO_VALUES, AO_PIECES };
 // the rays of the points: the inputs and the two ray arrays.
 enum { DIR_POINTS, DIR_NORMALS, DIR_SEEDS, DIR_ROWS, DIR_COUNTS, DIR_VALUES, DIR_BENT, DIR_PIECES };
 enum { AORAY_POINTS, AORAY_NORMALS, AORAY_SEEDS, AORAY_ORIGINS, AORAY_DIRECTIONS, AORAY_PIECES };
+// Visibility masks: the two inputs, the rows (staged whether they are copied back or not), the counts.
+enum { VIS_POINTS, VIS_TARGETS, VIS_ROWS, VIS_COUNTS, VIS_PIECES };
 // Frame layers: the hit flags, the five record arrays, then the four layers of their own.
 enum { LAYER_HIT, LAYER_RECORDS, LAYER_DIRECTION = LAYER_RECORDS + 5, LAYER_SHADE, LAYER_AO, LAYER_VALUE, LAYER_PIECES };
 // Multi-view rendering: the layers' pieces, then the 8-bit images.
@@ -50,7 +52,7 @@ RayQueries::~RayQueries() {
 		return;
 	if (timed)
 		(void) hipEventSynchronize((hipEvent_t) ev_stop);
-	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &ao_rows, &list, &views, &build, &coords_flag, &nearest_counts })
+	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &ao_rows, &vis_rows, &list, &views, &build, &coords_flag, &nearest_counts })
 		device_free(scratch->ptr);
 	for (void *ev : ev_build)
 		if (ev)
@@ -124,7 +126,7 @@ void RayQueries::sceneBox(const DeviceScene &scene, float lo[3], float scale[3])
 // synchronises), ev_start, and the sort of the n items keyed by (keys_a4, keys_b4) where the call allows it and makes
 // RT_QUERY_SORT_MIN `rays` or more.
 RayQueries::Enqueue RayQueries::begin(void *stream, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags,
-                                      std::initializer_list<Need> needs) {
+                                      std::initializer_list<Need> needs, bool segments) {
 	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
 	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
 	if (timed)
@@ -142,7 +144,7 @@ RayQueries::Enqueue RayQueries::begin(void *stream, const float *keys_a4, const 
 		sceneBox(*dev.deviceScene(), lo, scale);
 	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
 	if (sort && keys_b4)
-		launch_query_sort(keys_a4, keys_b4, n, lo, scale, count.ptr, order.ptr, s);
+		launch_query_sort(keys_a4, keys_b4, n, lo, scale, count.ptr, order.ptr, s, segments);
 	else if (sort)  // (points without a direction: the key of the position alone)
 		launch_nearest_sort(keys_a4, n, lo, scale, count.ptr, order.ptr, s);
 	return Enqueue{ s, sort ? order.ptr : nullptr };
@@ -248,6 +250,65 @@ void RayQueries::traceHost(bool closest, const float *origins4, const float *dir
 	recordDevice(p + RAY_RECORDS, out);
 	traceDevice(closest, (const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, max_distance, flags, out, s);
 	stageOut(p, RAY_PIECES, s);
+}
+
+void RayQueries::segmentsDevice(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+                                const QueryOutputs &out, void *stream) {
+	requireScene("segment query");
+	if (n == 0)
+		return;
+	const Enqueue q = begin(stream, from4, to4, n, n, flags, {}, true);
+	launch_segments(dev.deviceScene()->buffers(), dev.params().node_count, closest, from4, to4, q.order, n, t_lo, t_hi, out, q.stream);
+	end(q);
+}
+
+void RayQueries::segmentsHost(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+                              const QueryOutputs &host) {
+	requireScene("segment query");
+	if (n == 0)
+		return;
+	QueryOutputs want;  // (occlusion: the flags alone)
+	if (closest)
+		want = host;
+	want.hit = host.hit;
+	Staged p[RAY_PIECES] = { input(from4, (size_t) n * 16u), input(to4, (size_t) n * 16u), output(want.hit, n) };
+	recordPieces(p + RAY_RECORDS, want, n);
+	void *s = stageIn(p, RAY_PIECES);
+	QueryOutputs out;
+	out.hit = (unsigned char *) p[RAY_FIRST].device;
+	recordDevice(p + RAY_RECORDS, out);
+	segmentsDevice(closest, (const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, t_lo, t_hi, flags, out, s);
+	stageOut(p, RAY_PIECES, s);
+}
+
+void RayQueries::visibilityDevice(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
+                                  uint32_t flags, const VisibilityOutputs &out, void *stream) {
+	requireScene("visibility query");
+	if (np == 0 || nt == 0 || !out.any())
+		return;
+	const size_t row_bytes = (size_t) visibilityWords(nt) * sizeof(uint32_t);
+	// the POINTS are ordered, by position alone, from RT_QUERY_SORT_MIN of them on; the rows are the caller's, or scratch where
+	// only the counts are wanted
+	const Enqueue q = begin(stream, points4, nullptr, np, np, flags, { Need{ out.mask ? nullptr : &vis_rows, (size_t) np * row_bytes } });
+	launch_visibility(dev.deviceScene()->buffers(), dev.params().node_count, points4, np, targets4, nt, q.order, t_lo, t_hi,
+	                  out.mask ? out.mask : (uint32_t *) vis_rows.ptr, out.count, q.stream);
+	end(q);
+}
+
+void RayQueries::visibilityHost(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
+                                const VisibilityOutputs &host) {
+	requireScene("visibility query");
+	if (np == 0 || nt == 0 || !host.any())
+		return;
+	const size_t row_bytes = (size_t) visibilityWords(nt) * sizeof(uint32_t);
+	Staged p[VIS_PIECES] = { input(points4, (size_t) np * 16u), input(targets4, (size_t) nt * 16u), scratch(host.mask, (size_t) np * row_bytes),
+		                     output(host.count, (size_t) np * 4u) };
+	void *s = stageIn(p, VIS_PIECES);
+	VisibilityOutputs out;
+	out.mask = (uint32_t *) p[VIS_ROWS].device;
+	out.count = (uint32_t *) p[VIS_COUNTS].device;
+	visibilityDevice((const float *) p[VIS_POINTS].device, np, (const float *) p[VIS_TARGETS].device, nt, t_lo, t_hi, flags, out, s);
+	stageOut(p, VIS_PIECES, s);
 }
 
 // What the closest-point walk may do follows from the scene: where every box holds the triangles beneath it -- an upload the

@@ -1,6 +1,6 @@
 // ray_query.h -- ray queries, multi-hit queries, ambient-occlusion queries, frame layers and multi-view rendering on a render
 // host's uploaded scene (include/rt_hip_query.h, include/rt_hip_multihit.h, include/rt_hip_ao.h, include/rt_hip_directional.h,
-// include/rt_hip_layers.h, include/rt_hip_views.h; kernels/query.hip.h, kernels/multihit.hip.h, kernels/ao_query.hip.h,
+// include/rt_hip_layers.h, include/rt_hip_views.h, include/rt_hip_segment.h; kernels/query.hip.h, kernels/segment.hip.h, kernels/multihit.hip.h, kernels/ao_query.hip.h,
 // kernels/directional.hip.h, kernels/layers.hip.h, kernels/views.hip.h).
 #pragma once
 #include <cstdint>
@@ -45,6 +45,28 @@ class RayQueries {
 		// for a flag in the product library), and the counts of the last counted one (waits for it)
 		void setNearestWalk(uint32_t debug_flags);
 		void lastNearestCounts(uint64_t counts[2]);
+		// Segment queries (include/rt_hip_segment.h): segment i runs from from4[i] to to4[i]; its blockers are the triangles
+		// the reference accepts for the ray (from, to - from) with a plane parameter inside (t_lo, t_hi), behind boxes that
+		// pass the slab test with max_distance = t_hi.  `closest` false: occlusion into out.hit alone.
+		// Device memory, enqueued on `stream` (null: the renderer's).
+		void segmentsDevice(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+		                    const QueryOutputs &out, void *stream);
+		// Host memory, blocking.
+		void segmentsHost(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+		                  const QueryOutputs &out);
+		// The many-to-many form: np points against nt targets, bit j of point i's row (visibilityWords(nt) words) set where
+		// segment (i, j) is occluded, and the row's popcount.  Either output may be null.  No np x nt array is made.
+		struct VisibilityOutputs {
+			uint32_t *mask = nullptr, *count = nullptr;
+			bool any() const { return mask || count; }
+		};
+		static uint32_t visibilityWords(uint32_t nt) { return (nt + 31u) / 32u; }
+		// Device memory, enqueued on `stream` (null: the renderer's).
+		void visibilityDevice(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
+		                      const VisibilityOutputs &out, void *stream);
+		// Host memory, blocking.
+		void visibilityHost(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
+		                    const VisibilityOutputs &out);
 		// Ambient-occlusion queries (include/rt_hip_ao.h): the reference's ambient_occlusion() of n points with the options
 		// the scene was uploaded for -- table, mode, rays per point, divisor and reach come from the renderer's launch
 		// constants and its DeviceScene.  std::logic_error where those options have ambient occlusion off.
@@ -183,8 +205,9 @@ class RayQueries {
 		static ViewOutputs viewsFrom(const ViewOutputs &out, size_t view, const KernelParams &kp, size_t image_bytes);
 		void grow(Scratch &scratch, size_t bytes);
 		void sceneBox(const DeviceScene &scene, float lo[3], float scale[3]);
+		// (`segments`: keys_a4, keys_b4 are the two ends of segments, keyed as the rays (a, b - a))
 		Enqueue begin(void *stream, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags,
-		              std::initializer_list<Need> needs = {});
+		              std::initializer_list<Need> needs = {}, bool segments = false);
 		void end(const Enqueue &q);
 		// The ambient-occlusion step between begin() and end(): n entries -- point order[j], or j where `order` is null --,
 		// counted into `count` by point index (the caller's `occluded` or ao_hits).
@@ -198,6 +221,7 @@ class RayQueries {
 		Scratch stage;         // the host-memory forms' inputs and outputs
 		Scratch ao_hits;       // aoDevice without an `occluded` array: the points' counts
 		Scratch ao_rows;       // directionalDevice without a `mask` array: the points' rows
+		Scratch vis_rows;      // visibilityDevice without a `mask` array: the points' rows
 	Scratch list;          // multihitDevice: the rays' key lists, n * k * 8 bytes
 		Scratch views;         // layersDevice, viewsDevice (ChunkScratch): a chunk's poses, the points and normals of its
 		                       // ambient-occlusion step, the list of the hit ones (ViewList), its float images where the caller
@@ -231,13 +255,17 @@ class RayQueries {
 
 // kernels.hip
 void launch_query_sort(const void *origins, const void *directions, uint32_t n, const float lo[3], const float scale[3], void *count,
-                       void *order, void *stream);
+                       void *order, void *stream, bool segments = false);
 void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *origins, const void *directions,
                   const void *order, uint32_t n, float max_distance, const QueryOutputs &out, void *stream);
 void launch_nearest_sort(const void *points, uint32_t n, const float lo[3], const float scale[3], void *count, void *order, void *stream);
 void launch_nearest(const SceneBuffers &scene, uint32_t node_count, uint32_t tri_count, const void *points, const void *order, uint32_t n,
                     float max_distance, uint32_t walk, const QueryOutputs &out, const void *coords_flag, void *counts, void *stream);
 void launch_nearest_coordinates(const void *vertices4, uint32_t num_vertices, void *flag, void *stream);
+void launch_segments(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *from, const void *to, const void *order,
+                     uint32_t n, float t_lo, float t_hi, const QueryOutputs &out, void *stream);
+void launch_visibility(const SceneBuffers &scene, uint32_t node_count, const void *points, uint32_t np, const void *targets, uint32_t nt,
+                       const void *order, float t_lo, float t_hi, uint32_t *mask, uint32_t *count, void *stream);
 void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void *origins, const void *directions, const void *order,
                      uint32_t n, float max_distance, uint32_t k, void *list, const MultiHitOutputs &out, void *stream);
 void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,

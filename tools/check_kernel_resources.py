@@ -147,7 +147,10 @@ def main():
                # device-side builds (kernels/build.hip.h): a lane per face or node, nothing that should need scratch
                "build_boxes_kernel", "build_root_kernel", "build_keys_kernel", "build_tree_kernel", "build_layout_kernel",
                # closest-point queries (kernels/nearest.hip.h)
-               "nearest_key_kernel", "nearest_scatter_kernel", "nearest_coordinates_kernel", "nearest_kernel<false>", "nearest_kernel<true>")
+               "nearest_key_kernel", "nearest_scatter_kernel", "nearest_coordinates_kernel", "nearest_kernel<false>", "nearest_kernel<true>",
+               # segment queries (kernels/segment.hip.h)
+               "segment_kernel<true>", "segment_kernel<false>", "visibility_mask_kernel", "visibility_count_kernel",
+               "segment_key_kernel", "segment_scatter_kernel")
     # the directional occlusion queries' walk is ao_query_kernel's with another tail (kernels/directional.hip.h): it must keep
     # that kernel's occupancy, 8 waves per SIMD -- a tail that needs more live state than the old one shows here
     full_occupancy = ("ao_mask_kernel<1", "ao_mask_kernel<2")
