@@ -9,6 +9,8 @@ raises.
 """
 from .api import (  # noqa: F401
     DIRECTIONAL_OUTPUTS,
+    INSTANCE_NODE,
+    INSTANCE_OUTPUTS,
     LAYER_OUTPUTS,
     NEAREST_OUTPUTS,
     SEGMENT_INTERVAL,
@@ -29,6 +31,7 @@ from .api import (  # noqa: F401
     pgm_bytes,
     rccl_available,
     rccl_unique_id,
+    instance_plan,
     resize_cpu,
     unpack_ao_mask,
     unpack_visibility_mask,

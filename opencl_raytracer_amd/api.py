@@ -1,5 +1,5 @@
 """ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h, rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h,
-rt_hip_nearest.h, rt_hip_segment.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers
+rt_hip_nearest.h, rt_hip_segment.h, rt_hip_instances.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers
 for the contract)."""
 from __future__ import annotations
 
@@ -240,6 +240,19 @@ _SIGNATURES = {
                                       C.c_void_p]),
     "rt_visibility_masks_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_float,
                                              C.c_uint32, C.c_void_p, C.c_void_p]),
+    # include/rt_hip_instances.h
+    "rt_set_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rt_instance_count": (C.c_uint32, [C.c_void_p]),
+    "rt_instance_node_count": (C.c_uint32, [C.c_void_p]),
+    "rt_instances_object_from_world": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_instance_nodes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_trace_instances_closest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
+    "rt_trace_instances_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
+    "rt_trace_instances_closest_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
+                                                    C.c_void_p]),
+    "rt_trace_instances_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
+                                                     C.c_void_p]),
+    "rt_instance_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     # include/rt_hip_nearest.h
     "rt_closest_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
     "rt_closest_points_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
@@ -310,6 +323,11 @@ class _DirectionalArrays(C.Structure):
     _fields_ = [("ao", C.c_void_p), ("occluded", C.c_void_p), ("mask", C.c_void_p), ("bent", C.c_void_p)]
 
 
+class _InstanceHitArrays(C.Structure):
+    """rt_instance_hit_arrays (include/rt_hip_instances.h)."""
+    _fields_ = [("record", _HitArrays), ("instance", C.c_void_p)]
+
+
 class _VisibilityArrays(C.Structure):
     """rt_visibility_arrays (include/rt_hip_segment.h)."""
     _fields_ = [("mask", C.c_void_p), ("count", C.c_void_p)]
@@ -337,6 +355,10 @@ RT_MULTIHIT_MAX_K = 16
 MULTIHIT_OUTPUTS = ("count", "distance", "leaf", "barycentric", "position", "normal")
 QUERY_OUTPUTS = ("hit", "distance", "leaf", "barycentric", "position", "normal")
 NEAREST_OUTPUTS = QUERY_OUTPUTS  # closest-point queries: "hit" is `found`
+INSTANCE_OUTPUTS = QUERY_OUTPUTS + ("instance",)  # instanced ray queries: the record and the instance it lies in
+RT_INSTANCES_MAX = 1 << 20
+# the record of a top-level tree (include/rt_hip_instances.h): the node record the exact walk reads
+INSTANCE_NODE = np.dtype([("lo", np.float32, 3), ("skip", np.uint32), ("hi", np.float32, 3), ("leaf", np.uint32)])
 SEGMENT_OUTPUTS = QUERY_OUTPUTS  # segment queries, the closest form: "hit" is "the segment has a blocker"
 VISIBILITY_OUTPUTS = ("mask", "count")
 SEGMENT_INTERVAL = (1e-4, 1 - 1e-4)  # the default (t_lo, t_hi) of the segment queries, fractions of the segment
@@ -349,7 +371,7 @@ VIEW_OUTPUTS = LAYER_OUTPUTS + ("image",)
 _OUTPUT_LAYOUT = {"hit": (np.uint8, 1), "count": (np.uint32, 1), "ao": (np.float32, 1), "occluded": (np.uint32, 1),
                   "distance": (np.float32, 1), "leaf": (np.uint32, 1), "barycentric": (np.float32, 3), "position": (np.float32, 3),
                   "normal": (np.float32, 3), "direction": (np.float32, 3), "shade": (np.float32, 1), "value": (np.float32, 1),
-                  "bent": (np.float32, 3)}
+                  "bent": (np.float32, 3), "instance": (np.uint32, 1)}
 _RECORD_FIELDS = ("distance", "leaf", "barycentric", "position", "normal")
 
 
@@ -483,6 +505,27 @@ def unpack_visibility_mask(mask, targets: int):
     """The (P, W) uint32 mask rows of Host.visibility as booleans: (P, targets), [i, j] True iff the segment from point i to
     target j is OCCLUDED.  numpy in, numpy out; torch in, torch out on the same device."""
     return unpack_ao_mask(mask, targets)  # (the same layout: bit j & 31 of word j >> 5)
+
+
+def _transforms12(transforms) -> np.ndarray:
+    t = np.asarray(transforms)
+    if t.dtype != np.float32 or t.ndim != 3 or t.shape[1:] != (3, 4):
+        raise ValueError("transforms: expected a float32 array of shape (n, 3, 4), the rows of [A | t]")
+    return np.ascontiguousarray(t)
+
+
+def instance_plan(root_lo, root_hi, transforms) -> dict:
+    """The planner of an instance set alone (rt_instance_plan, include/rt_hip_instances.h; host only, no device):
+    {"object_from_world": float32 (n, 3, 4), "nodes": INSTANCE_NODE (2n - 1,)} for a scene whose root box is
+    (root_lo, root_hi).  RtError -1 for a refused transform."""
+    w = _transforms12(transforms)
+    lo, hi = np.ascontiguousarray(root_lo, np.float32).reshape(3), np.ascontiguousarray(root_hi, np.float32).reshape(3)
+    n = int(w.shape[0])
+    inverse, nodes = np.zeros((n, 3, 4), np.float32), np.zeros(max(2 * n - 1, 0), INSTANCE_NODE)
+    rc = load_library().rt_instance_plan(lo.ctypes.data, hi.ctypes.data, w.ctypes.data, n, inverse.ctypes.data, nodes.ctypes.data)
+    if rc != 0:
+        raise RtError(rc, "rt_instance_plan: no transforms, too many, or a refused transform")
+    return {"object_from_world": inverse, "nodes": nodes}
 
 
 def load_library() -> C.CDLL:
@@ -900,6 +943,51 @@ class Host:
             io.call(self._h, "rt_trace_closest", *args, C.byref(_HitArrays(*io.pointers(out, QUERY_OUTPUTS))))
         else:
             io.call(self._h, "rt_trace_occluded", *args, *io.pointers(out, ("hit",)))
+        return out
+
+    # ---- instanced ray queries (include/rt_hip_instances.h) ----
+    def set_instances(self, transforms) -> None:
+        """Poses n copies of the host's scene: float32 (n, 3, 4), the rows of world_from_object = [A | t]; n = 0 clears the
+        set.  The set outlives update_vertices, build_scene and uploads.  RtError -1 for a transform with an entry that is not
+        finite, a zero determinant or an inverse that is not finite: the host's set stays what it was."""
+        w = _transforms12(transforms)
+        _check(load_library().rt_set_instances(self._h, w.ctypes.data if len(w) else None, len(w)))
+        self._instance_transforms = w.copy()  # (what instances() hands back: the library keeps its own copy)
+
+    def instances(self) -> dict:
+        """{"world_from_object": float32 (n, 3, 4) as given, "object_from_world": float32 (n, 3, 4) as the kernel uses it,
+        "nodes": INSTANCE_NODE (2n - 1,), the top-level tree as it is on the device (made again first if the scene changed)}."""
+        lib = load_library()
+        n = int(lib.rt_instance_count(self._h))
+        world, inverse = getattr(self, "_instance_transforms", np.zeros((0, 3, 4), np.float32)).copy(), np.zeros((n, 3, 4), np.float32)
+        nodes = np.zeros(int(lib.rt_instance_node_count(self._h)), INSTANCE_NODE)
+        _check(lib.rt_instances_object_from_world(self._h, inverse.ctypes.data))
+        _check(lib.rt_instance_nodes(self._h, nodes.ctypes.data))
+        return {"world_from_object": world, "object_from_world": inverse, "nodes": nodes}
+
+    def trace_instances_closest(self, origins, directions, max_distance: float = 100000.0, outputs=INSTANCE_OUTPUTS,
+                                sort: bool = True) -> dict:
+        """Closest hit of every WORLD-space ray among the posed copies of the scene: the record of trace_closest -- position,
+        distance and normal in world space, leaf and barycentrics of the copy's triangle -- and "instance", the copy
+        (0xFFFFFFFF without a hit).  Inputs and forms as for trace_closest."""
+        return self._trace_instances(True, origins, directions, max_distance, tuple(outputs), sort)
+
+    def trace_instances_occluded(self, origins, directions, max_distance: float = 100000.0, sort: bool = True):
+        """Occlusion of every world-space ray by any copy (the `hit` of trace_instances_closest): uint8 (N,)."""
+        return self._trace_instances(False, origins, directions, max_distance, ("hit",), sort)["hit"]
+
+    def _trace_instances(self, closest: bool, origins, directions, max_distance: float, outputs: tuple, sort: bool) -> dict:
+        unknown = [o for o in outputs if o not in INSTANCE_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {INSTANCE_OUTPUTS}")
+        io = _QueryArrays(origins, directions, ("origins", "directions"), "rays")
+        out = io.outputs(outputs)
+        args = (io.n, float(max_distance), 0 if sort else RT_QUERY_NO_SORT)
+        if closest:
+            at = io.pointers(out, INSTANCE_OUTPUTS)
+            io.call(self._h, "rt_trace_instances_closest", *args, C.byref(_InstanceHitArrays(_HitArrays(*at[:-1]), at[-1])))
+        else:
+            io.call(self._h, "rt_trace_instances_occluded", *args, *io.pointers(out, ("hit",)))
         return out
 
     # ---- segment queries (include/rt_hip_segment.h) ----

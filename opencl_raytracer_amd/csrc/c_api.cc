@@ -11,6 +11,7 @@
 #include "../../include/rt_hip_nearest.h"
 #include "../../include/rt_hip_query.h"
 #include "../../include/rt_hip_segment.h"
+#include "../../include/rt_hip_instances.h"
 #include "../../include/rt_hip_views.h"
 #include "../../include/rt_hip_update.h"
 #include "../../include/rt_hip_build.h"
@@ -1047,6 +1048,117 @@ int rt_visibility_masks_device(rt_host *h, const float *points4, uint32_t np, co
 	if (!aligned({ q.mask, q.count }, 4))
 		return fail(RT_E_INVALID, "device uint32 outputs must be 4-byte aligned");
 	return guarded([&] { queries_of(h).visibilityDevice(points4, np, targets4, nt, t_lo, t_hi, flags, q, hip_stream); });
+}
+
+// ---- rt_hip_instances.h ----
+namespace {
+
+// The set's own entry points work before an upload too, but not on the hosts of a frame ring.
+int instance_set_precheck(const rt_host *h) {
+	if (!h)
+		return fail(RT_E_INVALID, "null host");
+	if (!h->owned)
+		return fail(RT_E_STATE, "instanced ray queries are not available on the hosts of a frame ring");
+	return RT_OK;
+}
+
+// The checks of include/rt_hip_instances.h ("Errors") before a query touches the device.
+int instance_precheck(rt_host *h, const float *origins4, const float *directions4, uint32_t n, bool device) {
+	int rc = host_precheck(h, "instanced ray");
+	if (rc != RT_OK)
+		return rc;
+	if (!h->queries || h->queries->instanceCount() == 0)
+		return fail(RT_E_STATE, "instanced ray query without an instance set (rt_set_instances)");
+	if (n > RT_QUERY_MAX_RAYS)
+		return fail(RT_E_INVALID, "more rays than RT_QUERY_MAX_RAYS in one call");
+	if (n > 0 && (!origins4 || !directions4))
+		return fail(RT_E_INVALID, "null ray arrays");
+	if (device && n > 0 && !aligned({ origins4, directions4 }, 16))
+		return fail(RT_E_INVALID, "device ray arrays must be 16-byte aligned");
+	return RT_OK;
+}
+
+}  // namespace
+
+int rt_set_instances(rt_host *h, const float *world_from_object, uint32_t n) {
+	const int rc = instance_set_precheck(h);
+	if (rc != RT_OK)
+		return rc;
+	if (n > RT_INSTANCES_MAX)
+		return fail(RT_E_INVALID, "more instances than RT_INSTANCES_MAX");
+	if (n > 0 && !world_from_object)
+		return fail(RT_E_INVALID, "null transform array");
+	if (n == 0 && !h->queries)
+		return RT_OK;
+	return guarded([&] { queries_of(h).setInstances(world_from_object, n); });
+}
+
+uint32_t rt_instance_count(const rt_host *h) { return h && h->queries ? h->queries->instanceCount() : 0u; }
+
+uint32_t rt_instance_node_count(const rt_host *h) {
+	const uint32_t n = rt_instance_count(h);
+	return n ? 2u * n - 1u : 0u;
+}
+
+int rt_instances_object_from_world(rt_host *h, float *out) {
+	const int rc = instance_set_precheck(h);
+	if (rc != RT_OK)
+		return rc;
+	if (out && h->queries)
+		std::copy(h->queries->instanceInverses().begin(), h->queries->instanceInverses().end(), out);
+	return RT_OK;
+}
+
+int rt_instance_nodes(rt_host *h, void *out) {
+	const int rc = host_precheck(h, "instanced ray");
+	if (rc != RT_OK)
+		return rc;
+	if (!h->queries || h->queries->instanceCount() == 0)
+		return fail(RT_E_STATE, "instance tree without an instance set (rt_set_instances)");
+	return guarded([&] { h->queries->instanceNodes(out); });
+}
+
+int rt_trace_instances_closest(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
+                               const rt_instance_hit_arrays *out) {
+	const int rc = instance_precheck(h, origins4, directions4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	return guarded([&] {
+		queries_of(h).instancesHost(true, origins4, directions4, n, max_distance, flags, hit_outputs(out ? &out->record : nullptr),
+		                            out ? out->instance : nullptr);
+	});
+}
+
+int rt_trace_instances_occluded(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
+                                uint8_t *occluded) {
+	const int rc = instance_precheck(h, origins4, directions4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	ocrt::QueryOutputs q;
+	q.hit = occluded;
+	return guarded([&] { queries_of(h).instancesHost(false, origins4, directions4, n, max_distance, flags, q, nullptr); });
+}
+
+int rt_trace_instances_closest_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
+                                      uint32_t flags, const rt_instance_hit_arrays *out, void *hip_stream) {
+	const int rc = instance_precheck(h, origins4, directions4, n, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	const ocrt::QueryOutputs q = hit_outputs(out ? &out->record : nullptr);
+	uint32_t *const instance = out ? out->instance : nullptr;
+	if (!records_aligned(q) || !aligned({ instance }, 4))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).instancesDevice(true, origins4, directions4, n, max_distance, flags, q, instance, hip_stream); });
+}
+
+int rt_trace_instances_occluded_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
+                                       uint32_t flags, uint8_t *occluded, void *hip_stream) {
+	const int rc = instance_precheck(h, origins4, directions4, n, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	ocrt::QueryOutputs q;
+	q.hit = occluded;
+	return guarded([&] { queries_of(h).instancesDevice(false, origins4, directions4, n, max_distance, flags, q, nullptr, hip_stream); });
 }
 
 // ---- rt_hip_nearest.h ----

@@ -1,0 +1,27 @@
+// instances.h -- the planner of an instance set (include/rt_hip_instances.h): from the scene's root box and the caller's
+// transforms to the inverses the kernel uses and the top-level tree it walks.  Host only; no HIP headers, so that the CPU
+// tests and a stand-alone sanitizer program take it without a device (rt_instance_plan, defined in instances.cc).
+#pragma once
+#include <cstdint>
+#include <vector>
+
+namespace ocrt {
+
+// The record the exact walk reads (device_types.h, NodeRec): `skip` the subtree's size, `leaf` the instance or INSTANCE_INNER.
+struct InstanceNode {
+	float lo[3];
+	uint32_t skip;
+	float hi[3];
+	uint32_t leaf;
+};
+static_assert(sizeof(InstanceNode) == 32, "InstanceNode is NodeRec");
+constexpr uint32_t INSTANCE_INNER = 0xFFFFFFFFu;
+
+// object_from_world of one transform by the header's formula; false where the header refuses the transform (`O` untouched).
+bool instance_inverse(const float W[12], float O[12]);
+// Every transform of the set, or none: false, and `O` untouched, where one is refused.  O: n * 12 floats.
+bool instance_inverses(const float *W, uint32_t n, std::vector<float> &O);
+// The tree over n >= 1 accepted transforms and their inverses: 2n - 1 records in pre-order.
+void instance_tree(const float root_lo[3], const float root_hi[3], const float *W, const float *O, uint32_t n, std::vector<InstanceNode> &nodes);
+
+}  // namespace ocrt

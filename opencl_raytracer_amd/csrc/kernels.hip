@@ -43,6 +43,9 @@
 //                   blocked first (segment_key_kernel / segment_scatter_kernel order the segments), visibility_mask_kernel
 //                   does so for P points against T targets, a bit per pair, visibility_count_kernel counts a point's bits
 //                   (kernels/segment.hip.h, include/rt_hip_segment.h).
+//                   instance_kernel<CLOSEST> casts caller-supplied rays against posed copies of the scene: an exact walk over a
+//                   top-level tree of instance boxes, and at each instance a packet enters the exact walk of the scene's own
+//                   tree with the rays mapped into the object's frame (kernels/instances.hip.h, include/rt_hip_instances.h).
 //                   layers_kernel<POSED, ARRAY> casts the frame's own rays for one pose or for every pose of a chunk of views, a wave
 //                   per (view, tile), and writes every sub-pixel's record, direction and head-light term (kernels/layers.hip.h,
 //                   include/rt_hip_layers.h, include/rt_hip_views.h).  ao_query_kernel runs over its points -- all of them
@@ -100,6 +103,7 @@
 #include "kernels/node_test_forms.hip.h"
 #include "kernels/nearest.hip.h"
 #include "kernels/segment.hip.h"
+#include "kernels/instances.hip.h"
 
 
 namespace ocrt {
@@ -467,6 +471,38 @@ void launch_segments(const SceneBuffers &scene, uint32_t node_count, bool closes
 		hipLaunchKernelGGL(segment_kernel<true>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
 	} else {
 		hipLaunchKernelGGL(segment_kernel<false>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
+	}
+}
+
+// Instanced ray queries (kernels/instances.hip.h); their sort is launch_query_sort's over the top-level root box.
+// `top`: the top-level records, `inverses`: three float4 per instance, both on the device.  `closest` false: occlusion into
+// out.hit alone.
+void launch_instances(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses, bool closest,
+                      const void *origins, const void *directions, const void *order, uint32_t n, float max_distance, const QueryOutputs &out,
+                      uint32_t *instance, void *stream) {
+	if (n == 0 || top_count == 0)
+		return;
+	InstanceArgs a{};
+	a.nodes_ptr = (const float4 *) scene.nodes;
+	a.tris_ptr = (const float4 *) scene.tris;
+	a.shade = (const float4 *) scene.shade;
+	a.origins = (const float4 *) origins;
+	a.directions = (const float4 *) directions;
+	a.order = (const uint32_t *) order;
+	a.n = n;
+	a.node_count = node_count;
+	a.max_distance = max_distance;
+	a.out = out;
+	a.top_ptr = (const float4 *) top;
+	a.inverses = (const float4 *) inverses;
+	a.top_count = top_count;
+	a.hit = out.hit;
+	a.instance = instance;
+	const uint32_t blocks = (n + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
+	if (closest) {
+		hipLaunchKernelGGL(instance_kernel<true>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
+	} else {
+		hipLaunchKernelGGL(instance_kernel<false>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
 	}
 }
 

@@ -59,7 +59,9 @@ __device__ __forceinline__ SignMasks sign_masks(const Ray &r) {
 typedef unsigned int u32x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ u32x8 scalar_load_node(const float4 *nodes_ptr, uint32_t at) {
 	u32x8 r;
-	const uint32_t offset = at * 32u;
+	// (readfirstlane: `at` is wave-uniform by construction; said so here, a walk nested in another walk's leaf step keeps its
+	// node index in a scalar register too -- the offset operand cannot take a vector register)
+	const uint32_t offset = (uint32_t) __builtin_amdgcn_readfirstlane((int) (at * 32u));
 	asm volatile("s_load_dwordx8 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(r) : "s"(nodes_ptr), "s"(offset));
 	return r;
 }

@@ -8,6 +8,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "../../include/rt_hip_instances.h"
 #include "device_internal.h"
 
 namespace ocrt {
@@ -25,6 +26,8 @@ enum { AO_POINTS, AO_NORMALS, AO_COUNTS, AO_SEEDS, AO_VALUES, AO_PIECES };
 // the rays of the points: the inputs and the two ray arrays.
 enum { DIR_POINTS, DIR_NORMALS, DIR_SEEDS, DIR_ROWS, DIR_COUNTS, DIR_VALUES, DIR_BENT, DIR_PIECES };
 enum { AORAY_POINTS, AORAY_NORMALS, AORAY_SEEDS, AORAY_ORIGINS, AORAY_DIRECTIONS, AORAY_PIECES };
+// Instanced ray queries: the rays' pieces, then the instance indices.
+enum { INST_INDEX = RAY_PIECES, INST_PIECES };
 // Visibility masks: the two inputs, the rows (staged whether they are copied back or not), the counts.
 enum { VIS_POINTS, VIS_TARGETS, VIS_ROWS, VIS_COUNTS, VIS_PIECES };
 // Frame layers: the hit flags, the five record arrays, then the four layers of their own.
@@ -52,7 +55,7 @@ RayQueries::~RayQueries() {
 		return;
 	if (timed)
 		(void) hipEventSynchronize((hipEvent_t) ev_stop);
-	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &ao_rows, &vis_rows, &list, &views, &build, &coords_flag, &nearest_counts })
+	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &ao_rows, &vis_rows, &list, &views, &build, &coords_flag, &nearest_counts, &inst_device })
 		device_free(scratch->ptr);
 	for (void *ev : ev_build)
 		if (ev)
@@ -126,7 +129,7 @@ void RayQueries::sceneBox(const DeviceScene &scene, float lo[3], float scale[3])
 // synchronises), ev_start, and the sort of the n items keyed by (keys_a4, keys_b4) where the call allows it and makes
 // RT_QUERY_SORT_MIN `rays` or more.
 RayQueries::Enqueue RayQueries::begin(void *stream, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags,
-                                      std::initializer_list<Need> needs, bool segments) {
+                                      std::initializer_list<Need> needs, bool segments, const float *box) {
 	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
 	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
 	if (timed)
@@ -140,8 +143,12 @@ RayQueries::Enqueue RayQueries::begin(void *stream, const float *keys_a4, const 
 		if (need.scratch)
 			grow(*need.scratch, need.bytes);
 	float lo[3], scale[3];
-	if (sort)
+	if (sort && box) {
+		std::copy(box, box + 3, lo);
+		std::copy(box + 3, box + 6, scale);
+	} else if (sort) {
 		sceneBox(*dev.deviceScene(), lo, scale);
+	}
 	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
 	if (sort && keys_b4)
 		launch_query_sort(keys_a4, keys_b4, n, lo, scale, count.ptr, order.ptr, s, segments);
@@ -250,6 +257,108 @@ void RayQueries::traceHost(bool closest, const float *origins4, const float *dir
 	recordDevice(p + RAY_RECORDS, out);
 	traceDevice(closest, (const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, max_distance, flags, out, s);
 	stageOut(p, RAY_PIECES, s);
+}
+
+// ---- instanced ray queries (include/rt_hip_instances.h) ----
+void RayQueries::setInstances(const float *world_from_object, uint32_t n) {
+	if (n > RT_INSTANCES_MAX)
+		throw std::invalid_argument("more instances than RT_INSTANCES_MAX");
+	if (n > 0 && !world_from_object)
+		throw std::invalid_argument("null transform array");
+	if (n > 0 && !instance_inverses(world_from_object, n, inst_inverse))  // (every transform or none: the set stays on a refusal)
+		throw std::invalid_argument("instance transform refused: an entry that is not finite, a zero determinant, or an inverse that is not finite");
+	if (n == 0) {
+		inst_inverse.clear();
+		inst_world.clear();
+	} else {
+		inst_world.assign(world_from_object, world_from_object + (size_t) n * 12u);
+	}
+	inst_nodes.clear();
+	inst_current = false;
+	if (n > 0 && dev.sceneReady() && dev.deviceScene())
+		refreshInstances();
+}
+
+void RayQueries::requireInstances(const char *what) const {
+	requireScene(what);
+	if (inst_world.empty())
+		throw std::logic_error(std::string(what) + " without an instance set (rt_set_instances)");
+}
+
+// The tree from the root box as it is on the device now, and the set's three arrays into inst_device.  Waits for this
+// host's queries (an update on its way to the root, a query still reading the old arrays) before it reads or writes.
+void RayQueries::refreshInstances() {
+	const std::shared_ptr<const DeviceScene> current = dev.deviceScene();
+	if (inst_current && inst_scene.lock() == current)
+		return;
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	if (timed)
+		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
+	NodeRec root{};
+	if (current->nodeCount() > 0)
+		OCRT_HIP(hipMemcpy(&root, current->buffers().nodes, sizeof root, hipMemcpyDeviceToHost));
+	const uint32_t n = instanceCount();
+	instance_tree(root.lo, root.hi, inst_world.data(), inst_inverse.data(), n, inst_nodes);
+	const size_t rows = (size_t) n * 12u * sizeof(float), tree = inst_nodes.size() * sizeof(InstanceNode);
+	grow(inst_device, 2u * rows + tree);
+	char *at = (char *) inst_device.ptr;
+	OCRT_HIP(hipMemcpy(at, inst_world.data(), rows, hipMemcpyHostToDevice));
+	OCRT_HIP(hipMemcpy(at + rows, inst_inverse.data(), rows, hipMemcpyHostToDevice));
+	OCRT_HIP(hipMemcpy(at + 2u * rows, inst_nodes.data(), tree, hipMemcpyHostToDevice));
+	for (int k = 0; k < 3; ++k) {  // (sceneBox's rule, on the top-level root)
+		const float lo = inst_nodes[0].lo[k], extent = inst_nodes[0].hi[k] - lo;
+		const bool usable = std::isfinite(lo) && std::isfinite(extent) && extent > 0.0f && std::isfinite(8.0f / extent);
+		inst_box[k] = usable ? lo : -1.0f;
+		inst_box[3 + k] = usable ? 8.0f / extent : 4.0f;
+	}
+	inst_scene = current;
+	inst_current = true;
+}
+
+void RayQueries::instanceNodes(void *out) {
+	requireInstances("instance tree");
+	refreshInstances();
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	if (timed)
+		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
+	const size_t rows = (size_t) instanceCount() * 12u * sizeof(float);
+	if (out)
+		OCRT_HIP(hipMemcpy(out, (const char *) inst_device.ptr + 2u * rows, inst_nodes.size() * sizeof(InstanceNode), hipMemcpyDeviceToHost));
+}
+
+void RayQueries::instancesDevice(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
+                                 const QueryOutputs &out, uint32_t *instance, void *stream) {
+	requireInstances("instanced ray query");
+	if (n == 0)
+		return;
+	refreshInstances();
+	const size_t rows = (size_t) instanceCount() * 12u * sizeof(float);
+	const char *set = (const char *) inst_device.ptr;
+	const Enqueue q = begin(stream, origins4, directions4, n, n, flags, {}, false, inst_box);
+	launch_instances(dev.deviceScene()->buffers(), dev.params().node_count, set + 2u * rows, (uint32_t) inst_nodes.size(), set + rows, closest,
+	                 origins4, directions4, q.order, n, max_distance, out, closest ? instance : nullptr, q.stream);
+	end(q);
+}
+
+void RayQueries::instancesHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
+                               const QueryOutputs &host, uint32_t *instance) {
+	requireInstances("instanced ray query");
+	if (n == 0)
+		return;
+	QueryOutputs want;  // (occlusion: the flags alone)
+	if (closest)
+		want = host;
+	want.hit = host.hit;
+	Staged p[INST_PIECES] = { input(origins4, (size_t) n * 16u), input(directions4, (size_t) n * 16u), output(want.hit, n) };
+	recordPieces(p + RAY_RECORDS, want, n);
+	p[INST_INDEX] = output(closest ? instance : nullptr, (size_t) n * 4u);
+	void *s = stageIn(p, INST_PIECES);
+	QueryOutputs out;
+	out.hit = (unsigned char *) p[RAY_FIRST].device;
+	recordDevice(p + RAY_RECORDS, out);
+	instancesDevice(closest, (const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, max_distance, flags, out,
+	                (uint32_t *) p[INST_INDEX].device, s);
+	stageOut(p, INST_PIECES, s);
 }
 
 void RayQueries::segmentsDevice(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
@@ -757,6 +866,7 @@ void RayQueries::updateDevice(const float *vertices4, const float *vnormals4, ui
 	// or not: no frame may lean on the old walk array again, and the sort's box is read afresh)
 	dev.markSceneUpdated();
 	boxed.reset();
+	inst_current = false;
 	grow(coords_flag, sizeof(uint32_t));
 	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
 	OCRT_HIP(hipEventRecord((hipEvent_t) ev_update_start, s));
@@ -831,6 +941,7 @@ void RayQueries::buildDevice(const float *vertices4, const float *vnormals4, uin
 	have_build_ms = false;
 	dev.adoptBuilt(std::move(made));  // (waits for the renderer's own stream and lets the old scene go)
 	boxed.reset();
+	inst_current = false;
 	checkCoordinates(dev.deviceScene(), vertices4, num_vertices, s);
 	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
 	end(Enqueue{ s, nullptr });

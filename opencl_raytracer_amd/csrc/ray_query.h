@@ -1,13 +1,16 @@
 // ray_query.h -- ray queries, multi-hit queries, ambient-occlusion queries, frame layers and multi-view rendering on a render
 // host's uploaded scene (include/rt_hip_query.h, include/rt_hip_multihit.h, include/rt_hip_ao.h, include/rt_hip_directional.h,
 // include/rt_hip_layers.h, include/rt_hip_views.h, include/rt_hip_segment.h; kernels/query.hip.h, kernels/segment.hip.h, kernels/multihit.hip.h, kernels/ao_query.hip.h,
-// kernels/directional.hip.h, kernels/layers.hip.h, kernels/views.hip.h).
+// kernels/directional.hip.h, kernels/layers.hip.h, kernels/views.hip.h); instanced ray queries (include/rt_hip_instances.h,
+// kernels/instances.hip.h, instances.h).
 #pragma once
 #include <cstdint>
 #include <initializer_list>
 #include <memory>
+#include <vector>
 
 #include "device_renderer.h"
+#include "instances.h"
 
 namespace ocrt {
 
@@ -67,6 +70,21 @@ class RayQueries {
 		// Host memory, blocking.
 		void visibilityHost(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
 		                    const VisibilityOutputs &out);
+		// Instanced ray queries (include/rt_hip_instances.h).  The set -- transforms, inverses and the top-level tree over the
+		// scene's root box (instances.h) -- is kept here and, as float4[3n] + float4[3n] + NodeRec[2n - 1], in device memory of
+		// this object's own; it outlives updates, builds and uploads, after which the tree is made again before its next use.
+		// std::invalid_argument for a refused transform or too many (the set stays what it was); n == 0 clears the set.
+		void setInstances(const float *world_from_object, uint32_t n);
+		uint32_t instanceCount() const { return (uint32_t) (inst_world.size() / 12u); }
+		const std::vector<float> &instanceInverses() const { return inst_inverse; }
+		// the tree as it is on the device, 2n - 1 records (waits for the queries; std::logic_error before an upload or a set)
+		void instanceNodes(void *out);
+		// Device memory, enqueued on `stream` (null: the renderer's); `closest` false: occlusion into out.hit alone.
+		void instancesDevice(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
+		                     const QueryOutputs &out, uint32_t *instance, void *stream);
+		// Host memory, blocking.
+		void instancesHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
+		                   const QueryOutputs &out, uint32_t *instance);
 		// Ambient-occlusion queries (include/rt_hip_ao.h): the reference's ambient_occlusion() of n points with the options
 		// the scene was uploaded for -- table, mode, rays per point, divisor and reach come from the renderer's launch
 		// constants and its DeviceScene.  std::logic_error where those options have ambient occlusion off.
@@ -205,9 +223,10 @@ class RayQueries {
 		static ViewOutputs viewsFrom(const ViewOutputs &out, size_t view, const KernelParams &kp, size_t image_bytes);
 		void grow(Scratch &scratch, size_t bytes);
 		void sceneBox(const DeviceScene &scene, float lo[3], float scale[3]);
-		// (`segments`: keys_a4, keys_b4 are the two ends of segments, keyed as the rays (a, b - a))
+		// (`segments`: keys_a4, keys_b4 are the two ends of segments, keyed as the rays (a, b - a); `box`: lo[3] and scale[3] of
+		// the origin cells where they are not the scene's root box's)
 		Enqueue begin(void *stream, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags,
-		              std::initializer_list<Need> needs = {}, bool segments = false);
+		              std::initializer_list<Need> needs = {}, bool segments = false, const float *box = nullptr);
 		void end(const Enqueue &q);
 		// The ambient-occlusion step between begin() and end(): n entries -- point order[j], or j where `order` is null --,
 		// counted into `count` by point index (the caller's `occluded` or ao_hits).
@@ -251,6 +270,16 @@ class RayQueries {
 		bool nearest_counted = false;
 		std::weak_ptr<const DeviceScene> boxed;  // the scene box_lo / box_scale were read from
 		float box_lo[3] = { 0, 0, 0 }, box_scale[3] = { 0, 0, 0 };
+		// The instance set.  inst_device: the transforms, the inverses, the tree; inst_scene / inst_current: the scene whose
+		// root box the tree was made from, and whether that box still stands (an update or a build drops it, as it drops `boxed`).
+		void requireInstances(const char *what) const;
+		void refreshInstances();
+		std::vector<float> inst_world, inst_inverse;
+		std::vector<InstanceNode> inst_nodes;
+		Scratch inst_device;
+		std::weak_ptr<const DeviceScene> inst_scene;
+		bool inst_current = false;
+		float inst_box[6] = { 0, 0, 0, 0, 0, 0 };  // the sort's origin cells over the top-level root box: lo, scale
 };
 
 // kernels.hip
@@ -266,6 +295,9 @@ void launch_segments(const SceneBuffers &scene, uint32_t node_count, bool closes
                      uint32_t n, float t_lo, float t_hi, const QueryOutputs &out, void *stream);
 void launch_visibility(const SceneBuffers &scene, uint32_t node_count, const void *points, uint32_t np, const void *targets, uint32_t nt,
                        const void *order, float t_lo, float t_hi, uint32_t *mask, uint32_t *count, void *stream);
+void launch_instances(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses, bool closest,
+                      const void *origins, const void *directions, const void *order, uint32_t n, float max_distance, const QueryOutputs &out,
+                      uint32_t *instance, void *stream);
 void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void *origins, const void *directions, const void *order,
                      uint32_t n, float max_distance, uint32_t k, void *list, const MultiHitOutputs &out, void *stream);
 void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,

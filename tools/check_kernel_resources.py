@@ -150,7 +150,9 @@ def main():
                "nearest_key_kernel", "nearest_scatter_kernel", "nearest_coordinates_kernel", "nearest_kernel<false>", "nearest_kernel<true>",
                # segment queries (kernels/segment.hip.h)
                "segment_kernel<true>", "segment_kernel<false>", "visibility_mask_kernel", "visibility_count_kernel",
-               "segment_key_kernel", "segment_scatter_kernel")
+               "segment_key_kernel", "segment_scatter_kernel",
+               # instanced ray queries (kernels/instances.hip.h): two nested exact walks
+               "instance_kernel<true>", "instance_kernel<false>")
     # the directional occlusion queries' walk is ao_query_kernel's with another tail (kernels/directional.hip.h): it must keep
     # that kernel's occupancy, 8 waves per SIMD -- a tail that needs more live state than the old one shows here
     full_occupancy = ("ao_mask_kernel<1", "ao_mask_kernel<2")
