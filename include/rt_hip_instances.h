@@ -3,8 +3,10 @@
  *
  * Beside rt_hip_query.h.  A render host holds ONE scene; an INSTANCE SET poses n copies of it in the world, each by an affine
  * map.  The two queries below cast world-space rays against all copies under the arithmetic contract (every
- * operation rounded on its own in binary32, in the order written here).  Frames, layers, ambient occlusion, segments,
- * multi-hit and closest-point queries ignore the set: nothing they compute changes when one is given.
+ * operation rounded on its own in binary32, in the order written here).  Every plain entry point -- frames, layers, views,
+ * ambient occlusion, segments, multi-hit and closest-point queries -- ignores the set: nothing they compute changes when
+ * one is given.  Ambient occlusion and views have instanced forms of their own, rt_trace_instances_ao and
+ * rt_render_instance_views (rt_hip_instance_views.h), defined by the rules below.
  *
  * Transforms.  world_from_object is twelve floats per instance, the rows of W = [A | t]: p_world = A p + t.  Every entry
  * must be finite, the determinant of A (binary64) non-zero and every entry of the inverse finite after its rounding to

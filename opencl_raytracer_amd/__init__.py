@@ -11,6 +11,7 @@ from .api import (  # noqa: F401
     DIRECTIONAL_OUTPUTS,
     INSTANCE_NODE,
     INSTANCE_OUTPUTS,
+    INSTANCE_VIEW_OUTPUTS,
     LAYER_OUTPUTS,
     NEAREST_OUTPUTS,
     SEGMENT_INTERVAL,

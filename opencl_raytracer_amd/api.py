@@ -1,5 +1,5 @@
 """ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h, rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h,
-rt_hip_nearest.h, rt_hip_segment.h, rt_hip_instances.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers
+rt_hip_nearest.h, rt_hip_segment.h, rt_hip_instances.h, rt_hip_instance_views.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers
 for the contract)."""
 from __future__ import annotations
 
@@ -280,8 +280,14 @@ _SIGNATURES = {
     # include/rt_hip_views.h
     "rt_render_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rt_render_views_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    # include/rt_hip_instance_views.h
+    "rt_trace_instances_ao": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_trace_instances_ao_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+    "rt_render_instance_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rt_render_instance_views_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     # include/rt_hip_update.h
-    "rt_update_vertices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rt_update_vertices":(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "rt_update_vertices_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rt_scene_refit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "rt_last_update_ms": (C.c_float, [C.c_void_p]),
@@ -343,6 +349,11 @@ class _ViewArrays(C.Structure):
     _fields_ = [("layers", _LayerArrays), ("image", C.c_void_p)]
 
 
+class _InstanceViewArrays(C.Structure):
+    """rt_instance_view_arrays (include/rt_hip_instance_views.h)."""
+    _fields_ = [("views", _ViewArrays), ("instance", C.c_void_p)]
+
+
 RT_QUERY_NO_SORT = 1
 # the records of a scene on the device (csrc/device_types.h: NodeRec, TriRec, ShadeRec), as Host.records() returns them
 NODE_RECORD = np.dtype([("lo", np.float32, 3), ("skip", np.uint32), ("hi", np.float32, 3), ("leaf", np.uint32)])
@@ -366,6 +377,7 @@ AO_OUTPUTS = ("ao", "occluded")
 DIRECTIONAL_OUTPUTS = ("ao", "occluded", "mask", "bent")
 LAYER_OUTPUTS = QUERY_OUTPUTS + ("direction", "shade", "ao", "value")
 VIEW_OUTPUTS = LAYER_OUTPUTS + ("image",)
+INSTANCE_VIEW_OUTPUTS = VIEW_OUTPUTS + ("instance",)  # instanced views: the copy a sub-pixel's record lies in
 # per output of any query: numpy dtype, values per record.  The first four are one value per ray or point; the others are
 # the fields of a hit record: one record per ray (closest hit) or k of them (multi-hit).
 _OUTPUT_LAYOUT = {"hit": (np.uint8, 1), "count": (np.uint32, 1), "ao": (np.float32, 1), "occluded": (np.uint32, 1),
@@ -990,6 +1002,24 @@ class Host:
             io.call(self._h, "rt_trace_instances_occluded", *args, *io.pointers(out, ("hit",)))
         return out
 
+    # ---- instanced ambient occlusion (include/rt_hip_instance_views.h) ----
+    def instances_ambient_occlusion(self, points, normals, seeds=None, outputs=AO_OUTPUTS, sort: bool = True) -> dict:
+        """ambient_occlusion at WORLD-space points against the posed copies of the scene (set_instances): the rays
+        ambient_occlusion makes for a point -- ao_rays writes them out --, each cast as trace_instances_occluded casts it with
+        max_distance = ao_max_distance: {"ao": float32 (N,), "occluded": uint32 (N,)} (those named in `outputs`).  Inputs,
+        seeds, sorting and the numpy / torch forms are ambient_occlusion's."""
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in AO_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {AO_OUTPUTS}")
+        io = _QueryArrays(points, normals, ("points", "normals", "seeds"), "points", also=seeds)
+        if seeds is not None:
+            seeds = io.seeds(seeds)
+        out = io.outputs(outputs)
+        io.call(self._h, "rt_trace_instances_ao", io.ptr(seeds) if seeds is not None and io.n else None, io.n,
+                0 if sort else RT_QUERY_NO_SORT, *io.pointers(out, AO_OUTPUTS))
+        return out
+
     # ---- segment queries (include/rt_hip_segment.h) ----
     def segments_occluded(self, a, b, interval=SEGMENT_INTERVAL, sort: bool = True):
         """Line of sight: uint8 (N,), 1 iff something blocks the segment from a[i] to b[i] at a fraction r of it with
@@ -1225,10 +1255,22 @@ class Host:
         up, forward per view, used as given).  The host's own pose plays no part.  numpy out (blocking), or with
         as_torch=True torch tensors on the host's GPU, enqueued on torch.cuda.current_stream() (the rules are
         render_layers')."""
-        outputs = tuple(outputs)
-        unknown = [o for o in outputs if o not in VIEW_OUTPUTS]
+        return self._render_views(cameras, tuple(outputs), as_torch, VIEW_OUTPUTS)
+
+    # ---- instanced views (include/rt_hip_instance_views.h) ----
+    def render_instance_views(self, cameras, outputs=("value",), as_torch: bool = False) -> dict:
+        """render_views of the posed copies of the scene (set_instances): every layer, the finished 8-bit image, and
+        "instance": uint32 (V, H, W), the copy a sub-pixel's record lies in (0xFFFFFFFF without a hit) (those named in
+        `outputs`, from INSTANCE_VIEW_OUTPUTS).  The record layers are trace_instances_closest's for the view's own rays, in
+        world space; "ao" is instances_ambient_occlusion at the record's position and normal; "value" and "image" are made
+        of them as render_views makes them.  Cameras and the numpy / torch forms are render_views'."""
+        return self._render_views(cameras, tuple(outputs), as_torch, INSTANCE_VIEW_OUTPUTS)
+
+    def _render_views(self, cameras, outputs: tuple, as_torch: bool, legal: tuple) -> dict:
+        unknown = [o for o in outputs if o not in legal]
         if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {VIEW_OUTPUTS}")
+            raise ValueError(f"unknown outputs {unknown}; choose from {legal}")
+        instanced = legal is INSTANCE_VIEW_OUTPUTS
         if isinstance(cameras, np.ndarray):
             if cameras.dtype != np.float32 or cameras.ndim != 3 or cameras.shape[1:] != (4, 3):
                 raise ValueError("cameras: expected a float32 array of shape (V, 4, 3), or a sequence of Camera")
@@ -1256,13 +1298,16 @@ class Host:
             out = {name: np.empty(shape, dtype=dtypes[name]) for name, shape in shapes.items()}
             address = lambda a: a.ctypes.data
         # (an array that holds nothing is not named: V = 0 asks for nothing)
-        pointers = [address(out[name]) if name in out and views else None for name in VIEW_OUTPUTS]
-        arrays = _ViewArrays(_LayerArrays(*pointers[:-1]), pointers[-1])
+        pointers = [address(out[name]) if name in out and views else None for name in INSTANCE_VIEW_OUTPUTS]
+        arrays = _ViewArrays(_LayerArrays(*pointers[:-2]), pointers[-2])
+        function = "rt_render_views"
+        if instanced:
+            arrays, function = _InstanceViewArrays(arrays, pointers[-1]), "rt_render_instance_views"
         if as_torch:
-            _check(lib.rt_render_views_device(self._h, poses.ctypes.data, views, C.byref(arrays),
-                                              torch.cuda.current_stream(device).cuda_stream))
+            _check(getattr(lib, function + "_device")(self._h, poses.ctypes.data, views, C.byref(arrays),
+                                                      torch.cuda.current_stream(device).cuda_stream))
         else:
-            _check(lib.rt_render_views(self._h, poses.ctypes.data, views, C.byref(arrays)))
+            _check(getattr(lib, function)(self._h, poses.ctypes.data, views, C.byref(arrays)))
         return out
 
     def set_views_chunk(self, max_views: int) -> None:

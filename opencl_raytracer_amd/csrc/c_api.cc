@@ -11,6 +11,7 @@
 #include "../../include/rt_hip_nearest.h"
 #include "../../include/rt_hip_query.h"
 #include "../../include/rt_hip_segment.h"
+#include "../../include/rt_hip_instance_views.h"
 #include "../../include/rt_hip_instances.h"
 #include "../../include/rt_hip_views.h"
 #include "../../include/rt_hip_update.h"
@@ -1441,6 +1442,72 @@ int rt_render_views_device(rt_host *h, const rt_camera *cameras, uint32_t views,
 	if (!(records_aligned(q) && aligned({ q.direction, q.shade, q.ao, q.value }, 4)))
 		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
 	return guarded([&] { queries_of(h).viewsDevice(reinterpret_cast<const ocrt::CameraPose *>(cameras), views, q, hip_stream); });
+}
+
+// ---- rt_hip_instance_views.h ----
+namespace {
+
+int instance_set_required(const rt_host *h, const char *what) {
+	if (!h->queries || h->queries->instanceCount() == 0)
+		return fail(RT_E_STATE, std::string(what) + " without an instance set (rt_set_instances)");
+	return RT_OK;
+}
+
+// The union of ao_precheck's and instance_precheck's checks (include/rt_hip_instance_views.h, "Errors").
+int instance_ao_precheck(const rt_host *h, const float *points4, const float *normals4, uint32_t n, bool device) {
+	int rc = host_precheck(h, "instanced ambient-occlusion");
+	if (rc == RT_OK)
+		rc = instance_set_required(h, "instanced ambient-occlusion query");
+	return rc != RT_OK ? rc : ao_precheck(h, points4, normals4, n, device, nullptr);
+}
+
+int instance_views_precheck(const rt_host *h, const rt_camera *cameras, uint32_t views, const rt_instance_view_arrays *out) {
+	int rc = host_precheck(h, "instanced multi-view");
+	if (rc == RT_OK)
+		rc = instance_set_required(h, "instanced views");
+	return rc != RT_OK ? rc : views_precheck(h, cameras, views, out ? &out->views : nullptr);
+}
+
+}  // namespace
+
+int rt_trace_instances_ao(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
+                          float *ao, uint32_t *occluded) {
+	const int rc = instance_ao_precheck(h, points4, normals4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	return guarded([&] { queries_of(h).instancesAoHost(points4, normals4, seeds, n, flags, ao, occluded); });
+}
+
+int rt_trace_instances_ao_device(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n,
+                                 uint32_t flags, float *ao, uint32_t *occluded, void *hip_stream) {
+	const int rc = instance_ao_precheck(h, points4, normals4, n, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	if (!aligned({ seeds, ao, occluded }, 4))
+		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).instancesAoDevice(points4, normals4, seeds, n, flags, ao, occluded, hip_stream); });
+}
+
+int rt_render_instance_views(rt_host *h, const rt_camera *cameras, uint32_t views, const rt_instance_view_arrays *out) {
+	const int rc = instance_views_precheck(h, cameras, views, out);
+	if (rc != RT_OK)
+		return rc;
+	return guarded([&] {
+		queries_of(h).instanceViewsHost(reinterpret_cast<const ocrt::CameraPose *>(cameras), views, view_outputs(out->views), out->instance);
+	});
+}
+
+int rt_render_instance_views_device(rt_host *h, const rt_camera *cameras, uint32_t views, const rt_instance_view_arrays *out,
+                                    void *hip_stream) {
+	const int rc = instance_views_precheck(h, cameras, views, out);
+	if (rc != RT_OK)
+		return rc;
+	const ocrt::ViewOutputs q = view_outputs(out->views);
+	if (!(records_aligned(q) && aligned({ q.direction, q.shade, q.ao, q.value, out->instance }, 4)))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	return guarded([&] {
+		queries_of(h).instanceViewsDevice(reinterpret_cast<const ocrt::CameraPose *>(cameras), views, q, out->instance, hip_stream);
+	});
 }
 
 int rt_debug_set_views_chunk(rt_host *h, uint32_t max_views) {

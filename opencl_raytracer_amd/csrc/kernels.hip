@@ -52,6 +52,10 @@
 //                   (a layers call) or the hit ones, listed (a views call: views_count_kernel, views_scan_sums_kernel,
 //                   views_order_kernel make their number and order) --, views_scatter_kernel writes their factors and
 //                   products, views_resize_kernel every view's 8-bit image (kernels/views.hip.h).
+//                   instance_layers_kernel and instance_ao_kernel<MODE> are layers_kernel<true, true> and ao_query_kernel
+//                   against the posed copies: the same rays, made in registers, through instance_kernel's two nested walks;
+//                   the list, the tail and the images between and behind them are the views' own (kernels/instance_views.hip.h,
+//                   include/rt_hip_instance_views.h).
 //   (scenes)        refit_leaves_kernel / refit_inner_kernel make the records and boxes of a scene again from new positions
 //                   (kernels/refit.hip.h, include/rt_hip_update.h); build_boxes_kernel, build_root_kernel, build_keys_kernel,
 //                   build_tree_kernel and build_layout_kernel make a scene's tree from triangles, around a sort that lives in
@@ -104,6 +108,7 @@
 #include "kernels/nearest.hip.h"
 #include "kernels/segment.hip.h"
 #include "kernels/instances.hip.h"
+#include "kernels/instance_views.hip.h"
 
 
 namespace ocrt {
@@ -568,6 +573,42 @@ void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode
 		                   divisor ? divisor : 1u);
 }
 
+// Instanced ambient-occlusion queries (kernels/instance_views.hip.h): launch_ao_query's arguments and rules, with the set's
+// top-level records and inverses (launch_instances').
+void launch_instance_ao(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses, int ao_mode,
+                        uint32_t rays_per_point, uint32_t divisor, float max_distance, const void *points, const void *normals,
+                        const uint32_t *seeds, const void *order, uint32_t n, uint32_t *count, float *ao, void *stream) {
+	if (n == 0 || rays_per_point == 0 || top_count == 0)
+		return;
+	hipStream_t s = (hipStream_t) stream;
+	InstanceAoArgs a{};
+	a.nodes_ptr = (const float4 *) scene.nodes;
+	a.tris_ptr = (const float4 *) scene.tris;
+	a.ao_table = (const float4 *) scene.ao_table;
+	a.points = (const float4 *) points;
+	a.normals = (const float4 *) normals;
+	a.seeds = seeds;
+	a.order = (const uint32_t *) order;
+	a.count = count;
+	a.n = n;
+	a.rays = rays_per_point;
+	a.total = n * rays_per_point;  // (<= RT_QUERY_MAX_RAYS: checked at the boundary)
+	a.node_count = node_count;
+	a.max_distance = max_distance;
+	a.top_ptr = (const float4 *) top;
+	a.inverses = (const float4 *) inverses;
+	a.top_count = top_count;
+	(void) hipMemsetAsync(count, 0, (size_t) n * sizeof(uint32_t), s);
+	const uint32_t blocks = (a.total + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
+	if (ao_mode == AO_RANDOM)
+		hipLaunchKernelGGL(instance_ao_kernel<AO_RANDOM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+	else
+		hipLaunchKernelGGL(instance_ao_kernel<AO_UNIFORM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+	if (ao)
+		hipLaunchKernelGGL(ao_query_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, (const uint32_t *) count, ao, n,
+		                   divisor ? divisor : 1u);
+}
+
 // Directional occlusion queries (kernels/directional.hip.h).  `mask`: n rows of ceil(rays_per_point / 32) words on the
 // device (the caller's array or scratch), zeroed here on the stream; `order`: launch_query_sort's order of the POINTS or
 // null; `occluded`, `ao`, `bent`: null = not written -- with all three null the resolve is not launched.
@@ -671,6 +712,15 @@ void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void 
 		hipLaunchKernelGGL(multihit_resolve_kernel, dim3((n * k + 255u) / 256u), dim3(256), 0, s, a);
 }
 
+// The list of a chunk's hit sub-pixels from the flags its ray kernel left (kernels/views.hip.h): m = the chunk's sub-pixels.
+static void launch_views_list(const ViewList &list, uint32_t m, hipStream_t s) {
+	const uint32_t scans = (m + VIEWS_SCAN - 1u) / VIEWS_SCAN;  // (m <= RT_QUERY_MAX_RAYS: RayQueries::viewsPerChunk)
+	hipLaunchKernelGGL(views_count_kernel, dim3(scans), dim3(VIEWS_SCAN), 0, s, (const uint8_t *) list.flags, list.sums, m);
+	hipLaunchKernelGGL(views_scan_sums_kernel, dim3(1), dim3(VIEWS_SUMS), 0, s, list.sums, scans, list.listed);
+	hipLaunchKernelGGL(views_order_kernel, dim3(scans), dim3(VIEWS_SCAN), 0, s, (const uint8_t *) list.flags, (const uint32_t *) list.sums,
+	                   list.order, m);
+}
+
 // Frame layers and multi-view rendering (kernels/layers.hip.h, kernels/views.hip.h): the frame's own rays of `views`
 // views.  `out`: the blocks of the first view.  The poses: `poses`, on the device, or -- null -- `pose` for every view (a
 // layers call: one view), which only a `posed` host reads: without a pose the kernel holds the reference's camera as
@@ -718,13 +768,54 @@ void launch_layers(const SceneBuffers &scene, const KernelParams &P, const void 
 		hipLaunchKernelGGL((layers_kernel<true, false>), blocks, lanes, 0, s, a);
 	else
 		hipLaunchKernelGGL((layers_kernel<false, false>), blocks, lanes, 0, s, a);
-	if (!list || !list->flags)
+	if (list && list->flags)
+		launch_views_list(*list, views * a.n, s);
+}
+
+// The instanced form (kernels/instance_views.hip.h): the views of a chunk -- `poses`, on the device -- against the set's
+// top-level records and inverses (launch_instances'), with `instance` beside the layers.  Always listing where `list` is given.
+void launch_instance_layers(const SceneBuffers &scene, const KernelParams &P, const void *top, uint32_t top_count, const void *inverses,
+                            const void *poses, uint32_t views, const LayerOutputs &out, uint32_t *instance, float *value, float *ao,
+                            float *product, const ViewList *list, void *stream) {
+	InstanceLayersArgs a{};
+	a.nodes_ptr = (const float4 *) scene.nodes;
+	a.tris_ptr = (const float4 *) scene.tris;
+	a.shade_recs = (const float4 *) scene.shade;
+	a.width = P.width;
+	a.height = P.height;
+	a.tiles_x = (P.width + TILE_W - 1u) / TILE_W;
+	a.tiles = a.tiles_x * ((P.height + TILE_H - 1u) / TILE_H);
+	a.node_count = P.node_count;
+	a.shading = P.shading;
+	a.a = P.a;
+	a.half_w = P.half_w;
+	a.half_h = P.half_h;
+	a.poses = (const CameraPose *) poses;
+	a.n = P.width * P.height;
+	a.hit = out.hit;
+	a.out = out;
+	a.direction = out.direction;
+	a.shade = out.shade;
+	a.value = value;
+	a.top_ptr = (const float4 *) top;
+	a.inverses = (const float4 *) inverses;
+	a.top_count = top_count;
+	a.instance = instance;
+	if (views == 0 || a.tiles == 0 || top_count == 0 || !poses)
 		return;
-	const uint32_t m = views * a.n, scans = (m + VIEWS_SCAN - 1u) / VIEWS_SCAN;  // (m <= RT_QUERY_MAX_RAYS: RayQueries::viewsPerChunk)
-	hipLaunchKernelGGL(views_count_kernel, dim3(scans), dim3(VIEWS_SCAN), 0, s, (const uint8_t *) list->flags, list->sums, m);
-	hipLaunchKernelGGL(views_scan_sums_kernel, dim3(1), dim3(VIEWS_SUMS), 0, s, list->sums, scans, list->listed);
-	hipLaunchKernelGGL(views_order_kernel, dim3(scans), dim3(VIEWS_SCAN), 0, s, (const uint8_t *) list->flags, (const uint32_t *) list->sums,
-	                   list->order, m);
+	hipStream_t s = (hipStream_t) stream;
+	if (list) {
+		a.points = (float4 *) list->points;
+		a.normals = (float4 *) list->normals;
+		a.flags = list->flags;
+		a.seeds = list->seeds;
+		a.ao = ao;
+		a.product = product;
+	}
+	const dim3 blocks((a.tiles + LAYERS_WAVES - 1u) / LAYERS_WAVES, views), lanes(64 * LAYERS_WAVES);  // (views <= 65535: RayQueries::viewsPerChunk)
+	hipLaunchKernelGGL(instance_layers_kernel, blocks, lanes, 0, s, a);
+	if (list && list->flags)
+		launch_views_list(*list, views * a.n, s);
 }
 
 // ... the factors of the step's `listed` entries, from its counts, to where they belong: list.order[j], or sub-pixel j

@@ -34,6 +34,8 @@ enum { VIS_POINTS, VIS_TARGETS, VIS_ROWS, VIS_COUNTS, VIS_PIECES };
 enum { LAYER_HIT, LAYER_RECORDS, LAYER_DIRECTION = LAYER_RECORDS + 5, LAYER_SHADE, LAYER_AO, LAYER_VALUE, LAYER_PIECES };
 // Multi-view rendering: the layers' pieces, then the 8-bit images.
 enum { VIEW_IMAGE = LAYER_PIECES, VIEW_PIECES };
+// Instanced views: the views' pieces, then the instance indices.
+enum { VIEW_INSTANCE = VIEW_PIECES, INSTANCE_VIEW_PIECES };
 constexpr uint32_t QUERY_MAX_RAYS = 1u << 27;  // include/rt_hip_query.h
 constexpr uint32_t VIEWS_MAX_CHUNK = 65535u;   // layers_kernel, views_resize_kernel: a grid's second and third dimension
 constexpr size_t PINNED_HEAD = 16u;            // viewsDevice: the read-back word in front of the poses
@@ -532,8 +534,15 @@ void RayQueries::aoDevice(const float *points4, const float *normals4, const uin
 }
 
 void RayQueries::aoEnqueue(const Enqueue &q, const float *points4, const float *normals4, const uint32_t *seeds, const void *order,
-                           uint32_t n, uint32_t *count, float *ao) {
+                           uint32_t n, uint32_t *count, float *ao, bool instanced) {
 	const KernelParams &kp = dev.params();
+	if (instanced) {
+		const size_t rows = (size_t) instanceCount() * 12u * sizeof(float);
+		const char *set = (const char *) inst_device.ptr;
+		launch_instance_ao(dev.deviceScene()->buffers(), kp.node_count, set + 2u * rows, (uint32_t) inst_nodes.size(), set + rows, kp.ao_mode,
+		                   kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4, normals4, seeds, order, n, count, ao, q.stream);
+		return;
+	}
 	launch_ao_query(dev.deviceScene()->buffers(), kp.node_count, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4,
 	                normals4, seeds, order, n, count, ao, q.stream);
 }
@@ -549,6 +558,37 @@ void RayQueries::aoHost(const float *points4, const float *normals4, const uint3
 	void *s = stageIn(p, AO_PIECES);
 	aoDevice((const float *) p[AO_POINTS].device, (const float *) p[AO_NORMALS].device, (const uint32_t *) p[AO_SEEDS].device, n, flags,
 	         (float *) p[AO_VALUES].device, (uint32_t *) p[AO_COUNTS].device, s);
+	stageOut(p, AO_PIECES, s);
+}
+
+// ---- instanced ambient occlusion (include/rt_hip_instance_views.h) ----
+void RayQueries::instancesAoDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
+                                   uint32_t *occluded, void *stream) {
+	requireInstances("instanced ambient-occlusion query");
+	requireAo();
+	if (n == 0 || (!ao && !occluded))
+		return;
+	refreshInstances();
+	const KernelParams &kp = dev.params();
+	// aoDevice's sort of the POINTS, their cells over the top-level root box
+	const Enqueue q = begin(stream, points4, normals4, n, (uint64_t) n * kp.ao_dirs, flags,
+	                        { Need{ occluded ? nullptr : &ao_hits, (size_t) n * sizeof(uint32_t) } }, false, inst_box);
+	aoEnqueue(q, points4, normals4, seeds, q.order, n, occluded ? occluded : (uint32_t *) ao_hits.ptr, ao, true);
+	end(q);
+}
+
+void RayQueries::instancesAoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
+                                 uint32_t *occluded) {
+	requireInstances("instanced ambient-occlusion query");
+	requireAo();
+	if (n == 0 || (!ao && !occluded))
+		return;
+	// (the counts are staged whether they are copied back or not: the kernel counts into them)
+	Staged p[AO_PIECES] = { input(points4, (size_t) n * 16u), input(normals4, (size_t) n * 16u), scratch(occluded, (size_t) n * 4u),
+		                    input(seeds, (size_t) n * 4u), output(ao, (size_t) n * 4u) };
+	void *s = stageIn(p, AO_PIECES);
+	instancesAoDevice((const float *) p[AO_POINTS].device, (const float *) p[AO_NORMALS].device, (const uint32_t *) p[AO_SEEDS].device, n, flags,
+	                  (float *) p[AO_VALUES].device, (uint32_t *) p[AO_COUNTS].device, s);
 	stageOut(p, AO_PIECES, s);
 }
 
@@ -655,7 +695,7 @@ RayQueries::ChunkScratch RayQueries::chunkScratch(size_t poses, size_t entries, 
 }
 
 uint32_t RayQueries::castChunk(const Enqueue &q, const ChunkScratch &at, bool listing, const void *poses, uint32_t views,
-                               const LayerOutputs &to, float *product, bool with_ao) {
+                               const LayerOutputs &to, float *product, bool with_ao, bool instanced, uint32_t *instance) {
 	const KernelParams &kp = dev.params();
 	hipStream_t s = (hipStream_t) q.stream;
 	char *const base = (char *) this->views.ptr;
@@ -672,8 +712,15 @@ uint32_t RayQueries::castChunk(const Enqueue &q, const ChunkScratch &at, bool li
 		list.listed = (uint32_t *) (base + at.listed);
 	}
 	// (without the ambient-occlusion step `value` is the head-light term itself)
-	launch_layers(dev.deviceScene()->buffers(), kp, poses, dev.camera(), dev.cameraIsSet(), views, to, with_ao ? nullptr : product, to.ao,
-	              product, with_ao ? &list : nullptr, s);
+	if (instanced) {
+		const size_t rows = (size_t) instanceCount() * 12u * sizeof(float);
+		const char *set = (const char *) inst_device.ptr;
+		launch_instance_layers(dev.deviceScene()->buffers(), kp, set + 2u * rows, (uint32_t) inst_nodes.size(), set + rows, poses, views, to,
+		                       instance, with_ao ? nullptr : product, to.ao, product, with_ao ? &list : nullptr, s);
+	} else {
+		launch_layers(dev.deviceScene()->buffers(), kp, poses, dev.camera(), dev.cameraIsSet(), views, to, with_ao ? nullptr : product, to.ao,
+		              product, with_ao ? &list : nullptr, s);
+	}
 	if (!with_ao)
 		return 0u;
 	// the reference's ambient_occlusion(position, normal, index) in index order: of every sub-pixel -- seed i for point i --
@@ -691,7 +738,7 @@ uint32_t RayQueries::castChunk(const Enqueue &q, const ChunkScratch &at, bool li
 			throw DeviceError("multi-view rendering: more sub-pixels listed than the chunk holds");
 		entries = *listed_host;
 	}
-	aoEnqueue(q, (const float *) list.points, (const float *) list.normals, list.seeds, list.order, entries, count, nullptr);
+	aoEnqueue(q, (const float *) list.points, (const float *) list.normals, list.seeds, list.order, entries, count, nullptr, instanced);
 	launch_views_scatter(list, count, kp.ao_divisor, to.ao, product, entries, s);
 	return entries;
 }
@@ -761,12 +808,32 @@ ViewOutputs RayQueries::viewsFrom(const ViewOutputs &out, size_t view, const Ker
 }
 
 void RayQueries::viewsDevice(const CameraPose *cameras, uint32_t views, const ViewOutputs &out, void *stream) {
+	viewsCall(false, cameras, views, out, nullptr, stream);
+}
+
+void RayQueries::viewsHost(const CameraPose *cameras, uint32_t views, const ViewOutputs &host) { viewsStaged(false, cameras, views, host, nullptr); }
+
+// ---- instanced views (include/rt_hip_instance_views.h) ----
+void RayQueries::instanceViewsDevice(const CameraPose *cameras, uint32_t views, const ViewOutputs &out, uint32_t *instance, void *stream) {
+	viewsCall(true, cameras, views, out, instance, stream);
+}
+
+void RayQueries::instanceViewsHost(const CameraPose *cameras, uint32_t views, const ViewOutputs &host, uint32_t *instance) {
+	viewsStaged(true, cameras, views, host, instance);
+}
+
+void RayQueries::viewsCall(bool instanced, const CameraPose *cameras, uint32_t views, const ViewOutputs &out, uint32_t *instance,
+                           void *stream) {
+	if (instanced)
+		requireInstances("instanced views");
 	const bool with_ao = requireViews(out);
 	const KernelParams &kp = dev.params();
 	const RayTracer &rt = dev.rayTracer();
 	const uint32_t n = kp.width * kp.height, grid = RayTracer::gridSize(rt.options.nSuperSamples);
-	if (views == 0 || n == 0 || !out.any())
+	if (views == 0 || n == 0 || !(out.any() || instance))
 		return;
+	if (instanced)
+		refreshInstances();
 	const uint32_t per_chunk = std::min(viewsPerChunk(with_ao), views);
 	const size_t most = (size_t) per_chunk * n, image_bytes = (size_t) rt.options.width * rt.options.height;
 	// the poses: into host memory of this host's own that the copies may read after the call has returned -- once the
@@ -801,7 +868,8 @@ void RayQueries::viewsDevice(const CameraPose *cameras, uint32_t views, const Vi
 		// (`product`: the chunk's float images -- the caller's `value`, or scratch for the 8-bit images alone)
 		float *const product = own_product ? (float *) (base + at.product) : to.value;
 		OCRT_HIP(hipMemcpyAsync(base + at.poses, poses_host + first, (size_t) chunk * sizeof(CameraPose), hipMemcpyHostToDevice, s));
-		done.ao_points += castChunk(q, at, true, base + at.poses, chunk, to, product, with_ao);
+		done.ao_points += castChunk(q, at, true, base + at.poses, chunk, to, product, with_ao, instanced,
+		                            instance ? instance + (size_t) first * n : nullptr);
 		if (to.image)
 			launch_views_resize(product, to.image, kp, rt.options.width, rt.options.height, grid, chunk, s);
 	}
@@ -809,12 +877,14 @@ void RayQueries::viewsDevice(const CameraPose *cameras, uint32_t views, const Vi
 	last_views = done;
 }
 
-void RayQueries::viewsHost(const CameraPose *cameras, uint32_t views, const ViewOutputs &host) {
+void RayQueries::viewsStaged(bool instanced, const CameraPose *cameras, uint32_t views, const ViewOutputs &host, uint32_t *instance) {
+	if (instanced)
+		requireInstances("instanced views");
 	const bool with_ao = requireViews(host);
 	const KernelParams &kp = dev.params();
 	const RayTracer &rt = dev.rayTracer();
 	const size_t n = (size_t) kp.width * kp.height, image_bytes = (size_t) rt.options.width * rt.options.height;
-	if (views == 0 || n == 0 || !host.any())
+	if (views == 0 || n == 0 || !(host.any() || instance))
 		return;
 	// chunk by chunk through the staging buffer, so that it holds one chunk's outputs, not the call's
 	const uint32_t per_chunk = std::min(viewsPerChunk(with_ao), views);
@@ -823,15 +893,16 @@ void RayQueries::viewsHost(const CameraPose *cameras, uint32_t views, const View
 	for (uint32_t first = 0; first < views; first += per_chunk) {
 		const size_t chunk = std::min(per_chunk, views - first), m = chunk * n;
 		const ViewOutputs to = viewsFrom(host, first, kp, image_bytes);
-		Staged p[VIEW_PIECES];
+		Staged p[INSTANCE_VIEW_PIECES];  // (the last piece: the instanced form's alone)
 		layerPieces(p, to, m);
 		p[VIEW_IMAGE] = output(to.image, chunk * image_bytes);
-		void *s = stageIn(p, VIEW_PIECES);
+		p[VIEW_INSTANCE] = output(instance ? instance + (size_t) first * n : nullptr, m * 4u);
+		void *s = stageIn(p, INSTANCE_VIEW_PIECES);
 		ViewOutputs out;
 		layerDevice(p, out);
 		out.image = (unsigned char *) p[VIEW_IMAGE].device;
-		viewsDevice(cameras + first, (uint32_t) chunk, out, s);
-		stageOut(p, VIEW_PIECES, s);
+		viewsCall(instanced, cameras + first, (uint32_t) chunk, out, (uint32_t *) p[VIEW_INSTANCE].device, s);
+		stageOut(p, INSTANCE_VIEW_PIECES, s);
 		ms += lastMs();
 		done.views += last_views.views;
 		done.chunks += last_views.chunks;

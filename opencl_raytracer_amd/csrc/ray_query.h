@@ -2,7 +2,8 @@
 // host's uploaded scene (include/rt_hip_query.h, include/rt_hip_multihit.h, include/rt_hip_ao.h, include/rt_hip_directional.h,
 // include/rt_hip_layers.h, include/rt_hip_views.h, include/rt_hip_segment.h; kernels/query.hip.h, kernels/segment.hip.h, kernels/multihit.hip.h, kernels/ao_query.hip.h,
 // kernels/directional.hip.h, kernels/layers.hip.h, kernels/views.hip.h); instanced ray queries (include/rt_hip_instances.h,
-// kernels/instances.hip.h, instances.h).
+// kernels/instances.hip.h, instances.h); instanced ambient occlusion and views (include/rt_hip_instance_views.h,
+// kernels/instance_views.hip.h).
 #pragma once
 #include <cstdint>
 #include <initializer_list>
@@ -85,6 +86,16 @@ class RayQueries {
 		// Host memory, blocking.
 		void instancesHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
 		                   const QueryOutputs &out, uint32_t *instance);
+		// Instanced ambient occlusion and instanced views (include/rt_hip_instance_views.h).  aoDevice's and viewsDevice's
+		// arguments and rules, the rays cast against the instance set: points and normals in world space, the point sort
+		// keyed over the top-level root box; the views' records are instancesDevice's, `instance` [views][N] beside the layers.
+		// std::logic_error without a set.  The tree is made again first if the scene changed (refreshInstances).
+		void instancesAoDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
+		                       uint32_t *occluded, void *stream);
+		void instancesAoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
+		                     uint32_t *occluded);
+		void instanceViewsDevice(const CameraPose *cameras, uint32_t views, const ViewOutputs &out, uint32_t *instance, void *stream);
+		void instanceViewsHost(const CameraPose *cameras, uint32_t views, const ViewOutputs &out, uint32_t *instance);
 		// Ambient-occlusion queries (include/rt_hip_ao.h): the reference's ambient_occlusion() of n points with the options
 		// the scene was uploaded for -- table, mode, rays per point, divisor and reach come from the renderer's launch
 		// constants and its DeviceScene.  std::logic_error where those options have ambient occlusion off.
@@ -218,8 +229,12 @@ class RayQueries {
 		// null: the host's own pose, one view -- into `to`, the blocks of the first view, then where `with_ao` the
 		// ambient-occlusion step and its tail into to.ao and `product`.  `listing`: the step runs over the hit sub-pixels
 		// alone, and the call waits for their number, which it returns; else over all of them, enqueued like the rest.
+		// `instanced`: both against the instance set (listing, poses on the device), `instance` its layer or null.
 		uint32_t castChunk(const Enqueue &q, const ChunkScratch &at, bool listing, const void *poses, uint32_t views, const LayerOutputs &to,
-		                   float *product, bool with_ao);
+		                   float *product, bool with_ao, bool instanced = false, uint32_t *instance = nullptr);
+		// viewsDevice and instanceViewsDevice, viewsHost and instanceViewsHost: one chunk loop each
+		void viewsCall(bool instanced, const CameraPose *cameras, uint32_t views, const ViewOutputs &out, uint32_t *instance, void *stream);
+		void viewsStaged(bool instanced, const CameraPose *cameras, uint32_t views, const ViewOutputs &host, uint32_t *instance);
 		static ViewOutputs viewsFrom(const ViewOutputs &out, size_t view, const KernelParams &kp, size_t image_bytes);
 		void grow(Scratch &scratch, size_t bytes);
 		void sceneBox(const DeviceScene &scene, float lo[3], float scale[3]);
@@ -229,9 +244,9 @@ class RayQueries {
 		              std::initializer_list<Need> needs = {}, bool segments = false, const float *box = nullptr);
 		void end(const Enqueue &q);
 		// The ambient-occlusion step between begin() and end(): n entries -- point order[j], or j where `order` is null --,
-		// counted into `count` by point index (the caller's `occluded` or ao_hits).
+		// counted into `count` by point index (the caller's `occluded` or ao_hits).  `instanced`: against the instance set.
 		void aoEnqueue(const Enqueue &q, const float *points4, const float *normals4, const uint32_t *seeds, const void *order, uint32_t n,
-		               uint32_t *count, float *ao);
+		               uint32_t *count, float *ao, bool instanced = false);
 		void *stageIn(Staged *pieces, size_t n);  // returns the stream
 		void stageOut(const Staged *pieces, size_t n, void *stream);
 
@@ -303,6 +318,9 @@ void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void 
 void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
                      float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
                      uint32_t *count, float *ao, void *stream);
+void launch_instance_ao(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses, int ao_mode,
+                        uint32_t rays_per_point, uint32_t divisor, float max_distance, const void *points, const void *normals,
+                        const uint32_t *seeds, const void *order, uint32_t n, uint32_t *count, float *ao, void *stream);
 void launch_ao_directional(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
                            float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
                            uint32_t *mask, uint32_t *occluded, float *ao, float *bent, void *stream);
@@ -310,6 +328,9 @@ void launch_ao_rays(const SceneBuffers &scene, int ao_mode, uint32_t rays_per_po
                     const uint32_t *seeds, uint32_t n, void *origins, void *directions, void *stream);
 void launch_layers(const SceneBuffers &scene, const KernelParams &P, const void *poses, const CameraPose &pose, bool posed, uint32_t views,
                    const LayerOutputs &out, float *value, float *ao, float *product, const ViewList *list, void *stream);
+void launch_instance_layers(const SceneBuffers &scene, const KernelParams &P, const void *top, uint32_t top_count, const void *inverses,
+                            const void *poses, uint32_t views, const LayerOutputs &out, uint32_t *instance, float *value, float *ao,
+                            float *product, const ViewList *list, void *stream);
 void launch_views_scatter(const ViewList &list, const uint32_t *count, uint32_t divisor, float *ao, float *product, uint32_t listed,
                           void *stream);
 void launch_views_resize(const float *value, unsigned char *image, const KernelParams &P, uint32_t out_width, uint32_t out_height,

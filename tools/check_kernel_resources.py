@@ -152,7 +152,9 @@ def main():
                "segment_kernel<true>", "segment_kernel<false>", "visibility_mask_kernel", "visibility_count_kernel",
                "segment_key_kernel", "segment_scatter_kernel",
                # instanced ray queries (kernels/instances.hip.h): two nested exact walks
-               "instance_kernel<true>", "instance_kernel<false>")
+               "instance_kernel<true>", "instance_kernel<false>",
+               # instanced ambient occlusion and views (kernels/instance_views.hip.h): the same nested walks
+               "instance_ao_kernel<1", "instance_ao_kernel<2", "instance_layers_kernel")
     # the directional occlusion queries' walk is ao_query_kernel's with another tail (kernels/directional.hip.h): it must keep
     # that kernel's occupancy, 8 waves per SIMD -- a tail that needs more live state than the old one shows here
     full_occupancy = ("ao_mask_kernel<1", "ao_mask_kernel<2")
