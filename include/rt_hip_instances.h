@@ -5,8 +5,10 @@
  * map.  The two queries below cast world-space rays against all copies under the arithmetic contract (every
  * operation rounded on its own in binary32, in the order written here).  Every plain entry point -- frames, layers, views,
  * ambient occlusion, segments, multi-hit and closest-point queries -- ignores the set: nothing they compute changes when
- * one is given.  Ambient occlusion and views have instanced forms of their own, rt_trace_instances_ao and
- * rt_render_instance_views (rt_hip_instance_views.h), defined by the rules below.
+ * one is given.  Ambient occlusion, views and segments have instanced forms of their own, defined by the rules below:
+ * rt_trace_instances_ao and rt_render_instance_views (rt_hip_instance_views.h), and rt_instances_segments_occluded,
+ * rt_instances_segments_closest and rt_instances_visibility_masks (rt_hip_instance_segments.h).  Multi-hit, closest-point and
+ * directional occlusion queries have none.
  *
  * Transforms.  world_from_object is twelve floats per instance, the rows of W = [A | t]: p_world = A p + t.  Every entry
  * must be finite, the determinant of A (binary64) non-zero and every entry of the inverse finite after its rounding to

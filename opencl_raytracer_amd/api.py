@@ -1,5 +1,5 @@
 """ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h, rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h,
-rt_hip_nearest.h, rt_hip_segment.h, rt_hip_instances.h, rt_hip_instance_views.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers
+rt_hip_nearest.h, rt_hip_segment.h, rt_hip_instances.h, rt_hip_instance_segments.h, rt_hip_instance_views.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers
 for the contract)."""
 from __future__ import annotations
 
@@ -240,6 +240,19 @@ _SIGNATURES = {
                                       C.c_void_p]),
     "rt_visibility_masks_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_float,
                                              C.c_uint32, C.c_void_p, C.c_void_p]),
+    # include/rt_hip_instance_segments.h
+    "rt_instances_segments_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32,
+                                                 C.c_void_p]),
+    "rt_instances_segments_closest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32,
+                                                C.c_void_p]),
+    "rt_instances_segments_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32,
+                                                        C.c_void_p, C.c_void_p]),
+    "rt_instances_segments_closest_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32,
+                                                       C.c_void_p, C.c_void_p]),
+    "rt_instances_visibility_masks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_float,
+                                                C.c_uint32, C.c_void_p]),
+    "rt_instances_visibility_masks_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_float,
+                                                       C.c_uint32, C.c_void_p, C.c_void_p]),
     # include/rt_hip_instances.h
     "rt_set_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "rt_instance_count": (C.c_uint32, [C.c_void_p]),
@@ -1033,18 +1046,23 @@ class Host:
         without a blocker: +inf, 0xFFFFFFFF, zeros.  Inputs and forms as for segments_occluded."""
         return self._segments(True, a, b, interval, tuple(outputs), sort)
 
-    def _segments(self, closest: bool, a, b, interval, outputs: tuple, sort: bool) -> dict:
-        unknown = [o for o in outputs if o not in SEGMENT_OUTPUTS]
+    def _segments(self, closest: bool, a, b, interval, outputs: tuple, sort: bool, instanced: bool = False) -> dict:
+        known = INSTANCE_OUTPUTS if instanced else SEGMENT_OUTPUTS
+        unknown = [o for o in outputs if o not in known]
         if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {SEGMENT_OUTPUTS}")
+            raise ValueError(f"unknown outputs {unknown}; choose from {known}")
         t_lo, t_hi = interval
         io = _QueryArrays(a, b, ("a", "b"), "points")
         out = io.outputs(outputs)
         args = (io.n, float(t_lo), float(t_hi), 0 if sort else RT_QUERY_NO_SORT)
-        if closest:
-            io.call(self._h, "rt_segments_closest", *args, C.byref(_HitArrays(*io.pointers(out, SEGMENT_OUTPUTS))))
+        family = "rt_instances_segments" if instanced else "rt_segments"
+        if closest and instanced:
+            at = io.pointers(out, INSTANCE_OUTPUTS)
+            io.call(self._h, family + "_closest", *args, C.byref(_InstanceHitArrays(_HitArrays(*at[:-1]), at[-1])))
+        elif closest:
+            io.call(self._h, family + "_closest", *args, C.byref(_HitArrays(*io.pointers(out, SEGMENT_OUTPUTS))))
         else:
-            io.call(self._h, "rt_segments_occluded", *args, *io.pointers(out, ("hit",)))
+            io.call(self._h, family + "_occluded", *args, *io.pointers(out, ("hit",)))
         return out
 
     def visibility(self, points, targets, interval=SEGMENT_INTERVAL, outputs=VISIBILITY_OUTPUTS, sort: bool = True) -> dict:
@@ -1053,6 +1071,9 @@ class Host:
         of it) --, "count": uint32 (P,), the row's popcount: the targets point i does NOT see} (those named in `outputs`).
         points: (P, 3) / (P, 4), targets: (T, 3) / (T, 4) float32, P T <= 2^27; the P x T rays are never written out.
         numpy / torch forms as for segments_occluded."""
+        return self._visibility("rt_visibility_masks", points, targets, interval, outputs, sort)
+
+    def _visibility(self, function: str, points, targets, interval, outputs, sort: bool) -> dict:
         outputs = tuple(outputs)
         unknown = [o for o in outputs if o not in VISIBILITY_OUTPUTS]
         if unknown:
@@ -1073,11 +1094,29 @@ class Host:
         if io.n and nt == 0:  # (nothing is launched: the rows have no words, every count is 0)
             for name in out:
                 out[name][...] = 0
-        io.call(self._h, "rt_visibility_masks", io.n, io.ptr(targets4) if nt else None, nt, float(t_lo), float(t_hi),
+        io.call(self._h, function, io.n, io.ptr(targets4) if nt else None, nt, float(t_lo), float(t_hi),
                 0 if sort else RT_QUERY_NO_SORT, C.byref(_VisibilityArrays(*pointers)))
         if io.torch and targets4 is not targets:  # (the padded copy must live until the kernels have read it)
             targets4.record_stream(io.current)
         return out
+
+    # ---- instanced segment queries (include/rt_hip_instance_segments.h) ----
+    def instances_segments_occluded(self, a, b, interval=SEGMENT_INTERVAL, sort: bool = True):
+        """segments_occluded with every posed copy of the scene (set_instances) in the way: uint8 (N,), 1 iff some copy
+        blocks the WORLD-space segment from a[i] to b[i] at a fraction r of it with interval[0] < r < interval[1].  Inputs
+        and the numpy / torch forms as for segments_occluded."""
+        return self._segments(False, a, b, interval, ("hit",), sort, instanced=True)["hit"]
+
+    def instances_segments_closest(self, a, b, interval=SEGMENT_INTERVAL, outputs=INSTANCE_OUTPUTS, sort: bool = True) -> dict:
+        """The first blocker of every world-space segment among the posed copies, the record of trace_instances_closest:
+        position, distance (a length from a[i]) and normal in world space, leaf and barycentrics of the copy's triangle,
+        and "instance", the copy (those named in `outputs`); without a blocker: +inf, 0xFFFFFFFF, zeros."""
+        return self._segments(True, a, b, interval, tuple(outputs), sort, instanced=True)
+
+    def instances_visibility(self, points, targets, interval=SEGMENT_INTERVAL, outputs=VISIBILITY_OUTPUTS, sort: bool = True) -> dict:
+        """visibility with every posed copy of the scene in the way: the mask rows and counts of world-space points against
+        world-space targets, laid out as visibility lays them out; the P x T rays are never written out."""
+        return self._visibility("rt_instances_visibility_masks", points, targets, interval, outputs, sort)
 
     # ---- closest-point queries (include/rt_hip_nearest.h) ----
     def closest_points(self, points, max_distance: float = float("inf"), outputs=NEAREST_OUTPUTS, sort: bool = True) -> dict:

@@ -11,6 +11,7 @@
 #include "../../include/rt_hip_nearest.h"
 #include "../../include/rt_hip_query.h"
 #include "../../include/rt_hip_segment.h"
+#include "../../include/rt_hip_instance_segments.h"
 #include "../../include/rt_hip_instance_views.h"
 #include "../../include/rt_hip_instances.h"
 #include "../../include/rt_hip_views.h"
@@ -1160,6 +1161,92 @@ int rt_trace_instances_occluded_device(rt_host *h, const float *origins4, const 
 	ocrt::QueryOutputs q;
 	q.hit = occluded;
 	return guarded([&] { queries_of(h).instancesDevice(false, origins4, directions4, n, max_distance, flags, q, nullptr, hip_stream); });
+}
+
+// ---- rt_hip_instance_segments.h ----
+namespace {
+
+// The union of segment_precheck's and instance_precheck's checks (include/rt_hip_instance_segments.h, "Errors").
+int instance_segment_precheck(rt_host *h, const float *a4, const float *b4, uint64_t items, bool device) {
+	const int rc = host_precheck(h, "instanced segment");
+	if (rc != RT_OK)
+		return rc;
+	if (!h->queries || h->queries->instanceCount() == 0)
+		return fail(RT_E_STATE, "instanced segment query without an instance set (rt_set_instances)");
+	if (items > RT_QUERY_MAX_RAYS)
+		return fail(RT_E_INVALID, "more segments than RT_QUERY_MAX_RAYS in one call");
+	if (items > 0 && (!a4 || !b4))
+		return fail(RT_E_INVALID, "null point arrays");
+	if (device && items > 0 && !aligned({ a4, b4 }, 16))
+		return fail(RT_E_INVALID, "device point arrays must be 16-byte aligned");
+	return RT_OK;
+}
+
+}  // namespace
+
+int rt_instances_segments_closest(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+                                  const rt_instance_hit_arrays *out) {
+	const int rc = instance_segment_precheck(h, from4, to4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	return guarded([&] {
+		queries_of(h).instanceSegmentsHost(true, from4, to4, n, t_lo, t_hi, flags, hit_outputs(out ? &out->record : nullptr),
+		                                   out ? out->instance : nullptr);
+	});
+}
+
+int rt_instances_segments_occluded(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+                                   uint8_t *occluded) {
+	const int rc = instance_segment_precheck(h, from4, to4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	ocrt::QueryOutputs q;
+	q.hit = occluded;
+	return guarded([&] { queries_of(h).instanceSegmentsHost(false, from4, to4, n, t_lo, t_hi, flags, q, nullptr); });
+}
+
+int rt_instances_segments_closest_device(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi,
+                                         uint32_t flags, const rt_instance_hit_arrays *out, void *hip_stream) {
+	const int rc = instance_segment_precheck(h, from4, to4, n, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	const ocrt::QueryOutputs q = hit_outputs(out ? &out->record : nullptr);
+	uint32_t *const instance = out ? out->instance : nullptr;
+	if (!records_aligned(q) || !aligned({ instance }, 4))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).instanceSegmentsDevice(true, from4, to4, n, t_lo, t_hi, flags, q, instance, hip_stream); });
+}
+
+int rt_instances_segments_occluded_device(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi,
+                                          uint32_t flags, uint8_t *occluded, void *hip_stream) {
+	const int rc = instance_segment_precheck(h, from4, to4, n, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	ocrt::QueryOutputs q;
+	q.hit = occluded;
+	return guarded([&] { queries_of(h).instanceSegmentsDevice(false, from4, to4, n, t_lo, t_hi, flags, q, nullptr, hip_stream); });
+}
+
+int rt_instances_visibility_masks(rt_host *h, const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
+                                  uint32_t flags, const rt_visibility_arrays *out) {
+	const uint64_t pairs = (uint64_t) np * nt;
+	const int rc = instance_segment_precheck(h, points4, targets4, pairs, false);
+	if (rc != RT_OK || pairs == 0)
+		return rc;
+	const ocrt::RayQueries::VisibilityOutputs q = visibility_outputs(out);
+	return guarded([&] { queries_of(h).instanceVisibilityHost(points4, np, targets4, nt, t_lo, t_hi, flags, q); });
+}
+
+int rt_instances_visibility_masks_device(rt_host *h, const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo,
+                                         float t_hi, uint32_t flags, const rt_visibility_arrays *out, void *hip_stream) {
+	const uint64_t pairs = (uint64_t) np * nt;
+	const int rc = instance_segment_precheck(h, points4, targets4, pairs, true);
+	if (rc != RT_OK || pairs == 0)
+		return rc;
+	const ocrt::RayQueries::VisibilityOutputs q = visibility_outputs(out);
+	if (!aligned({ q.mask, q.count }, 4))
+		return fail(RT_E_INVALID, "device uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).instanceVisibilityDevice(points4, np, targets4, nt, t_lo, t_hi, flags, q, hip_stream); });
 }
 
 // ---- rt_hip_nearest.h ----

@@ -56,6 +56,10 @@
 //                   against the posed copies: the same rays, made in registers, through instance_kernel's two nested walks;
 //                   the list, the tail and the images between and behind them are the views' own (kernels/instance_views.hip.h,
 //                   include/rt_hip_instance_views.h).
+//                   instance_segment_kernel<CLOSEST> and instance_visibility_kernel are segment_kernel and
+//                   visibility_mask_kernel against the posed copies: the same packets and tails around the two nested walks,
+//                   the interval test on the object ray's plane parameter (kernels/instance_segments.hip.h,
+//                   include/rt_hip_instance_segments.h).
 //   (scenes)        refit_leaves_kernel / refit_inner_kernel make the records and boxes of a scene again from new positions
 //                   (kernels/refit.hip.h, include/rt_hip_update.h); build_boxes_kernel, build_root_kernel, build_keys_kernel,
 //                   build_tree_kernel and build_layout_kernel make a scene's tree from triangles, around a sort that lives in
@@ -109,6 +113,7 @@
 #include "kernels/segment.hip.h"
 #include "kernels/instances.hip.h"
 #include "kernels/instance_views.hip.h"
+#include "kernels/instance_segments.hip.h"
 
 
 namespace ocrt {
@@ -536,6 +541,70 @@ void launch_visibility(const SceneBuffers &scene, uint32_t node_count, const voi
 	(void) hipMemsetAsync(mask, 0, (size_t) np * a.words * sizeof(uint32_t), s);
 	const uint32_t blocks = (a.total + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
 	hipLaunchKernelGGL(visibility_mask_kernel, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+	if (count)
+		hipLaunchKernelGGL(visibility_count_kernel, dim3((np + 255u) / 256u), dim3(256), 0, s, (const uint32_t *) mask, count, np, a.words);
+}
+
+// Instanced segment queries (kernels/instance_segments.hip.h): launch_segments' arguments with the set's top-level records
+// and inverses (launch_instances'); their sort is launch_query_sort's with `segments`, over the top-level root box.
+void launch_instance_segments(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses,
+                              bool closest, const void *from, const void *to, const void *order, uint32_t n, float t_lo, float t_hi,
+                              const QueryOutputs &out, uint32_t *instance, void *stream) {
+	if (n == 0 || top_count == 0)
+		return;
+	InstanceSegmentArgs a{};
+	a.nodes_ptr = (const float4 *) scene.nodes;
+	a.tris_ptr = (const float4 *) scene.tris;
+	a.shade = (const float4 *) scene.shade;
+	a.from = (const float4 *) from;
+	a.to = (const float4 *) to;
+	a.order = (const uint32_t *) order;
+	a.n = n;
+	a.node_count = node_count;
+	a.t_lo = t_lo;
+	a.t_hi = t_hi;
+	a.out = out;
+	a.hit = out.hit;
+	a.top_ptr = (const float4 *) top;
+	a.inverses = (const float4 *) inverses;
+	a.top_count = top_count;
+	a.instance = instance;
+	const uint32_t blocks = (n + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
+	if (closest) {
+		hipLaunchKernelGGL(instance_segment_kernel<true>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
+	} else {
+		hipLaunchKernelGGL(instance_segment_kernel<false>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
+	}
+}
+
+// ... and their many-to-many form: launch_visibility's arguments and steps with the set's records and inverses.
+void launch_instance_visibility(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses,
+                                const void *points, uint32_t np, const void *targets, uint32_t nt, const void *order, float t_lo, float t_hi,
+                                uint32_t *mask, uint32_t *count, void *stream) {
+	if (np == 0 || nt == 0 || top_count == 0)
+		return;
+	hipStream_t s = (hipStream_t) stream;
+	InstanceVisibilityArgs a{};
+	a.nodes_ptr = (const float4 *) scene.nodes;
+	a.tris_ptr = (const float4 *) scene.tris;
+	a.points = (const float4 *) points;
+	a.targets = (const float4 *) targets;
+	a.order = (const uint32_t *) order;
+	a.mask = mask;
+	a.np = np;
+	a.nt = nt;
+	a.words = (nt + 31u) / 32u;
+	a.total = np * nt;  // (<= RT_QUERY_MAX_RAYS: checked at the boundary)
+	visibility_divisor(nt, a.magic, a.shift);
+	a.node_count = node_count;
+	a.t_lo = t_lo;
+	a.t_hi = t_hi;
+	a.top_ptr = (const float4 *) top;
+	a.inverses = (const float4 *) inverses;
+	a.top_count = top_count;
+	(void) hipMemsetAsync(mask, 0, (size_t) np * a.words * sizeof(uint32_t), s);
+	const uint32_t blocks = (a.total + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
+	hipLaunchKernelGGL(instance_visibility_kernel, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
 	if (count)
 		hipLaunchKernelGGL(visibility_count_kernel, dim3((np + 255u) / 256u), dim3(256), 0, s, (const uint32_t *) mask, count, np, a.words);
 }

@@ -422,6 +422,77 @@ void RayQueries::visibilityHost(const float *points4, uint32_t np, const float *
 	stageOut(p, VIS_PIECES, s);
 }
 
+// ---- instanced segment queries (include/rt_hip_instance_segments.h) ----
+void RayQueries::instanceSegmentsDevice(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+                                        const QueryOutputs &out, uint32_t *instance, void *stream) {
+	requireInstances("instanced segment query");
+	if (n == 0)
+		return;
+	refreshInstances();
+	const size_t rows = (size_t) instanceCount() * 12u * sizeof(float);
+	const char *set = (const char *) inst_device.ptr;
+	const Enqueue q = begin(stream, from4, to4, n, n, flags, {}, true, inst_box);
+	launch_instance_segments(dev.deviceScene()->buffers(), dev.params().node_count, set + 2u * rows, (uint32_t) inst_nodes.size(), set + rows,
+	                         closest, from4, to4, q.order, n, t_lo, t_hi, out, closest ? instance : nullptr, q.stream);
+	end(q);
+}
+
+void RayQueries::instanceSegmentsHost(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+                                      const QueryOutputs &host, uint32_t *instance) {
+	requireInstances("instanced segment query");
+	if (n == 0)
+		return;
+	QueryOutputs want;  // (occlusion: the flags alone)
+	if (closest)
+		want = host;
+	want.hit = host.hit;
+	Staged p[INST_PIECES] = { input(from4, (size_t) n * 16u), input(to4, (size_t) n * 16u), output(want.hit, n) };
+	recordPieces(p + RAY_RECORDS, want, n);
+	p[INST_INDEX] = output(closest ? instance : nullptr, (size_t) n * 4u);
+	void *s = stageIn(p, INST_PIECES);
+	QueryOutputs out;
+	out.hit = (unsigned char *) p[RAY_FIRST].device;
+	recordDevice(p + RAY_RECORDS, out);
+	instanceSegmentsDevice(closest, (const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, t_lo, t_hi, flags, out,
+	                       (uint32_t *) p[INST_INDEX].device, s);
+	stageOut(p, INST_PIECES, s);
+}
+
+void RayQueries::instanceVisibilityDevice(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
+                                          uint32_t flags, const VisibilityOutputs &out, void *stream) {
+	requireInstances("instanced visibility query");
+	if (np == 0 || nt == 0 || !out.any())
+		return;
+	refreshInstances();
+	const size_t rows = (size_t) instanceCount() * 12u * sizeof(float);
+	const char *set = (const char *) inst_device.ptr;
+	const size_t row_bytes = (size_t) visibilityWords(nt) * sizeof(uint32_t);
+	// the POINTS are ordered, by position over the top-level root box; the rows are the caller's, or scratch where only the
+	// counts are wanted
+	const Enqueue q = begin(stream, points4, nullptr, np, np, flags, { Need{ out.mask ? nullptr : &vis_rows, (size_t) np * row_bytes } }, false,
+	                        inst_box);
+	launch_instance_visibility(dev.deviceScene()->buffers(), dev.params().node_count, set + 2u * rows, (uint32_t) inst_nodes.size(), set + rows,
+	                           points4, np, targets4, nt, q.order, t_lo, t_hi, out.mask ? out.mask : (uint32_t *) vis_rows.ptr, out.count,
+	                           q.stream);
+	end(q);
+}
+
+void RayQueries::instanceVisibilityHost(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
+                                        uint32_t flags, const VisibilityOutputs &host) {
+	requireInstances("instanced visibility query");
+	if (np == 0 || nt == 0 || !host.any())
+		return;
+	const size_t row_bytes = (size_t) visibilityWords(nt) * sizeof(uint32_t);
+	Staged p[VIS_PIECES] = { input(points4, (size_t) np * 16u), input(targets4, (size_t) nt * 16u), scratch(host.mask, (size_t) np * row_bytes),
+		                     output(host.count, (size_t) np * 4u) };
+	void *s = stageIn(p, VIS_PIECES);
+	VisibilityOutputs out;
+	out.mask = (uint32_t *) p[VIS_ROWS].device;
+	out.count = (uint32_t *) p[VIS_COUNTS].device;
+	instanceVisibilityDevice((const float *) p[VIS_POINTS].device, np, (const float *) p[VIS_TARGETS].device, nt, t_lo, t_hi, flags, out, s);
+	stageOut(p, VIS_PIECES, s);
+}
+
 // What the closest-point walk may do follows from the scene: where every box holds the triangles beneath it -- an upload the
 // packer found so, the refit rule's boxes after an update or a build -- each lane descends for a starting bound and boxes are
 // passed by (kernels/nearest.hip.h); otherwise (damaged arrays) every leaf is tested.  After an update or a build whose

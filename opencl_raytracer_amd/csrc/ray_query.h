@@ -3,7 +3,8 @@
 // include/rt_hip_layers.h, include/rt_hip_views.h, include/rt_hip_segment.h; kernels/query.hip.h, kernels/segment.hip.h, kernels/multihit.hip.h, kernels/ao_query.hip.h,
 // kernels/directional.hip.h, kernels/layers.hip.h, kernels/views.hip.h); instanced ray queries (include/rt_hip_instances.h,
 // kernels/instances.hip.h, instances.h); instanced ambient occlusion and views (include/rt_hip_instance_views.h,
-// kernels/instance_views.hip.h).
+// kernels/instance_views.hip.h); instanced segment queries (include/rt_hip_instance_segments.h,
+// kernels/instance_segments.hip.h).
 #pragma once
 #include <cstdint>
 #include <initializer_list>
@@ -86,6 +87,18 @@ class RayQueries {
 		// Host memory, blocking.
 		void instancesHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
 		                   const QueryOutputs &out, uint32_t *instance);
+		// Instanced segment queries (include/rt_hip_instance_segments.h): segmentsDevice's and visibilityDevice's arguments
+		// and rules, the segments in world space against the instance set; the pair forms' sort is keyed over the top-level
+		// root box, as the mask form's sort of the points is; `instance` beside the closest form's record.  std::logic_error
+		// without a set.  The tree is made again first if the scene changed (refreshInstances).
+		void instanceSegmentsDevice(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+		                            const QueryOutputs &out, uint32_t *instance, void *stream);
+		void instanceSegmentsHost(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+		                          const QueryOutputs &out, uint32_t *instance);
+		void instanceVisibilityDevice(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
+		                              uint32_t flags, const VisibilityOutputs &out, void *stream);
+		void instanceVisibilityHost(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
+		                            const VisibilityOutputs &out);
 		// Instanced ambient occlusion and instanced views (include/rt_hip_instance_views.h).  aoDevice's and viewsDevice's
 		// arguments and rules, the rays cast against the instance set: points and normals in world space, the point sort
 		// keyed over the top-level root box; the views' records are instancesDevice's, `instance` [views][N] beside the layers.
@@ -255,7 +268,7 @@ class RayQueries {
 		Scratch stage;         // the host-memory forms' inputs and outputs
 		Scratch ao_hits;       // aoDevice without an `occluded` array: the points' counts
 		Scratch ao_rows;       // directionalDevice without a `mask` array: the points' rows
-		Scratch vis_rows;      // visibilityDevice without a `mask` array: the points' rows
+		Scratch vis_rows;      // visibilityDevice, instanceVisibilityDevice without a `mask` array: the points' rows
 	Scratch list;          // multihitDevice: the rays' key lists, n * k * 8 bytes
 		Scratch views;         // layersDevice, viewsDevice (ChunkScratch): a chunk's poses, the points and normals of its
 		                       // ambient-occlusion step, the list of the hit ones (ViewList), its float images where the caller
@@ -313,6 +326,12 @@ void launch_visibility(const SceneBuffers &scene, uint32_t node_count, const voi
 void launch_instances(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses, bool closest,
                       const void *origins, const void *directions, const void *order, uint32_t n, float max_distance, const QueryOutputs &out,
                       uint32_t *instance, void *stream);
+void launch_instance_segments(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses,
+                              bool closest, const void *from, const void *to, const void *order, uint32_t n, float t_lo, float t_hi,
+                              const QueryOutputs &out, uint32_t *instance, void *stream);
+void launch_instance_visibility(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses,
+                                const void *points, uint32_t np, const void *targets, uint32_t nt, const void *order, float t_lo, float t_hi,
+                                uint32_t *mask, uint32_t *count, void *stream);
 void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void *origins, const void *directions, const void *order,
                      uint32_t n, float max_distance, uint32_t k, void *list, const MultiHitOutputs &out, void *stream);
 void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,

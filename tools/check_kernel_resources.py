@@ -154,7 +154,9 @@ def main():
                # instanced ray queries (kernels/instances.hip.h): two nested exact walks
                "instance_kernel<true>", "instance_kernel<false>",
                # instanced ambient occlusion and views (kernels/instance_views.hip.h): the same nested walks
-               "instance_ao_kernel<1", "instance_ao_kernel<2", "instance_layers_kernel")
+               "instance_ao_kernel<1", "instance_ao_kernel<2", "instance_layers_kernel",
+               # instanced segment queries (kernels/instance_segments.hip.h): the nested walks with the interval at the leaves
+               "instance_segment_kernel<true>", "instance_segment_kernel<false>", "instance_visibility_kernel")
     # the directional occlusion queries' walk is ao_query_kernel's with another tail (kernels/directional.hip.h): it must keep
     # that kernel's occupancy, 8 waves per SIMD -- a tail that needs more live state than the old one shows here
     full_occupancy = ("ao_mask_kernel<1", "ao_mask_kernel<2")
