@@ -873,7 +873,10 @@ RenderStats DeviceRenderer::stats() {
 			std::fprintf(stderr, " %.1f:%llu", k * 0.1, c.stamp[10 + k]);
 	std::fprintf(stderr, "\n   of the walks: node loop %.3f ms in %llu entries, batches %.3f ms in %llu batches, %llu leaf stops\n",
 	             c.stamp[42] * 1e-5, c.stamp[44], c.stamp[43] * 1e-5, c.stamp[45], c.stamp[46]);
-	std::fprintf(stderr, "   batched pairs %llu, of which the leaf's own box passes %llu\n", c.stamp[47], c.stamp[48]);
+	std::fprintf(stderr, "   batched pairs %llu, with an accepted triangle %llu, of which the leaf's own box passes %llu\n", c.stamp[47], c.stamp[65], c.stamp[48]);
+	std::fprintf(stderr, "   full batches %llu, partial batches %llu holding %llu pairs, leaves tested on the spot %llu\n", c.stamp[66], c.stamp[67],
+	             c.stamp[68], c.stamp[69]);
+	std::fprintf(stderr, "   leaf-test events in which no lane's triangle was accepted: %llu batches, %llu on the spot\n", c.stamp[70], c.stamp[71]);
 	std::fprintf(stderr, "   jobs by duration (from 2^k us on):");
 	for (int k = 0; k < 14; ++k)
 		if (c.stamp[49 + k])

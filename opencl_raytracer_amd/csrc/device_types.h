@@ -88,7 +88,7 @@ struct FrameCounters {
 	// event-record nodes); these say when its passes ran.
 	unsigned long long tick_begin, tick_ao_begin, tick_ao_end;
 #if defined(OCRT_STAMPS) || defined(OCRT_TAIL)
-	unsigned long long stamp[10 + 32 + 7 + 16];  // debug build: wave-time (10 ns ticks) per phase of the AO pass, jobs, packets
+	unsigned long long stamp[10 + 32 + 7 + 16 + 7];  // debug build: wave-time (10 ns ticks) per phase of the AO pass, jobs, packets, leaf-test events
 #endif
 };
 

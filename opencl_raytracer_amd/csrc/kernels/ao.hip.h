@@ -93,6 +93,9 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 	unsigned long long t_last_claim = t_begin;
 	unsigned long long walk_prof_store[7] = { 0, 0, 0, 0, 0, 0, 0 };
 	unsigned long long *walk_prof = walk_prof_store;
+	if (fresh_lane() < 8u)
+		sh.batch.events[fresh_lane()] = 0u;
+	wave_lds_sync();
 #endif
 	if (blockIdx.x == 0u && threadIdx.x == 0u) {  // (when the pass began, by the device's clock: frames replayed from a graph have no events inside)
 		FrameCounters *const counters = OCRT_COLD_PTR(FrameCounters *, counters);
@@ -488,6 +491,8 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 			atomicAdd(&A.counters->stamp[9], 1ull);                    // waves that got any work
 		for (int k = 0; k < 7; ++k)
 			atomicAdd(&A.counters->stamp[42 + k], walk_prof_store[k]);  // time in the node loop, in batches; loop entries, batches, leaf stops
+		for (int k = 0; k < 7; ++k)
+			atomicAdd(&A.counters->stamp[65 + k], (unsigned long long) sh.batch.events[k]);  // the leaf-test events by kind (LeafBatch)
 		// when this wave ended, counted from the first wave's start (settled long before any wave ends), 0.1 ms buckets:
 		// how the occupancy decays towards the end of the launch
 		(void) t_last_claim;

@@ -413,6 +413,11 @@ __device__ __forceinline__ bool exact_leaf_gate(const float4 lo, const float4 hi
 struct LeafBatch {
 	unsigned int entry[128];       // leaf | owning lane << 26; up to 63 waiting + 64 appended at one leaf
 	unsigned int occluded_bits[2];  // lanes whose ray was found occluded by the batch just run
+#ifdef OCRT_STAMPS
+	// pairs with an accepted triangle; full batches; partial batches, the pairs they held; leaves tested on the spot;
+	// batches, leaves tested on the spot in which no lane's triangle was accepted
+	unsigned int events[8];
+#endif
 };
 
 // The same for a closest-hit packet (primary rays).  The reference keeps the first hit in
@@ -434,7 +439,11 @@ constexpr uint32_t INF_BITS = 0x7F800000u;
 // triangle and bumps *occluded (reference :251 only uses the boolean).
 // EXACT walks `nodes_ptr` (exact boxes); the fast form walks `walk_ptr` (padded boxes) and gates every candidate
 // leaf with its own box, the head of its leaf record (scalar loads for a leaf tested on the spot; in a batch each lane
-// loads its pair's record relative to the same scalar base: no buffer descriptor held across the walk).
+// loads its pair's record relative to the same scalar base: no buffer descriptor held across the walk).  The gate is
+// applied AFTER the triangle test and only where some lane of the wave accepted its triangle: it passes 99.97 % of the
+// candidates, while 70 % of the batches and 82 % of the leaves tested on the spot hold no accepted triangle at all on the
+// headline frame, and those skip the box's loads, the gate's 27 vector instructions and the bookkeeping behind a batch
+// (counted and measured: profiles/ao_leaf_batches_notes.md).
 template <bool EXACT, bool PREFETCH = false>
 __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ nodes_ptr, const float4 *__restrict__ walk_ptr,
                                                     const float4 *__restrict__ tris_ptr,
@@ -443,7 +452,7 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
                                                     unsigned int *occluded, LeafBatch &batch, uint32_t batch_below,
                                                     unsigned long long *prof, uint32_t entry_begin = 0u, uint32_t entry_end = 0xFFFFFFFFu,
                                                     uint32_t copy = 0u) {  // (`copy`: KernelParams::walk_ce_bytes, the fast form only)
-	(void) prof;  // (-DOCRT_STAMPS builds: time in the node loop / in batches, loop entries, batches, leaf stops)
+	(void) prof;  // (-DOCRT_STAMPS builds: time in the node loop / in batches, loop entries, batches, leaf stops; the leaf-test events by kind go to batch.events)
 	// the live lanes as a scalar mask: the node steps then need no per-lane bookkeeping at all
 	unsigned long long alive_mask = wave_ballot(alive);
 	// Registers held across the walk are scarce (64 per lane at 8 waves per SIMD, 7 of them the loop's own): the
@@ -464,6 +473,14 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 		// the leaf, which only lets it ride along a little longer.
 		uint32_t waiting = 0u;  // pairs in batch.entry (wave-uniform)
 		uint32_t leaf_stops = 0u;  // (not used by this pass)
+#ifdef OCRT_STAMPS
+		// the leaf-test events by kind, counted in the wave's LDS slice: seven more accumulators in registers made the
+		// instrumented kernel spill, and its times are what the build is for
+		auto count_event = [&](uint32_t slot, uint32_t by) {
+			if (fresh_lane() == 0u)
+				batch.events[slot] += by;
+		};
+#endif
 		auto run_batch = [&](uint32_t n) {
 #ifdef OCRT_STAMPS
 			const unsigned long long tb0 = __builtin_amdgcn_s_memrealtime();
@@ -476,32 +493,48 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 			Ray theirs;
 			theirs.ox = __shfl(ray.ox, owner); theirs.oy = __shfl(ray.oy, owner); theirs.oz = __shfl(ray.oz, owner);
 			theirs.dx = __shfl(ray.dx, owner); theirs.dy = __shfl(ray.dy, owner); theirs.dz = __shfl(ray.dz, owner);
-			theirs.ix = __shfl(ray.ix, owner); theirs.iy = __shfl(ray.iy, owner); theirs.iz = __shfl(ray.iz, owner);
-			if (lane < n) {
-				// the pair is a candidate of the padded walk: the leaf's own box decides whether the reference tests it
-				const uint32_t pair_leaf = pair & 0x03FFFFFFu;
-				const float4 *rec = (const float4 *) ((const char *) tris_ptr + pair_leaf * LEAF_BYTES);  // (scalar base + 32-bit lane offset)
-				const float4 lo = rec[0], hi = rec[1];
-				const bool gate = exact_leaf_gate(lo, hi, theirs, below);
+			theirs.ix = theirs.iy = theirs.iz = 0.0f;  // (the triangle test reads no reciprocal: they come with the box, below)
+			// The pair is a candidate of the padded walk, and the reference tests its triangle only if the ray passes the
+			// leaf's own box: occluded = box && triangle.  The triangle test has no side effect, so it runs FIRST, and the
+			// box -- its two loads, the owners' reciprocals, exact_leaf_gate -- is looked at only if some lane of the wave
+			// has an accepted triangle (wave-uniform; how rarely: profiles/ao_leaf_batches_notes.md).  A batch without
+			// one sets no bit, so what follows the tests -- the bits, the counts, the live mask -- is skipped with it.
+			const uint32_t pair_leaf = pair & 0x03FFFFFFu;
+			const float4 *rec = (const float4 *) ((const char *) tris_ptr + pair_leaf * LEAF_BYTES);  // (scalar base + 32-bit lane offset)
+			bool accepted = false;
+			if (lane < n)
+				accepted = tri_any_hit(rec[2], rec[3], rec[4], rec[5], rec[1].w, theirs);
+			const bool any_accepted = wave_ballot(accepted) != 0ull;
 #ifdef OCRT_STAMPS
-				prof[5] += n;  // candidate pairs / pairs whose own box passes
-				prof[6] += (unsigned long long) __popcll(wave_ballot(gate));
+			prof[5] += n;  // candidate pairs, those with an accepted triangle, and of these the ones whose own box passes (below)
+			count_event(0u, (uint32_t) __popcll(wave_ballot(accepted)));
+			count_event(n == 64u ? 1u : 2u, 1u);  // full batches; partial ones (the flush at a packet's end) and the pairs they held
+			count_event(3u, n == 64u ? 0u : n);
+			count_event(5u, any_accepted ? 0u : 1u);  // batches in which no lane's triangle was accepted
 #endif
-				if (gate) {
-					if (tri_any_hit(rec[2], rec[3], rec[4], rec[5], hi.w, theirs))
+			if (any_accepted) {
+				theirs.ix = __shfl(ray.ix, owner); theirs.iy = __shfl(ray.iy, owner); theirs.iz = __shfl(ray.iz, owner);
+				bool gate = false;
+				if (accepted) {
+					const float4 lo = rec[0], hi = rec[1];
+					gate = exact_leaf_gate(lo, hi, theirs, below);
+					if (gate)
 						atomicOr(&batch.occluded_bits[owner >> 5], 1u << (owner & 31));
 				}
+#ifdef OCRT_STAMPS
+				prof[6] += (unsigned long long) __popcll(wave_ballot(gate));
+#endif
+				wave_lds_sync();
+				const uint32_t bits = batch.occluded_bits[lane >> 5];
+				if (alive && ((bits >> (lane & 31u)) & 1u)) {
+					atomicAdd(occluded, 1u);  // once per ray, however many of its pairs were accepted
+					alive = false;
+				}
+				wave_lds_sync();
+				if (lane < 2u)
+					batch.occluded_bits[lane] = 0u;
+				alive_mask = wave_ballot(alive);
 			}
-			wave_lds_sync();
-			const uint32_t bits = batch.occluded_bits[lane >> 5];
-			if (alive && ((bits >> (lane & 31u)) & 1u)) {
-				atomicAdd(occluded, 1u);  // once per ray, however many of its pairs were accepted
-				alive = false;
-			}
-			wave_lds_sync();
-			if (lane < 2u)
-				batch.occluded_bits[lane] = 0u;
-			alive_mask = wave_ballot(alive);
 #ifdef OCRT_STAMPS
 			prof[1] += __builtin_amdgcn_s_memrealtime() - tb0;
 			prof[3] += 1;
@@ -534,17 +567,28 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 			if (status == 0u)
 				break;
 			if (status == 1u) {
-				// enough of the packet is at this leaf: test it here, box and triangle out of SGPRs
+				// enough of the packet is at this leaf: test it here, the triangle and -- only if some lane accepts it, as in
+				// run_batch -- the leaf's own box out of SGPRs
 				const float4 *rec = tris_ptr + LEAF_F4 * leaf;
-				const float4 lo = rec[0], hi = rec[1], q0 = rec[2], q1 = rec[3], q2 = rec[4], q3 = rec[5];
+				const float4 q0 = rec[2], q1 = rec[3], q2 = rec[4], q3 = rec[5];
+				const float inv_d = rec[1].w;
 				const Ray ray = with_origin();
-				if (((hit_mask >> fresh_lane()) & 1ull) && exact_leaf_gate(lo, hi, ray, below)) {
-					if (tri_any_hit(q0, q1, q2, q3, hi.w, ray)) {
+				bool accepted = false;
+				if ((hit_mask >> fresh_lane()) & 1ull)
+					accepted = tri_any_hit(q0, q1, q2, q3, inv_d, ray);
+				const bool any_accepted = wave_ballot(accepted) != 0ull;
+#ifdef OCRT_STAMPS
+				count_event(4u, 1u);  // leaves tested on the spot, and those at which no lane's triangle was accepted
+				count_event(6u, any_accepted ? 0u : 1u);
+#endif
+				if (any_accepted) {
+					const float4 lo = rec[0], hi = rec[1];
+					if (accepted && exact_leaf_gate(lo, hi, ray, below)) {
 						atomicAdd(occluded, 1u);
 						alive = false;
 					}
+					alive_mask = wave_ballot(alive);
 				}
-				alive_mask = wave_ballot(alive);
 			} else {
 				run_batch(64u);
 				waiting -= 64u;
