@@ -71,14 +71,29 @@ int fail(int code, const std::string &message) {
 	return code;
 }
 
-// What every query entry point checks first; `family` names the queries in the messages ("ray", "ambient-occlusion").
-int host_precheck(const rt_host *h, const char *family) {
+// What the entry points of a host's own state check first -- they work before an upload too, but not on the hosts of a
+// frame ring --; `family` names the queries in the message ("ray", "closest-point").
+int owned_precheck(const rt_host *h, const char *family) {
 	if (!h)
 		return fail(RT_E_INVALID, "null host");
 	if (!h->owned)
 		return fail(RT_E_STATE, std::string(family) + " queries are not available on the hosts of a frame ring");
+	return RT_OK;
+}
+
+// ... and what every query entry point does.
+int host_precheck(const rt_host *h, const char *family) {
+	const int rc = owned_precheck(h, family);
+	if (rc != RT_OK)
+		return rc;
 	if (!h->dev->sceneReady())
 		return fail(RT_E_STATE, std::string(family) + " query before a scene was uploaded");
+	return RT_OK;
+}
+
+int instance_set_required(const rt_host *h, const char *what) {
+	if (!h->queries || h->queries->instanceCount() == 0)
+		return fail(RT_E_STATE, std::string(what) + " without an instance set (rt_set_instances)");
 	return RT_OK;
 }
 
@@ -89,17 +104,36 @@ bool aligned(std::initializer_list<const void *> pointers, uintptr_t bytes) {
 	return (all & (bytes - 1u)) == 0;
 }
 
-// ... and what every ray query checks before it touches the device (include/rt_hip_query.h, "Errors").
-int query_precheck(rt_host *h, const float *origins4, const float *directions4, uint32_t n, bool device) {
-	const int rc = host_precheck(h, "ray");
+// A family of queries over `items` read from one or two float4 arrays, as its messages name it.
+struct Family {
+	const char *name;         // "<name> queries are not available ...", "<name> query before ...", "<name> query without an instance set"
+	const char *items;        // "more <items> than RT_QUERY_MAX_RAYS in one call"
+	const char *null_arrays;  // the message for a null array
+	const char *unaligned;    // the message for a device array that is not 16-byte aligned
+	bool instanced;           // the host's instance set is asked for
+};
+constexpr Family RAYS = { "ray", "rays", "null ray arrays", "device ray arrays must be 16-byte aligned", false };
+constexpr Family INSTANCED_RAYS = { "instanced ray", "rays", "null ray arrays", "device ray arrays must be 16-byte aligned", true };
+constexpr Family SEGMENTS = { "segment", "segments", "null point arrays", "device point arrays must be 16-byte aligned", false };
+constexpr Family INSTANCED_SEGMENTS = { "instanced segment", "segments", "null point arrays", "device point arrays must be 16-byte aligned",
+	                                    true };
+constexpr Family POINTS = { "closest-point", "points", "null point array", "the device point array must be 16-byte aligned", false };
+
+// What these families check before they touch the device ("Errors" of include/rt_hip_query.h, rt_hip_segment.h,
+// rt_hip_nearest.h, rt_hip_instances.h, rt_hip_instance_segments.h), in this order: the host, the set, the count -- `items`
+// rays, segments, pairs of a mask or points --, the arrays (`b4`: `a4` once more for a family with one).
+int query_precheck(const rt_host *h, const Family &f, const float *a4, const float *b4, uint64_t items, bool device) {
+	int rc = host_precheck(h, f.name);
+	if (rc == RT_OK && f.instanced)
+		rc = instance_set_required(h, (std::string(f.name) + " query").c_str());
 	if (rc != RT_OK)
 		return rc;
-	if (n > RT_QUERY_MAX_RAYS)
-		return fail(RT_E_INVALID, "more rays than RT_QUERY_MAX_RAYS in one call");
-	if (n > 0 && (!origins4 || !directions4))
-		return fail(RT_E_INVALID, "null ray arrays");
-	if (device && n > 0 && !aligned({ origins4, directions4 }, 16))
-		return fail(RT_E_INVALID, "device ray arrays must be 16-byte aligned");
+	if (items > RT_QUERY_MAX_RAYS)
+		return fail(RT_E_INVALID, "more " + std::string(f.items) + " than RT_QUERY_MAX_RAYS in one call");
+	if (items > 0 && (!a4 || !b4))
+		return fail(RT_E_INVALID, f.null_arrays);
+	if (device && items > 0 && !aligned({ a4, b4 }, 16))
+		return fail(RT_E_INVALID, f.unaligned);
 	return RT_OK;
 }
 
@@ -137,6 +171,12 @@ template <class Arrays> void record_outputs(const Arrays *from, ocrt::RecordOutp
 	to.barycentric = from->barycentric;
 	to.position = from->position;
 	to.normal = from->normal;
+}
+// The occlusion forms' output: the flags alone.
+ocrt::QueryOutputs occlusion_outputs(uint8_t *occluded) {
+	ocrt::QueryOutputs q;
+	q.hit = occluded;
+	return q;
 }
 ocrt::QueryOutputs hit_outputs(const rt_hit_arrays *from) {
 	ocrt::QueryOutputs q;
@@ -926,7 +966,7 @@ void rt_print_info(void) { HipHost::printInfo(); }
 // ---- rt_hip_query.h ----
 int rt_trace_closest(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
                      const rt_hit_arrays *out) {
-	const int rc = query_precheck(h, origins4, directions4, n, false);
+	const int rc = query_precheck(h, RAYS, origins4, directions4, n, false);
 	if (rc != RT_OK || n == 0)
 		return rc;
 	return guarded([&] { queries_of(h).traceHost(true, origins4, directions4, n, max_distance, flags, hit_outputs(out)); });
@@ -934,17 +974,15 @@ int rt_trace_closest(rt_host *h, const float *origins4, const float *directions4
 
 int rt_trace_occluded(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
                       uint8_t *occluded) {
-	const int rc = query_precheck(h, origins4, directions4, n, false);
+	const int rc = query_precheck(h, RAYS, origins4, directions4, n, false);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	ocrt::QueryOutputs q;
-	q.hit = occluded;
-	return guarded([&] { queries_of(h).traceHost(false, origins4, directions4, n, max_distance, flags, q); });
+	return guarded([&] { queries_of(h).traceHost(false, origins4, directions4, n, max_distance, flags, occlusion_outputs(occluded)); });
 }
 
 int rt_trace_closest_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
                             uint32_t flags, const rt_hit_arrays *out, void *hip_stream) {
-	const int rc = query_precheck(h, origins4, directions4, n, true);
+	const int rc = query_precheck(h, RAYS, origins4, directions4, n, true);
 	if (rc != RT_OK || n == 0)
 		return rc;
 	const ocrt::QueryOutputs q = hit_outputs(out);
@@ -955,30 +993,14 @@ int rt_trace_closest_device(rt_host *h, const float *origins4, const float *dire
 
 int rt_trace_occluded_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
                              uint32_t flags, uint8_t *occluded, void *hip_stream) {
-	const int rc = query_precheck(h, origins4, directions4, n, true);
+	const int rc = query_precheck(h, RAYS, origins4, directions4, n, true);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	ocrt::QueryOutputs q;
-	q.hit = occluded;
-	return guarded([&] { queries_of(h).traceDevice(false, origins4, directions4, n, max_distance, flags, q, hip_stream); });
+	return guarded([&] { queries_of(h).traceDevice(false, origins4, directions4, n, max_distance, flags, occlusion_outputs(occluded), hip_stream); });
 }
 
 // ---- rt_hip_segment.h ----
 namespace {
-
-// The checks of include/rt_hip_segment.h ("Errors"): `items` segments -- or pairs of a mask -- between the points of two arrays.
-int segment_precheck(rt_host *h, const float *a4, const float *b4, uint64_t items, bool device) {
-	const int rc = host_precheck(h, "segment");
-	if (rc != RT_OK)
-		return rc;
-	if (items > RT_QUERY_MAX_RAYS)
-		return fail(RT_E_INVALID, "more segments than RT_QUERY_MAX_RAYS in one call");
-	if (items > 0 && (!a4 || !b4))
-		return fail(RT_E_INVALID, "null point arrays");
-	if (device && items > 0 && !aligned({ a4, b4 }, 16))
-		return fail(RT_E_INVALID, "device point arrays must be 16-byte aligned");
-	return RT_OK;
-}
 
 ocrt::RayQueries::VisibilityOutputs visibility_outputs(const rt_visibility_arrays *from) {
 	ocrt::RayQueries::VisibilityOutputs q;
@@ -993,7 +1015,7 @@ ocrt::RayQueries::VisibilityOutputs visibility_outputs(const rt_visibility_array
 
 int rt_segments_closest(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
                         const rt_hit_arrays *out) {
-	const int rc = segment_precheck(h, from4, to4, n, false);
+	const int rc = query_precheck(h, SEGMENTS, from4, to4, n, false);
 	if (rc != RT_OK || n == 0)
 		return rc;
 	return guarded([&] { queries_of(h).segmentsHost(true, from4, to4, n, t_lo, t_hi, flags, hit_outputs(out)); });
@@ -1001,17 +1023,15 @@ int rt_segments_closest(rt_host *h, const float *from4, const float *to4, uint32
 
 int rt_segments_occluded(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
                          uint8_t *occluded) {
-	const int rc = segment_precheck(h, from4, to4, n, false);
+	const int rc = query_precheck(h, SEGMENTS, from4, to4, n, false);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	ocrt::QueryOutputs q;
-	q.hit = occluded;
-	return guarded([&] { queries_of(h).segmentsHost(false, from4, to4, n, t_lo, t_hi, flags, q); });
+	return guarded([&] { queries_of(h).segmentsHost(false, from4, to4, n, t_lo, t_hi, flags, occlusion_outputs(occluded)); });
 }
 
 int rt_segments_closest_device(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
                                const rt_hit_arrays *out, void *hip_stream) {
-	const int rc = segment_precheck(h, from4, to4, n, true);
+	const int rc = query_precheck(h, SEGMENTS, from4, to4, n, true);
 	if (rc != RT_OK || n == 0)
 		return rc;
 	const ocrt::QueryOutputs q = hit_outputs(out);
@@ -1022,18 +1042,16 @@ int rt_segments_closest_device(rt_host *h, const float *from4, const float *to4,
 
 int rt_segments_occluded_device(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
                                 uint8_t *occluded, void *hip_stream) {
-	const int rc = segment_precheck(h, from4, to4, n, true);
+	const int rc = query_precheck(h, SEGMENTS, from4, to4, n, true);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	ocrt::QueryOutputs q;
-	q.hit = occluded;
-	return guarded([&] { queries_of(h).segmentsDevice(false, from4, to4, n, t_lo, t_hi, flags, q, hip_stream); });
+	return guarded([&] { queries_of(h).segmentsDevice(false, from4, to4, n, t_lo, t_hi, flags, occlusion_outputs(occluded), hip_stream); });
 }
 
 int rt_visibility_masks(rt_host *h, const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
                         uint32_t flags, const rt_visibility_arrays *out) {
 	const uint64_t pairs = (uint64_t) np * nt;
-	const int rc = segment_precheck(h, points4, targets4, pairs, false);
+	const int rc = query_precheck(h, SEGMENTS, points4, targets4, pairs, false);
 	if (rc != RT_OK || pairs == 0)
 		return rc;
 	const ocrt::RayQueries::VisibilityOutputs q = visibility_outputs(out);
@@ -1043,7 +1061,7 @@ int rt_visibility_masks(rt_host *h, const float *points4, uint32_t np, const flo
 int rt_visibility_masks_device(rt_host *h, const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo,
                                float t_hi, uint32_t flags, const rt_visibility_arrays *out, void *hip_stream) {
 	const uint64_t pairs = (uint64_t) np * nt;
-	const int rc = segment_precheck(h, points4, targets4, pairs, true);
+	const int rc = query_precheck(h, SEGMENTS, points4, targets4, pairs, true);
 	if (rc != RT_OK || pairs == 0)
 		return rc;
 	const ocrt::RayQueries::VisibilityOutputs q = visibility_outputs(out);
@@ -1053,37 +1071,9 @@ int rt_visibility_masks_device(rt_host *h, const float *points4, uint32_t np, co
 }
 
 // ---- rt_hip_instances.h ----
-namespace {
-
-// The set's own entry points work before an upload too, but not on the hosts of a frame ring.
-int instance_set_precheck(const rt_host *h) {
-	if (!h)
-		return fail(RT_E_INVALID, "null host");
-	if (!h->owned)
-		return fail(RT_E_STATE, "instanced ray queries are not available on the hosts of a frame ring");
-	return RT_OK;
-}
-
-// The checks of include/rt_hip_instances.h ("Errors") before a query touches the device.
-int instance_precheck(rt_host *h, const float *origins4, const float *directions4, uint32_t n, bool device) {
-	int rc = host_precheck(h, "instanced ray");
-	if (rc != RT_OK)
-		return rc;
-	if (!h->queries || h->queries->instanceCount() == 0)
-		return fail(RT_E_STATE, "instanced ray query without an instance set (rt_set_instances)");
-	if (n > RT_QUERY_MAX_RAYS)
-		return fail(RT_E_INVALID, "more rays than RT_QUERY_MAX_RAYS in one call");
-	if (n > 0 && (!origins4 || !directions4))
-		return fail(RT_E_INVALID, "null ray arrays");
-	if (device && n > 0 && !aligned({ origins4, directions4 }, 16))
-		return fail(RT_E_INVALID, "device ray arrays must be 16-byte aligned");
-	return RT_OK;
-}
-
-}  // namespace
-
+// (the set's own entry points work before an upload too: owned_precheck)
 int rt_set_instances(rt_host *h, const float *world_from_object, uint32_t n) {
-	const int rc = instance_set_precheck(h);
+	const int rc = owned_precheck(h, "instanced ray");
 	if (rc != RT_OK)
 		return rc;
 	if (n > RT_INSTANCES_MAX)
@@ -1103,7 +1093,7 @@ uint32_t rt_instance_node_count(const rt_host *h) {
 }
 
 int rt_instances_object_from_world(rt_host *h, float *out) {
-	const int rc = instance_set_precheck(h);
+	const int rc = owned_precheck(h, "instanced ray");
 	if (rc != RT_OK)
 		return rc;
 	if (out && h->queries)
@@ -1122,154 +1112,112 @@ int rt_instance_nodes(rt_host *h, void *out) {
 
 int rt_trace_instances_closest(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
                                const rt_instance_hit_arrays *out) {
-	const int rc = instance_precheck(h, origins4, directions4, n, false);
+	const int rc = query_precheck(h, INSTANCED_RAYS, origins4, directions4, n, false);
 	if (rc != RT_OK || n == 0)
 		return rc;
 	return guarded([&] {
-		queries_of(h).instancesHost(true, origins4, directions4, n, max_distance, flags, hit_outputs(out ? &out->record : nullptr),
-		                            out ? out->instance : nullptr);
+		queries_of(h).traceHost(true, origins4, directions4, n, max_distance, flags, hit_outputs(out ? &out->record : nullptr), true,
+		                        out ? out->instance : nullptr);
 	});
 }
 
 int rt_trace_instances_occluded(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
                                 uint8_t *occluded) {
-	const int rc = instance_precheck(h, origins4, directions4, n, false);
+	const int rc = query_precheck(h, INSTANCED_RAYS, origins4, directions4, n, false);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	ocrt::QueryOutputs q;
-	q.hit = occluded;
-	return guarded([&] { queries_of(h).instancesHost(false, origins4, directions4, n, max_distance, flags, q, nullptr); });
+	return guarded([&] { queries_of(h).traceHost(false, origins4, directions4, n, max_distance, flags, occlusion_outputs(occluded), true, nullptr); });
 }
 
 int rt_trace_instances_closest_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
                                       uint32_t flags, const rt_instance_hit_arrays *out, void *hip_stream) {
-	const int rc = instance_precheck(h, origins4, directions4, n, true);
+	const int rc = query_precheck(h, INSTANCED_RAYS, origins4, directions4, n, true);
 	if (rc != RT_OK || n == 0)
 		return rc;
 	const ocrt::QueryOutputs q = hit_outputs(out ? &out->record : nullptr);
 	uint32_t *const instance = out ? out->instance : nullptr;
 	if (!records_aligned(q) || !aligned({ instance }, 4))
 		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).instancesDevice(true, origins4, directions4, n, max_distance, flags, q, instance, hip_stream); });
+	return guarded([&] { queries_of(h).traceDevice(true, origins4, directions4, n, max_distance, flags, q, hip_stream, true, instance); });
 }
 
 int rt_trace_instances_occluded_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
                                        uint32_t flags, uint8_t *occluded, void *hip_stream) {
-	const int rc = instance_precheck(h, origins4, directions4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	ocrt::QueryOutputs q;
-	q.hit = occluded;
-	return guarded([&] { queries_of(h).instancesDevice(false, origins4, directions4, n, max_distance, flags, q, nullptr, hip_stream); });
-}
-
-// ---- rt_hip_instance_segments.h ----
-namespace {
-
-// The union of segment_precheck's and instance_precheck's checks (include/rt_hip_instance_segments.h, "Errors").
-int instance_segment_precheck(rt_host *h, const float *a4, const float *b4, uint64_t items, bool device) {
-	const int rc = host_precheck(h, "instanced segment");
-	if (rc != RT_OK)
-		return rc;
-	if (!h->queries || h->queries->instanceCount() == 0)
-		return fail(RT_E_STATE, "instanced segment query without an instance set (rt_set_instances)");
-	if (items > RT_QUERY_MAX_RAYS)
-		return fail(RT_E_INVALID, "more segments than RT_QUERY_MAX_RAYS in one call");
-	if (items > 0 && (!a4 || !b4))
-		return fail(RT_E_INVALID, "null point arrays");
-	if (device && items > 0 && !aligned({ a4, b4 }, 16))
-		return fail(RT_E_INVALID, "device point arrays must be 16-byte aligned");
-	return RT_OK;
-}
-
-}  // namespace
-
-int rt_instances_segments_closest(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
-                                  const rt_instance_hit_arrays *out) {
-	const int rc = instance_segment_precheck(h, from4, to4, n, false);
+	const int rc = query_precheck(h, INSTANCED_RAYS, origins4, directions4, n, true);
 	if (rc != RT_OK || n == 0)
 		return rc;
 	return guarded([&] {
-		queries_of(h).instanceSegmentsHost(true, from4, to4, n, t_lo, t_hi, flags, hit_outputs(out ? &out->record : nullptr),
-		                                   out ? out->instance : nullptr);
+		queries_of(h).traceDevice(false, origins4, directions4, n, max_distance, flags, occlusion_outputs(occluded), hip_stream, true, nullptr);
+	});
+}
+
+// ---- rt_hip_instance_segments.h ----
+int rt_instances_segments_closest(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+                                  const rt_instance_hit_arrays *out) {
+	const int rc = query_precheck(h, INSTANCED_SEGMENTS, from4, to4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	return guarded([&] {
+		queries_of(h).segmentsHost(true, from4, to4, n, t_lo, t_hi, flags, hit_outputs(out ? &out->record : nullptr), true,
+		                           out ? out->instance : nullptr);
 	});
 }
 
 int rt_instances_segments_occluded(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
                                    uint8_t *occluded) {
-	const int rc = instance_segment_precheck(h, from4, to4, n, false);
+	const int rc = query_precheck(h, INSTANCED_SEGMENTS, from4, to4, n, false);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	ocrt::QueryOutputs q;
-	q.hit = occluded;
-	return guarded([&] { queries_of(h).instanceSegmentsHost(false, from4, to4, n, t_lo, t_hi, flags, q, nullptr); });
+	return guarded([&] { queries_of(h).segmentsHost(false, from4, to4, n, t_lo, t_hi, flags, occlusion_outputs(occluded), true, nullptr); });
 }
 
 int rt_instances_segments_closest_device(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi,
                                          uint32_t flags, const rt_instance_hit_arrays *out, void *hip_stream) {
-	const int rc = instance_segment_precheck(h, from4, to4, n, true);
+	const int rc = query_precheck(h, INSTANCED_SEGMENTS, from4, to4, n, true);
 	if (rc != RT_OK || n == 0)
 		return rc;
 	const ocrt::QueryOutputs q = hit_outputs(out ? &out->record : nullptr);
 	uint32_t *const instance = out ? out->instance : nullptr;
 	if (!records_aligned(q) || !aligned({ instance }, 4))
 		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).instanceSegmentsDevice(true, from4, to4, n, t_lo, t_hi, flags, q, instance, hip_stream); });
+	return guarded([&] { queries_of(h).segmentsDevice(true, from4, to4, n, t_lo, t_hi, flags, q, hip_stream, true, instance); });
 }
 
 int rt_instances_segments_occluded_device(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi,
                                           uint32_t flags, uint8_t *occluded, void *hip_stream) {
-	const int rc = instance_segment_precheck(h, from4, to4, n, true);
+	const int rc = query_precheck(h, INSTANCED_SEGMENTS, from4, to4, n, true);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	ocrt::QueryOutputs q;
-	q.hit = occluded;
-	return guarded([&] { queries_of(h).instanceSegmentsDevice(false, from4, to4, n, t_lo, t_hi, flags, q, nullptr, hip_stream); });
+	return guarded([&] {
+		queries_of(h).segmentsDevice(false, from4, to4, n, t_lo, t_hi, flags, occlusion_outputs(occluded), hip_stream, true, nullptr);
+	});
 }
 
 int rt_instances_visibility_masks(rt_host *h, const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
                                   uint32_t flags, const rt_visibility_arrays *out) {
 	const uint64_t pairs = (uint64_t) np * nt;
-	const int rc = instance_segment_precheck(h, points4, targets4, pairs, false);
+	const int rc = query_precheck(h, INSTANCED_SEGMENTS, points4, targets4, pairs, false);
 	if (rc != RT_OK || pairs == 0)
 		return rc;
 	const ocrt::RayQueries::VisibilityOutputs q = visibility_outputs(out);
-	return guarded([&] { queries_of(h).instanceVisibilityHost(points4, np, targets4, nt, t_lo, t_hi, flags, q); });
+	return guarded([&] { queries_of(h).visibilityHost(points4, np, targets4, nt, t_lo, t_hi, flags, q, true); });
 }
 
 int rt_instances_visibility_masks_device(rt_host *h, const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo,
                                          float t_hi, uint32_t flags, const rt_visibility_arrays *out, void *hip_stream) {
 	const uint64_t pairs = (uint64_t) np * nt;
-	const int rc = instance_segment_precheck(h, points4, targets4, pairs, true);
+	const int rc = query_precheck(h, INSTANCED_SEGMENTS, points4, targets4, pairs, true);
 	if (rc != RT_OK || pairs == 0)
 		return rc;
 	const ocrt::RayQueries::VisibilityOutputs q = visibility_outputs(out);
 	if (!aligned({ q.mask, q.count }, 4))
 		return fail(RT_E_INVALID, "device uint32 outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).instanceVisibilityDevice(points4, np, targets4, nt, t_lo, t_hi, flags, q, hip_stream); });
+	return guarded([&] { queries_of(h).visibilityDevice(points4, np, targets4, nt, t_lo, t_hi, flags, q, hip_stream, true); });
 }
 
 // ---- rt_hip_nearest.h ----
-namespace {
-
-// The checks of include/rt_hip_nearest.h ("Errors").
-int nearest_precheck(rt_host *h, const float *points4, uint32_t n, bool device) {
-	const int rc = host_precheck(h, "closest-point");
-	if (rc != RT_OK)
-		return rc;
-	if (n > RT_QUERY_MAX_RAYS)
-		return fail(RT_E_INVALID, "more points than RT_QUERY_MAX_RAYS in one call");
-	if (n > 0 && !points4)
-		return fail(RT_E_INVALID, "null point array");
-	if (device && n > 0 && !aligned({ points4 }, 16))
-		return fail(RT_E_INVALID, "the device point array must be 16-byte aligned");
-	return RT_OK;
-}
-
-}  // namespace
-
 int rt_closest_points(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags, const rt_hit_arrays *out) {
-	const int rc = nearest_precheck(h, points4, n, false);
+	const int rc = query_precheck(h, POINTS, points4, points4, n, false);
 	if (rc != RT_OK || n == 0)
 		return rc;
 	return guarded([&] { queries_of(h).nearestHost(points4, n, max_distance, flags, hit_outputs(out)); });
@@ -1277,7 +1225,7 @@ int rt_closest_points(rt_host *h, const float *points4, uint32_t n, float max_di
 
 int rt_closest_points_device(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags, const rt_hit_arrays *out,
                              void *hip_stream) {
-	const int rc = nearest_precheck(h, points4, n, true);
+	const int rc = query_precheck(h, POINTS, points4, points4, n, true);
 	if (rc != RT_OK || n == 0)
 		return rc;
 	const ocrt::QueryOutputs q = hit_outputs(out);
@@ -1287,18 +1235,14 @@ int rt_closest_points_device(rt_host *h, const float *points4, uint32_t n, float
 }
 
 int rt_debug_set_nearest_walk(rt_host *h, uint32_t flags) {
-	if (!h)
-		return fail(RT_E_INVALID, "null host");
-	if (!h->owned)
-		return fail(RT_E_STATE, "closest-point queries are not available on the hosts of a frame ring");
+	if (const int rc = owned_precheck(h, "closest-point"); rc != RT_OK)
+		return rc;
 	return guarded([&] { queries_of(h).setNearestWalk(flags); });
 }
 
 int rt_debug_last_nearest_counts(rt_host *h, uint64_t *node_tests, uint64_t *triangle_tests) {
-	if (!h)
-		return fail(RT_E_INVALID, "null host");
-	if (!h->owned)
-		return fail(RT_E_STATE, "closest-point queries are not available on the hosts of a frame ring");
+	if (const int rc = owned_precheck(h, "closest-point"); rc != RT_OK)
+		return rc;
 	uint64_t counts[2] = { 0u, 0u };
 	const int rc = h->queries ? guarded([&] { h->queries->lastNearestCounts(counts); }) : RT_OK;
 	if (node_tests)
@@ -1314,7 +1258,7 @@ namespace {
 // The checks of include/rt_hip_multihit.h ("Errors") beyond query_precheck's; `q`: the outputs asked for.
 int multihit_precheck(rt_host *h, const float *origins4, const float *directions4, uint32_t n, uint32_t k, const ocrt::MultiHitOutputs &q,
                       bool device) {
-	const int rc = query_precheck(h, origins4, directions4, n, device);
+	const int rc = query_precheck(h, RAYS, origins4, directions4, n, device);
 	if (rc != RT_OK)
 		return rc;
 	if (k > RT_MULTIHIT_MAX_K)
@@ -1534,12 +1478,6 @@ int rt_render_views_device(rt_host *h, const rt_camera *cameras, uint32_t views,
 // ---- rt_hip_instance_views.h ----
 namespace {
 
-int instance_set_required(const rt_host *h, const char *what) {
-	if (!h->queries || h->queries->instanceCount() == 0)
-		return fail(RT_E_STATE, std::string(what) + " without an instance set (rt_set_instances)");
-	return RT_OK;
-}
-
 // The union of ao_precheck's and instance_precheck's checks (include/rt_hip_instance_views.h, "Errors").
 int instance_ao_precheck(const rt_host *h, const float *points4, const float *normals4, uint32_t n, bool device) {
 	int rc = host_precheck(h, "instanced ambient-occlusion");
@@ -1562,7 +1500,7 @@ int rt_trace_instances_ao(rt_host *h, const float *points4, const float *normals
 	const int rc = instance_ao_precheck(h, points4, normals4, n, false);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	return guarded([&] { queries_of(h).instancesAoHost(points4, normals4, seeds, n, flags, ao, occluded); });
+	return guarded([&] { queries_of(h).aoHost(points4, normals4, seeds, n, flags, ao, occluded, true); });
 }
 
 int rt_trace_instances_ao_device(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n,
@@ -1572,7 +1510,7 @@ int rt_trace_instances_ao_device(rt_host *h, const float *points4, const float *
 		return rc;
 	if (!aligned({ seeds, ao, occluded }, 4))
 		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).instancesAoDevice(points4, normals4, seeds, n, flags, ao, occluded, hip_stream); });
+	return guarded([&] { queries_of(h).aoDevice(points4, normals4, seeds, n, flags, ao, occluded, hip_stream, true); });
 }
 
 int rt_render_instance_views(rt_host *h, const rt_camera *cameras, uint32_t views, const rt_instance_view_arrays *out) {
@@ -1598,18 +1536,14 @@ int rt_render_instance_views_device(rt_host *h, const rt_camera *cameras, uint32
 }
 
 int rt_debug_set_views_chunk(rt_host *h, uint32_t max_views) {
-	if (!h)
-		return fail(RT_E_INVALID, "null host");
-	if (!h->owned)
-		return fail(RT_E_STATE, "multi-view queries are not available on the hosts of a frame ring");
+	if (const int rc = owned_precheck(h, "multi-view"); rc != RT_OK)
+		return rc;
 	return guarded([&] { queries_of(h).setViewsChunk(max_views); });
 }
 
 int rt_debug_last_views(rt_host *h, uint32_t *views, uint32_t *chunks, uint64_t *ao_points) {
-	if (!h)
-		return fail(RT_E_INVALID, "null host");
-	if (!h->owned)
-		return fail(RT_E_STATE, "multi-view queries are not available on the hosts of a frame ring");
+	if (const int rc = owned_precheck(h, "multi-view"); rc != RT_OK)
+		return rc;
 	const ocrt::RayQueries::ViewsDone done = h->queries ? h->queries->lastViews() : ocrt::RayQueries::ViewsDone();
 	if (views)
 		*views = done.views;

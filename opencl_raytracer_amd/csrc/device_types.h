@@ -173,6 +173,14 @@ struct SceneBuffers {  // device pointers of one uploaded scene
 	const void *ao_table;    // float4[ao_dirs] (UNIFORM)
 };
 
+// Device pointers of a host's instance set (ray_query.h), as the launchers of kernels.hip take them: a pointer to one
+// sends a family's call against the posed copies, null against the uploaded scene alone.
+struct InstanceBuffers {
+	const void *top;       // the top-level tree: NodeRec[top_count], `leaf` the instance index
+	const void *inverses;  // object_from_world, three float4 rows per instance
+	uint32_t top_count;    // 2 * instances - 1
+};
+
 // What the launches of a device-side build work on (kernels/build.hip.h, BuildArgs: every array's size is given there).
 struct BuildBuffers {
 	const void *faces, *vertices;

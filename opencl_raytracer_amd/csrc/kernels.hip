@@ -45,7 +45,8 @@
 //                   (kernels/segment.hip.h, include/rt_hip_segment.h).
 //                   instance_kernel<CLOSEST> casts caller-supplied rays against posed copies of the scene: an exact walk over a
 //                   top-level tree of instance boxes, and at each instance a packet enters the exact walk of the scene's own
-//                   tree with the rays mapped into the object's frame (kernels/instances.hip.h, include/rt_hip_instances.h).
+//                   tree with the rays mapped into the object's frame -- the nested walk that the instanced kernels below
+//                   share as instance_walk (kernels/instances.hip.h, include/rt_hip_instances.h).
 //                   layers_kernel<POSED, ARRAY> casts the frame's own rays for one pose or for every pose of a chunk of views, a wave
 //                   per (view, tile), and writes every sub-pixel's record, direction and head-light term (kernels/layers.hip.h,
 //                   include/rt_hip_layers.h, include/rt_hip_views.h).  ao_query_kernel runs over its points -- all of them
@@ -53,12 +54,12 @@
 //                   views_order_kernel make their number and order) --, views_scatter_kernel writes their factors and
 //                   products, views_resize_kernel every view's 8-bit image (kernels/views.hip.h).
 //                   instance_layers_kernel and instance_ao_kernel<MODE> are layers_kernel<true, true> and ao_query_kernel
-//                   against the posed copies: the same rays, made in registers, through instance_kernel's two nested walks;
+//                   against the posed copies: the same rays, made in registers by the same functions, through instance_walk;
 //                   the list, the tail and the images between and behind them are the views' own (kernels/instance_views.hip.h,
 //                   include/rt_hip_instance_views.h).
 //                   instance_segment_kernel<CLOSEST> and instance_visibility_kernel are segment_kernel and
-//                   visibility_mask_kernel against the posed copies: the same packets and tails around the two nested walks,
-//                   the interval test on the object ray's plane parameter (kernels/instance_segments.hip.h,
+//                   visibility_mask_kernel against the posed copies: the same packets and tails, shared functions, around
+//                   instance_walk with the interval test on the object ray's plane parameter (kernels/instance_segments.hip.h,
 //                   include/rt_hip_instance_segments.h).
 //   (scenes)        refit_leaves_kernel / refit_inner_kernel make the records and boxes of a scene again from new positions
 //                   (kernels/refit.hip.h, include/rt_hip_update.h); build_boxes_kernel, build_root_kernel, build_keys_kernel,
@@ -366,7 +367,12 @@ void launch_query_sort(const void *origins, const void *directions, uint32_t n, 
 	hipLaunchKernelGGL(scatter_kernel, dim3(blocks), dim3(256), 0, s, a);
 }
 
-// (what query_kernel and the multi-hit kernels are launched with alike)
+// (the instance set as the kernels take it)
+static InstanceSet instance_set(const InstanceBuffers &set) {
+	return InstanceSet{ (const float4 *) set.top, (const float4 *) set.inverses, set.top_count };
+}
+
+// (what query_kernel, instance_kernel and the multi-hit kernels are launched with alike)
 static void fill(RayQueryArgs &a, const SceneBuffers &scene, uint32_t node_count, const void *origins, const void *directions,
                  const void *order, uint32_t n, float max_distance, const RecordOutputs &out) {
 	a.nodes_ptr = (const float4 *) scene.nodes;
@@ -381,14 +387,29 @@ static void fill(RayQueryArgs &a, const SceneBuffers &scene, uint32_t node_count
 	a.out = out;
 }
 
-void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *origins, const void *directions,
-                  const void *order, uint32_t n, float max_distance, const QueryOutputs &out, void *stream) {
-	if (n == 0)
+// `set`: null, or the instance set the rays are cast against (kernels/instances.hip.h), `instance` beside the closest form's
+// record; the sort is then keyed over the top-level root box.  `closest` false: occlusion into out.hit alone.
+void launch_query(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, bool closest, const void *origins,
+                  const void *directions, const void *order, uint32_t n, float max_distance, const QueryOutputs &out, uint32_t *instance,
+                  void *stream) {
+	if (n == 0 || (set && set->top_count == 0))
 		return;
+	const uint32_t blocks = (n + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
+	if (set) {
+		InstanceArgs a{};
+		fill(a, scene, node_count, origins, directions, order, n, max_distance, out);
+		a.set = instance_set(*set);
+		a.hit = out.hit;
+		a.instance = instance;
+		if (closest)
+			hipLaunchKernelGGL(instance_kernel<true>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
+		else
+			hipLaunchKernelGGL(instance_kernel<false>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
+		return;
+	}
 	QueryArgs a{};
 	fill(a, scene, node_count, origins, directions, order, n, max_distance, out);
 	a.hit = out.hit;
-	const uint32_t blocks = (n + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
 	if (closest) {
 		hipLaunchKernelGGL(query_kernel<true>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
 	} else {
@@ -457,100 +478,11 @@ void launch_nearest(const SceneBuffers &scene, uint32_t node_count, uint32_t tri
 	}
 }
 
-// Segment queries (kernels/segment.hip.h); their sort is launch_query_sort's with `segments`.
-// `closest` false: occlusion into out.hit alone.
-void launch_segments(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *from, const void *to, const void *order,
-                     uint32_t n, float t_lo, float t_hi, const QueryOutputs &out, void *stream) {
-	if (n == 0)
-		return;
-	SegmentArgs a{};
-	a.nodes_ptr = (const float4 *) scene.nodes;
-	a.tris_ptr = (const float4 *) scene.tris;
-	a.shade = (const float4 *) scene.shade;
-	a.from = (const float4 *) from;
-	a.to = (const float4 *) to;
-	a.order = (const uint32_t *) order;
-	a.n = n;
-	a.node_count = node_count;
-	a.t_lo = t_lo;
-	a.t_hi = t_hi;
-	a.out = out;
-	a.hit = out.hit;
-	const uint32_t blocks = (n + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
-	if (closest) {
-		hipLaunchKernelGGL(segment_kernel<true>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
-	} else {
-		hipLaunchKernelGGL(segment_kernel<false>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
-	}
-}
-
-// Instanced ray queries (kernels/instances.hip.h); their sort is launch_query_sort's over the top-level root box.
-// `top`: the top-level records, `inverses`: three float4 per instance, both on the device.  `closest` false: occlusion into
-// out.hit alone.
-void launch_instances(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses, bool closest,
-                      const void *origins, const void *directions, const void *order, uint32_t n, float max_distance, const QueryOutputs &out,
-                      uint32_t *instance, void *stream) {
-	if (n == 0 || top_count == 0)
-		return;
-	InstanceArgs a{};
-	a.nodes_ptr = (const float4 *) scene.nodes;
-	a.tris_ptr = (const float4 *) scene.tris;
-	a.shade = (const float4 *) scene.shade;
-	a.origins = (const float4 *) origins;
-	a.directions = (const float4 *) directions;
-	a.order = (const uint32_t *) order;
-	a.n = n;
-	a.node_count = node_count;
-	a.max_distance = max_distance;
-	a.out = out;
-	a.top_ptr = (const float4 *) top;
-	a.inverses = (const float4 *) inverses;
-	a.top_count = top_count;
-	a.hit = out.hit;
-	a.instance = instance;
-	const uint32_t blocks = (n + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
-	if (closest) {
-		hipLaunchKernelGGL(instance_kernel<true>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
-	} else {
-		hipLaunchKernelGGL(instance_kernel<false>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
-	}
-}
-
-// The many-to-many form.  `mask`: np rows of ceil(nt / 32) words on the device (the caller's array or scratch), zeroed here
-// on the stream; `order`: launch_nearest_sort's order of the POINTS or null; `count`: null = not written.
-void launch_visibility(const SceneBuffers &scene, uint32_t node_count, const void *points, uint32_t np, const void *targets, uint32_t nt,
-                       const void *order, float t_lo, float t_hi, uint32_t *mask, uint32_t *count, void *stream) {
-	if (np == 0 || nt == 0)
-		return;
-	hipStream_t s = (hipStream_t) stream;
-	VisibilityArgs a{};
-	a.nodes_ptr = (const float4 *) scene.nodes;
-	a.tris_ptr = (const float4 *) scene.tris;
-	a.points = (const float4 *) points;
-	a.targets = (const float4 *) targets;
-	a.order = (const uint32_t *) order;
-	a.mask = mask;
-	a.np = np;
-	a.nt = nt;
-	a.words = (nt + 31u) / 32u;
-	a.total = np * nt;  // (<= RT_QUERY_MAX_RAYS: checked at the boundary)
-	visibility_divisor(nt, a.magic, a.shift);
-	a.node_count = node_count;
-	a.t_lo = t_lo;
-	a.t_hi = t_hi;
-	(void) hipMemsetAsync(mask, 0, (size_t) np * a.words * sizeof(uint32_t), s);
-	const uint32_t blocks = (a.total + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
-	hipLaunchKernelGGL(visibility_mask_kernel, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
-	if (count)
-		hipLaunchKernelGGL(visibility_count_kernel, dim3((np + 255u) / 256u), dim3(256), 0, s, (const uint32_t *) mask, count, np, a.words);
-}
-
-// Instanced segment queries (kernels/instance_segments.hip.h): launch_segments' arguments with the set's top-level records
-// and inverses (launch_instances'); their sort is launch_query_sort's with `segments`, over the top-level root box.
-void launch_instance_segments(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses,
-                              bool closest, const void *from, const void *to, const void *order, uint32_t n, float t_lo, float t_hi,
-                              const QueryOutputs &out, uint32_t *instance, void *stream) {
-	if (n == 0 || top_count == 0)
+// Segment queries (kernels/segment.hip.h); their sort is launch_query_sort's with `segments`.  `set`, `instance`: as for
+// launch_query (kernels/instance_segments.hip.h).  `closest` false: occlusion into out.hit alone.
+void launch_segments(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, bool closest, const void *from, const void *to,
+                     const void *order, uint32_t n, float t_lo, float t_hi, const QueryOutputs &out, uint32_t *instance, void *stream) {
+	if (n == 0 || (set && set->top_count == 0))
 		return;
 	InstanceSegmentArgs a{};
 	a.nodes_ptr = (const float4 *) scene.nodes;
@@ -565,23 +497,29 @@ void launch_instance_segments(const SceneBuffers &scene, uint32_t node_count, co
 	a.t_hi = t_hi;
 	a.out = out;
 	a.hit = out.hit;
-	a.top_ptr = (const float4 *) top;
-	a.inverses = (const float4 *) inverses;
-	a.top_count = top_count;
-	a.instance = instance;
-	const uint32_t blocks = (n + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
-	if (closest) {
-		hipLaunchKernelGGL(instance_segment_kernel<true>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
+	const SegmentArgs &plain = a;
+	const dim3 blocks((n + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES)), lanes(64 * QUERY_WAVES);
+	if (set) {
+		a.set = instance_set(*set);
+		a.instance = instance;
+		if (closest)
+			hipLaunchKernelGGL(instance_segment_kernel<true>, blocks, lanes, 0, (hipStream_t) stream, a);
+		else
+			hipLaunchKernelGGL(instance_segment_kernel<false>, blocks, lanes, 0, (hipStream_t) stream, a);
+	} else if (closest) {
+		hipLaunchKernelGGL(segment_kernel<true>, blocks, lanes, 0, (hipStream_t) stream, plain);
 	} else {
-		hipLaunchKernelGGL(instance_segment_kernel<false>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, (hipStream_t) stream, a);
+		hipLaunchKernelGGL(segment_kernel<false>, blocks, lanes, 0, (hipStream_t) stream, plain);
 	}
 }
 
-// ... and their many-to-many form: launch_visibility's arguments and steps with the set's records and inverses.
-void launch_instance_visibility(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses,
-                                const void *points, uint32_t np, const void *targets, uint32_t nt, const void *order, float t_lo, float t_hi,
-                                uint32_t *mask, uint32_t *count, void *stream) {
-	if (np == 0 || nt == 0 || top_count == 0)
+// The many-to-many form.  `mask`: np rows of ceil(nt / 32) words on the device (the caller's array or scratch), zeroed here
+// on the stream; `order`: launch_nearest_sort's order of the POINTS or null; `count`: null = not written; `set`: null, or
+// the instance set the segments are cast against.
+void launch_visibility(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, const void *points, uint32_t np,
+                       const void *targets, uint32_t nt, const void *order, float t_lo, float t_hi, uint32_t *mask, uint32_t *count,
+                       void *stream) {
+	if (np == 0 || nt == 0 || (set && set->top_count == 0))
 		return;
 	hipStream_t s = (hipStream_t) stream;
 	InstanceVisibilityArgs a{};
@@ -599,55 +537,26 @@ void launch_instance_visibility(const SceneBuffers &scene, uint32_t node_count, 
 	a.node_count = node_count;
 	a.t_lo = t_lo;
 	a.t_hi = t_hi;
-	a.top_ptr = (const float4 *) top;
-	a.inverses = (const float4 *) inverses;
-	a.top_count = top_count;
 	(void) hipMemsetAsync(mask, 0, (size_t) np * a.words * sizeof(uint32_t), s);
 	const uint32_t blocks = (a.total + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
-	hipLaunchKernelGGL(instance_visibility_kernel, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+	if (set) {
+		a.set = instance_set(*set);
+		hipLaunchKernelGGL(instance_visibility_kernel, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+	} else {
+		const VisibilityArgs &plain = a;
+		hipLaunchKernelGGL(visibility_mask_kernel, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, plain);
+	}
 	if (count)
 		hipLaunchKernelGGL(visibility_count_kernel, dim3((np + 255u) / 256u), dim3(256), 0, s, (const uint32_t *) mask, count, np, a.words);
 }
 
 // Ambient-occlusion queries (kernels/ao_query.hip.h).  `count`: n words on the device (the caller's `occluded` array or
-// scratch), zeroed here on the stream; `order`: launch_query_sort's order of the POINTS or null; `ao`: null = not written.
-void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
-                     float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
-                     uint32_t *count, float *ao, void *stream) {
-	if (n == 0 || rays_per_point == 0)
-		return;
-	hipStream_t s = (hipStream_t) stream;
-	AoQueryArgs a{};
-	a.nodes_ptr = (const float4 *) scene.nodes;
-	a.tris_ptr = (const float4 *) scene.tris;
-	a.ao_table = (const float4 *) scene.ao_table;
-	a.points = (const float4 *) points;
-	a.normals = (const float4 *) normals;
-	a.seeds = seeds;
-	a.order = (const uint32_t *) order;
-	a.count = count;
-	a.n = n;
-	a.rays = rays_per_point;
-	a.total = n * rays_per_point;  // (<= RT_QUERY_MAX_RAYS: checked at the boundary)
-	a.node_count = node_count;
-	a.max_distance = max_distance;
-	(void) hipMemsetAsync(count, 0, (size_t) n * sizeof(uint32_t), s);
-	const uint32_t blocks = (a.total + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
-	if (ao_mode == AO_RANDOM)
-		hipLaunchKernelGGL(ao_query_kernel<AO_RANDOM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
-	else
-		hipLaunchKernelGGL(ao_query_kernel<AO_UNIFORM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
-	if (ao)
-		hipLaunchKernelGGL(ao_query_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, (const uint32_t *) count, ao, n,
-		                   divisor ? divisor : 1u);
-}
-
-// Instanced ambient-occlusion queries (kernels/instance_views.hip.h): launch_ao_query's arguments and rules, with the set's
-// top-level records and inverses (launch_instances').
-void launch_instance_ao(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses, int ao_mode,
-                        uint32_t rays_per_point, uint32_t divisor, float max_distance, const void *points, const void *normals,
-                        const uint32_t *seeds, const void *order, uint32_t n, uint32_t *count, float *ao, void *stream) {
-	if (n == 0 || rays_per_point == 0 || top_count == 0)
+// scratch), zeroed here on the stream; `order`: launch_query_sort's order of the POINTS or null; `ao`: null = not written;
+// `set`: null, or the instance set the rays are cast against (kernels/instance_views.hip.h).
+void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, int ao_mode, uint32_t rays_per_point,
+                     uint32_t divisor, float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order,
+                     uint32_t n, uint32_t *count, float *ao, void *stream) {
+	if (n == 0 || rays_per_point == 0 || (set && set->top_count == 0))
 		return;
 	hipStream_t s = (hipStream_t) stream;
 	InstanceAoArgs a{};
@@ -664,15 +573,20 @@ void launch_instance_ao(const SceneBuffers &scene, uint32_t node_count, const vo
 	a.total = n * rays_per_point;  // (<= RT_QUERY_MAX_RAYS: checked at the boundary)
 	a.node_count = node_count;
 	a.max_distance = max_distance;
-	a.top_ptr = (const float4 *) top;
-	a.inverses = (const float4 *) inverses;
-	a.top_count = top_count;
+	const AoQueryArgs &plain = a;
 	(void) hipMemsetAsync(count, 0, (size_t) n * sizeof(uint32_t), s);
-	const uint32_t blocks = (a.total + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
-	if (ao_mode == AO_RANDOM)
-		hipLaunchKernelGGL(instance_ao_kernel<AO_RANDOM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
-	else
-		hipLaunchKernelGGL(instance_ao_kernel<AO_UNIFORM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+	const dim3 blocks((a.total + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES)), lanes(64 * QUERY_WAVES);
+	if (set) {
+		a.set = instance_set(*set);
+		if (ao_mode == AO_RANDOM)
+			hipLaunchKernelGGL(instance_ao_kernel<AO_RANDOM>, blocks, lanes, 0, s, a);
+		else
+			hipLaunchKernelGGL(instance_ao_kernel<AO_UNIFORM>, blocks, lanes, 0, s, a);
+	} else if (ao_mode == AO_RANDOM) {
+		hipLaunchKernelGGL(ao_query_kernel<AO_RANDOM>, blocks, lanes, 0, s, plain);
+	} else {
+		hipLaunchKernelGGL(ao_query_kernel<AO_UNIFORM>, blocks, lanes, 0, s, plain);
+	}
 	if (ao)
 		hipLaunchKernelGGL(ao_query_finish_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, (const uint32_t *) count, ao, n,
 		                   divisor ? divisor : 1u);
@@ -796,9 +710,12 @@ static void launch_views_list(const ViewList &list, uint32_t m, hipStream_t s) {
 // constants.  `value`: where the head-light term goes once more (no ambient-occlusion step) or null.  `list`: null = no
 // such step follows; else its points and normals get the step's entries, and with list->flags -- listing -- only the hit
 // sub-pixels do: their flags, seeds, order and, in *list->listed, their number, and `ao`, `product` the missed ones' 1 and 0.
-void launch_layers(const SceneBuffers &scene, const KernelParams &P, const void *poses, const CameraPose &pose, bool posed, uint32_t views,
-                   const LayerOutputs &out, float *value, float *ao, float *product, const ViewList *list, void *stream) {
-	LayersArgs a{};
+// `set`: null, or the instance set the rays are cast against (kernels/instance_views.hip.h: `poses` on the device, always
+// listing where `list` is given), `instance` its layer beside the others.
+void launch_layers(const SceneBuffers &scene, const KernelParams &P, const InstanceBuffers *set, const void *poses, const CameraPose &pose,
+                   bool posed, uint32_t views, const LayerOutputs &out, uint32_t *instance, float *value, float *ao, float *product,
+                   const ViewList *list, void *stream) {
+	InstanceLayersArgs a{};
 	a.nodes_ptr = (const float4 *) scene.nodes;
 	a.tris_ptr = (const float4 *) scene.tris;
 	a.shade_recs = (const float4 *) scene.shade;
@@ -819,7 +736,7 @@ void launch_layers(const SceneBuffers &scene, const KernelParams &P, const void 
 	a.direction = out.direction;
 	a.shade = out.shade;
 	a.value = value;
-	if (views == 0 || a.tiles == 0)
+	if (views == 0 || a.tiles == 0 || (set && (set->top_count == 0 || !poses)))
 		return;
 	hipStream_t s = (hipStream_t) stream;
 	if (list) {
@@ -831,58 +748,18 @@ void launch_layers(const SceneBuffers &scene, const KernelParams &P, const void 
 		a.product = product;
 	}
 	const dim3 blocks((a.tiles + LAYERS_WAVES - 1u) / LAYERS_WAVES, views), lanes(64 * LAYERS_WAVES);  // (views <= 65535: RayQueries::viewsPerChunk)
-	if (poses)
-		hipLaunchKernelGGL((layers_kernel<true, true>), blocks, lanes, 0, s, a);
-	else if (posed)
-		hipLaunchKernelGGL((layers_kernel<true, false>), blocks, lanes, 0, s, a);
-	else
-		hipLaunchKernelGGL((layers_kernel<false, false>), blocks, lanes, 0, s, a);
-	if (list && list->flags)
-		launch_views_list(*list, views * a.n, s);
-}
-
-// The instanced form (kernels/instance_views.hip.h): the views of a chunk -- `poses`, on the device -- against the set's
-// top-level records and inverses (launch_instances'), with `instance` beside the layers.  Always listing where `list` is given.
-void launch_instance_layers(const SceneBuffers &scene, const KernelParams &P, const void *top, uint32_t top_count, const void *inverses,
-                            const void *poses, uint32_t views, const LayerOutputs &out, uint32_t *instance, float *value, float *ao,
-                            float *product, const ViewList *list, void *stream) {
-	InstanceLayersArgs a{};
-	a.nodes_ptr = (const float4 *) scene.nodes;
-	a.tris_ptr = (const float4 *) scene.tris;
-	a.shade_recs = (const float4 *) scene.shade;
-	a.width = P.width;
-	a.height = P.height;
-	a.tiles_x = (P.width + TILE_W - 1u) / TILE_W;
-	a.tiles = a.tiles_x * ((P.height + TILE_H - 1u) / TILE_H);
-	a.node_count = P.node_count;
-	a.shading = P.shading;
-	a.a = P.a;
-	a.half_w = P.half_w;
-	a.half_h = P.half_h;
-	a.poses = (const CameraPose *) poses;
-	a.n = P.width * P.height;
-	a.hit = out.hit;
-	a.out = out;
-	a.direction = out.direction;
-	a.shade = out.shade;
-	a.value = value;
-	a.top_ptr = (const float4 *) top;
-	a.inverses = (const float4 *) inverses;
-	a.top_count = top_count;
-	a.instance = instance;
-	if (views == 0 || a.tiles == 0 || top_count == 0 || !poses)
-		return;
-	hipStream_t s = (hipStream_t) stream;
-	if (list) {
-		a.points = (float4 *) list->points;
-		a.normals = (float4 *) list->normals;
-		a.flags = list->flags;
-		a.seeds = list->seeds;
-		a.ao = ao;
-		a.product = product;
+	const LayersArgs &plain = a;
+	if (set) {
+		a.set = instance_set(*set);
+		a.instance = instance;
+		hipLaunchKernelGGL(instance_layers_kernel, blocks, lanes, 0, s, a);
+	} else if (poses) {
+		hipLaunchKernelGGL((layers_kernel<true, true>), blocks, lanes, 0, s, plain);
+	} else if (posed) {
+		hipLaunchKernelGGL((layers_kernel<true, false>), blocks, lanes, 0, s, plain);
+	} else {
+		hipLaunchKernelGGL((layers_kernel<false, false>), blocks, lanes, 0, s, plain);
 	}
-	const dim3 blocks((a.tiles + LAYERS_WAVES - 1u) / LAYERS_WAVES, views), lanes(64 * LAYERS_WAVES);  // (views <= 65535: RayQueries::viewsPerChunk)
-	hipLaunchKernelGGL(instance_layers_kernel, blocks, lanes, 0, s, a);
 	if (list && list->flags)
 		launch_views_list(*list, views * a.n, s);
 }

@@ -37,12 +37,14 @@ struct AoQueryArgs {
 	float max_distance;
 };
 
-// MODE is AO_UNIFORM or AO_RANDOM, as for ao_kernel: the sampler's code and registers stay out of the default path.
+// Ray `r` of the flattened list, made in registers: direction r % rays of the point in slot r / rays (ao_query_kernel and
+// its instanced form, kernels/instance_views.hip.h).  MODE is AO_UNIFORM or AO_RANDOM, as for ao_kernel: the sampler's code
+// and registers stay out of the default path.
 template <int MODE>
-__global__ __launch_bounds__(64 * QUERY_WAVES) void ao_query_kernel(AoQueryArgs a) {
-	const uint32_t r = blockIdx.x * (64u * QUERY_WAVES) + threadIdx.x;
-	const bool live = r < a.total;  // (a partial last packet: its dead lanes walk nothing and count nothing)
-	uint32_t slot = 0u, idx = 0u;
+__device__ __forceinline__ Ray ao_query_ray(const AoQueryArgs &a, uint32_t r, bool &live, uint32_t &slot, uint32_t &idx) {
+	live = r < a.total;  // (a partial last packet: its dead lanes walk nothing and count nothing)
+	slot = 0u;
+	idx = 0u;
 	float ox = 0.0f, oy = 0.0f, oz = 0.0f, rx = 1.0f, ry = 1.0f, rz = 1.0f;
 	if (live) {
 		slot = r / a.rays;
@@ -78,7 +80,32 @@ __global__ __launch_bounds__(64 * QUERY_WAVES) void ao_query_kernel(AoQueryArgs 
 			}
 		}
 	}
-	const Ray ray = make_ray(ox, oy, oz, rx, ry, rz);
+	return make_ray(ox, oy, oz, rx, ry, rz);
+}
+
+// The packet's hits by point: the first lane of a point's run adds the run's share of the ballot.
+__device__ __forceinline__ void ao_query_count(const AoQueryArgs &a, uint32_t r, bool live, uint32_t slot, uint32_t idx, bool hit) {
+	const unsigned long long hits = wave_ballot(hit);
+	if (!live)
+		return;
+	const uint32_t lane = threadIdx.x & 63u, packet = r - lane;  // (the packet's first ray)
+	const uint32_t run = slot * a.rays;                          // (the point's first ray)
+	const uint32_t first = run > packet ? run - packet : 0u;
+	if (lane != first)
+		return;
+	const uint32_t end = run + a.rays - packet;  // (> first: ray r is the point's; may lie beyond the packet)
+	const unsigned long long below_end = end >= 64u ? ~0ull : (1ull << end) - 1ull;
+	const uint32_t occluded = (uint32_t) __popcll(hits & below_end & ~((1ull << first) - 1ull));
+	if (occluded)
+		atomicAdd(&a.count[idx], occluded);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(64 * QUERY_WAVES) void ao_query_kernel(AoQueryArgs a) {
+	const uint32_t r = blockIdx.x * (64u * QUERY_WAVES) + threadIdx.x;
+	bool live;
+	uint32_t slot, idx;
+	const Ray ray = ao_query_ray<MODE>(a, r, live, slot, idx);
 	bool alive = live, hit = false;
 	// a lane leaves at its first accepted triangle
 	exact_walk(a.nodes_ptr, a.node_count, ray, a.max_distance, alive, [&](uint32_t leaf, bool box) {
@@ -93,20 +120,7 @@ __global__ __launch_bounds__(64 * QUERY_WAVES) void ao_query_kernel(AoQueryArgs 
 		}
 		return wave_ballot(alive) == 0ull;
 	});
-	// the packet's hits by point: the first lane of a point's run adds the run's share of the ballot
-	const unsigned long long hits = wave_ballot(hit);
-	if (!live)
-		return;
-	const uint32_t lane = threadIdx.x & 63u, packet = r - lane;  // (the packet's first ray)
-	const uint32_t run = slot * a.rays;                          // (the point's first ray)
-	const uint32_t first = run > packet ? run - packet : 0u;
-	if (lane != first)
-		return;
-	const uint32_t end = run + a.rays - packet;  // (> first: ray r is the point's; may lie beyond the packet)
-	const unsigned long long below_end = end >= 64u ? ~0ull : (1ull << end) - 1ull;
-	const uint32_t occluded = (uint32_t) __popcll(hits & below_end & ~((1ull << first) - 1ull));
-	if (occluded)
-		atomicAdd(&a.count[idx], occluded);
+	ao_query_count(a, r, live, slot, idx, hit);
 }
 
 // ao[i] = 1.0f - ((float) hits / (float) n), reference :256 / :275 (as the frame's finishing sweep resolves a sub-pixel).

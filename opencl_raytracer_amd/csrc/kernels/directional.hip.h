@@ -6,8 +6,8 @@
 // k of the point in slot `slot`, a wave casts a packet of 64 consecutive rays, and the walk is the exact form.  What a ray
 // IS -- its origin, its point's tangent frame, its direction -- has one definition here, ao_point / ao_direction, used by
 // the three kernels below: the walk that makes the masks, the resolve that sums directions, and the kernel that writes the
-// rays out for the caller.  (ao_query_kernel keeps its own text: it is the frame layers' and views' kernel too, and its
-// listing is pinned.)
+// rays out for the caller.  (ao_query_kernel keeps a text of its own, ao_query_ray, shared with its instanced form alone: it
+// is the frame layers' and views' kernel too.)
 //
 // Masks: hit flags are integers, and a flag has one place -- bit k & 31 of word k >> 5 of its point's row -- so the order
 // in which the packets of a point arrive is free.  Per packet the flags are balloted; the first lane of every run of lanes

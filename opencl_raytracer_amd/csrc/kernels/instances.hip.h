@@ -1,26 +1,37 @@
 // kernels/instances.hip.h -- instanced ray queries: closest hit and occlusion against posed copies of the uploaded scene
-// under a top-level tree (include/rt_hip_instances.h)
+// under a top-level tree (include/rt_hip_instances.h), and what every instanced kernel shares: the set, the nested walk, the
+// closest candidate and the record's epilogue
 // (part of the one translation unit kernels.hip; see its head for the passes and the arithmetic contract)
 //
-// instance_kernel<CLOSEST>: a ray per lane, a packet of 64 per wave, query_kernel's shape, and two nested exact walks
-// (walk.hip.h, exact_walk).  The OUTER walk runs over the top-level records (csrc/instances.cc) with the world ray: lane by
-// lane the reference's slab test where the lane's own walk stands, so a lane ENTERS an instance iff every box on the way to
-// its leaf passes.  At a leaf the instance index is wave-uniform: the twelve floats of its object_from_world arrive by
-// scalar loads, every lane forms its object ray -- products and sums in the header's order, each rounded on its own -- and
-// the INNER walk runs over the scene's own records with `alive && entered` as its `alive`.  Its leaf step is tri_eval's
-// operations in tri_eval's order handing the plane parameter r back (instance_tri_eval; not segment_tri_eval, whose
-// interval rejects a NaN r): an affine map keeps ray parameters, so the world position is o + r d with the WORLD ray, and
-// the distance its length from o.  Nothing is pruned by the best distance so far: the reference's walk has no such step.
-// In the occlusion form a lane leaves both walks at its first candidate, and both end once the packet has no lane left.
+// instance_walk<CLOSEST> is two nested exact walks (walk.hip.h, exact_walk).  The OUTER walk runs over the top-level records
+// (csrc/instances.cc) with the world ray: lane by lane the reference's slab test where the lane's own walk stands, so a lane
+// ENTERS an instance iff every box on the way to its leaf passes.  At a leaf the instance index is wave-uniform: the twelve
+// floats of its object_from_world arrive by scalar loads, every lane forms its object ray -- products and sums in the
+// header's order, each rounded on its own -- and the INNER walk runs over the scene's own records with `alive && entered`
+// as its `alive`.  Its leaf step is the caller's triangle test on the OBJECT ray handing the plane parameter r back: for
+// rays, ambient occlusion and layers tri_eval's operations in tri_eval's order (instance_tri_eval; not segment_tri_eval,
+// whose interval rejects a NaN r), for segments and masks segment_tri_eval<false> with the call's interval.  An affine map
+// keeps ray parameters, so a candidate's world position is o + r d with the WORLD ray, and the distance its length from o
+// (instance_candidate).  Nothing is pruned by the best distance so far: the reference's walk has no such step.  In the
+// occlusion form a lane leaves both walks at its first candidate, and both end once the packet has no lane left.
+//
+// instance_kernel<CLOSEST>: a ray per lane, a packet of 64 per wave, query_kernel's shape, around that walk -- written out in
+// the kernel, the one caller that measured slower through the function; the candidate and the
+// record's epilogue are the shared ones.
 #pragma once
 #include "query.hip.h"
 
 namespace ocrt {
 
+// The instance set on the device, as every instanced kernel is handed it.
+struct InstanceSet {
+	const float4 *top_ptr;   // the top-level tree: NodeRec[top_count], `leaf` the instance index
+	const float4 *inverses;  // object_from_world, three float4 rows per instance
+	uint32_t top_count;      // 2 * instances - 1
+};
+
 struct InstanceArgs : RayQueryArgs {  // (nodes_ptr, tris_ptr, shade: the scene's own; max_distance: the call's, in both spaces)
-	const float4 *top_ptr;    // the top-level tree: NodeRec[top_count], `leaf` the instance index
-	const float4 *inverses;   // object_from_world, three float4 rows per instance
-	uint32_t top_count;       // 2 * instances - 1
+	InstanceSet set;
 	uint8_t *hit;             // by ray index, or null.  CLOSEST: the hit flag; ANY: the occlusion flag
 	uint32_t *instance;       // by ray index, or null (CLOSEST)
 };
@@ -84,19 +95,18 @@ __device__ __forceinline__ bool instance_nearer(float distance, uint32_t instanc
 	return best.distance > distance || (best.distance == distance && lower && distance < __builtin_inff());
 }
 
-template <bool CLOSEST>
-__global__ __launch_bounds__(64 * QUERY_WAVES) void instance_kernel(InstanceArgs a) {
-	bool live;
-	uint32_t idx;
-	const Ray ray = packet_ray(a, blockIdx.x * (64u * QUERY_WAVES) + threadIdx.x, live, idx);
-	const float max_distance = a.max_distance;
+// The nested walk.  Returns whether the lane has a candidate: a leaf whose triangle leaf_test(q0, q1, q2, q3, object, r)
+// accepts for the lane's object ray, r the test's plane parameter.  CLOSEST: every candidate goes to candidate(k, leaf, tr,
+// r) -- instance, leaf, the object-space test's result and r --, nobody leaves; else a lane leaves both walks at its first
+// candidate, and both end once the packet has no lane left.
+template <bool CLOSEST, class LeafTest, class Candidate>
+__device__ __forceinline__ bool instance_walk(const InstanceSet &set, const float4 *nodes_ptr, uint32_t node_count, const float4 *tris_ptr,
+                                              const Ray &ray, float max_distance, bool live, LeafTest &&leaf_test, Candidate &&candidate) {
 	bool alive = live, hit = false;
-	Hit best = closest_entry();
-	uint32_t best_instance = 0u;
-	exact_walk(a.top_ptr, a.top_count, ray, max_distance, alive, [&](uint32_t k, bool entered) {
+	exact_walk(set.top_ptr, set.top_count, ray, max_distance, alive, [&](uint32_t k, bool entered) {
 		// (k comes out of a scalar register: the rows arrive by scalar loads, into SGPRs)
 		float4 m0, m1, m2;
-		scalar_load_rows(a.inverses, k, m0, m1, m2);
+		scalar_load_rows(set.inverses, k, m0, m1, m2);
 		const float ox = ((m0.x * ray.ox + m0.y * ray.oy) + m0.z * ray.oz) + m0.w;
 		const float oy = ((m1.x * ray.ox + m1.y * ray.oy) + m1.z * ray.oz) + m1.w;
 		const float oz = ((m2.x * ray.ox + m2.y * ray.oy) + m2.z * ray.oz) + m2.w;
@@ -107,6 +117,127 @@ __global__ __launch_bounds__(64 * QUERY_WAVES) void instance_kernel(InstanceArgs
 		const Ray object = make_ray(entered ? ox : 0.0f, entered ? oy : 0.0f, entered ? oz : 0.0f, entered ? dx : 1.0f, entered ? dy : 1.0f,
 		                            entered ? dz : 1.0f);
 		bool inside = entered;  // (`entered` implies `alive`: exact_box)
+		exact_walk(nodes_ptr, node_count, object, max_distance, inside, [&](uint32_t leaf, bool box) {
+			const float4 *tri = tris_ptr + LEAF_F4 * leaf + LEAF_TRI_F4;
+			const float4 q0 = tri[0], q1 = tri[1], q2 = tri[2], q3 = tri[3];
+			if (box) {
+				float r;
+				const TriResult tr = leaf_test(q0, q1, q2, q3, object, r);
+				if (tr.accepted) {
+					hit = true;
+					if (CLOSEST) {
+						candidate(k, leaf, tr, r);
+					} else {
+						alive = false;
+						inside = false;
+					}
+				}
+			}
+			return !CLOSEST && wave_ballot(inside) == 0ull;
+		});
+		return !CLOSEST && wave_ballot(alive) == 0ull;
+	});
+	return hit;
+}
+
+// The leaf test of rays, ambient occlusion and layers, and the candidate of the occlusion forms, which is never called.
+struct InstanceTriEval {
+	__device__ __forceinline__ TriResult operator()(const float4 q0, const float4 q1, const float4 q2, const float4 q3, const Ray &object,
+	                                                float &r) const {
+		return instance_tri_eval(q0, q1, q2, q3, object, r);
+	}
+};
+struct NoCandidate {
+	__device__ __forceinline__ void operator()(uint32_t, uint32_t, const TriResult &, float) const {}
+};
+
+// A candidate of the closest forms: the record is the WORLD ray's (an affine map keeps r), the minimum by instance_nearer.
+__device__ __forceinline__ void instance_candidate(const Ray &ray, uint32_t k, uint32_t leaf, const TriResult &tr, float r, Hit &best,
+                                                   uint32_t &best_instance) {
+	const float px = ray.ox + r * ray.dx, py = ray.oy + r * ray.dy, pz = ray.oz + r * ray.dz;
+	const float distance = length3(px - ray.ox, py - ray.oy, pz - ray.oz);
+	if (instance_nearer(distance, k, leaf, best, best_instance)) {
+		best.distance = distance;
+		best.leaf = leaf;
+		best.s = tr.s;
+		best.t = tr.t;
+		best.px = px; best.py = py; best.pz = pz;
+		best_instance = k;
+	}
+}
+
+// The instanced record's normal where there is a hit: get_smooth_normal's weighted sum in the object's frame, the inverse's
+// transpose, ONE normalisation.
+__device__ __forceinline__ void instance_normal(const float4 *shade, const float4 *inverses, uint32_t leaf, uint32_t instance, float b0,
+                                                float b1, float b2, float &wx, float &wy, float &wz) {
+	const float4 n0 = shade[3 * (size_t) leaf + 0], n1 = shade[3 * (size_t) leaf + 1], n2 = shade[3 * (size_t) leaf + 2];
+	const float rx = (n0.x * b0 + n1.x * b1) + n2.x * b2;
+	const float ry = (n0.y * b0 + n1.y * b1) + n2.y * b2;
+	const float rz = (n0.z * b0 + n1.z * b1) + n2.z * b2;
+	const float4 *rows = inverses + 3u * (size_t) instance;
+	const float4 m0 = rows[0], m1 = rows[1], m2 = rows[2];
+	wx = (m0.x * rx + m1.x * ry) + m2.x * rz;
+	wy = (m0.y * rx + m1.y * ry) + m2.y * rz;
+	wz = (m0.z * rx + m1.z * ry) + m2.z * rz;
+	normalize3(wx, wy, wz);
+}
+
+// The closest forms' record into `idx` of the arrays that were asked for (the flag is the caller's).  Where some triangle
+// is accepted but none replaces the record it keeps its entry values, as closest_store's does.
+__device__ __forceinline__ void instance_record_store(const RecordOutputs &out, uint32_t *instance, uint32_t idx, const float4 *shade,
+                                                      const float4 *inverses, bool hit, const Hit &best, uint32_t best_instance) {
+	const bool kept = hit && best.distance < __builtin_inff();  // (the record was replaced at least once)
+	if (instance)
+		instance[idx] = hit ? best_instance : NONE;
+	if (out.distance)
+		out.distance[idx] = best.distance;
+	if (out.leaf)
+		out.leaf[idx] = hit ? best.leaf : NONE;
+	const float b0 = kept ? 1.0f - best.s - best.t : 0.0f, b1 = kept ? best.s : 0.0f, b2 = kept ? best.t : 0.0f;
+	if (out.barycentric) {
+		out.barycentric[3u * (size_t) idx + 0u] = b0;
+		out.barycentric[3u * (size_t) idx + 1u] = b1;
+		out.barycentric[3u * (size_t) idx + 2u] = b2;
+	}
+	if (out.position) {
+		out.position[3u * (size_t) idx + 0u] = kept ? best.px : 0.0f;
+		out.position[3u * (size_t) idx + 1u] = kept ? best.py : 0.0f;
+		out.position[3u * (size_t) idx + 2u] = kept ? best.pz : 0.0f;
+	}
+	if (out.normal) {
+		float wx = 0.0f, wy = 0.0f, wz = 0.0f;
+		if (hit)
+			instance_normal(shade, inverses, best.leaf, best_instance, b0, b1, b2, wx, wy, wz);
+		out.normal[3u * (size_t) idx + 0u] = wx;
+		out.normal[3u * (size_t) idx + 1u] = wy;
+		out.normal[3u * (size_t) idx + 2u] = wz;
+	}
+}
+
+// (instance_kernel keeps the walk's lines inline: through instance_walk the compiler schedules both instantiations
+// differently, and they measured 2 to 5 % slower on the MI355X -- DESIGN.md section 24.  What the walk does is
+// instance_walk's comment, word for word, with instance_tri_eval at the leaf.)
+template <bool CLOSEST>
+__global__ __launch_bounds__(64 * QUERY_WAVES) void instance_kernel(InstanceArgs a) {
+	bool live;
+	uint32_t idx;
+	const Ray ray = packet_ray(a, blockIdx.x * (64u * QUERY_WAVES) + threadIdx.x, live, idx);
+	const float max_distance = a.max_distance;
+	bool alive = live, hit = false;
+	Hit best = closest_entry();
+	uint32_t best_instance = 0u;
+	exact_walk(a.set.top_ptr, a.set.top_count, ray, max_distance, alive, [&](uint32_t k, bool entered) {
+		float4 m0, m1, m2;
+		scalar_load_rows(a.set.inverses, k, m0, m1, m2);
+		const float ox = ((m0.x * ray.ox + m0.y * ray.oy) + m0.z * ray.oz) + m0.w;
+		const float oy = ((m1.x * ray.ox + m1.y * ray.oy) + m1.z * ray.oz) + m1.w;
+		const float oz = ((m2.x * ray.ox + m2.y * ray.oy) + m2.z * ray.oz) + m2.w;
+		const float dx = (m0.x * ray.dx + m0.y * ray.dy) + m0.z * ray.dz;
+		const float dy = (m1.x * ray.dx + m1.y * ray.dy) + m1.z * ray.dz;
+		const float dz = (m2.x * ray.dx + m2.y * ray.dy) + m2.z * ray.dz;
+		const Ray object = make_ray(entered ? ox : 0.0f, entered ? oy : 0.0f, entered ? oz : 0.0f, entered ? dx : 1.0f, entered ? dy : 1.0f,
+		                            entered ? dz : 1.0f);
+		bool inside = entered;
 		exact_walk(a.nodes_ptr, a.node_count, object, max_distance, inside, [&](uint32_t leaf, bool box) {
 			const float4 *tri = a.tris_ptr + LEAF_F4 * leaf + LEAF_TRI_F4;
 			const float4 q0 = tri[0], q1 = tri[1], q2 = tri[2], q3 = tri[3];
@@ -116,16 +247,7 @@ __global__ __launch_bounds__(64 * QUERY_WAVES) void instance_kernel(InstanceArgs
 				if (tr.accepted) {
 					hit = true;
 					if (CLOSEST) {
-						const float px = ray.ox + r * ray.dx, py = ray.oy + r * ray.dy, pz = ray.oz + r * ray.dz;
-						const float distance = length3(px - ray.ox, py - ray.oy, pz - ray.oz);
-						if (instance_nearer(distance, k, leaf, best, best_instance)) {
-							best.distance = distance;
-							best.leaf = leaf;
-							best.s = tr.s;
-							best.t = tr.t;
-							best.px = px; best.py = py; best.pz = pz;
-							best_instance = k;
-						}
+						instance_candidate(ray, k, leaf, tr, r, best, best_instance);
 					} else {
 						alive = false;
 						inside = false;
@@ -140,45 +262,8 @@ __global__ __launch_bounds__(64 * QUERY_WAVES) void instance_kernel(InstanceArgs
 		return;
 	if (a.hit)
 		a.hit[idx] = hit ? 1u : 0u;
-	if (!CLOSEST)
-		return;
-	const bool kept = hit && best.distance < __builtin_inff();  // (the record was replaced at least once)
-	if (a.instance)
-		a.instance[idx] = hit ? best_instance : NONE;
-	if (a.out.distance)
-		a.out.distance[idx] = best.distance;
-	if (a.out.leaf)
-		a.out.leaf[idx] = hit ? best.leaf : NONE;
-	const float b0 = kept ? 1.0f - best.s - best.t : 0.0f, b1 = kept ? best.s : 0.0f, b2 = kept ? best.t : 0.0f;
-	if (a.out.barycentric) {
-		a.out.barycentric[3u * (size_t) idx + 0u] = b0;
-		a.out.barycentric[3u * (size_t) idx + 1u] = b1;
-		a.out.barycentric[3u * (size_t) idx + 2u] = b2;
-	}
-	if (a.out.position) {
-		a.out.position[3u * (size_t) idx + 0u] = kept ? best.px : 0.0f;
-		a.out.position[3u * (size_t) idx + 1u] = kept ? best.py : 0.0f;
-		a.out.position[3u * (size_t) idx + 2u] = kept ? best.pz : 0.0f;
-	}
-	if (a.out.normal) {
-		// get_smooth_normal's weighted sum in the object's frame, the inverse's transpose, ONE normalisation
-		float wx = 0.0f, wy = 0.0f, wz = 0.0f;
-		if (hit) {
-			const float4 n0 = a.shade[3 * (size_t) best.leaf + 0], n1 = a.shade[3 * (size_t) best.leaf + 1], n2 = a.shade[3 * (size_t) best.leaf + 2];
-			const float rx = (n0.x * b0 + n1.x * b1) + n2.x * b2;
-			const float ry = (n0.y * b0 + n1.y * b1) + n2.y * b2;
-			const float rz = (n0.z * b0 + n1.z * b1) + n2.z * b2;
-			const float4 *rows = a.inverses + 3u * (size_t) best_instance;
-			const float4 m0 = rows[0], m1 = rows[1], m2 = rows[2];
-			wx = (m0.x * rx + m1.x * ry) + m2.x * rz;
-			wy = (m0.y * rx + m1.y * ry) + m2.y * rz;
-			wz = (m0.z * rx + m1.z * ry) + m2.z * rz;
-			normalize3(wx, wy, wz);
-		}
-		a.out.normal[3u * (size_t) idx + 0u] = wx;
-		a.out.normal[3u * (size_t) idx + 1u] = wy;
-		a.out.normal[3u * (size_t) idx + 2u] = wz;
-	}
+	if (CLOSEST)
+		instance_record_store(a.out, a.instance, idx, a.shade, a.set.inverses, hit, best, best_instance);
 }
 
 }  // namespace ocrt

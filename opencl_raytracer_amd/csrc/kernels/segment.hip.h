@@ -122,21 +122,29 @@ struct SegmentArgs {
 	uint8_t *hit;             // by segment index, or null.  CLOSEST: the hit flag; ANY: the occlusion flag
 };
 
+// The ray of packet lane `k`: segment `idx` of the call (segment_kernel and its instanced form,
+// kernels/instance_segments.hip.h).  A partial last packet's dead lanes get a ray that walks nothing and write nothing.
+__device__ __forceinline__ Ray segment_packet_ray(const float4 *from, const float4 *to, const uint32_t *order, uint32_t n, uint32_t k,
+                                                  bool &live, uint32_t &idx) {
+	live = k < n;
+	idx = k;
+	if (live && order)
+		idx = order[k];
+	float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f), e = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+	if (live) {
+		o = from[idx];
+		e = to[idx];
+	}
+	return make_ray(o.x, o.y, o.z, e.x - o.x, e.y - o.y, e.z - o.z);
+}
+
 // CLOSEST: the record of the blocker with the minimum of (distance, leaf) -- closest_entry, nearer, take and closest_store,
 // the closest hit's own.  ANY: a lane leaves the walk at its first blocker; the walk ends when the packet has no live lane.
 template <bool CLOSEST>
 __global__ __launch_bounds__(64 * QUERY_WAVES) void segment_kernel(SegmentArgs a) {
-	const uint32_t k = blockIdx.x * (64u * QUERY_WAVES) + threadIdx.x;
-	const bool live = k < a.n;  // (a partial last packet: its dead lanes walk nothing and write nothing)
-	uint32_t idx = k;
-	if (live && a.order)
-		idx = a.order[k];
-	float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f), e = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-	if (live) {
-		o = a.from[idx];
-		e = a.to[idx];
-	}
-	const Ray ray = make_ray(o.x, o.y, o.z, e.x - o.x, e.y - o.y, e.z - o.z);
+	bool live;
+	uint32_t idx;
+	const Ray ray = segment_packet_ray(a.from, a.to, a.order, a.n, blockIdx.x * (64u * QUERY_WAVES) + threadIdx.x, live, idx);
 	const float t_lo = a.t_lo, t_hi = a.t_hi;
 	bool alive = live, hit = false;
 	Hit best = closest_entry();
@@ -196,10 +204,12 @@ inline void visibility_divisor(uint32_t nt, uint32_t &magic, uint32_t &shift) {
 	magic = (uint32_t) (((1ull << shift) + nt - 1u) / nt);
 }
 
-__global__ __launch_bounds__(64 * QUERY_WAVES) void visibility_mask_kernel(VisibilityArgs a) {
-	const uint32_t r = blockIdx.x * (64u * QUERY_WAVES) + threadIdx.x;
-	const bool live = r < a.total;  // (a partial last packet: its dead lanes walk nothing and flag nothing)
-	uint32_t idx = 0u, j = 0u;
+// Ray `r` of the P x T list: the point `idx` of slot r / nt towards target `j` (visibility_mask_kernel and its instanced
+// form).  A partial last packet's dead lanes walk nothing and flag nothing.
+__device__ __forceinline__ Ray visibility_ray(const VisibilityArgs &a, uint32_t r, bool &live, uint32_t &idx, uint32_t &j) {
+	live = r < a.total;
+	idx = 0u;
+	j = 0u;
 	float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f), e = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
 	if (live) {
 		// (r / nt by a multiplication: a 32-bit division is some thirty vector instructions, a tenth of a short walk)
@@ -209,7 +219,30 @@ __global__ __launch_bounds__(64 * QUERY_WAVES) void visibility_mask_kernel(Visib
 		o = a.points[idx];
 		e = a.targets[j];
 	}
-	const Ray ray = make_ray(o.x, o.y, o.z, e.x - o.x, e.y - o.y, e.z - o.z);
+	return make_ray(o.x, o.y, o.z, e.x - o.x, e.y - o.y, e.z - o.z);
+}
+
+// The packet's flags by (point, mask word): the first lane of a run of lanes that shares both ORs the run's bits in.
+__device__ __forceinline__ void visibility_mask_store(const VisibilityArgs &a, bool live, uint32_t idx, uint32_t j, bool hit) {
+	const unsigned long long hits = wave_ballot(hit);
+	if (!live)
+		return;
+	const uint32_t lane = threadIdx.x & 63u, bit = j & 31u;
+	if (!(lane == 0u || j == 0u || bit == 0u))
+		return;
+	// the run ends with the word, with the point or with the packet: 1 .. 32 lanes
+	uint32_t len = 32u - bit;
+	len = a.nt - j < len ? a.nt - j : len;
+	len = 64u - lane < len ? 64u - lane : len;
+	const uint32_t flags = (uint32_t) ((hits >> lane) & ((1ull << len) - 1ull)) << bit;
+	if (flags)
+		atomicOr(&a.mask[(size_t) idx * a.words + (j >> 5)], flags);
+}
+
+__global__ __launch_bounds__(64 * QUERY_WAVES) void visibility_mask_kernel(VisibilityArgs a) {
+	bool live;
+	uint32_t idx, j;
+	const Ray ray = visibility_ray(a, blockIdx.x * (64u * QUERY_WAVES) + threadIdx.x, live, idx, j);
 	const float t_lo = a.t_lo, t_hi = a.t_hi;
 	bool alive = live, hit = false;
 	// a lane leaves at its first blocker
@@ -226,20 +259,7 @@ __global__ __launch_bounds__(64 * QUERY_WAVES) void visibility_mask_kernel(Visib
 		}
 		return wave_ballot(alive) == 0ull;
 	});
-	// the packet's flags by (point, mask word): the first lane of a run of lanes that shares both ORs the run's bits in
-	const unsigned long long hits = wave_ballot(hit);
-	if (!live)
-		return;
-	const uint32_t lane = threadIdx.x & 63u, bit = j & 31u;
-	if (!(lane == 0u || j == 0u || bit == 0u))
-		return;
-	// the run ends with the word, with the point or with the packet: 1 .. 32 lanes
-	uint32_t len = 32u - bit;
-	len = a.nt - j < len ? a.nt - j : len;
-	len = 64u - lane < len ? 64u - lane : len;
-	const uint32_t flags = (uint32_t) ((hits >> lane) & ((1ull << len) - 1ull)) << bit;
-	if (flags)
-		atomicOr(&a.mask[(size_t) idx * a.words + (j >> 5)], flags);
+	visibility_mask_store(a, live, idx, j, hit);
 }
 
 // One thread per point: the popcount of its row -- the targets the point does NOT see.

@@ -26,7 +26,7 @@ enum { AO_POINTS, AO_NORMALS, AO_COUNTS, AO_SEEDS, AO_VALUES, AO_PIECES };
 // the rays of the points: the inputs and the two ray arrays.
 enum { DIR_POINTS, DIR_NORMALS, DIR_SEEDS, DIR_ROWS, DIR_COUNTS, DIR_VALUES, DIR_BENT, DIR_PIECES };
 enum { AORAY_POINTS, AORAY_NORMALS, AORAY_SEEDS, AORAY_ORIGINS, AORAY_DIRECTIONS, AORAY_PIECES };
-// Instanced ray queries: the rays' pieces, then the instance indices.
+// Instanced ray and segment queries: the rays' pieces, then the instance indices (absent for a plain call).
 enum { INST_INDEX = RAY_PIECES, INST_PIECES };
 // Visibility masks: the two inputs, the rows (staged whether they are copied back or not), the counts.
 enum { VIS_POINTS, VIS_TARGETS, VIS_ROWS, VIS_COUNTS, VIS_PIECES };
@@ -231,37 +231,62 @@ void RayQueries::layerDevice(const Staged *p, LayerOutputs &out) {
 	out.value = (float *) p[LAYER_VALUE].device;
 }
 
+void RayQueries::requireQuery(bool instanced, const char *query) const {
+	if (instanced)
+		requireInstances(("instanced " + std::string(query)).c_str());
+	else
+		requireScene(query);
+}
+
+RayQueries::Target RayQueries::target(bool instanced) {
+	if (!instanced)
+		return Target{ nullptr, nullptr };
+	refreshInstances();  // (an update, a build or a new upload is picked up before the launch)
+	return Target{ &inst_set, inst_box };
+}
+
+template <class Run>
+void RayQueries::stagedRecords(const float *a4, const float *b4, uint32_t n, bool records, const QueryOutputs &host, uint32_t *instance,
+                               Run &&run) {
+	QueryOutputs want;  // (occlusion: the flags alone)
+	if (records)
+		want = host;
+	want.hit = host.hit;
+	Staged p[INST_PIECES] = { input(a4, (size_t) n * 16u), input(b4, b4 ? (size_t) n * 16u : 0u), output(want.hit, n) };
+	recordPieces(p + RAY_RECORDS, want, n);
+	p[INST_INDEX] = output(records ? instance : nullptr, (size_t) n * 4u);
+	void *s = stageIn(p, INST_PIECES);
+	QueryOutputs out;
+	out.hit = (unsigned char *) p[RAY_FIRST].device;
+	recordDevice(p + RAY_RECORDS, out);
+	run((const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, out, (uint32_t *) p[INST_INDEX].device, s);
+	stageOut(p, INST_PIECES, s);
+}
+
 void RayQueries::traceDevice(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
-                             uint32_t flags, const QueryOutputs &out, void *stream) {
-	requireScene("ray query");
+                             uint32_t flags, const QueryOutputs &out, void *stream, bool instanced, uint32_t *instance) {
+	requireQuery(instanced, "ray query");
 	if (n == 0)
 		return;
-	const Enqueue q = begin(stream, origins4, directions4, n, n, flags);
-	launch_query(dev.deviceScene()->buffers(), dev.params().node_count, closest, origins4, directions4, q.order, n, max_distance, out,
-	             q.stream);
+	const Target to = target(instanced);
+	const Enqueue q = begin(stream, origins4, directions4, n, n, flags, {}, false, to.box);
+	launch_query(dev.deviceScene()->buffers(), dev.params().node_count, to.set, closest, origins4, directions4, q.order, n, max_distance, out,
+	             closest ? instance : nullptr, q.stream);
 	end(q);
 }
 
 void RayQueries::traceHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
-                           uint32_t flags, const QueryOutputs &host) {
-	requireScene("ray query");
+                           uint32_t flags, const QueryOutputs &host, bool instanced, uint32_t *instance) {
+	requireQuery(instanced, "ray query");
 	if (n == 0)
 		return;
-	QueryOutputs want;  // (occlusion: the flags alone)
-	if (closest)
-		want = host;
-	want.hit = host.hit;
-	Staged p[RAY_PIECES] = { input(origins4, (size_t) n * 16u), input(directions4, (size_t) n * 16u), output(want.hit, n) };
-	recordPieces(p + RAY_RECORDS, want, n);
-	void *s = stageIn(p, RAY_PIECES);
-	QueryOutputs out;
-	out.hit = (unsigned char *) p[RAY_FIRST].device;
-	recordDevice(p + RAY_RECORDS, out);
-	traceDevice(closest, (const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, max_distance, flags, out, s);
-	stageOut(p, RAY_PIECES, s);
+	stagedRecords(origins4, directions4, n, closest, host, instance,
+	              [&](const float *o4, const float *d4, const QueryOutputs &out, uint32_t *inst, void *s) {
+		              traceDevice(closest, o4, d4, n, max_distance, flags, out, s, instanced, inst);
+	              });
 }
 
-// ---- instanced ray queries (include/rt_hip_instances.h) ----
+// ---- the instance set (include/rt_hip_instances.h) ----
 void RayQueries::setInstances(const float *world_from_object, uint32_t n) {
 	if (n > RT_INSTANCES_MAX)
 		throw std::invalid_argument("more instances than RT_INSTANCES_MAX");
@@ -307,6 +332,7 @@ void RayQueries::refreshInstances() {
 	OCRT_HIP(hipMemcpy(at, inst_world.data(), rows, hipMemcpyHostToDevice));
 	OCRT_HIP(hipMemcpy(at + rows, inst_inverse.data(), rows, hipMemcpyHostToDevice));
 	OCRT_HIP(hipMemcpy(at + 2u * rows, inst_nodes.data(), tree, hipMemcpyHostToDevice));
+	inst_set = InstanceBuffers{ at + 2u * rows, at + rows, (uint32_t) inst_nodes.size() };
 	for (int k = 0; k < 3; ++k) {  // (sceneBox's rule, on the top-level root)
 		const float lo = inst_nodes[0].lo[k], extent = inst_nodes[0].hi[k] - lo;
 		const bool usable = std::isfinite(lo) && std::isfinite(extent) && extent > 0.0f && std::isfinite(8.0f / extent);
@@ -323,92 +349,52 @@ void RayQueries::instanceNodes(void *out) {
 	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
 	if (timed)
 		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
-	const size_t rows = (size_t) instanceCount() * 12u * sizeof(float);
 	if (out)
-		OCRT_HIP(hipMemcpy(out, (const char *) inst_device.ptr + 2u * rows, inst_nodes.size() * sizeof(InstanceNode), hipMemcpyDeviceToHost));
-}
-
-void RayQueries::instancesDevice(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
-                                 const QueryOutputs &out, uint32_t *instance, void *stream) {
-	requireInstances("instanced ray query");
-	if (n == 0)
-		return;
-	refreshInstances();
-	const size_t rows = (size_t) instanceCount() * 12u * sizeof(float);
-	const char *set = (const char *) inst_device.ptr;
-	const Enqueue q = begin(stream, origins4, directions4, n, n, flags, {}, false, inst_box);
-	launch_instances(dev.deviceScene()->buffers(), dev.params().node_count, set + 2u * rows, (uint32_t) inst_nodes.size(), set + rows, closest,
-	                 origins4, directions4, q.order, n, max_distance, out, closest ? instance : nullptr, q.stream);
-	end(q);
-}
-
-void RayQueries::instancesHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
-                               const QueryOutputs &host, uint32_t *instance) {
-	requireInstances("instanced ray query");
-	if (n == 0)
-		return;
-	QueryOutputs want;  // (occlusion: the flags alone)
-	if (closest)
-		want = host;
-	want.hit = host.hit;
-	Staged p[INST_PIECES] = { input(origins4, (size_t) n * 16u), input(directions4, (size_t) n * 16u), output(want.hit, n) };
-	recordPieces(p + RAY_RECORDS, want, n);
-	p[INST_INDEX] = output(closest ? instance : nullptr, (size_t) n * 4u);
-	void *s = stageIn(p, INST_PIECES);
-	QueryOutputs out;
-	out.hit = (unsigned char *) p[RAY_FIRST].device;
-	recordDevice(p + RAY_RECORDS, out);
-	instancesDevice(closest, (const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, max_distance, flags, out,
-	                (uint32_t *) p[INST_INDEX].device, s);
-	stageOut(p, INST_PIECES, s);
+		OCRT_HIP(hipMemcpy(out, inst_set.top, inst_nodes.size() * sizeof(InstanceNode), hipMemcpyDeviceToHost));
 }
 
 void RayQueries::segmentsDevice(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
-                                const QueryOutputs &out, void *stream) {
-	requireScene("segment query");
+                                const QueryOutputs &out, void *stream, bool instanced, uint32_t *instance) {
+	requireQuery(instanced, "segment query");
 	if (n == 0)
 		return;
-	const Enqueue q = begin(stream, from4, to4, n, n, flags, {}, true);
-	launch_segments(dev.deviceScene()->buffers(), dev.params().node_count, closest, from4, to4, q.order, n, t_lo, t_hi, out, q.stream);
+	const Target to = target(instanced);
+	const Enqueue q = begin(stream, from4, to4, n, n, flags, {}, true, to.box);
+	launch_segments(dev.deviceScene()->buffers(), dev.params().node_count, to.set, closest, from4, to4, q.order, n, t_lo, t_hi, out,
+	                closest ? instance : nullptr, q.stream);
 	end(q);
 }
 
 void RayQueries::segmentsHost(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
-                              const QueryOutputs &host) {
-	requireScene("segment query");
+                              const QueryOutputs &host, bool instanced, uint32_t *instance) {
+	requireQuery(instanced, "segment query");
 	if (n == 0)
 		return;
-	QueryOutputs want;  // (occlusion: the flags alone)
-	if (closest)
-		want = host;
-	want.hit = host.hit;
-	Staged p[RAY_PIECES] = { input(from4, (size_t) n * 16u), input(to4, (size_t) n * 16u), output(want.hit, n) };
-	recordPieces(p + RAY_RECORDS, want, n);
-	void *s = stageIn(p, RAY_PIECES);
-	QueryOutputs out;
-	out.hit = (unsigned char *) p[RAY_FIRST].device;
-	recordDevice(p + RAY_RECORDS, out);
-	segmentsDevice(closest, (const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, t_lo, t_hi, flags, out, s);
-	stageOut(p, RAY_PIECES, s);
+	stagedRecords(from4, to4, n, closest, host, instance,
+	              [&](const float *a4, const float *b4, const QueryOutputs &out, uint32_t *inst, void *s) {
+		              segmentsDevice(closest, a4, b4, n, t_lo, t_hi, flags, out, s, instanced, inst);
+	              });
 }
 
 void RayQueries::visibilityDevice(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
-                                  uint32_t flags, const VisibilityOutputs &out, void *stream) {
-	requireScene("visibility query");
+                                  uint32_t flags, const VisibilityOutputs &out, void *stream, bool instanced) {
+	requireQuery(instanced, "visibility query");
 	if (np == 0 || nt == 0 || !out.any())
 		return;
+	const Target to = target(instanced);
 	const size_t row_bytes = (size_t) visibilityWords(nt) * sizeof(uint32_t);
 	// the POINTS are ordered, by position alone, from RT_QUERY_SORT_MIN of them on; the rows are the caller's, or scratch where
 	// only the counts are wanted
-	const Enqueue q = begin(stream, points4, nullptr, np, np, flags, { Need{ out.mask ? nullptr : &vis_rows, (size_t) np * row_bytes } });
-	launch_visibility(dev.deviceScene()->buffers(), dev.params().node_count, points4, np, targets4, nt, q.order, t_lo, t_hi,
+	const Enqueue q = begin(stream, points4, nullptr, np, np, flags, { Need{ out.mask ? nullptr : &vis_rows, (size_t) np * row_bytes } }, false,
+	                        to.box);
+	launch_visibility(dev.deviceScene()->buffers(), dev.params().node_count, to.set, points4, np, targets4, nt, q.order, t_lo, t_hi,
 	                  out.mask ? out.mask : (uint32_t *) vis_rows.ptr, out.count, q.stream);
 	end(q);
 }
 
 void RayQueries::visibilityHost(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
-                                const VisibilityOutputs &host) {
-	requireScene("visibility query");
+                                const VisibilityOutputs &host, bool instanced) {
+	requireQuery(instanced, "visibility query");
 	if (np == 0 || nt == 0 || !host.any())
 		return;
 	const size_t row_bytes = (size_t) visibilityWords(nt) * sizeof(uint32_t);
@@ -418,78 +404,7 @@ void RayQueries::visibilityHost(const float *points4, uint32_t np, const float *
 	VisibilityOutputs out;
 	out.mask = (uint32_t *) p[VIS_ROWS].device;
 	out.count = (uint32_t *) p[VIS_COUNTS].device;
-	visibilityDevice((const float *) p[VIS_POINTS].device, np, (const float *) p[VIS_TARGETS].device, nt, t_lo, t_hi, flags, out, s);
-	stageOut(p, VIS_PIECES, s);
-}
-
-// ---- instanced segment queries (include/rt_hip_instance_segments.h) ----
-void RayQueries::instanceSegmentsDevice(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
-                                        const QueryOutputs &out, uint32_t *instance, void *stream) {
-	requireInstances("instanced segment query");
-	if (n == 0)
-		return;
-	refreshInstances();
-	const size_t rows = (size_t) instanceCount() * 12u * sizeof(float);
-	const char *set = (const char *) inst_device.ptr;
-	const Enqueue q = begin(stream, from4, to4, n, n, flags, {}, true, inst_box);
-	launch_instance_segments(dev.deviceScene()->buffers(), dev.params().node_count, set + 2u * rows, (uint32_t) inst_nodes.size(), set + rows,
-	                         closest, from4, to4, q.order, n, t_lo, t_hi, out, closest ? instance : nullptr, q.stream);
-	end(q);
-}
-
-void RayQueries::instanceSegmentsHost(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
-                                      const QueryOutputs &host, uint32_t *instance) {
-	requireInstances("instanced segment query");
-	if (n == 0)
-		return;
-	QueryOutputs want;  // (occlusion: the flags alone)
-	if (closest)
-		want = host;
-	want.hit = host.hit;
-	Staged p[INST_PIECES] = { input(from4, (size_t) n * 16u), input(to4, (size_t) n * 16u), output(want.hit, n) };
-	recordPieces(p + RAY_RECORDS, want, n);
-	p[INST_INDEX] = output(closest ? instance : nullptr, (size_t) n * 4u);
-	void *s = stageIn(p, INST_PIECES);
-	QueryOutputs out;
-	out.hit = (unsigned char *) p[RAY_FIRST].device;
-	recordDevice(p + RAY_RECORDS, out);
-	instanceSegmentsDevice(closest, (const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, t_lo, t_hi, flags, out,
-	                       (uint32_t *) p[INST_INDEX].device, s);
-	stageOut(p, INST_PIECES, s);
-}
-
-void RayQueries::instanceVisibilityDevice(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
-                                          uint32_t flags, const VisibilityOutputs &out, void *stream) {
-	requireInstances("instanced visibility query");
-	if (np == 0 || nt == 0 || !out.any())
-		return;
-	refreshInstances();
-	const size_t rows = (size_t) instanceCount() * 12u * sizeof(float);
-	const char *set = (const char *) inst_device.ptr;
-	const size_t row_bytes = (size_t) visibilityWords(nt) * sizeof(uint32_t);
-	// the POINTS are ordered, by position over the top-level root box; the rows are the caller's, or scratch where only the
-	// counts are wanted
-	const Enqueue q = begin(stream, points4, nullptr, np, np, flags, { Need{ out.mask ? nullptr : &vis_rows, (size_t) np * row_bytes } }, false,
-	                        inst_box);
-	launch_instance_visibility(dev.deviceScene()->buffers(), dev.params().node_count, set + 2u * rows, (uint32_t) inst_nodes.size(), set + rows,
-	                           points4, np, targets4, nt, q.order, t_lo, t_hi, out.mask ? out.mask : (uint32_t *) vis_rows.ptr, out.count,
-	                           q.stream);
-	end(q);
-}
-
-void RayQueries::instanceVisibilityHost(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
-                                        uint32_t flags, const VisibilityOutputs &host) {
-	requireInstances("instanced visibility query");
-	if (np == 0 || nt == 0 || !host.any())
-		return;
-	const size_t row_bytes = (size_t) visibilityWords(nt) * sizeof(uint32_t);
-	Staged p[VIS_PIECES] = { input(points4, (size_t) np * 16u), input(targets4, (size_t) nt * 16u), scratch(host.mask, (size_t) np * row_bytes),
-		                     output(host.count, (size_t) np * 4u) };
-	void *s = stageIn(p, VIS_PIECES);
-	VisibilityOutputs out;
-	out.mask = (uint32_t *) p[VIS_ROWS].device;
-	out.count = (uint32_t *) p[VIS_COUNTS].device;
-	instanceVisibilityDevice((const float *) p[VIS_POINTS].device, np, (const float *) p[VIS_TARGETS].device, nt, t_lo, t_hi, flags, out, s);
+	visibilityDevice((const float *) p[VIS_POINTS].device, np, (const float *) p[VIS_TARGETS].device, nt, t_lo, t_hi, flags, out, s, instanced);
 	stageOut(p, VIS_PIECES, s);
 }
 
@@ -520,14 +435,9 @@ void RayQueries::nearestHost(const float *points4, uint32_t n, float max_distanc
 	if (n == 0)
 		return;
 	// (the second piece stays empty: the points have no directions)
-	Staged p[RAY_PIECES] = { input(points4, (size_t) n * 16u), input(nullptr, 0u), output(host.hit, n) };
-	recordPieces(p + RAY_RECORDS, host, n);
-	void *s = stageIn(p, RAY_PIECES);
-	QueryOutputs out;
-	out.hit = (unsigned char *) p[RAY_FIRST].device;
-	recordDevice(p + RAY_RECORDS, out);
-	nearestDevice((const float *) p[RAY_ORIGINS].device, n, max_distance, flags, out, s);
-	stageOut(p, RAY_PIECES, s);
+	stagedRecords(points4, nullptr, n, true, host, nullptr, [&](const float *p4, const float *, const QueryOutputs &out, uint32_t *, void *s) {
+		nearestDevice(p4, n, max_distance, flags, out, s);
+	});
 }
 
 void RayQueries::setNearestWalk(uint32_t debug_flags) {
@@ -592,34 +502,32 @@ uint32_t RayQueries::aoRaysPerPoint(const DeviceRenderer &renderer) {
 uint32_t RayQueries::aoDivisor(const DeviceRenderer &renderer) { return aoRaysPerPoint(renderer) ? renderer.params().ao_divisor : 0u; }
 
 void RayQueries::aoDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
-                          uint32_t *occluded, void *stream) {
+                          uint32_t *occluded, void *stream, bool instanced) {
+	if (instanced)
+		requireInstances("instanced ambient-occlusion query");
 	requireAo();
 	if (n == 0 || (!ao && !occluded))
 		return;
+	const Target to = target(instanced);
 	const KernelParams &kp = dev.params();
 	// the POINTS are ordered (key: point and normal) from as many on as make RT_QUERY_SORT_MIN rays
 	const Enqueue q = begin(stream, points4, normals4, n, (uint64_t) n * kp.ao_dirs, flags,
-	                        { Need{ occluded ? nullptr : &ao_hits, (size_t) n * sizeof(uint32_t) } });
-	aoEnqueue(q, points4, normals4, seeds, q.order, n, occluded ? occluded : (uint32_t *) ao_hits.ptr, ao);
+	                        { Need{ occluded ? nullptr : &ao_hits, (size_t) n * sizeof(uint32_t) } }, false, to.box);
+	aoEnqueue(q, points4, normals4, seeds, q.order, n, occluded ? occluded : (uint32_t *) ao_hits.ptr, ao, instanced);
 	end(q);
 }
 
 void RayQueries::aoEnqueue(const Enqueue &q, const float *points4, const float *normals4, const uint32_t *seeds, const void *order,
                            uint32_t n, uint32_t *count, float *ao, bool instanced) {
 	const KernelParams &kp = dev.params();
-	if (instanced) {
-		const size_t rows = (size_t) instanceCount() * 12u * sizeof(float);
-		const char *set = (const char *) inst_device.ptr;
-		launch_instance_ao(dev.deviceScene()->buffers(), kp.node_count, set + 2u * rows, (uint32_t) inst_nodes.size(), set + rows, kp.ao_mode,
-		                   kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4, normals4, seeds, order, n, count, ao, q.stream);
-		return;
-	}
-	launch_ao_query(dev.deviceScene()->buffers(), kp.node_count, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4,
-	                normals4, seeds, order, n, count, ao, q.stream);
+	launch_ao_query(dev.deviceScene()->buffers(), kp.node_count, instanced ? &inst_set : nullptr, kp.ao_mode, kp.ao_dirs, kp.ao_divisor,
+	                kp.ao_max_distance, points4, normals4, seeds, order, n, count, ao, q.stream);
 }
 
 void RayQueries::aoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
-                        uint32_t *occluded) {
+                        uint32_t *occluded, bool instanced) {
+	if (instanced)
+		requireInstances("instanced ambient-occlusion query");
 	requireAo();
 	if (n == 0 || (!ao && !occluded))
 		return;
@@ -628,38 +536,7 @@ void RayQueries::aoHost(const float *points4, const float *normals4, const uint3
 		                    input(seeds, (size_t) n * 4u), output(ao, (size_t) n * 4u) };
 	void *s = stageIn(p, AO_PIECES);
 	aoDevice((const float *) p[AO_POINTS].device, (const float *) p[AO_NORMALS].device, (const uint32_t *) p[AO_SEEDS].device, n, flags,
-	         (float *) p[AO_VALUES].device, (uint32_t *) p[AO_COUNTS].device, s);
-	stageOut(p, AO_PIECES, s);
-}
-
-// ---- instanced ambient occlusion (include/rt_hip_instance_views.h) ----
-void RayQueries::instancesAoDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
-                                   uint32_t *occluded, void *stream) {
-	requireInstances("instanced ambient-occlusion query");
-	requireAo();
-	if (n == 0 || (!ao && !occluded))
-		return;
-	refreshInstances();
-	const KernelParams &kp = dev.params();
-	// aoDevice's sort of the POINTS, their cells over the top-level root box
-	const Enqueue q = begin(stream, points4, normals4, n, (uint64_t) n * kp.ao_dirs, flags,
-	                        { Need{ occluded ? nullptr : &ao_hits, (size_t) n * sizeof(uint32_t) } }, false, inst_box);
-	aoEnqueue(q, points4, normals4, seeds, q.order, n, occluded ? occluded : (uint32_t *) ao_hits.ptr, ao, true);
-	end(q);
-}
-
-void RayQueries::instancesAoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
-                                 uint32_t *occluded) {
-	requireInstances("instanced ambient-occlusion query");
-	requireAo();
-	if (n == 0 || (!ao && !occluded))
-		return;
-	// (the counts are staged whether they are copied back or not: the kernel counts into them)
-	Staged p[AO_PIECES] = { input(points4, (size_t) n * 16u), input(normals4, (size_t) n * 16u), scratch(occluded, (size_t) n * 4u),
-		                    input(seeds, (size_t) n * 4u), output(ao, (size_t) n * 4u) };
-	void *s = stageIn(p, AO_PIECES);
-	instancesAoDevice((const float *) p[AO_POINTS].device, (const float *) p[AO_NORMALS].device, (const uint32_t *) p[AO_SEEDS].device, n, flags,
-	                  (float *) p[AO_VALUES].device, (uint32_t *) p[AO_COUNTS].device, s);
+	         (float *) p[AO_VALUES].device, (uint32_t *) p[AO_COUNTS].device, s, instanced);
 	stageOut(p, AO_PIECES, s);
 }
 
@@ -783,15 +660,8 @@ uint32_t RayQueries::castChunk(const Enqueue &q, const ChunkScratch &at, bool li
 		list.listed = (uint32_t *) (base + at.listed);
 	}
 	// (without the ambient-occlusion step `value` is the head-light term itself)
-	if (instanced) {
-		const size_t rows = (size_t) instanceCount() * 12u * sizeof(float);
-		const char *set = (const char *) inst_device.ptr;
-		launch_instance_layers(dev.deviceScene()->buffers(), kp, set + 2u * rows, (uint32_t) inst_nodes.size(), set + rows, poses, views, to,
-		                       instance, with_ao ? nullptr : product, to.ao, product, with_ao ? &list : nullptr, s);
-	} else {
-		launch_layers(dev.deviceScene()->buffers(), kp, poses, dev.camera(), dev.cameraIsSet(), views, to, with_ao ? nullptr : product, to.ao,
-		              product, with_ao ? &list : nullptr, s);
-	}
+	launch_layers(dev.deviceScene()->buffers(), kp, instanced ? &inst_set : nullptr, poses, dev.camera(), dev.cameraIsSet(), views, to, instance,
+	              with_ao ? nullptr : product, to.ao, product, with_ao ? &list : nullptr, s);
 	if (!with_ao)
 		return 0u;
 	// the reference's ambient_occlusion(position, normal, index) in index order: of every sub-pixel -- seed i for point i --

@@ -28,12 +28,17 @@ class RayQueries {
 		RayQueries(const RayQueries &) = delete;
 		RayQueries &operator=(const RayQueries &) = delete;
 
+		// Rays, segments, visibility masks and ambient-occlusion points are cast against the uploaded scene or -- `instanced`
+		// -- in world space against the host's instance set (setInstances below; include/rt_hip_instances.h,
+		// rt_hip_instance_segments.h, rt_hip_instance_views.h): the family's own arguments and rules, the sort keyed over the
+		// top-level root box, `instance` (or null) beside a closest form's record.  std::logic_error without a set; its tree
+		// is made again first if the scene changed.
 		// Device memory, enqueued on `stream` (null: the renderer's); `closest` false: occlusion into out.hit alone.
 		void traceDevice(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
-		                 uint32_t flags, const QueryOutputs &out, void *stream);
+		                 uint32_t flags, const QueryOutputs &out, void *stream, bool instanced = false, uint32_t *instance = nullptr);
 		// Host memory, blocking: the rays go through the staging buffers on the renderer's stream.
 		void traceHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
-		               const QueryOutputs &out);
+		               const QueryOutputs &out, bool instanced = false, uint32_t *instance = nullptr);
 		// Multi-hit queries (include/rt_hip_multihit.h): the count of accepted triangles per ray and the first k of them.
 		// Device memory, enqueued on `stream` (null: the renderer's); k <= RT_MULTIHIT_MAX_K, 0 = the count alone.
 		void multihitDevice(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
@@ -55,10 +60,10 @@ class RayQueries {
 		// pass the slab test with max_distance = t_hi.  `closest` false: occlusion into out.hit alone.
 		// Device memory, enqueued on `stream` (null: the renderer's).
 		void segmentsDevice(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
-		                    const QueryOutputs &out, void *stream);
+		                    const QueryOutputs &out, void *stream, bool instanced = false, uint32_t *instance = nullptr);
 		// Host memory, blocking.
 		void segmentsHost(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
-		                  const QueryOutputs &out);
+		                  const QueryOutputs &out, bool instanced = false, uint32_t *instance = nullptr);
 		// The many-to-many form: np points against nt targets, bit j of point i's row (visibilityWords(nt) words) set where
 		// segment (i, j) is occluded, and the row's popcount.  Either output may be null.  No np x nt array is made.
 		struct VisibilityOutputs {
@@ -68,11 +73,11 @@ class RayQueries {
 		static uint32_t visibilityWords(uint32_t nt) { return (nt + 31u) / 32u; }
 		// Device memory, enqueued on `stream` (null: the renderer's).
 		void visibilityDevice(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
-		                      const VisibilityOutputs &out, void *stream);
+		                      const VisibilityOutputs &out, void *stream, bool instanced = false);
 		// Host memory, blocking.
 		void visibilityHost(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
-		                    const VisibilityOutputs &out);
-		// Instanced ray queries (include/rt_hip_instances.h).  The set -- transforms, inverses and the top-level tree over the
+		                    const VisibilityOutputs &out, bool instanced = false);
+		// The instance set (include/rt_hip_instances.h).  The set -- transforms, inverses and the top-level tree over the
 		// scene's root box (instances.h) -- is kept here and, as float4[3n] + float4[3n] + NodeRec[2n - 1], in device memory of
 		// this object's own; it outlives updates, builds and uploads, after which the tree is made again before its next use.
 		// std::invalid_argument for a refused transform or too many (the set stays what it was); n == 0 clears the set.
@@ -81,32 +86,8 @@ class RayQueries {
 		const std::vector<float> &instanceInverses() const { return inst_inverse; }
 		// the tree as it is on the device, 2n - 1 records (waits for the queries; std::logic_error before an upload or a set)
 		void instanceNodes(void *out);
-		// Device memory, enqueued on `stream` (null: the renderer's); `closest` false: occlusion into out.hit alone.
-		void instancesDevice(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
-		                     const QueryOutputs &out, uint32_t *instance, void *stream);
-		// Host memory, blocking.
-		void instancesHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
-		                   const QueryOutputs &out, uint32_t *instance);
-		// Instanced segment queries (include/rt_hip_instance_segments.h): segmentsDevice's and visibilityDevice's arguments
-		// and rules, the segments in world space against the instance set; the pair forms' sort is keyed over the top-level
-		// root box, as the mask form's sort of the points is; `instance` beside the closest form's record.  std::logic_error
-		// without a set.  The tree is made again first if the scene changed (refreshInstances).
-		void instanceSegmentsDevice(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
-		                            const QueryOutputs &out, uint32_t *instance, void *stream);
-		void instanceSegmentsHost(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
-		                          const QueryOutputs &out, uint32_t *instance);
-		void instanceVisibilityDevice(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
-		                              uint32_t flags, const VisibilityOutputs &out, void *stream);
-		void instanceVisibilityHost(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
-		                            const VisibilityOutputs &out);
-		// Instanced ambient occlusion and instanced views (include/rt_hip_instance_views.h).  aoDevice's and viewsDevice's
-		// arguments and rules, the rays cast against the instance set: points and normals in world space, the point sort
-		// keyed over the top-level root box; the views' records are instancesDevice's, `instance` [views][N] beside the layers.
-		// std::logic_error without a set.  The tree is made again first if the scene changed (refreshInstances).
-		void instancesAoDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
-		                       uint32_t *occluded, void *stream);
-		void instancesAoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
-		                     uint32_t *occluded);
+		// Instanced views (include/rt_hip_instance_views.h): viewsDevice's arguments and rules, the rays cast against the
+		// instance set; the records are the instanced ray queries', `instance` [views][N] beside the layers.
 		void instanceViewsDevice(const CameraPose *cameras, uint32_t views, const ViewOutputs &out, uint32_t *instance, void *stream);
 		void instanceViewsHost(const CameraPose *cameras, uint32_t views, const ViewOutputs &out, uint32_t *instance);
 		// Ambient-occlusion queries (include/rt_hip_ao.h): the reference's ambient_occlusion() of n points with the options
@@ -117,10 +98,10 @@ class RayQueries {
 		static uint32_t aoDivisor(const DeviceRenderer &renderer);
 		// Device memory, enqueued on `stream` (null: the renderer's); `seeds`, `ao`, `occluded` may be null.
 		void aoDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
-		              uint32_t *occluded, void *stream);
+		              uint32_t *occluded, void *stream, bool instanced = false);
 		// Host memory, blocking.
 		void aoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
-		            uint32_t *occluded);
+		            uint32_t *occluded, bool instanced = false);
 		// Directional occlusion queries (include/rt_hip_directional.h): the same rays, their hit flags a bit each in `mask`
 		// (aoMaskWords() words per point), the count and value made of a point's row, and the ordered sum of its open rays'
 		// directions.  Any output may be null; errors as for aoDevice.
@@ -226,6 +207,19 @@ class RayQueries {
 		};
 
 		void requireScene(const char *query) const;
+		// The way into a call of `query` that may run against the instance set: the scene and -- `instanced` -- the set, or
+		// std::logic_error; then, once the call knows that it has work, what it hands begin() and its launcher.
+		void requireQuery(bool instanced, const char *query) const;
+		struct Target {
+			const InstanceBuffers *set;  // null: the uploaded scene alone
+			const float *box;            // the sort's origin cells where they are not the scene's root box's, or null
+		};
+		Target target(bool instanced);
+		// The host-memory form of a family with two float4 inputs of n items (`b4` may be null), the hit flags and the five
+		// record arrays -- `records` false: the flags alone --, and `instance`: staged, run(a4, b4, out, instance, stream) on
+		// the device pointers, copied back.
+		template <class Run>
+		void stagedRecords(const float *a4, const float *b4, uint32_t n, bool records, const QueryOutputs &host, uint32_t *instance, Run &&run);
 		void requireSlots(uint32_t k) const;
 		void requireAo() const;
 		bool requireLayers(const LayerOutputs &out) const;  // true: the call needs the ambient-occlusion step
@@ -268,7 +262,7 @@ class RayQueries {
 		Scratch stage;         // the host-memory forms' inputs and outputs
 		Scratch ao_hits;       // aoDevice without an `occluded` array: the points' counts
 		Scratch ao_rows;       // directionalDevice without a `mask` array: the points' rows
-		Scratch vis_rows;      // visibilityDevice, instanceVisibilityDevice without a `mask` array: the points' rows
+		Scratch vis_rows;      // visibilityDevice without a `mask` array: the points' rows
 	Scratch list;          // multihitDevice: the rays' key lists, n * k * 8 bytes
 		Scratch views;         // layersDevice, viewsDevice (ChunkScratch): a chunk's poses, the points and normals of its
 		                       // ambient-occlusion step, the list of the hit ones (ViewList), its float images where the caller
@@ -298,13 +292,15 @@ class RayQueries {
 		bool nearest_counted = false;
 		std::weak_ptr<const DeviceScene> boxed;  // the scene box_lo / box_scale were read from
 		float box_lo[3] = { 0, 0, 0 }, box_scale[3] = { 0, 0, 0 };
-		// The instance set.  inst_device: the transforms, the inverses, the tree; inst_scene / inst_current: the scene whose
-		// root box the tree was made from, and whether that box still stands (an update or a build drops it, as it drops `boxed`).
+		// The instance set.  inst_device: the transforms, the inverses, the tree -- inst_set: where the last two lie in it --;
+		// inst_scene / inst_current: the scene whose root box the tree was made from, and whether that box still stands (an
+		// update or a build drops it, as it drops `boxed`).
 		void requireInstances(const char *what) const;
 		void refreshInstances();
 		std::vector<float> inst_world, inst_inverse;
 		std::vector<InstanceNode> inst_nodes;
 		Scratch inst_device;
+		InstanceBuffers inst_set = { nullptr, nullptr, 0u };
 		std::weak_ptr<const DeviceScene> inst_scene;
 		bool inst_current = false;
 		float inst_box[6] = { 0, 0, 0, 0, 0, 0 };  // the sort's origin cells over the top-level root box: lo, scale
@@ -313,43 +309,32 @@ class RayQueries {
 // kernels.hip
 void launch_query_sort(const void *origins, const void *directions, uint32_t n, const float lo[3], const float scale[3], void *count,
                        void *order, void *stream, bool segments = false);
-void launch_query(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *origins, const void *directions,
-                  const void *order, uint32_t n, float max_distance, const QueryOutputs &out, void *stream);
+// (`set`: null, or the instance set a family's rays are cast against; `instance`: its index beside a closest form's record)
+void launch_query(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, bool closest, const void *origins,
+                  const void *directions, const void *order, uint32_t n, float max_distance, const QueryOutputs &out, uint32_t *instance,
+                  void *stream);
 void launch_nearest_sort(const void *points, uint32_t n, const float lo[3], const float scale[3], void *count, void *order, void *stream);
 void launch_nearest(const SceneBuffers &scene, uint32_t node_count, uint32_t tri_count, const void *points, const void *order, uint32_t n,
                     float max_distance, uint32_t walk, const QueryOutputs &out, const void *coords_flag, void *counts, void *stream);
 void launch_nearest_coordinates(const void *vertices4, uint32_t num_vertices, void *flag, void *stream);
-void launch_segments(const SceneBuffers &scene, uint32_t node_count, bool closest, const void *from, const void *to, const void *order,
-                     uint32_t n, float t_lo, float t_hi, const QueryOutputs &out, void *stream);
-void launch_visibility(const SceneBuffers &scene, uint32_t node_count, const void *points, uint32_t np, const void *targets, uint32_t nt,
-                       const void *order, float t_lo, float t_hi, uint32_t *mask, uint32_t *count, void *stream);
-void launch_instances(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses, bool closest,
-                      const void *origins, const void *directions, const void *order, uint32_t n, float max_distance, const QueryOutputs &out,
-                      uint32_t *instance, void *stream);
-void launch_instance_segments(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses,
-                              bool closest, const void *from, const void *to, const void *order, uint32_t n, float t_lo, float t_hi,
-                              const QueryOutputs &out, uint32_t *instance, void *stream);
-void launch_instance_visibility(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses,
-                                const void *points, uint32_t np, const void *targets, uint32_t nt, const void *order, float t_lo, float t_hi,
-                                uint32_t *mask, uint32_t *count, void *stream);
+void launch_segments(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, bool closest, const void *from, const void *to,
+                     const void *order, uint32_t n, float t_lo, float t_hi, const QueryOutputs &out, uint32_t *instance, void *stream);
+void launch_visibility(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, const void *points, uint32_t np,
+                       const void *targets, uint32_t nt, const void *order, float t_lo, float t_hi, uint32_t *mask, uint32_t *count,
+                       void *stream);
 void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void *origins, const void *directions, const void *order,
                      uint32_t n, float max_distance, uint32_t k, void *list, const MultiHitOutputs &out, void *stream);
-void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
-                     float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
-                     uint32_t *count, float *ao, void *stream);
-void launch_instance_ao(const SceneBuffers &scene, uint32_t node_count, const void *top, uint32_t top_count, const void *inverses, int ao_mode,
-                        uint32_t rays_per_point, uint32_t divisor, float max_distance, const void *points, const void *normals,
-                        const uint32_t *seeds, const void *order, uint32_t n, uint32_t *count, float *ao, void *stream);
+void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, int ao_mode, uint32_t rays_per_point,
+                     uint32_t divisor, float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order,
+                     uint32_t n, uint32_t *count, float *ao, void *stream);
 void launch_ao_directional(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
                            float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
                            uint32_t *mask, uint32_t *occluded, float *ao, float *bent, void *stream);
 void launch_ao_rays(const SceneBuffers &scene, int ao_mode, uint32_t rays_per_point, const void *points, const void *normals,
                     const uint32_t *seeds, uint32_t n, void *origins, void *directions, void *stream);
-void launch_layers(const SceneBuffers &scene, const KernelParams &P, const void *poses, const CameraPose &pose, bool posed, uint32_t views,
-                   const LayerOutputs &out, float *value, float *ao, float *product, const ViewList *list, void *stream);
-void launch_instance_layers(const SceneBuffers &scene, const KernelParams &P, const void *top, uint32_t top_count, const void *inverses,
-                            const void *poses, uint32_t views, const LayerOutputs &out, uint32_t *instance, float *value, float *ao,
-                            float *product, const ViewList *list, void *stream);
+void launch_layers(const SceneBuffers &scene, const KernelParams &P, const InstanceBuffers *set, const void *poses, const CameraPose &pose,
+                   bool posed, uint32_t views, const LayerOutputs &out, uint32_t *instance, float *value, float *ao, float *product,
+                   const ViewList *list, void *stream);
 void launch_views_scatter(const ViewList &list, const uint32_t *count, uint32_t divisor, float *ao, float *product, uint32_t listed,
                           void *stream);
 void launch_views_resize(const float *value, unsigned char *image, const KernelParams &P, uint32_t out_width, uint32_t out_height,
