@@ -91,6 +91,16 @@ int rt_debug_set_tile_order(rt_host *h, const uint32_t *order, uint32_t slots, c
  * that ends a half-tile claim holds 15 bits).  A read-only copy: a test that means to exercise those claims asserts from
  * it that there were some. */
 int rt_debug_split_tiles(rt_host *h, uint32_t out[8]);
+/* The cheap suffix of the lists: the tiles at a group's END whose measured cost lies below `cheap_below` x the reference
+ * cost (the upper quartile) are claimed four whole tiles at a time, one per wave (orderByMeasuredCost's `cheap`).
+ * rt_debug_set_cheap_claims sets the boundary -- 0: no region, a huge value: every tile that is not split -- and makes the
+ * order again from the costs already held (nothing happens without measured costs).  rt_debug_cheap_tiles: per XCD group,
+ * how many tiles the region holds; all 0 without measured costs.  Results never depend on either.  The region travels with
+ * the list: rt_debug_measure_tile_costs without `reorder` keeps list, split prefix and region as they are (its measuring
+ * frames themselves always claim as if there were no region, so that a tile's cost keeps its meaning);
+ * rt_debug_set_tile_order installs the caller's list with neither. */
+int rt_debug_set_cheap_claims(rt_host *h, float cheap_below);
+int rt_debug_cheap_tiles(rt_host *h, uint32_t out[8]);
 
 /* What the closest-hit walk's pruning rests on in the uploaded scene (scene_pack.h, WalkArray): `prune_margin` (+inf: this
  * host does not prune -- a one-shot host, or a scene no prunable tree can be formed of), the bytes at the head of the primary

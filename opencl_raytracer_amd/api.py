@@ -216,6 +216,8 @@ _SIGNATURES = {
     "rt_debug_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_set_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rt_debug_split_tiles": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_debug_set_cheap_claims": (C.c_int, [C.c_void_p, C.c_float]),
+    "rt_debug_cheap_tiles": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_debug_prune_facts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_poison_hit_list": (C.c_int, [C.c_void_p]),
     "rt_debug_node_test_forms": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
@@ -903,6 +905,18 @@ class Host:
         (include/rt_hip_debug.h, rt_debug_split_tiles)."""
         out = np.zeros(8, np.uint32)
         _check(load_library().rt_debug_split_tiles(self._h, out.ctypes.data))
+        return out
+
+    def set_cheap_claims(self, cheap_below: float) -> None:
+        """The boundary of the lists' cheap suffix in reference costs (include/rt_hip_debug.h, rt_debug_set_cheap_claims):
+        0 turns the region off, a huge value puts every unsplit tile in it; re-orders if costs have been measured."""
+        _check(load_library().rt_debug_set_cheap_claims(self._h, float(cheap_below)))
+
+    def cheap_tiles(self) -> np.ndarray:
+        """Per XCD group, the tiles at the end of its list that the AO pass claims whole, one per wave
+        (include/rt_hip_debug.h, rt_debug_cheap_tiles)."""
+        out = np.zeros(8, np.uint32)
+        _check(load_library().rt_debug_cheap_tiles(self._h, out.ctypes.data))
         return out
 
     def prune_facts(self) -> dict:

@@ -626,15 +626,8 @@ int rt_debug_measure_tile_costs(rt_host *h, uint32_t frames, int reorder) {
 	if (!h)
 		return fail(RT_E_INVALID, "null argument");
 	return guarded([&] {
-		if (reorder) {
-			h->dev->measureTileCosts(frames);
-			return;
-		}
-		std::vector<uint32_t> order, constants, words;
-		std::vector<float> cost;
-		h->dev->tileOrder(order, constants, words, cost);
-		h->dev->measureTileCosts(frames);      // (measures and reorders ...)
-		h->dev->setTileOrder(order, constants);  // (... and the list that was in place goes back)
+		// (without `reorder` the list in place stays, and its split prefix and cheap suffix with it)
+		h->dev->measureTileCosts(frames, reorder != 0);
 	});
 }
 
@@ -701,6 +694,21 @@ int rt_debug_split_tiles(rt_host *h, uint32_t out[8]) {
 	return guarded([&] {
 		const auto &splits = h->dev->splitTiles();
 		std::copy(splits.begin(), splits.end(), out);
+	});
+}
+
+int rt_debug_set_cheap_claims(rt_host *h, float cheap_below) {
+	if (!h)
+		return fail(RT_E_INVALID, "null argument");
+	return guarded([&] { h->dev->setCheapClaims(cheap_below); });
+}
+
+int rt_debug_cheap_tiles(rt_host *h, uint32_t out[8]) {
+	if (!h || !out)
+		return fail(RT_E_INVALID, "null argument");
+	return guarded([&] {
+		const auto &cheap = h->dev->cheapTiles();
+		std::copy(cheap.begin(), cheap.end(), out);
 	});
 }
 

@@ -155,6 +155,8 @@ DeviceRenderer::DeviceRenderer(const RayTracer::Options &options, int device_, u
 #ifdef OCRT_DEBUG_KNOBS
 	if (const char *env = std::getenv("OCRT_AO_BLOCKS"))  // workgroups of the persistent ambient-occlusion pass
 		ao_blocks_override = (uint32_t) std::atoi(env);
+	if (const char *env = std::getenv("OCRT_CHEAP_BELOW"))  // the cheap suffix's boundary in reference costs (0: no region)
+		order_policy.cheap_below = (float) std::atof(env);
 	if (const char *env = std::getenv("OCRT_PRIMARY_BY_COST"))  // 0: the primary pass's workgroups take their blocks in spatial order
 		primary_by_cost = std::atoi(env) != 0;
 #endif
@@ -377,7 +379,7 @@ void DeviceRenderer::sizeHitList(const DeviceRenderer *layout_from) {
 		// ... and the order its tiles are claimed in by the ambient-occlusion pass
 		tile_words = layout_from->tile_words;
 		tile_cost = layout_from->tile_cost;
-		installOrder(layout_from->order_host, layout_from->queue_static, layout_from->split_tiles);
+		installOrder(layout_from->order_host, layout_from->queue_static, layout_from->split_tiles, layout_from->cheap_tiles);
 		d_hits = device_alloc((hit_slots ? hit_slots : 1) * sizeof(HitRec));
 		d_occluded = device_alloc((hit_slots ? hit_slots : 1) * sizeof(uint32_t));
 		clock.mark("hit list laid out like the ring's first host");

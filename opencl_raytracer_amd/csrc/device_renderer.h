@@ -247,6 +247,7 @@ class DeviceRenderer {
 		// and a frame ring -- which announces a stream -- also measures the tiles' costs and the form of the node loop.
 		// Callable before or after the upload (after: the hit list is laid out again if the answer changes).
 		static constexpr uint64_t FRAMES_WORTH_INTERVALS = 16;
+		static constexpr float CHEAP_BELOW_DEFAULT = 0.15f;  // (OrderPolicy::cheap_below; swept over 0 / 0.15 / 0.25 / 0.4: profiles/ao_cheap_claims_notes.md)
 		void expectFrames(uint64_t frames);
 		uint64_t expectedFrames() const { return expected_frames; }
 		bool walkIntervalsInUse() const { return intervals_in_use; }
@@ -254,7 +255,8 @@ class DeviceRenderer {
 		// (orderByMeasuredCost): `frames` frames one at a time (plain launches) whose AO pass books every claim's duration
 		// -- device clock, between the workgroup's barriers -- to the claim's tiles.  Once per upload, for callers that
 		// announce a stream of frames (a frame ring); returns false where there is nothing to measure.
-		bool measureTileCosts(unsigned frames = 2);
+		// `reorder` false: the costs are taken and the list in place stays as it is, its split prefix and cheap suffix with it.
+		bool measureTileCosts(unsigned frames = 2, bool reorder = true);
 		// ... and the order another renderer of the same frame (scene, options, partition) has arrived at
 		void takeOrderFrom(const DeviceRenderer &other);
 		bool orderIsMeasured() const { return tile_cost.size() == tile_count && tile_count != 0; }
@@ -271,6 +273,10 @@ class DeviceRenderer {
 		void setTileOrder(const std::vector<uint32_t> &order, const std::vector<uint32_t> &constants);
 		// (... per group: how many tiles at the head of its list the pass claims half a tile at a time)
 		const std::array<uint32_t, XCD_GROUPS> &splitTiles() const { return split_tiles; }
+		// (... and how many at its END are claimed four whole tiles at a time, one per wave: the cheap suffix)
+		const std::array<uint32_t, XCD_GROUPS> &cheapTiles() const { return cheap_tiles; }
+		// (test aid, include/rt_hip_debug.h: the suffix's boundary in reference costs -- 0: no region --; re-orders from the costs held)
+		void setCheapClaims(float cheap_below);
 		bool calibrateAoPrefetch(float *ms_without = nullptr, float *ms_with = nullptr);
 		// (A scene far beyond the caches is another matter: its pass waits for memory, and what it needs is loads in
 		// flight -- every host keeps the full grid: 2 M-triangle field, three hosts, 11.93 ms per frame with 4.5 per CU,
@@ -346,17 +352,19 @@ class DeviceRenderer {
 		void orderBlocksByCost();
 		void uploadBlocksByCost();
 		std::array<uint32_t, XCD_GROUPS> split_tiles{};  // per group: the tiles at the head of its list that are claimed half a tile at a time
+		std::array<uint32_t, XCD_GROUPS> cheap_tiles{};  // per group: the tiles at the end of its list that are claimed whole, one per wave
 		struct OrderPolicy {  // (orderByMeasuredCost; swept in profiles/r05_order_policies.txt)
 			float heavy = 2.0f;   // tiles beyond this many reference costs (the upper quartile) are claimed first
 			float runway = 2.0f;  // what is held back for the end, by falling cost: this many reference claims per workgroup
 			uint32_t primary_split_waves = 4096;  // ... unless those tiles, four waves each, are more than this many waves (half the chip's slots: then the slots are full anyway)
 			uint32_t primary_split_above = 64;  // primary pass: tiles of this cost class (leaves their packet stops at, 1 ... 64) or more are cast in quarters (0: none)
 			float split_above = 0.25f;  // tiles that cost more than this share of the pass's ideal length: half a tile per claim (0: none)
+			float cheap_below = CHEAP_BELOW_DEFAULT;  // tiles at the list's end below this many reference costs: a whole tile per wave and claim (0: none)
 		} order_policy;
 		void orderTiles();
-		std::vector<uint32_t> orderByMeasuredCost(const std::vector<float> &cost, uint32_t *split = nullptr) const;
+		std::vector<uint32_t> orderByMeasuredCost(const std::vector<float> &cost, uint32_t *split = nullptr, uint32_t *cheap = nullptr) const;
 		void installOrder(const std::vector<uint32_t> &order, const std::array<std::array<uint32_t, 3>, XCD_GROUPS> &constants,
-		                  const std::array<uint32_t, XCD_GROUPS> &splits = {});
+		                  const std::array<uint32_t, XCD_GROUPS> &splits = {}, const std::array<uint32_t, XCD_GROUPS> &cheap = {});
 		size_t image_bytes;  // float image of this rank's bands
 		size_t tile_count;
 		uint32_t compute_units;

@@ -73,7 +73,11 @@ struct alignas(128) GroupQueue {
 	// The first `split_units` units of the list -- its heaviest tiles, by measured cost -- are claimed HALF A TILE at a time
 	// from a cursor of their own (kernels/ao.hip.h; per upload; 0: none).  `head` starts at split_units.
 	uint32_t split_units;
-	uint32_t pad0[27];
+	// From unit `cheap_from` on -- the cheap suffix of the list, by measured cost (DeviceRenderer::orderByMeasuredCost) -- a
+	// claim is four whole tiles, one per wave (kernels/ao.hip.h; per upload like split_units, nothing resets it per frame).
+	// work_tiles x ao_dirs, the list's end, where there is no such region: a zero here would make every tile cheap.
+	uint32_t cheap_from;
+	uint32_t pad0[26];
 	// ... the cursor of the split tiles, claimed at the beginning of a frame, in a line of its own (`head` is hammered at its end)
 	uint32_t split_head;
 	uint32_t pad1[31];

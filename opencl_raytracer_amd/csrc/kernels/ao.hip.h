@@ -116,7 +116,7 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 				segment += ((strips + XCD_GROUPS - 1u - g) >> 3) * strip_tiles * rows;
 		}
 		// the group's work in units of (tile, table direction), tile-major
-		uint32_t units, claim_max, split_units;
+		uint32_t units, claim_max, split_units, cheap_from;
 		{
 		FrameCounters *const counters = OCRT_COLD_PTR(FrameCounters *, counters);
 		const uint32_t ao_dirs = OCRT_COLD_U32(P.ao_dirs);
@@ -126,11 +126,19 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 		// return is made scalar again by hand)
 		const uint32_t queued_tiles = (uint32_t) __builtin_amdgcn_readfirstlane((int) counters->queue[group].work_tiles);
 		units = queued_tiles * ao_dirs;
+		// (the list's cheap suffix, by measured cost: from this unit on a claim is four whole tiles -- below.  The list's end
+		// where there is none, and in a measuring frame, whose claims must be the ones the tiles' costs are defined by.)
+		cheap_from = (uint32_t) __builtin_amdgcn_readfirstlane((int) counters->queue[group].cheap_from);
+		cheap_from = OCRT_COLD_PTR(uint32_t *, tile_cost) ? units : cheap_from;
 		// A wave's largest claim.  A quarter of a tile's directions, so that the workgroup's four waves take ONE tile
 		// together (the best locality, and the finest balance); whole tiles per wave where packets are cheap and
-		// plentiful -- a tile's mean cost class (the leaves its primary packet stopped at) below 8 and 512 or more
-		// units per wave: 16+ samples per pixel -- because there the ~12 us of set-up per claim (hit records,
-		// tangent frames) weigh more than the locality.  Swept per workload: profiles/r02_notes.md.
+		// plentiful -- queue-wide: a tile's mean cost class (the leaves its primary packet stopped at) below 8 and 512
+		// or more units per wave: 16+ samples per pixel; per region of the list: the tiles behind `cheap_from`, which
+		// the upload measured to cost less than 0.15 of the reference tile -- because there the ~12 us of set-up
+		// per claim (hit records, tangent frames) weigh more than the locality.  Swept per workload:
+		// profiles/r02_notes.md; the region: profiles/ao_cheap_claims_notes.md.  BOTH rules stay: the region is the
+		// cheapest tiles RELATIVE to their list's upper quartile, the queue-wide rule says that the whole list is
+		// cheap per unit -- at 64 samples per pixel the region alone (this rule off) is 10 % slower, at 16 6 %.
 		claim_max = OCRT_COLD_U32(P.ao_claim_max);
 		if (claim_max == 0u) {
 			const uint32_t tiles = queued_tiles, cost = (uint32_t) __builtin_amdgcn_readfirstlane((int) counters->queue[group].cost_sum);
@@ -193,6 +201,14 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 					const uint32_t guide = OCRT_COLD_U32(P.ao_guide);
 					per_wave = guide ? (units - seen) / guide : claim_max;
 					per_wave = per_wave < 1u ? 1u : per_wave > claim_max ? claim_max : per_wave;
+					// The list's CHEAP SUFFIX (by measured cost, DeviceRenderer::orderByMeasuredCost): a head seen at or behind
+					// `cheap_from` is answered with four whole tiles, one per wave, in fixed shares.  Such a tile is seven short
+					// packets per wave behind a full claim and a set-up that four waves make for the same tile, and every
+					// workgroup ends the pass on a few of them in a row, where a claim's latency is the critical path.  Nothing
+					// depends on where a claim lands: the atomic partitions the units whatever the sizes, `seen` is only a hint,
+					// and a claim that straddles `cheap_from`, a tile's end or the list's is walked by the job loop like any
+					// other (a last claim that lies in one tile is dealt by the cursor, by that rule's own words).
+					per_wave = seen >= cheap_from ? OCRT_COLD_U32(P.ao_dirs) : per_wave;
 					uint32_t got = 0u;
 					if (fresh_lane() == 0u)
 						got = atomicAdd(&counters->queue[group].head, per_wave * AO_WAVES);

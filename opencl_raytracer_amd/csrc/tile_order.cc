@@ -24,7 +24,7 @@ void DeviceRenderer::orderTiles() {
 	const size_t order_slots = (size_t) ((tiles_x + MAX_STRIP_TILES - 1) / MAX_STRIP_TILES) * MAX_STRIP_TILES * rows;
 	std::vector<uint32_t> order(order_slots ? order_slots : 1, 0u);
 	std::array<std::array<uint32_t, 3>, XCD_GROUPS> constants{};
-	std::array<uint32_t, XCD_GROUPS> splits{};
+	std::array<uint32_t, XCD_GROUPS> splits{}, cheap{};
 	const bool measured = tile_cost.size() == tile_count;
 	size_t segment = 0;
 	for (uint32_t group = 0; group < XCD_GROUPS; ++group) {
@@ -62,10 +62,11 @@ void DeviceRenderer::orderTiles() {
 			std::vector<float> cost(candidates.size());
 			for (size_t i = 0; i < candidates.size(); ++i)
 				cost[i] = tile_cost[elements[candidates[i]].tile];
-			uint32_t split = 0;
-			for (uint32_t at : orderByMeasuredCost(cost, &split))
+			uint32_t split = 0, cheap_here = 0;
+			for (uint32_t at : orderByMeasuredCost(cost, &split, &cheap_here))
 				listed.push_back(candidates[at]);
 			splits[group] = split;
+			cheap[group] = cheap_here;
 		} else {
 			const uint32_t n_blocks = (tiles_here + 63u) >> 6;
 			std::vector<std::pair<uint32_t, uint32_t>> blocks;  // (key, block), stable by block
@@ -89,7 +90,7 @@ void DeviceRenderer::orderTiles() {
 		constants[group] = { work, cost_total, hit_total };
 		segment += tiles_here;
 	}
-	installOrder(order, constants, splits);
+	installOrder(order, constants, splits, cheap);
 }
 
 // Claim order of one group's tiles from their MEASURED costs (device-clock ticks a tile's claims kept their workgroups
@@ -106,12 +107,24 @@ void DeviceRenderer::orderTiles() {
 //      (kernels/ao.hip.h): those whose cost exceeds `split_above` x the pass's ideal length (the group's total cost over its
 //      workgroups).  A tile that keeps a workgroup for a quarter of the pass decides when the pass ends -- at 600 x 600 -s 4
 //      the costliest tile takes as long as the whole pass should, and so it does in one GPU's share of a frame split eight ways.
-std::vector<uint32_t> DeviceRenderer::orderByMeasuredCost(const std::vector<float> &cost, uint32_t *split) const {
+//   5. `*cheap` (out): how many tiles at the END of the list -- behind the split ones -- cost less than `cheap_below` x the
+//      reference: the cheap suffix, claimed FOUR WHOLE TILES at a time, one per wave (kernels/ao.hip.h).  Such a tile is
+//      seven short packets per wave behind a claim (a returning atomic, two barriers) and a set-up that each of the four waves
+//      makes for the same tile: it costs little more than that, and every workgroup ends the pass on a few of them in a row.
+//      The suffix stands in SPATIAL order, not by falling cost: its costs are equal within what the measurement resolves, and
+//      the four tiles of a claim are then neighbours (adjacent hit records, the same top of the tree).  The boundary is
+//      BELOW rule 3's quarter (0.15: the headline frame's ground-plane tiles, 36 % of its tiles and 6.6 % of their cost): the
+//      tiles between the two are fewer and less alike, and stay in the runway, by falling cost, in front of the suffix
+//      (0.15 and 0.2 are alike; with the suffix up to the quarter the headline frame is 1 ... 2 % longer than with 0.15, up
+//      to 0.4 it is 5 % longer than without the rule: profiles/ao_cheap_claims_notes.md).
+std::vector<uint32_t> DeviceRenderer::orderByMeasuredCost(const std::vector<float> &cost, uint32_t *split, uint32_t *cheap) const {
 	const size_t n = cost.size();
 	std::vector<uint32_t> out;
 	out.reserve(n);
 	if (split)
 		*split = 0;
+	if (cheap)
+		*cheap = 0;
 	if (n == 0)
 		return out;
 	std::vector<float> sorted(cost);
@@ -156,6 +169,14 @@ std::vector<uint32_t> DeviceRenderer::orderByMeasuredCost(const std::vector<floa
 	out.insert(out.end(), heavy.begin(), heavy.end());
 	out.insert(out.end(), spatial.begin(), spatial.end());
 	out.insert(out.end(), runway.begin(), runway.end());
+	if (cheap && order_policy.cheap_below > 0.0f) {
+		const size_t keep = split ? *split : 0u;
+		size_t from = n;
+		while (from > keep && cost[out[from - 1]] < (double) order_policy.cheap_below * reference)
+			--from;
+		*cheap = (uint32_t) (n - from);
+		std::sort(out.begin() + from, out.end());
+	}
 	return out;
 }
 
@@ -261,10 +282,11 @@ void DeviceRenderer::setPrimarySplit(uint32_t above) {
 
 
 void DeviceRenderer::installOrder(const std::vector<uint32_t> &order, const std::array<std::array<uint32_t, 3>, XCD_GROUPS> &constants,
-                                  const std::array<uint32_t, XCD_GROUPS> &splits) {
+                                  const std::array<uint32_t, XCD_GROUPS> &splits, const std::array<uint32_t, XCD_GROUPS> &cheap) {
 	order_host = order;
 	queue_static = constants;
 	split_tiles = splits;
+	cheap_tiles = cheap;
 	OCRT_HIP(hipStreamSynchronize((hipStream_t) stream));
 	OCRT_HIP(hipMemcpy(d_order, order_host.data(), order_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
 	orderBlocksByCost();
@@ -276,6 +298,10 @@ void DeviceRenderer::installOrder(const std::vector<uint32_t> &order, const std:
 		fresh.queue[g].hits = constants[g][2];
 		fresh.queue[g].split_units = std::min(split_tiles[g], constants[g][0]) * kp.ao_dirs;
 		fresh.queue[g].head = fresh.queue[g].split_units;
+		// (the cheap suffix begins behind the split prefix at the earliest; no suffix: the list's end)
+		const uint32_t split_here = std::min(split_tiles[g], constants[g][0]);
+		cheap_tiles[g] = std::min(cheap_tiles[g], constants[g][0] - split_here);
+		fresh.queue[g].cheap_from = (constants[g][0] - cheap_tiles[g]) * kp.ao_dirs;
 	}
 	OCRT_HIP(hipMemcpy(d_counters, &fresh, sizeof fresh, hipMemcpyHostToDevice));
 	OCRT_HIP(hipStreamSynchronize((hipStream_t) stream));
@@ -286,7 +312,7 @@ void DeviceRenderer::installOrder(const std::vector<uint32_t> &order, const std:
 #ifdef OCRT_PRIMARY_TICKS
 extern void *primary_ticks_probe;  // (kernels.hip)
 #endif
-bool DeviceRenderer::measureTileCosts(unsigned frames) {
+bool DeviceRenderer::measureTileCosts(unsigned frames, bool reorder) {
 	if (!scene_ready)
 		throw std::logic_error("measurement before upload");
 	requireFramePath("measurement");
@@ -320,7 +346,8 @@ bool DeviceRenderer::measureTileCosts(unsigned frames) {
 	}
 	device_free(d_cost);
 	tile_cost = std::move(sum);
-	orderTiles();
+	if (reorder)
+		orderTiles();
 	frame_ready = false;
 	return true;
 }
@@ -332,7 +359,7 @@ void DeviceRenderer::takeOrderFrom(const DeviceRenderer &other) {
 	synchronize();
 	tile_words = other.tile_words;
 	tile_cost = other.tile_cost;
-	installOrder(other.order_host, other.queue_static, other.split_tiles);
+	installOrder(other.order_host, other.queue_static, other.split_tiles, other.cheap_tiles);
 }
 
 void DeviceRenderer::tileOrder(std::vector<uint32_t> &order, std::vector<uint32_t> &constants, std::vector<uint32_t> &words, std::vector<float> &cost) const {
@@ -361,7 +388,18 @@ void DeviceRenderer::setTileOrder(const std::vector<uint32_t> &order, const std:
 	}
 	useDevice();
 	synchronize();
-	installOrder(order, c);
+	// (a list made elsewhere: neither the split prefix nor the cheap suffix of the list it replaces says anything about it)
+	installOrder(order, c, {}, {});
+}
+
+void DeviceRenderer::setCheapClaims(float cheap_below) {
+	order_policy.cheap_below = cheap_below > 0.0f ? cheap_below : 0.0f;
+	if (scene_ready && orderIsMeasured()) {
+		useDevice();
+		synchronize();
+		orderTiles();
+		frame_ready = false;
+	}
 }
 
 void DeviceRenderer::setOrderPolicy(float heavy, float runway, float split_above) {
