@@ -7,7 +7,8 @@
  * ambient occlusion, segments, multi-hit and closest-point queries -- ignores the set: nothing they compute changes when
  * one is given.  Ambient occlusion, views and segments have instanced forms of their own, defined by the rules below:
  * rt_trace_instances_ao and rt_render_instance_views (rt_hip_instance_views.h), and rt_instances_segments_occluded,
- * rt_instances_segments_closest and rt_instances_visibility_masks (rt_hip_instance_segments.h).  Multi-hit, closest-point and
+ * rt_instances_segments_closest and rt_instances_visibility_masks (rt_hip_instance_segments.h).  Closest-point queries have
+ * one with rules of its own, in world space: rt_instances_closest_points (rt_hip_instance_nearest.h).  Multi-hit and
  * directional occlusion queries have none.
  *
  * Transforms.  world_from_object is twelve floats per instance, the rows of W = [A | t]: p_world = A p + t.  Every entry

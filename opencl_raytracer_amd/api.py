@@ -271,6 +271,8 @@ _SIGNATURES = {
     # include/rt_hip_nearest.h
     "rt_closest_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
     "rt_closest_points_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_instances_closest_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
+    "rt_instances_closest_points_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_debug_set_nearest_walk": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rt_debug_last_nearest_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     # include/rt_hip_multihit.h
@@ -1149,8 +1151,26 @@ class Host:
                 C.byref(_HitArrays(*io.pointers(out, NEAREST_OUTPUTS))))
         return out
 
+    # ---- instanced closest-point queries (include/rt_hip_instance_nearest.h) ----
+    def instances_closest_points(self, points, max_distance: float = float("inf"), outputs=INSTANCE_OUTPUTS, sort: bool = True) -> dict:
+        """The nearest point of the surface among the posed copies of the scene (set_instances) for every WORLD-space point:
+        the record of closest_points in world space -- distance, position, normal; leaf and barycentrics of the copy's
+        triangle -- and "instance", the copy (those named in `outputs`); without one: +inf, 0xFFFFFFFF, zeros.  Inputs and
+        the numpy / torch forms as for closest_points."""
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in INSTANCE_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {INSTANCE_OUTPUTS}")
+        io = _QueryArrays(points, None, ("points",), "points")
+        out = io.outputs(outputs)
+        at = io.pointers(out, INSTANCE_OUTPUTS)
+        io.call(self._h, "rt_instances_closest_points", io.n, float(max_distance), 0 if sort else RT_QUERY_NO_SORT,
+                C.byref(_InstanceHitArrays(_HitArrays(*at[:-1]), at[-1])))
+        return out
+
     def set_nearest_walk(self, no_start: bool = False, no_prune: bool = False, count: bool = False) -> None:
-        """(rt_debug_set_nearest_walk) How later closest_points calls walk; anything but the default needs the A/B build."""
+        """(rt_debug_set_nearest_walk) How later closest_points and instances_closest_points calls walk; anything but the
+        default needs the A/B build."""
         _check(load_library().rt_debug_set_nearest_walk(self._h, (1 if no_start else 0) | (2 if no_prune else 0) | (4 if count else 0)))
 
     def last_nearest_counts(self) -> tuple:

@@ -11,6 +11,7 @@
 #include "../../include/rt_hip_nearest.h"
 #include "../../include/rt_hip_query.h"
 #include "../../include/rt_hip_segment.h"
+#include "../../include/rt_hip_instance_nearest.h"
 #include "../../include/rt_hip_instance_segments.h"
 #include "../../include/rt_hip_instance_views.h"
 #include "../../include/rt_hip_instances.h"
@@ -118,6 +119,8 @@ constexpr Family SEGMENTS = { "segment", "segments", "null point arrays", "devic
 constexpr Family INSTANCED_SEGMENTS = { "instanced segment", "segments", "null point arrays", "device point arrays must be 16-byte aligned",
 	                                    true };
 constexpr Family POINTS = { "closest-point", "points", "null point array", "the device point array must be 16-byte aligned", false };
+constexpr Family INSTANCED_POINTS = { "instanced closest-point", "points", "null point array",
+	                                  "the device point array must be 16-byte aligned", true };
 
 // What these families check before they touch the device ("Errors" of include/rt_hip_query.h, rt_hip_segment.h,
 // rt_hip_nearest.h, rt_hip_instances.h, rt_hip_instance_segments.h), in this order: the host, the set, the count -- `items`
@@ -1240,6 +1243,29 @@ int rt_closest_points_device(rt_host *h, const float *points4, uint32_t n, float
 	if (!records_aligned(q))
 		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
 	return guarded([&] { queries_of(h).nearestDevice(points4, n, max_distance, flags, q, hip_stream); });
+}
+
+// ---- rt_hip_instance_nearest.h ----
+int rt_instances_closest_points(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags,
+                                const rt_instance_hit_arrays *out) {
+	const int rc = query_precheck(h, INSTANCED_POINTS, points4, points4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	return guarded([&] {
+		queries_of(h).nearestHost(points4, n, max_distance, flags, hit_outputs(out ? &out->record : nullptr), true, out ? out->instance : nullptr);
+	});
+}
+
+int rt_instances_closest_points_device(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags,
+                                       const rt_instance_hit_arrays *out, void *hip_stream) {
+	const int rc = query_precheck(h, INSTANCED_POINTS, points4, points4, n, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	const ocrt::QueryOutputs q = hit_outputs(out ? &out->record : nullptr);
+	uint32_t *const instance = out ? out->instance : nullptr;
+	if (!records_aligned(q) || !aligned({ instance }, 4))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).nearestDevice(points4, n, max_distance, flags, q, hip_stream, true, instance); });
 }
 
 int rt_debug_set_nearest_walk(rt_host *h, uint32_t flags) {

@@ -183,6 +183,8 @@ struct InstanceBuffers {
 	const void *top;       // the top-level tree: NodeRec[top_count], `leaf` the instance index
 	const void *inverses;  // object_from_world, three float4 rows per instance
 	uint32_t top_count;    // 2 * instances - 1
+	const void *world = nullptr;   // world_from_object as the caller gave it, three float4 rows per instance
+	const void *bounds = nullptr;  // inp_bounds (instance_nearest.h), one float4 per instance: the closest-point walk's alone
 };
 
 // What the launches of a device-side build work on (kernels/build.hip.h, BuildArgs: every array's size is given there).

@@ -182,7 +182,114 @@ void split(const std::vector<InstanceNode> &leaves, std::vector<uint32_t> &order
 	node.leaf = INSTANCE_INNER;
 }
 
+// An upper bound of the largest eigenvalue of the symmetric S, and a lower bound of the smallest (not below 0): cyclic Jacobi
+// sweeps, then Gershgorin's discs of what is left -- exact for the matrix the sweeps arrived at, whose spectrum is S's but
+// for the rotations' roundings (a few 2^-53 of the largest entry per rotation: the 2^-40 below).
+void eigen_bounds(double S[3][3], double &largest, double &smallest) {
+	double peak = 0.0;
+	for (int i = 0; i < 3; ++i)
+		for (int j = 0; j < 3; ++j)
+			peak = std::max(peak, std::fabs(S[i][j]));
+	for (int sweep = 0; sweep < 8; ++sweep)
+		for (int p = 0; p < 2; ++p)
+			for (int q = p + 1; q < 3; ++q) {
+				if (S[p][q] == 0.0)
+					continue;
+				const double theta = (S[q][q] - S[p][p]) / (2.0 * S[p][q]);
+				const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+				const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+				for (int k = 0; k < 3; ++k) {  // S <- S J
+					const double kp = S[k][p], kq = S[k][q];
+					S[k][p] = c * kp - s * kq;
+					S[k][q] = s * kp + c * kq;
+				}
+				for (int k = 0; k < 3; ++k) {  // S <- J^T S
+					const double pk = S[p][k], qk = S[q][k];
+					S[p][k] = c * pk - s * qk;
+					S[q][k] = s * pk + c * qk;
+				}
+			}
+	largest = -std::numeric_limits<double>::infinity();
+	smallest = std::numeric_limits<double>::infinity();
+	for (int i = 0; i < 3; ++i) {
+		double off = 0.0;
+		for (int j = 0; j < 3; ++j)
+			if (j != i)
+				off += 0.5 * (std::fabs(S[i][j]) + std::fabs(S[j][i]));
+		largest = std::max(largest, S[i][i] + off);
+		smallest = std::min(smallest, S[i][i] - off);
+	}
+	largest += peak * 0x1.0p-40;
+	smallest = std::max(0.0, smallest - peak * 0x1.0p-40);
+}
+
+float rounded_down(double v) {  // a binary32 number <= v, not below 0
+	const float f = (float) v;
+	return v > 0.0 && f > 0.0f ? std::nextafterf(f, 0.0f) : 0.0f;
+}
+
+// inp_bounds of one instance (instance_nearest.h has the proof these figures serve).
+void instance_bound(const float root_lo[3], const float root_hi[3], const float W[12], const float O[12], float out[4]) {
+	double R[3];  // the root box's largest coordinate per axis
+	bool finite = true;
+	for (int j = 0; j < 3; ++j) {
+		finite = finite && std::isfinite(root_lo[j]) && std::isfinite(root_hi[j]);
+		R[j] = std::max(std::fabs((double) root_lo[j]), std::fabs((double) root_hi[j]));
+	}
+	// scale: min(sigma_min(A), 1 / |N|_2), from the eigenvalues of A^T A and N^T N
+	double AtA[3][3], NtN[3][3];
+	for (int i = 0; i < 3; ++i)
+		for (int j = 0; j < 3; ++j) {
+			AtA[i][j] = NtN[i][j] = 0.0;
+			for (int k = 0; k < 3; ++k) {
+				AtA[i][j] += (double) W[4 * k + i] * W[4 * k + j];
+				NtN[i][j] += (double) O[4 * k + i] * O[4 * k + j];
+			}
+		}
+	double a_hi, a_lo, n_hi, n_lo;
+	eigen_bounds(AtA, a_hi, a_lo);
+	eigen_bounds(NtN, n_hi, n_lo);
+	const double sigma = std::sqrt(a_lo) * (1.0 - 0x1.0p-40), by_inverse = n_hi > 0.0 ? (1.0 - 0x1.0p-40) / std::sqrt(n_hi) : 0.0;
+	out[0] = finite ? rounded_down(std::min(sigma, by_inverse)) : 0.0f;
+	// the object point's slack: the roundings of fl(O q) (16u, 6.95u needed), |E x| over the root box, |m + N t|
+	double per_q = 0.0, offset = 0.0, e1 = 0.0, e2 = 0.0;
+	for (int i = 0; i < 3; ++i) {
+		per_q = std::max(per_q, std::fabs((double) O[4 * i]) + std::fabs((double) O[4 * i + 1]) + std::fabs((double) O[4 * i + 2]));
+		offset = std::max(offset, std::fabs((double) O[4 * i + 3]));
+		double row = 0.0;  // sum_j |E_ij| R_j, the binary64 evaluation's own error (2^-50 of the absolute sums) included
+		for (int j = 0; j < 3; ++j) {
+			double e = i == j ? -1.0 : 0.0, mass = i == j ? 1.0 : 0.0;
+			for (int l = 0; l < 3; ++l) {
+				e += (double) O[4 * i + l] * W[4 * l + j];
+				mass += std::fabs((double) O[4 * i + l] * W[4 * l + j]);
+			}
+			row += (std::fabs(e) + mass * 0x1.0p-50) * R[j];
+		}
+		e1 += row * row;
+		double r = O[4 * i + 3], mass = std::fabs(r);  // (m + N t)_i
+		for (int l = 0; l < 3; ++l) {
+			r += (double) O[4 * i + l] * W[4 * l + 3];
+			mass += std::fabs((double) O[4 * i + l] * W[4 * l + 3]);
+		}
+		r = std::fabs(r) + mass * 0x1.0p-50;
+		e2 += r * r;
+	}
+	out[1] = outward_up(per_q * 0x1.0p-20);
+	out[2] = outward_up(offset * 0x1.0p-20 + (std::sqrt(e1) + std::sqrt(e2)) * (1.0 + 0x1.0p-40));
+	// the world triangle's rounding: 32u S (21u needed), S the instance's reach
+	out[3] = outward_up(instance_reach(root_lo, root_hi, W) * 0x1.0p-19);
+	for (int k = 1; k < 4; ++k)
+		if (!finite || !std::isfinite(out[k]))
+			out[0] = 0.0f;  // (nothing is passed by)
+}
+
 }  // namespace
+
+void instance_bounds(const float root_lo[3], const float root_hi[3], const float *W, const float *O, uint32_t n, std::vector<float> &bounds) {
+	bounds.assign((size_t) n * 4u, 0.0f);
+	for (uint32_t k = 0; k < n; ++k)
+		instance_bound(root_lo, root_hi, W + 12u * (size_t) k, O + 12u * (size_t) k, bounds.data() + 4u * (size_t) k);
+}
 
 void instance_tree(const float root_lo[3], const float root_hi[3], const float *W, const float *O, uint32_t n, std::vector<InstanceNode> &nodes) {
 	std::vector<InstanceNode> leaves(n);

@@ -21,6 +21,10 @@ constexpr uint32_t INSTANCE_INNER = 0xFFFFFFFFu;
 bool instance_inverse(const float W[12], float O[12]);
 // Every transform of the set, or none: false, and `O` untouched, where one is refused.  O: n * 12 floats.
 bool instance_inverses(const float *W, uint32_t n, std::vector<float> &O);
+// What the instanced closest-point walk holds a copy's object-space boxes against (instance_nearest.h, inp_bounds: scale,
+// per_q, fixed, world), four floats per instance, from the transforms, their binary32 inverses and the scene's root box; made
+// in binary64 and rounded in the safe direction.  A root box that is not finite gives scale 0: nothing is passed by.
+void instance_bounds(const float root_lo[3], const float root_hi[3], const float *W, const float *O, uint32_t n, std::vector<float> &bounds);
 // The tree over n >= 1 accepted transforms and their inverses: 2n - 1 records in pre-order.
 void instance_tree(const float root_lo[3], const float root_hi[3], const float *W, const float *O, uint32_t n, std::vector<InstanceNode> &nodes);
 

@@ -38,7 +38,9 @@
 //                   multihit_walk_kernel<K> counts every triangle a caller-supplied ray's walk accepts and keeps the first K,
 //                   multihit_resolve_kernel writes their records (kernels/multihit.hip.h, include/rt_hip_multihit.h).
 //                   nearest_key_kernel / nearest_scatter_kernel order caller-supplied POINTS by position, nearest_kernel finds
-//                   the nearest point of the surface for each (kernels/nearest.hip.h, include/rt_hip_nearest.h).
+//                   the nearest point of the surface for each (kernels/nearest.hip.h, include/rt_hip_nearest.h);
+//                   instance_nearest_kernel finds it among the posed copies of an instance set, measured in world space
+//                   (kernels/instance_nearest.hip.h, include/rt_hip_instance_nearest.h).
 //                   segment_kernel<CLOSEST> answers whether the line between two caller-supplied points is free, or where it is
 //                   blocked first (segment_key_kernel / segment_scatter_kernel order the segments), visibility_mask_kernel
 //                   does so for P points against T targets, a bit per pair, visibility_count_kernel counts a point's bits
@@ -93,6 +95,7 @@
 #include "exact_reciprocal.h"
 #include "lbvh.h"
 #include "nearest_point.h"
+#include "instance_nearest.h"
 #include "tri_predicate.h"
 
 #include "kernels/common.hip.h"
@@ -115,6 +118,7 @@
 #include "kernels/instances.hip.h"
 #include "kernels/instance_views.hip.h"
 #include "kernels/instance_segments.hip.h"
+#include "kernels/instance_nearest.hip.h"
 
 
 namespace ocrt {
@@ -449,12 +453,10 @@ void launch_nearest_coordinates(const void *vertices4, uint32_t num_vertices, vo
 
 // `walk`: NEAREST_START | NEAREST_PRUNE as far as the scene allows them (ray_query.cc); `coords_flag`: that word, or null:
 // the host has seen the scene's coordinates; `counts`: two 64-bit words on the device, zeroed here on the stream, for the
-// counted form -- or null: the product's form.
-void launch_nearest(const SceneBuffers &scene, uint32_t node_count, uint32_t tri_count, const void *points, const void *order, uint32_t n,
-                    float max_distance, uint32_t walk, const QueryOutputs &out, const void *coords_flag, void *counts, void *stream) {
-	if (n == 0)
-		return;
-	NearestArgs a{};
+// counted form -- or null: the product's form.  `set`: null, or the instance set the points are held against
+// (kernels/instance_nearest.hip.h), `instance` beside the record.
+static void fill(NearestArgs &a, const SceneBuffers &scene, uint32_t node_count, uint32_t tri_count, const void *points, const void *order,
+                 uint32_t n, float max_distance, uint32_t walk, const QueryOutputs &out, const void *coords_flag, void *counts) {
 	a.coords_flag = (const uint32_t *) coords_flag;
 	a.nodes_ptr = (const float4 *) scene.nodes;
 	a.tris_ptr = (const float4 *) scene.tris;
@@ -469,9 +471,32 @@ void launch_nearest(const SceneBuffers &scene, uint32_t node_count, uint32_t tri
 	a.out = out;
 	a.hit = out.hit;
 	a.counts = (unsigned long long *) counts;
+}
+
+void launch_nearest(const SceneBuffers &scene, uint32_t node_count, uint32_t tri_count, const InstanceBuffers *set, const void *points,
+                    const void *order, uint32_t n, float max_distance, uint32_t walk, const QueryOutputs &out, uint32_t *instance,
+                    const void *coords_flag, void *counts, void *stream) {
+	if (n == 0 || (set && set->top_count == 0))
+		return;
 	const uint32_t blocks = (n + 64u * NEAREST_WAVES - 1u) / (64u * NEAREST_WAVES);
-	if (counts) {
+	if (counts)
 		(void) hipMemsetAsync(counts, 0, 2u * sizeof(unsigned long long), (hipStream_t) stream);
+	if (set) {
+		InstanceNearestArgs a{};
+		fill(a, scene, node_count, tri_count, points, order, n, max_distance, walk, out, coords_flag, counts);
+		a.set = instance_set(*set);
+		a.world = (const float4 *) set->world;
+		a.bounds = (const float4 *) set->bounds;
+		a.instance = instance;
+		if (counts)
+			hipLaunchKernelGGL(instance_nearest_kernel<true>, dim3(blocks), dim3(64 * NEAREST_WAVES), 0, (hipStream_t) stream, a);
+		else
+			hipLaunchKernelGGL(instance_nearest_kernel<false>, dim3(blocks), dim3(64 * NEAREST_WAVES), 0, (hipStream_t) stream, a);
+		return;
+	}
+	NearestArgs a{};
+	fill(a, scene, node_count, tri_count, points, order, n, max_distance, walk, out, coords_flag, counts);
+	if (counts) {
 		hipLaunchKernelGGL(nearest_kernel<true>, dim3(blocks), dim3(64 * NEAREST_WAVES), 0, (hipStream_t) stream, a);
 	} else {
 		hipLaunchKernelGGL(nearest_kernel<false>, dim3(blocks), dim3(64 * NEAREST_WAVES), 0, (hipStream_t) stream, a);

@@ -326,13 +326,17 @@ void RayQueries::refreshInstances() {
 		OCRT_HIP(hipMemcpy(&root, current->buffers().nodes, sizeof root, hipMemcpyDeviceToHost));
 	const uint32_t n = instanceCount();
 	instance_tree(root.lo, root.hi, inst_world.data(), inst_inverse.data(), n, inst_nodes);
+	std::vector<float> bounds;  // (the closest-point walk's: instance_nearest.h)
+	instance_bounds(root.lo, root.hi, inst_world.data(), inst_inverse.data(), n, bounds);
 	const size_t rows = (size_t) n * 12u * sizeof(float), tree = inst_nodes.size() * sizeof(InstanceNode);
-	grow(inst_device, 2u * rows + tree);
+	const size_t bound_bytes = bounds.size() * sizeof(float);
+	grow(inst_device, 2u * rows + tree + bound_bytes);
 	char *at = (char *) inst_device.ptr;
 	OCRT_HIP(hipMemcpy(at, inst_world.data(), rows, hipMemcpyHostToDevice));
 	OCRT_HIP(hipMemcpy(at + rows, inst_inverse.data(), rows, hipMemcpyHostToDevice));
 	OCRT_HIP(hipMemcpy(at + 2u * rows, inst_nodes.data(), tree, hipMemcpyHostToDevice));
-	inst_set = InstanceBuffers{ at + 2u * rows, at + rows, (uint32_t) inst_nodes.size() };
+	OCRT_HIP(hipMemcpy(at + 2u * rows + tree, bounds.data(), bound_bytes, hipMemcpyHostToDevice));
+	inst_set = InstanceBuffers{ at + 2u * rows, at + rows, (uint32_t) inst_nodes.size(), at, at + 2u * rows + tree };
 	for (int k = 0; k < 3; ++k) {  // (sceneBox's rule, on the top-level root)
 		const float lo = inst_nodes[0].lo[k], extent = inst_nodes[0].hi[k] - lo;
 		const bool usable = std::isfinite(lo) && std::isfinite(extent) && extent > 0.0f && std::isfinite(8.0f / extent);
@@ -412,10 +416,14 @@ void RayQueries::visibilityHost(const float *points4, uint32_t np, const float *
 // packer found so, the refit rule's boxes after an update or a build -- each lane descends for a starting bound and boxes are
 // passed by (kernels/nearest.hip.h); otherwise (damaged arrays) every leaf is tested.  After an update or a build whose
 // coordinates only the device has seen, the word they left (checkCoordinates) decides it once more, in the kernel.
-void RayQueries::nearestDevice(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, void *stream) {
-	requireScene("closest-point query");
+// `instanced` (include/rt_hip_instance_nearest.h): the same rules decide what the nested walk may do in both of its trees --
+// the top-level boxes are made from the scene's root box and promise what it promises (kernels/instance_nearest.hip.h).
+void RayQueries::nearestDevice(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, void *stream,
+                               bool instanced, uint32_t *instance) {
+	requireQuery(instanced, "closest-point query");
 	if (n == 0)
 		return;
+	const Target to = target(instanced);
 	const std::shared_ptr<const DeviceScene> scene = dev.deviceScene();
 	uint32_t walk = scene->boxesEnclose() ? 3u : 0u;  // NEAREST_START | NEAREST_PRUNE
 	if (nearest_debug & 1u)
@@ -423,20 +431,22 @@ void RayQueries::nearestDevice(const float *points4, uint32_t n, float max_dista
 	if (nearest_debug & 2u)
 		walk = 0u;
 	const bool counting = (nearest_debug & 4u) != 0u;
-	const Enqueue q = begin(stream, points4, nullptr, n, n, flags, { Need{ counting ? &nearest_counts : nullptr, 2u * sizeof(uint64_t) } });
-	launch_nearest(scene->buffers(), scene->nodeCount(), scene->triCount(), points4, q.order, n, max_distance, walk, out,
+	const Enqueue q = begin(stream, points4, nullptr, n, n, flags, { Need{ counting ? &nearest_counts : nullptr, 2u * sizeof(uint64_t) } }, false,
+	                        to.box);
+	launch_nearest(scene->buffers(), scene->nodeCount(), scene->triCount(), to.set, points4, q.order, n, max_distance, walk, out, instance,
 	               flagged.lock() == scene ? coords_flag.ptr : nullptr, counting ? nearest_counts.ptr : nullptr, q.stream);
 	nearest_counted = counting;
 	end(q);
 }
 
-void RayQueries::nearestHost(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &host) {
-	requireScene("closest-point query");
+void RayQueries::nearestHost(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &host, bool instanced,
+                             uint32_t *instance) {
+	requireQuery(instanced, "closest-point query");
 	if (n == 0)
 		return;
 	// (the second piece stays empty: the points have no directions)
-	stagedRecords(points4, nullptr, n, true, host, nullptr, [&](const float *p4, const float *, const QueryOutputs &out, uint32_t *, void *s) {
-		nearestDevice(p4, n, max_distance, flags, out, s);
+	stagedRecords(points4, nullptr, n, true, host, instance, [&](const float *p4, const float *, const QueryOutputs &out, uint32_t *inst, void *s) {
+		nearestDevice(p4, n, max_distance, flags, out, s, instanced, inst);
 	});
 }
 

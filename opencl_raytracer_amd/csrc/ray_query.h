@@ -48,9 +48,12 @@ class RayQueries {
 		                  const MultiHitOutputs &out);
 		// Closest-point queries (include/rt_hip_nearest.h): the nearest point of the surface for each of n points, the record
 		// of a closest hit (out.hit: `found`).  Device memory, enqueued on `stream` (null: the renderer's).
-		void nearestDevice(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, void *stream);
+		// `instanced` (include/rt_hip_instance_nearest.h): the nearest point among the posed copies, in world space.
+		void nearestDevice(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, void *stream,
+		                   bool instanced = false, uint32_t *instance = nullptr);
 		// Host memory, blocking.
-		void nearestHost(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out);
+		void nearestHost(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, bool instanced = false,
+		                 uint32_t *instance = nullptr);
 		// (include/rt_hip_debug.h) how the later closest-point queries walk (RT_DEBUG_NEAREST_*; the A/B build's: std::logic_error
 		// for a flag in the product library), and the counts of the last counted one (waits for it)
 		void setNearestWalk(uint32_t debug_flags);
@@ -78,8 +81,8 @@ class RayQueries {
 		void visibilityHost(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
 		                    const VisibilityOutputs &out, bool instanced = false);
 		// The instance set (include/rt_hip_instances.h).  The set -- transforms, inverses and the top-level tree over the
-		// scene's root box (instances.h) -- is kept here and, as float4[3n] + float4[3n] + NodeRec[2n - 1], in device memory of
-		// this object's own; it outlives updates, builds and uploads, after which the tree is made again before its next use.
+		// scene's root box (instances.h) -- is kept here and, as float4[3n] + float4[3n] + NodeRec[2n - 1] + float4[n] (the
+		// closest-point walk's bounds), in device memory of this object's own; it outlives updates, builds and uploads, after which the tree is made again before its next use.
 		// std::invalid_argument for a refused transform or too many (the set stays what it was); n == 0 clears the set.
 		void setInstances(const float *world_from_object, uint32_t n);
 		uint32_t instanceCount() const { return (uint32_t) (inst_world.size() / 12u); }
@@ -314,8 +317,9 @@ void launch_query(const SceneBuffers &scene, uint32_t node_count, const Instance
                   const void *directions, const void *order, uint32_t n, float max_distance, const QueryOutputs &out, uint32_t *instance,
                   void *stream);
 void launch_nearest_sort(const void *points, uint32_t n, const float lo[3], const float scale[3], void *count, void *order, void *stream);
-void launch_nearest(const SceneBuffers &scene, uint32_t node_count, uint32_t tri_count, const void *points, const void *order, uint32_t n,
-                    float max_distance, uint32_t walk, const QueryOutputs &out, const void *coords_flag, void *counts, void *stream);
+void launch_nearest(const SceneBuffers &scene, uint32_t node_count, uint32_t tri_count, const InstanceBuffers *set, const void *points,
+                    const void *order, uint32_t n, float max_distance, uint32_t walk, const QueryOutputs &out, uint32_t *instance,
+                    const void *coords_flag, void *counts, void *stream);
 void launch_nearest_coordinates(const void *vertices4, uint32_t num_vertices, void *flag, void *stream);
 void launch_segments(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, bool closest, const void *from, const void *to,
                      const void *order, uint32_t n, float t_lo, float t_hi, const QueryOutputs &out, uint32_t *instance, void *stream);
