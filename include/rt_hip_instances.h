@@ -9,7 +9,8 @@
  * rt_trace_instances_ao and rt_render_instance_views (rt_hip_instance_views.h), and rt_instances_segments_occluded,
  * rt_instances_segments_closest and rt_instances_visibility_masks (rt_hip_instance_segments.h).  Closest-point queries have
  * one with rules of its own, in world space: rt_instances_closest_points (rt_hip_instance_nearest.h).  Multi-hit and
- * directional occlusion queries have none.
+ * directional occlusion queries have theirs by the same rules: rt_trace_instances_multihit (rt_hip_instance_multihit.h) and
+ * rt_trace_instances_ao_directional (rt_hip_instance_directional.h).
  *
  * Transforms.  world_from_object is twelve floats per instance, the rows of W = [A | t]: p_world = A p + t.  Every entry
  * must be finite, the determinant of A (binary64) non-zero and every entry of the inverse finite after its rounding to

@@ -9,6 +9,7 @@ raises.
 """
 from .api import (  # noqa: F401
     DIRECTIONAL_OUTPUTS,
+    INSTANCE_MULTIHIT_OUTPUTS,
     INSTANCE_NODE,
     INSTANCE_OUTPUTS,
     INSTANCE_VIEW_OUTPUTS,

@@ -1,5 +1,5 @@
 """ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h, rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h,
-rt_hip_nearest.h, rt_hip_segment.h, rt_hip_instances.h, rt_hip_instance_segments.h, rt_hip_instance_views.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers
+rt_hip_nearest.h, rt_hip_segment.h, rt_hip_instances.h, rt_hip_instance_segments.h, rt_hip_instance_views.h, rt_hip_instance_multihit.h, rt_hip_instance_directional.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers
 for the contract)."""
 from __future__ import annotations
 
@@ -284,6 +284,15 @@ _SIGNATURES = {
     "rt_trace_ao": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_trace_ao_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    # include/rt_hip_instance_multihit.h
+    "rt_trace_instances_multihit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32,
+                                              C.c_void_p]),
+    "rt_trace_instances_multihit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p]),
+    # include/rt_hip_instance_directional.h
+    "rt_trace_instances_ao_directional": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_trace_instances_ao_directional_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                           C.c_void_p, C.c_void_p]),
     # include/rt_hip_directional.h
     "rt_ao_mask_words": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rt_trace_ao_directional": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
@@ -351,6 +360,11 @@ class _InstanceHitArrays(C.Structure):
     _fields_ = [("record", _HitArrays), ("instance", C.c_void_p)]
 
 
+class _InstanceMultiHitArrays(C.Structure):
+    """rt_instance_multihit_arrays (include/rt_hip_instance_multihit.h)."""
+    _fields_ = [("slots", _MultiHitArrays), ("instance", C.c_void_p)]
+
+
 class _VisibilityArrays(C.Structure):
     """rt_visibility_arrays (include/rt_hip_segment.h)."""
     _fields_ = [("mask", C.c_void_p), ("count", C.c_void_p)]
@@ -383,6 +397,7 @@ RT_MULTIHIT_MAX_K = 16
 MULTIHIT_OUTPUTS = ("count", "distance", "leaf", "barycentric", "position", "normal")
 QUERY_OUTPUTS = ("hit", "distance", "leaf", "barycentric", "position", "normal")
 NEAREST_OUTPUTS = QUERY_OUTPUTS  # closest-point queries: "hit" is `found`
+INSTANCE_MULTIHIT_OUTPUTS = MULTIHIT_OUTPUTS + ("instance",)  # instanced multi-hit queries: the copy of every slot beside it
 INSTANCE_OUTPUTS = QUERY_OUTPUTS + ("instance",)  # instanced ray queries: the record and the instance it lies in
 RT_INSTANCES_MAX = 1 << 20
 # the record of a top-level tree (include/rt_hip_instances.h): the node record the exact walk reads
@@ -1047,6 +1062,52 @@ class Host:
         out = io.outputs(outputs)
         io.call(self._h, "rt_trace_instances_ao", io.ptr(seeds) if seeds is not None and io.n else None, io.n,
                 0 if sort else RT_QUERY_NO_SORT, *io.pointers(out, AO_OUTPUTS))
+        return out
+
+    # ---- instanced multi-hit queries (include/rt_hip_instance_multihit.h) ----
+    def trace_instances_multihit(self, origins, directions, max_distance: float = 100000.0, k: int = 4,
+                                 outputs=INSTANCE_MULTIHIT_OUTPUTS, sort: bool = True) -> dict:
+        """Everything a WORLD-space ray crosses among the posed copies of the scene (set_instances): trace_multihit's
+        outputs -- "count": uint32 (N,), every (copy, triangle) pair the walks accept, whatever k; the first k of them by
+        (distance, instance, leaf index), records as trace_instances_closest makes them -- and "instance": uint32 (N, k),
+        the copy of every slot (0xFFFFFFFF in unused slots) (those named in `outputs`).  k, inputs and the numpy / torch
+        forms are trace_multihit's."""
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in INSTANCE_MULTIHIT_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {INSTANCE_MULTIHIT_OUTPUTS}")
+        k = int(k)
+        if k < 0:
+            raise ValueError("k must not be negative")
+        io = _QueryArrays(origins, directions, ("origins", "directions"), "rays")
+        out = io.outputs(outputs, k, shapes={"instance": (np.uint32, (k,))})
+        at = io.pointers(out, INSTANCE_MULTIHIT_OUTPUTS, name_empty=True)
+        io.call(self._h, "rt_trace_instances_multihit", io.n, float(max_distance), k, 0 if sort else RT_QUERY_NO_SORT,
+                C.byref(_InstanceMultiHitArrays(_MultiHitArrays(*at[:-1]), at[-1])))
+        return out
+
+    def count_instances_hits(self, origins, directions, max_distance: float = 100000.0, sort: bool = True):
+        """The number of (copy, triangle) pairs the walks accept for every world-space ray (trace_instances_multihit's
+        "count", the k = 0 form that keeps no list): uint32 (N,)."""
+        return self.trace_instances_multihit(origins, directions, max_distance, k=0, outputs=("count",), sort=sort)["count"]
+
+    # ---- instanced directional occlusion (include/rt_hip_instance_directional.h) ----
+    def instances_directional_occlusion(self, points, normals, seeds=None, outputs=DIRECTIONAL_OUTPUTS, sort: bool = True) -> dict:
+        """directional_occlusion at WORLD-space points against the posed copies of the scene (set_instances): the rays of a
+        point are ao_rays's, each cast as trace_instances_occluded casts it with max_distance = ao_max_distance; "mask",
+        "occluded", "ao" and "bent" are made of those flags as directional_occlusion makes them ("occluded" and "ao" are
+        instances_ambient_occlusion's).  Inputs, seeds, sorting and the numpy / torch forms are ambient_occlusion's."""
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in DIRECTIONAL_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {DIRECTIONAL_OUTPUTS}")
+        io = _QueryArrays(points, normals, ("points", "normals", "seeds"), "points", also=seeds)
+        if seeds is not None:
+            seeds = io.seeds(seeds)
+        out = io.outputs(outputs, shapes={"mask": (np.uint32, (self.ao_mask_words,))} if "mask" in outputs else None)
+        arrays = _DirectionalArrays(*io.pointers(out, DIRECTIONAL_OUTPUTS))
+        io.call(self._h, "rt_trace_instances_ao_directional", io.ptr(seeds) if seeds is not None and io.n else None, io.n,
+                0 if sort else RT_QUERY_NO_SORT, C.byref(arrays))
         return out
 
     # ---- segment queries (include/rt_hip_segment.h) ----

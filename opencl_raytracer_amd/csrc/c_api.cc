@@ -11,6 +11,8 @@
 #include "../../include/rt_hip_nearest.h"
 #include "../../include/rt_hip_query.h"
 #include "../../include/rt_hip_segment.h"
+#include "../../include/rt_hip_instance_directional.h"
+#include "../../include/rt_hip_instance_multihit.h"
 #include "../../include/rt_hip_instance_nearest.h"
 #include "../../include/rt_hip_instance_segments.h"
 #include "../../include/rt_hip_instance_views.h"
@@ -1290,18 +1292,19 @@ int rt_debug_last_nearest_counts(rt_host *h, uint64_t *node_tests, uint64_t *tri
 namespace {
 
 // The checks of include/rt_hip_multihit.h ("Errors") beyond query_precheck's; `q`: the outputs asked for.
+// (`f`: RAYS, or INSTANCED_RAYS with the slots' `instance` array beside them -- include/rt_hip_instance_multihit.h)
 int multihit_precheck(rt_host *h, const float *origins4, const float *directions4, uint32_t n, uint32_t k, const ocrt::MultiHitOutputs &q,
-                      bool device) {
-	const int rc = query_precheck(h, RAYS, origins4, directions4, n, device);
+                      bool device, const Family &f = RAYS, const uint32_t *instance = nullptr) {
+	const int rc = query_precheck(h, f, origins4, directions4, n, device);
 	if (rc != RT_OK)
 		return rc;
 	if (k > RT_MULTIHIT_MAX_K)
 		return fail(RT_E_INVALID, "more slots per ray than RT_MULTIHIT_MAX_K");
-	if (k == 0 && q.anySlot())
+	if (k == 0 && (q.anySlot() || instance))
 		return fail(RT_E_INVALID, "k == 0 asks for the count alone: the slot arrays must be null");
 	if ((uint64_t) n * (k ? k : 1u) > RT_QUERY_MAX_RAYS)
 		return fail(RT_E_INVALID, "more than RT_QUERY_MAX_RAYS slots (n * k) in one call");
-	if (device && !(aligned({ q.count }, 4) && records_aligned(q)))
+	if (device && !(aligned({ q.count, instance }, 4) && records_aligned(q)))
 		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
 	return RT_OK;
 }
@@ -1324,6 +1327,27 @@ int rt_trace_multihit_device(rt_host *h, const float *origins4, const float *dir
 	if (rc != RT_OK || n == 0)
 		return rc;
 	return guarded([&] { queries_of(h).multihitDevice(origins4, directions4, n, max_distance, k, flags, q, hip_stream); });
+}
+
+// ---- rt_hip_instance_multihit.h ----
+int rt_trace_instances_multihit(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
+                                uint32_t flags, const rt_instance_multihit_arrays *out) {
+	const ocrt::MultiHitOutputs q = multihit_outputs(out ? &out->slots : nullptr);
+	uint32_t *const instance = out ? out->instance : nullptr;
+	const int rc = multihit_precheck(h, origins4, directions4, n, k, q, false, INSTANCED_RAYS, instance);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	return guarded([&] { queries_of(h).multihitHost(origins4, directions4, n, max_distance, k, flags, q, true, instance); });
+}
+
+int rt_trace_instances_multihit_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
+                                       uint32_t k, uint32_t flags, const rt_instance_multihit_arrays *out, void *hip_stream) {
+	const ocrt::MultiHitOutputs q = multihit_outputs(out ? &out->slots : nullptr);
+	uint32_t *const instance = out ? out->instance : nullptr;
+	const int rc = multihit_precheck(h, origins4, directions4, n, k, q, true, INSTANCED_RAYS, instance);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	return guarded([&] { queries_of(h).multihitDevice(origins4, directions4, n, max_distance, k, flags, q, hip_stream, true, instance); });
 }
 
 // ---- rt_hip_ao.h ----
@@ -1547,6 +1571,28 @@ int rt_trace_instances_ao_device(rt_host *h, const float *points4, const float *
 	return guarded([&] { queries_of(h).aoDevice(points4, normals4, seeds, n, flags, ao, occluded, hip_stream, true); });
 }
 
+// ---- rt_hip_instance_directional.h ----
+int rt_trace_instances_ao_directional(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n,
+                                      uint32_t flags, const rt_ao_directional_arrays *out) {
+	const int rc = instance_ao_precheck(h, points4, normals4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	const ocrt::RayQueries::DirectionalOutputs q = directional_outputs(out);
+	return guarded([&] { queries_of(h).directionalHost(points4, normals4, seeds, n, flags, q, true); });
+}
+
+int rt_trace_instances_ao_directional_device(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds,
+                                             uint32_t n, uint32_t flags, const rt_ao_directional_arrays *out, void *hip_stream) {
+	const int rc = instance_ao_precheck(h, points4, normals4, n, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	const ocrt::RayQueries::DirectionalOutputs q = directional_outputs(out);
+	if (!aligned({ seeds, q.ao, q.occluded, q.mask, q.bent }, 4))
+		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).directionalDevice(points4, normals4, seeds, n, flags, q, hip_stream, true); });
+}
+
+// ---- rt_hip_instance_views.h: the views ----
 int rt_render_instance_views(rt_host *h, const rt_camera *cameras, uint32_t views, const rt_instance_view_arrays *out) {
 	const int rc = instance_views_precheck(h, cameras, views, out);
 	if (rc != RT_OK)

@@ -63,6 +63,11 @@
 //                   visibility_mask_kernel against the posed copies: the same packets and tails, shared functions, around
 //                   instance_walk with the interval test on the object ray's plane parameter (kernels/instance_segments.hip.h,
 //                   include/rt_hip_instance_segments.h).
+//                   instance_multihit_walk_kernel<K> and instance_multihit_resolve_kernel are the multi-hit kernels against the
+//                   posed copies: the lane's list keyed by (distance, instance, leaf), around instance_walk in its closest form
+//                   (kernels/instance_multihit.hip.h, include/rt_hip_instance_multihit.h); instance_ao_mask_kernel<MODE> is
+//                   ao_mask_kernel against them: the same rays and tail, shared functions, around instance_walk in its occlusion
+//                   form (kernels/instance_directional.hip.h, include/rt_hip_instance_directional.h).
 //   (scenes)        refit_leaves_kernel / refit_inner_kernel make the records and boxes of a scene again from new positions
 //                   (kernels/refit.hip.h, include/rt_hip_update.h); build_boxes_kernel, build_root_kernel, build_keys_kernel,
 //                   build_tree_kernel and build_layout_kernel make a scene's tree from triangles, around a sort that lives in
@@ -119,6 +124,8 @@
 #include "kernels/instance_views.hip.h"
 #include "kernels/instance_segments.hip.h"
 #include "kernels/instance_nearest.hip.h"
+#include "kernels/instance_multihit.hip.h"
+#include "kernels/instance_directional.hip.h"
 
 
 namespace ocrt {
@@ -619,14 +626,15 @@ void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, const Insta
 
 // Directional occlusion queries (kernels/directional.hip.h).  `mask`: n rows of ceil(rays_per_point / 32) words on the
 // device (the caller's array or scratch), zeroed here on the stream; `order`: launch_query_sort's order of the POINTS or
-// null; `occluded`, `ao`, `bent`: null = not written -- with all three null the resolve is not launched.
-void launch_ao_directional(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
+// null; `occluded`, `ao`, `bent`: null = not written -- with all three null the resolve is not launched; `set`: null, or the
+// instance set the rays are cast against (kernels/instance_directional.hip.h).
+void launch_ao_directional(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
                            float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
                            uint32_t *mask, uint32_t *occluded, float *ao, float *bent, void *stream) {
-	if (n == 0 || rays_per_point == 0)
+	if (n == 0 || rays_per_point == 0 || (set && set->top_count == 0))
 		return;
 	hipStream_t s = (hipStream_t) stream;
-	AoMaskArgs a{};
+	InstanceAoMaskArgs a{};
 	a.nodes_ptr = (const float4 *) scene.nodes;
 	a.tris_ptr = (const float4 *) scene.tris;
 	a.ao_table = (const float4 *) scene.ao_table;
@@ -642,11 +650,19 @@ void launch_ao_directional(const SceneBuffers &scene, uint32_t node_count, int a
 	a.node_count = node_count;
 	a.max_distance = max_distance;
 	(void) hipMemsetAsync(mask, 0, (size_t) n * a.words * sizeof(uint32_t), s);
+	const AoMaskArgs &plain = a;
 	const uint32_t blocks = (a.total + 64u * QUERY_WAVES - 1u) / (64u * QUERY_WAVES);
-	if (ao_mode == AO_RANDOM)
-		hipLaunchKernelGGL(ao_mask_kernel<AO_RANDOM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
-	else
-		hipLaunchKernelGGL(ao_mask_kernel<AO_UNIFORM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+	if (set) {
+		a.set = instance_set(*set);
+		if (ao_mode == AO_RANDOM)
+			hipLaunchKernelGGL(instance_ao_mask_kernel<AO_RANDOM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+		else
+			hipLaunchKernelGGL(instance_ao_mask_kernel<AO_UNIFORM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, a);
+	} else if (ao_mode == AO_RANDOM) {
+		hipLaunchKernelGGL(ao_mask_kernel<AO_RANDOM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, plain);
+	} else {
+		hipLaunchKernelGGL(ao_mask_kernel<AO_UNIFORM>, dim3(blocks), dim3(64 * QUERY_WAVES), 0, s, plain);
+	}
 	if (!occluded && !ao && !bent)
 		return;
 	AoResolveArgs f{};
@@ -692,31 +708,56 @@ void launch_ao_rays(const SceneBuffers &scene, int ao_mode, uint32_t rays_per_po
 
 // Multi-hit queries (kernels/multihit.hip.h).  `k` <= MULTIHIT_MAX_K slots per ray (0: the count alone); `list`: n * k
 // uint2 of scratch on the device; `count` and the slot arrays: null = not written.  The resolve pass is launched only if
-// a slot array is given.
-void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void *origins, const void *directions, const void *order,
-                     uint32_t n, float max_distance, uint32_t k, void *list, const MultiHitOutputs &out, void *stream) {
-	if (n == 0 || k > MULTIHIT_MAX_K)
+// a slot array is given.  `set`: null, or the instance set the rays are cast against (kernels/instance_multihit.hip.h):
+// `list` is then n * k * 3 words, and `instance` the slot array beside the record's.
+template <uint32_t K>
+static void launch_multihit_walk(const MultiHitArgs &plain, const InstanceMultiHitArgs *instanced, dim3 blocks, dim3 lanes, hipStream_t s) {
+	if (instanced)
+		hipLaunchKernelGGL(instance_multihit_walk_kernel<K>, blocks, lanes, 0, s, *instanced);
+	else
+		hipLaunchKernelGGL(multihit_walk_kernel<K>, blocks, lanes, 0, s, plain);
+}
+
+void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, const void *origins, const void *directions,
+                     const void *order, uint32_t n, float max_distance, uint32_t k, void *list, const MultiHitOutputs &out, uint32_t *instance,
+                     void *stream) {
+	if (n == 0 || k > MULTIHIT_MAX_K || (set && set->top_count == 0))
 		return;
 	hipStream_t s = (hipStream_t) stream;
 	MultiHitArgs a{};
-	fill(a, scene, node_count, origins, directions, order, n, max_distance, out);
-	a.k = k;
-	a.list = (uint2 *) list;
-	a.count = out.count;
+	InstanceMultiHitArgs b{};
+	if (set) {
+		fill(b, scene, node_count, origins, directions, order, n, max_distance, out);
+		b.set = instance_set(*set);
+		b.k = k;
+		b.list = (uint32_t *) list;
+		b.count = out.count;
+		b.instance = instance;
+	} else {
+		fill(a, scene, node_count, origins, directions, order, n, max_distance, out);
+		a.k = k;
+		a.list = (uint2 *) list;
+		a.count = out.count;
+	}
+	const InstanceMultiHitArgs *const instanced = set ? &b : nullptr;
 	const dim3 blocks((n + MULTIHIT_LANES - 1u) / MULTIHIT_LANES), lanes(MULTIHIT_LANES);
 	if (k == 0u)
-		hipLaunchKernelGGL(multihit_walk_kernel<0u>, blocks, lanes, 0, s, a);
+		launch_multihit_walk<0u>(a, instanced, blocks, lanes, s);
 	else if (k == 1u)
-		hipLaunchKernelGGL(multihit_walk_kernel<1u>, blocks, lanes, 0, s, a);
+		launch_multihit_walk<1u>(a, instanced, blocks, lanes, s);
 	else if (k <= 2u)
-		hipLaunchKernelGGL(multihit_walk_kernel<2u>, blocks, lanes, 0, s, a);
+		launch_multihit_walk<2u>(a, instanced, blocks, lanes, s);
 	else if (k <= 4u)
-		hipLaunchKernelGGL(multihit_walk_kernel<4u>, blocks, lanes, 0, s, a);
+		launch_multihit_walk<4u>(a, instanced, blocks, lanes, s);
 	else if (k <= 8u)
-		hipLaunchKernelGGL(multihit_walk_kernel<8u>, blocks, lanes, 0, s, a);
+		launch_multihit_walk<8u>(a, instanced, blocks, lanes, s);
 	else
-		hipLaunchKernelGGL(multihit_walk_kernel<16u>, blocks, lanes, 0, s, a);
-	if (k > 0u && out.anySlot())
+		launch_multihit_walk<16u>(a, instanced, blocks, lanes, s);
+	if (k == 0u || !(out.anySlot() || (set && instance)))
+		return;
+	if (set)
+		hipLaunchKernelGGL(instance_multihit_resolve_kernel, dim3((n * k + 255u) / 256u), dim3(256), 0, s, b);
+	else
 		hipLaunchKernelGGL(multihit_resolve_kernel, dim3((n * k + 255u) / 256u), dim3(256), 0, s, a);
 }
 

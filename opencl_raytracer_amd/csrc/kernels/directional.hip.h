@@ -6,8 +6,9 @@
 // k of the point in slot `slot`, a wave casts a packet of 64 consecutive rays, and the walk is the exact form.  What a ray
 // IS -- its origin, its point's tangent frame, its direction -- has one definition here, ao_point / ao_direction, used by
 // the three kernels below: the walk that makes the masks, the resolve that sums directions, and the kernel that writes the
-// rays out for the caller.  (ao_query_kernel keeps a text of its own, ao_query_ray, shared with its instanced form alone: it
-// is the frame layers' and views' kernel too.)
+// rays out for the caller.  The walk's packet ray and its tail are functions (ao_mask_ray, ao_mask_flags) that its instanced
+// form shares (kernels/instance_directional.hip.h).  (ao_query_kernel keeps a text of its own, ao_query_ray, shared with its
+// instanced form alone: it is the frame layers' and views' kernel too.)
 //
 // Masks: hit flags are integers, and a flag has one place -- bit k & 31 of word k >> 5 of its point's row -- so the order
 // in which the packets of a point arrive is free.  Per packet the flags are balloted; the first lane of every run of lanes
@@ -102,25 +103,58 @@ struct AoMaskArgs {
 	float max_distance;
 };
 
+// The tail of the mask kernels (ao_mask_kernel, instance_ao_mask_kernel): the packet's flags by (point, mask word) -- the
+// first lane of a run of lanes that shares both ORs the run's bits in.  The whole wave calls it (the ballot).
+__device__ __forceinline__ void ao_mask_flags(const AoMaskArgs &a, bool live, uint32_t idx, uint32_t k, bool hit) {
+	const unsigned long long hits = wave_ballot(hit);
+	if (!live)
+		return;
+	const uint32_t lane = threadIdx.x & 63u, bit = k & 31u;
+	if (!(lane == 0u || k == 0u || bit == 0u))
+		return;
+	// the run ends with the word, with the point or with the packet: 1 .. 32 lanes
+	uint32_t len = 32u - bit;
+	len = a.rays - k < len ? a.rays - k : len;
+	len = 64u - lane < len ? 64u - lane : len;
+	const uint32_t flags = (uint32_t) ((hits >> lane) & ((1ull << len) - 1ull)) << bit;
+	if (flags)
+		atomicOr(&a.mask[idx * a.words + (k >> 5)], flags);
+}
+
+// The packet's ray of the mask kernels: ray r of the flattened (slot, direction) list, made in registers; a dead lane (a
+// partial last packet) gets a ray that walks nothing.  The whole wave calls it (make_ray ballots).  (Locals of its own,
+// handed out at the end: written straight into the references the compiler allots ao_mask_kernel's registers in another
+// order -- the same instructions under other names, and that kernel's assembly is not to move.)
+template <int MODE>
+__device__ __forceinline__ Ray ao_mask_ray(const AoMaskArgs &a, uint32_t r, bool &live, uint32_t &idx, uint32_t &k) {
+	const bool in_range = r < a.total;
+	uint32_t point = 0u, dir = 0u;
+	float ox = 0.0f, oy = 0.0f, oz = 0.0f, rx = 1.0f, ry = 1.0f, rz = 1.0f;
+	if (in_range) {
+		const uint32_t slot = r / a.rays;
+		dir = r - slot * a.rays;
+		point = a.order ? a.order[slot] : slot;
+		const AoPoint f = ao_point<MODE>(a.points[point], a.normals[point]);
+		ox = f.ox; oy = f.oy; oz = f.oz;
+		Rng rng{};
+		if (MODE == AO_RANDOM)
+			rng = ao_rng_at(a.seeds ? a.seeds[point] : point, dir);
+		ao_direction<MODE>(f, a.ao_table, rng, dir, rx, ry, rz);
+	}
+	const Ray ray = make_ray(ox, oy, oz, rx, ry, rz);
+	live = in_range;
+	idx = point;
+	k = dir;
+	return ray;
+}
+
 // The packet shape, the rays and the walk of ao_query_kernel<MODE>; the tail keeps the hit flags apart.
 template <int MODE>
 __global__ __launch_bounds__(64 * QUERY_WAVES) void ao_mask_kernel(AoMaskArgs a) {
 	const uint32_t r = blockIdx.x * (64u * QUERY_WAVES) + threadIdx.x;
-	const bool live = r < a.total;  // (a partial last packet: its dead lanes walk nothing and flag nothing)
-	uint32_t idx = 0u, k = 0u;
-	float ox = 0.0f, oy = 0.0f, oz = 0.0f, rx = 1.0f, ry = 1.0f, rz = 1.0f;
-	if (live) {
-		const uint32_t slot = r / a.rays;
-		k = r - slot * a.rays;
-		idx = a.order ? a.order[slot] : slot;
-		const AoPoint f = ao_point<MODE>(a.points[idx], a.normals[idx]);
-		ox = f.ox; oy = f.oy; oz = f.oz;
-		Rng rng{};
-		if (MODE == AO_RANDOM)
-			rng = ao_rng_at(a.seeds ? a.seeds[idx] : idx, k);
-		ao_direction<MODE>(f, a.ao_table, rng, k, rx, ry, rz);
-	}
-	const Ray ray = make_ray(ox, oy, oz, rx, ry, rz);
+	bool live;  // (a partial last packet: its dead lanes walk nothing and flag nothing)
+	uint32_t idx, k;
+	const Ray ray = ao_mask_ray<MODE>(a, r, live, idx, k);
 	bool alive = live, hit = false;
 	// a lane leaves at its first accepted triangle
 	exact_walk(a.nodes_ptr, a.node_count, ray, a.max_distance, alive, [&](uint32_t leaf, bool box) {
@@ -135,20 +169,7 @@ __global__ __launch_bounds__(64 * QUERY_WAVES) void ao_mask_kernel(AoMaskArgs a)
 		}
 		return wave_ballot(alive) == 0ull;
 	});
-	// the packet's flags by (point, mask word): the first lane of a run of lanes that shares both ORs the run's bits in
-	const unsigned long long hits = wave_ballot(hit);
-	if (!live)
-		return;
-	const uint32_t lane = threadIdx.x & 63u, bit = k & 31u;
-	if (!(lane == 0u || k == 0u || bit == 0u))
-		return;
-	// the run ends with the word, with the point or with the packet: 1 .. 32 lanes
-	uint32_t len = 32u - bit;
-	len = a.rays - k < len ? a.rays - k : len;
-	len = 64u - lane < len ? 64u - lane : len;
-	const uint32_t flags = (uint32_t) ((hits >> lane) & ((1ull << len) - 1ull)) << bit;
-	if (flags)
-		atomicOr(&a.mask[idx * a.words + (k >> 5)], flags);
+	ao_mask_flags(a, live, idx, k, hit);
 }
 
 struct AoResolveArgs {

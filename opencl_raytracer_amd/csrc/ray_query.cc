@@ -475,32 +475,42 @@ void RayQueries::checkCoordinates(const std::shared_ptr<const DeviceScene> &scen
 }
 
 void RayQueries::multihitDevice(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
-                                uint32_t flags, const MultiHitOutputs &out, void *stream) {
+                                uint32_t flags, const MultiHitOutputs &out, void *stream, bool instanced, uint32_t *instance) {
+	if (instanced)
+		requireInstances("instanced multi-hit query");
 	requireSlots(k);
 	// without a slot array the lists are not wanted: the count-only walk
-	const uint32_t slots = out.anySlot() ? k : 0u;
+	const uint32_t slots = out.anySlot() || (instanced && instance) ? k : 0u;
 	if (n == 0 || (slots == 0 && !out.count))
 		return;
-	const Enqueue q = begin(stream, origins4, directions4, n, n, flags, { Need{ slots ? &list : nullptr, (size_t) n * slots * 8u } });
-	launch_multihit(dev.deviceScene()->buffers(), dev.params().node_count, origins4, directions4, q.order, n, max_distance, slots,
-	                list.ptr, out, q.stream);
+	const Target to = target(instanced);
+	const Enqueue q = begin(stream, origins4, directions4, n, n, flags,
+	                        { Need{ slots ? &list : nullptr, (size_t) n * slots * (instanced ? 12u : 8u) } }, false, to.box);
+	launch_multihit(dev.deviceScene()->buffers(), dev.params().node_count, to.set, origins4, directions4, q.order, n, max_distance, slots,
+	                list.ptr, out, instanced ? instance : nullptr, q.stream);
 	end(q);
 }
 
 void RayQueries::multihitHost(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
-                              const MultiHitOutputs &host) {
+                              const MultiHitOutputs &host, bool instanced, uint32_t *instance) {
+	if (instanced)
+		requireInstances("instanced multi-hit query");
 	requireSlots(k);
-	if (n == 0 || (!host.count && !host.anySlot()))
+	if (!instanced)
+		instance = nullptr;
+	if (n == 0 || (!host.count && !host.anySlot() && !instance))
 		return;
-	Staged p[RAY_PIECES] = { input(origins4, (size_t) n * 16u), input(directions4, (size_t) n * 16u),
-		                     output(host.count, (size_t) n * 4u) };
+	Staged p[INST_PIECES] = { input(origins4, (size_t) n * 16u), input(directions4, (size_t) n * 16u),
+		                       output(host.count, (size_t) n * 4u) };
 	recordPieces(p + RAY_RECORDS, host, (size_t) n * k);
-	void *s = stageIn(p, RAY_PIECES);
+	p[INST_INDEX] = output(instance, (size_t) n * k * 4u);
+	void *s = stageIn(p, INST_PIECES);
 	MultiHitOutputs out;
 	out.count = (uint32_t *) p[RAY_FIRST].device;
 	recordDevice(p + RAY_RECORDS, out);
-	multihitDevice((const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, max_distance, k, flags, out, s);
-	stageOut(p, RAY_PIECES, s);
+	multihitDevice((const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, max_distance, k, flags, out, s, instanced,
+	               (uint32_t *) p[INST_INDEX].device);
+	stageOut(p, INST_PIECES, s);
 }
 
 uint32_t RayQueries::aoRaysPerPoint(const DeviceRenderer &renderer) {
@@ -551,23 +561,28 @@ void RayQueries::aoHost(const float *points4, const float *normals4, const uint3
 }
 
 void RayQueries::directionalDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
-                                   const DirectionalOutputs &out, void *stream) {
+                                   const DirectionalOutputs &out, void *stream, bool instanced) {
+	if (instanced)
+		requireInstances("instanced directional occlusion query");
 	requireAo();
 	if (n == 0 || !out.any())
 		return;
+	const Target to = target(instanced);
 	const KernelParams &kp = dev.params();
 	const size_t row_bytes = (size_t) aoMaskWords(dev) * sizeof(uint32_t);
 	// the POINTS are ordered as for aoDevice; the rows are the caller's, or scratch where only what is made of them is wanted
 	const Enqueue q = begin(stream, points4, normals4, n, (uint64_t) n * kp.ao_dirs, flags,
-	                        { Need{ out.mask ? nullptr : &ao_rows, (size_t) n * row_bytes } });
-	launch_ao_directional(dev.deviceScene()->buffers(), kp.node_count, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4,
+	                        { Need{ out.mask ? nullptr : &ao_rows, (size_t) n * row_bytes } }, false, to.box);
+	launch_ao_directional(dev.deviceScene()->buffers(), kp.node_count, to.set, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4,
 	                      normals4, seeds, q.order, n, out.mask ? out.mask : (uint32_t *) ao_rows.ptr, out.occluded, out.ao, out.bent,
 	                      q.stream);
 	end(q);
 }
 
 void RayQueries::directionalHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
-                                 const DirectionalOutputs &host) {
+                                 const DirectionalOutputs &host, bool instanced) {
+	if (instanced)
+		requireInstances("instanced directional occlusion query");
 	requireAo();
 	if (n == 0 || !host.any())
 		return;
@@ -582,7 +597,7 @@ void RayQueries::directionalHost(const float *points4, const float *normals4, co
 	out.ao = (float *) p[DIR_VALUES].device;
 	out.bent = (float *) p[DIR_BENT].device;
 	directionalDevice((const float *) p[DIR_POINTS].device, (const float *) p[DIR_NORMALS].device, (const uint32_t *) p[DIR_SEEDS].device, n,
-	                  flags, out, s);
+	                  flags, out, s, instanced);
 	stageOut(p, DIR_PIECES, s);
 }
 

@@ -4,7 +4,8 @@
 // kernels/directional.hip.h, kernels/layers.hip.h, kernels/views.hip.h); instanced ray queries (include/rt_hip_instances.h,
 // kernels/instances.hip.h, instances.h); instanced ambient occlusion and views (include/rt_hip_instance_views.h,
 // kernels/instance_views.hip.h); instanced segment queries (include/rt_hip_instance_segments.h,
-// kernels/instance_segments.hip.h).
+// kernels/instance_segments.hip.h); instanced multi-hit and directional occlusion queries (include/rt_hip_instance_multihit.h,
+// include/rt_hip_instance_directional.h, kernels/instance_multihit.hip.h, kernels/instance_directional.hip.h).
 #pragma once
 #include <cstdint>
 #include <initializer_list>
@@ -41,11 +42,13 @@ class RayQueries {
 		               const QueryOutputs &out, bool instanced = false, uint32_t *instance = nullptr);
 		// Multi-hit queries (include/rt_hip_multihit.h): the count of accepted triangles per ray and the first k of them.
 		// Device memory, enqueued on `stream` (null: the renderer's); k <= RT_MULTIHIT_MAX_K, 0 = the count alone.
+		// `instanced` (include/rt_hip_instance_multihit.h): the (instance, triangle) pairs among the posed copies, `instance`
+		// [n * k] (or null) beside the slot arrays.
 		void multihitDevice(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
-		                    const MultiHitOutputs &out, void *stream);
+		                    const MultiHitOutputs &out, void *stream, bool instanced = false, uint32_t *instance = nullptr);
 		// Host memory, blocking.
 		void multihitHost(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
-		                  const MultiHitOutputs &out);
+		                  const MultiHitOutputs &out, bool instanced = false, uint32_t *instance = nullptr);
 		// Closest-point queries (include/rt_hip_nearest.h): the nearest point of the surface for each of n points, the record
 		// of a closest hit (out.hit: `found`).  Device memory, enqueued on `stream` (null: the renderer's).
 		// `instanced` (include/rt_hip_instance_nearest.h): the nearest point among the posed copies, in world space.
@@ -115,12 +118,13 @@ class RayQueries {
 			bool any() const { return ao || occluded || mask || bent; }
 		};
 		static uint32_t aoMaskWords(const DeviceRenderer &renderer) { return (aoRaysPerPoint(renderer) + 31u) / 32u; }
-		// Device memory, enqueued on `stream` (null: the renderer's).
+		// Device memory, enqueued on `stream` (null: the renderer's).  `instanced` (include/rt_hip_instance_directional.h):
+		// world-space points, the rays cast against the instance set.
 		void directionalDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
-		                       const DirectionalOutputs &out, void *stream);
+		                       const DirectionalOutputs &out, void *stream, bool instanced = false);
 		// Host memory, blocking.
 		void directionalHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
-		                     const DirectionalOutputs &out);
+		                     const DirectionalOutputs &out, bool instanced = false);
 		// The rays themselves: origins4 float4[n], directions4 float4[n * rays per point]; either may be null; no walk is run.
 		void aoRaysDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4, float *directions4,
 		                  void *stream);
@@ -266,7 +270,7 @@ class RayQueries {
 		Scratch ao_hits;       // aoDevice without an `occluded` array: the points' counts
 		Scratch ao_rows;       // directionalDevice without a `mask` array: the points' rows
 		Scratch vis_rows;      // visibilityDevice without a `mask` array: the points' rows
-	Scratch list;          // multihitDevice: the rays' key lists, n * k * 8 bytes
+	Scratch list;          // multihitDevice: the rays' key lists, n * k * 8 bytes (instanced: 12)
 		Scratch views;         // layersDevice, viewsDevice (ChunkScratch): a chunk's poses, the points and normals of its
 		                       // ambient-occlusion step, the list of the hit ones (ViewList), its float images where the caller
 		                       // gave no `value` array
@@ -326,12 +330,13 @@ void launch_segments(const SceneBuffers &scene, uint32_t node_count, const Insta
 void launch_visibility(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, const void *points, uint32_t np,
                        const void *targets, uint32_t nt, const void *order, float t_lo, float t_hi, uint32_t *mask, uint32_t *count,
                        void *stream);
-void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const void *origins, const void *directions, const void *order,
-                     uint32_t n, float max_distance, uint32_t k, void *list, const MultiHitOutputs &out, void *stream);
+void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, const void *origins, const void *directions,
+                     const void *order, uint32_t n, float max_distance, uint32_t k, void *list, const MultiHitOutputs &out, uint32_t *instance,
+                     void *stream);
 void launch_ao_query(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, int ao_mode, uint32_t rays_per_point,
                      uint32_t divisor, float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order,
                      uint32_t n, uint32_t *count, float *ao, void *stream);
-void launch_ao_directional(const SceneBuffers &scene, uint32_t node_count, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
+void launch_ao_directional(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, int ao_mode, uint32_t rays_per_point, uint32_t divisor,
                            float max_distance, const void *points, const void *normals, const uint32_t *seeds, const void *order, uint32_t n,
                            uint32_t *mask, uint32_t *occluded, float *ao, float *bent, void *stream);
 void launch_ao_rays(const SceneBuffers &scene, int ao_mode, uint32_t rays_per_point, const void *points, const void *normals,

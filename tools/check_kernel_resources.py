@@ -156,7 +156,13 @@ def main():
                # instanced ambient occlusion and views (kernels/instance_views.hip.h): the same nested walks
                "instance_ao_kernel<1", "instance_ao_kernel<2", "instance_layers_kernel",
                # instanced segment queries (kernels/instance_segments.hip.h): the nested walks with the interval at the leaves
-               "instance_segment_kernel<true>", "instance_segment_kernel<false>", "instance_visibility_kernel")
+               "instance_segment_kernel<true>", "instance_segment_kernel<false>", "instance_visibility_kernel",
+               # instanced multi-hit queries (kernels/instance_multihit.hip.h): the nested walks around the lane's list in LDS
+               "instance_multihit_walk_kernel<0", "instance_multihit_walk_kernel<1u", "instance_multihit_walk_kernel<2",
+               "instance_multihit_walk_kernel<4", "instance_multihit_walk_kernel<8", "instance_multihit_walk_kernel<16",
+               "instance_multihit_resolve_kernel",
+               # instanced directional occlusion (kernels/instance_directional.hip.h): the nested walks, ao_mask_kernel's tail
+               "instance_ao_mask_kernel<1", "instance_ao_mask_kernel<2")
     # the directional occlusion queries' walk is ao_query_kernel's with another tail (kernels/directional.hip.h): it must keep
     # that kernel's occupancy, 8 waves per SIMD -- a tail that needs more live state than the old one shows here
     full_occupancy = ("ao_mask_kernel<1", "ao_mask_kernel<2")
@@ -171,7 +177,8 @@ def main():
         for k in found:
             if k.get("VGPRs Spill") != "0" or k.get("ScratchSize [bytes/lane]") != "0":
                 errors.append(f"{q}: VGPR spill {k.get('VGPRs Spill')}, scratch {k.get('ScratchSize [bytes/lane]')} B/lane in a ray-query kernel")
-            if k.get("SGPRs Spill") != "0" and q.startswith(("ao_mask_kernel", "ao_directional_finish_kernel", "ao_rays_kernel")):
+            if k.get("SGPRs Spill") != "0" and q.startswith(("ao_mask_kernel", "ao_directional_finish_kernel", "ao_rays_kernel",
+                                                                 "instance_ao_mask_kernel")):
                 errors.append(f"{q}: SGPR spill {k.get('SGPRs Spill')} in a directional-occlusion kernel")
             if q in full_occupancy and k.get("Occupancy [waves/SIMD]") != "8":
                 errors.append(f"{q}: occupancy {k.get('Occupancy [waves/SIMD]')} waves/SIMD, ao_query_kernel's walk runs at 8")
