@@ -711,9 +711,10 @@ void launch_ao_rays(const SceneBuffers &scene, int ao_mode, uint32_t rays_per_po
 // a slot array is given.  `set`: null, or the instance set the rays are cast against (kernels/instance_multihit.hip.h):
 // `list` is then n * k * 3 words, and `instance` the slot array beside the record's.
 template <uint32_t K>
-static void launch_multihit_walk(const MultiHitArgs &plain, const InstanceMultiHitArgs *instanced, dim3 blocks, dim3 lanes, hipStream_t s) {
+static void launch_multihit_walk(const InstanceMultiHitArgs &a, bool instanced, dim3 blocks, dim3 lanes, hipStream_t s) {
+	const MultiHitArgs &plain = a;
 	if (instanced)
-		hipLaunchKernelGGL(instance_multihit_walk_kernel<K>, blocks, lanes, 0, s, *instanced);
+		hipLaunchKernelGGL(instance_multihit_walk_kernel<K>, blocks, lanes, 0, s, a);
 	else
 		hipLaunchKernelGGL(multihit_walk_kernel<K>, blocks, lanes, 0, s, plain);
 }
@@ -724,22 +725,16 @@ void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const Insta
 	if (n == 0 || k > MULTIHIT_MAX_K || (set && set->top_count == 0))
 		return;
 	hipStream_t s = (hipStream_t) stream;
-	MultiHitArgs a{};
-	InstanceMultiHitArgs b{};
+	InstanceMultiHitArgs a{};
+	fill(a, scene, node_count, origins, directions, order, n, max_distance, out);
+	a.k = k;
+	a.list = (uint32_t *) list;
+	a.count = out.count;
 	if (set) {
-		fill(b, scene, node_count, origins, directions, order, n, max_distance, out);
-		b.set = instance_set(*set);
-		b.k = k;
-		b.list = (uint32_t *) list;
-		b.count = out.count;
-		b.instance = instance;
-	} else {
-		fill(a, scene, node_count, origins, directions, order, n, max_distance, out);
-		a.k = k;
-		a.list = (uint2 *) list;
-		a.count = out.count;
+		a.set = instance_set(*set);
+		a.instance = instance;
 	}
-	const InstanceMultiHitArgs *const instanced = set ? &b : nullptr;
+	const bool instanced = set != nullptr;
 	const dim3 blocks((n + MULTIHIT_LANES - 1u) / MULTIHIT_LANES), lanes(MULTIHIT_LANES);
 	if (k == 0u)
 		launch_multihit_walk<0u>(a, instanced, blocks, lanes, s);
@@ -755,10 +750,11 @@ void launch_multihit(const SceneBuffers &scene, uint32_t node_count, const Insta
 		launch_multihit_walk<16u>(a, instanced, blocks, lanes, s);
 	if (k == 0u || !(out.anySlot() || (set && instance)))
 		return;
+	const MultiHitArgs &plain = a;
 	if (set)
-		hipLaunchKernelGGL(instance_multihit_resolve_kernel, dim3((n * k + 255u) / 256u), dim3(256), 0, s, b);
+		hipLaunchKernelGGL(instance_multihit_resolve_kernel, dim3((n * k + 255u) / 256u), dim3(256), 0, s, a);
 	else
-		hipLaunchKernelGGL(multihit_resolve_kernel, dim3((n * k + 255u) / 256u), dim3(256), 0, s, a);
+		hipLaunchKernelGGL(multihit_resolve_kernel, dim3((n * k + 255u) / 256u), dim3(256), 0, s, plain);
 }
 
 // The list of a chunk's hit sub-pixels from the flags its ray kernel left (kernels/views.hip.h): m = the chunk's sub-pixels.

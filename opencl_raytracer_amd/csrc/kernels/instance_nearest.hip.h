@@ -235,25 +235,8 @@ __global__ __launch_bounds__(64 * NEAREST_WAVES) __attribute__((amdgpu_waves_per
 		a.out.distance[idx] = found ? distance : __builtin_inff();
 	if (a.out.leaf)
 		a.out.leaf[idx] = found ? best.leaf : NONE;
-	const float b0 = found ? 1.0f - best.s - best.t : 0.0f, b1 = found ? best.s : 0.0f, b2 = found ? best.t : 0.0f;
-	if (a.out.barycentric) {
-		a.out.barycentric[3u * (size_t) idx + 0u] = b0;
-		a.out.barycentric[3u * (size_t) idx + 1u] = b1;
-		a.out.barycentric[3u * (size_t) idx + 2u] = b2;
-	}
-	if (a.out.position) {
-		a.out.position[3u * (size_t) idx + 0u] = found ? best.px : 0.0f;
-		a.out.position[3u * (size_t) idx + 1u] = found ? best.py : 0.0f;
-		a.out.position[3u * (size_t) idx + 2u] = found ? best.pz : 0.0f;
-	}
-	if (a.out.normal) {  // the instanced record's normal (instance_normal)
-		float wx = 0.0f, wy = 0.0f, wz = 0.0f;
-		if (found)
-			instance_normal(a.shade, a.set.inverses, best.leaf, best_instance, b0, b1, b2, wx, wy, wz);
-		a.out.normal[3u * (size_t) idx + 0u] = wx;
-		a.out.normal[3u * (size_t) idx + 1u] = wy;
-		a.out.normal[3u * (size_t) idx + 2u] = wz;
-	}
+	instance_store_record(a.out, idx, a.shade, a.set.inverses, best.leaf, best_instance, found, found ? 1.0f - best.s - best.t : 0.0f,
+	                      found ? best.s : 0.0f, found ? best.t : 0.0f, found ? best.px : 0.0f, found ? best.py : 0.0f, found ? best.pz : 0.0f);
 }
 
 }  // namespace ocrt

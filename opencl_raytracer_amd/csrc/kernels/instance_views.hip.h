@@ -65,7 +65,7 @@ __global__ __launch_bounds__(64 * LAYERS_WAVES) void instance_layers_kernel(Inst
 		return;
 	const uint32_t seed = y * a.width + x;          // the sub-pixel's index within its view
 	const size_t idx = (size_t) view * a.n + seed;  // ... and within the launch: view v's block of every layer
-	// the record, as instance_kernel<true> writes it
+	// the record, as instance_kernel<true> writes it (not through instance_store_record: the normal also feeds the head-light term and the list)
 	if (a.hit)
 		a.hit[idx] = hit ? 1u : 0u;
 	const bool kept = hit && best.distance < __builtin_inff();  // (the record was replaced at least once)

@@ -6,8 +6,8 @@
 // instance_walk<CLOSEST> is two nested exact walks (walk.hip.h, exact_walk).  The OUTER walk runs over the top-level records
 // (csrc/instances.cc) with the world ray: lane by lane the reference's slab test where the lane's own walk stands, so a lane
 // ENTERS an instance iff every box on the way to its leaf passes.  At a leaf the instance index is wave-uniform: the twelve
-// floats of its object_from_world arrive by scalar loads, every lane forms its object ray -- products and sums in the
-// header's order, each rounded on its own -- and the INNER walk runs over the scene's own records with `alive && entered`
+// floats of its object_from_world arrive by scalar loads, every lane forms its object ray (instance_object_ray: products and
+// sums in the header's order, each rounded on its own) and the INNER walk runs over the scene's own records with `alive && entered`
 // as its `alive`.  Its leaf step is the caller's triangle test on the OBJECT ray handing the plane parameter r back: for
 // rays, ambient occlusion and layers tri_eval's operations in tri_eval's order (instance_tri_eval; not segment_tri_eval,
 // whose interval rejects a NaN r), for segments and masks segment_tri_eval<false> with the call's interval.  An affine map
@@ -18,6 +18,10 @@
 // instance_kernel<CLOSEST>: a ray per lane, a packet of 64 per wave, query_kernel's shape, around that walk -- written out in
 // the kernel, the one caller that measured slower through the function; the candidate and the
 // record's epilogue are the shared ones.
+//
+// The record's epilogue of every instanced kernel that writes one is instance_store_record: query.hip.h's store_record with
+// instance_normal for the normal (the instanced multi-hit resolve: the same two inside multihit.hip.h's resolve body).
+// (instance_layers_kernel alone forms the normal itself: the head-light term and the ambient-occlusion list read it.)
 #pragma once
 #include "query.hip.h"
 
@@ -88,6 +92,18 @@ __device__ __forceinline__ TriResult instance_tri_eval(const float4 q0, const fl
 	return out;
 }
 
+// The object ray of a world ray under the rows m0, m1, m2 of an object_from_world: origin O o + t, direction O d, products
+// and sums in the header's order.
+__device__ __forceinline__ void instance_object_ray(const float4 m0, const float4 m1, const float4 m2, float wox, float woy, float woz, float wdx,
+                                                    float wdy, float wdz, float &ox, float &oy, float &oz, float &dx, float &dy, float &dz) {
+	ox = ((m0.x * wox + m0.y * woy) + m0.z * woz) + m0.w;
+	oy = ((m1.x * wox + m1.y * woy) + m1.z * woz) + m1.w;
+	oz = ((m2.x * wox + m2.y * woy) + m2.z * woz) + m2.w;
+	dx = (m0.x * wdx + m0.y * wdy) + m0.z * wdz;
+	dy = (m1.x * wdx + m1.y * wdy) + m1.z * wdz;
+	dz = (m2.x * wdx + m2.y * wdy) + m2.z * wdz;
+}
+
 // nearer() with the instance between the distance and the leaf: a strictly smaller distance wins, and among equal
 // distances below +inf the lower (instance, leaf) pair -- the top-level tree lists the instances in an order of its own.
 __device__ __forceinline__ bool instance_nearer(float distance, uint32_t instance, uint32_t leaf, const Hit &best, uint32_t best_instance) {
@@ -107,12 +123,8 @@ __device__ __forceinline__ bool instance_walk(const InstanceSet &set, const floa
 		// (k comes out of a scalar register: the rows arrive by scalar loads, into SGPRs)
 		float4 m0, m1, m2;
 		scalar_load_rows(set.inverses, k, m0, m1, m2);
-		const float ox = ((m0.x * ray.ox + m0.y * ray.oy) + m0.z * ray.oz) + m0.w;
-		const float oy = ((m1.x * ray.ox + m1.y * ray.oy) + m1.z * ray.oz) + m1.w;
-		const float oz = ((m2.x * ray.ox + m2.y * ray.oy) + m2.z * ray.oz) + m2.w;
-		const float dx = (m0.x * ray.dx + m0.y * ray.dy) + m0.z * ray.dz;
-		const float dy = (m1.x * ray.dx + m1.y * ray.dy) + m1.z * ray.dz;
-		const float dz = (m2.x * ray.dx + m2.y * ray.dy) + m2.z * ray.dz;
+		float ox, oy, oz, dx, dy, dz;
+		instance_object_ray(m0, m1, m2, ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz, ox, oy, oz, dx, dy, dz);
 		// make_ray ballots: the whole wave calls it, the lanes that did not enter with a ray that walks nothing
 		const Ray object = make_ray(entered ? ox : 0.0f, entered ? oy : 0.0f, entered ? oz : 0.0f, entered ? dx : 1.0f, entered ? dy : 1.0f,
 		                            entered ? dz : 1.0f);
@@ -182,6 +194,14 @@ __device__ __forceinline__ void instance_normal(const float4 *shade, const float
 	normalize3(wx, wy, wz);
 }
 
+// The instanced record's epilogue: store_record (query.hip.h) with instance_normal.
+__device__ __forceinline__ void instance_store_record(const RecordOutputs &out, size_t slot, const float4 *shade, const float4 *inverses,
+                                                      uint32_t leaf, uint32_t instance, bool shaded, float b0, float b1, float b2, float px,
+                                                      float py, float pz) {
+	store_record(out, slot, shaded, b0, b1, b2, px, py, pz,
+	             [&](float &wx, float &wy, float &wz) { instance_normal(shade, inverses, leaf, instance, b0, b1, b2, wx, wy, wz); });
+}
+
 // The closest forms' record into `idx` of the arrays that were asked for (the flag is the caller's).  Where some triangle
 // is accepted but none replaces the record it keeps its entry values, as closest_store's does.
 __device__ __forceinline__ void instance_record_store(const RecordOutputs &out, uint32_t *instance, uint32_t idx, const float4 *shade,
@@ -193,30 +213,14 @@ __device__ __forceinline__ void instance_record_store(const RecordOutputs &out, 
 		out.distance[idx] = best.distance;
 	if (out.leaf)
 		out.leaf[idx] = hit ? best.leaf : NONE;
-	const float b0 = kept ? 1.0f - best.s - best.t : 0.0f, b1 = kept ? best.s : 0.0f, b2 = kept ? best.t : 0.0f;
-	if (out.barycentric) {
-		out.barycentric[3u * (size_t) idx + 0u] = b0;
-		out.barycentric[3u * (size_t) idx + 1u] = b1;
-		out.barycentric[3u * (size_t) idx + 2u] = b2;
-	}
-	if (out.position) {
-		out.position[3u * (size_t) idx + 0u] = kept ? best.px : 0.0f;
-		out.position[3u * (size_t) idx + 1u] = kept ? best.py : 0.0f;
-		out.position[3u * (size_t) idx + 2u] = kept ? best.pz : 0.0f;
-	}
-	if (out.normal) {
-		float wx = 0.0f, wy = 0.0f, wz = 0.0f;
-		if (hit)
-			instance_normal(shade, inverses, best.leaf, best_instance, b0, b1, b2, wx, wy, wz);
-		out.normal[3u * (size_t) idx + 0u] = wx;
-		out.normal[3u * (size_t) idx + 1u] = wy;
-		out.normal[3u * (size_t) idx + 2u] = wz;
-	}
+	instance_store_record(out, idx, shade, inverses, best.leaf, best_instance, hit, kept ? 1.0f - best.s - best.t : 0.0f, kept ? best.s : 0.0f,
+	                      kept ? best.t : 0.0f, kept ? best.px : 0.0f, kept ? best.py : 0.0f, kept ? best.pz : 0.0f);
 }
 
 // (instance_kernel keeps the walk's lines inline: through instance_walk the compiler schedules both instantiations
 // differently, and they measured 2 to 5 % slower on the MI355X -- DESIGN.md section 24.  What the walk does is
-// instance_walk's comment, word for word, with instance_tri_eval at the leaf.)
+// instance_walk's comment, word for word, with instance_tri_eval at the leaf; the object ray's six lines are
+// instance_object_ray's.)
 template <bool CLOSEST>
 __global__ __launch_bounds__(64 * QUERY_WAVES) void instance_kernel(InstanceArgs a) {
 	bool live;

@@ -161,10 +161,11 @@ __device__ __forceinline__ Ray packet_ray(const RayQueryArgs &a, uint32_t k, boo
 	return make_ray(o.x, o.y, o.z, d.x, d.y, d.z);
 }
 
-// Barycentrics, point and smooth normal of a record into `slot` of the arrays that were asked for; `shaded` false: a
-// zero normal.
-__device__ __forceinline__ void store_record(const RecordOutputs &out, size_t slot, const float4 *shade, uint32_t leaf, bool shaded,
-                                             float b0, float b1, float b2, float px, float py, float pz) {
+// Barycentrics, point and normal of a record into `slot` of the arrays that were asked for.  The normal is
+// normal(nx, ny, nz)'s, called only where one is asked for and the record is `shaded`; else zeros.
+template <class Normal>
+__device__ __forceinline__ void store_record(const RecordOutputs &out, size_t slot, bool shaded, float b0, float b1, float b2, float px, float py,
+                                             float pz, Normal &&normal) {
 	if (out.barycentric) {
 		out.barycentric[3u * slot + 0u] = b0;
 		out.barycentric[3u * slot + 1u] = b1;
@@ -178,11 +179,17 @@ __device__ __forceinline__ void store_record(const RecordOutputs &out, size_t sl
 	if (out.normal) {
 		float nx = 0.0f, ny = 0.0f, nz = 0.0f;
 		if (shaded)
-			smooth_normal(shade, leaf, b0, b1, b2, nx, ny, nz);
+			normal(nx, ny, nz);
 		out.normal[3u * slot + 0u] = nx;
 		out.normal[3u * slot + 1u] = ny;
 		out.normal[3u * slot + 2u] = nz;
 	}
+}
+
+// The plain kernels' form: the smooth normal of `leaf` (smooth_normal).
+__device__ __forceinline__ void store_record(const RecordOutputs &out, size_t slot, const float4 *shade, uint32_t leaf, bool shaded,
+                                             float b0, float b1, float b2, float px, float py, float pz) {
+	store_record(out, slot, shaded, b0, b1, b2, px, py, pz, [&](float &nx, float &ny, float &nz) { smooth_normal(shade, leaf, b0, b1, b2, nx, ny, nz); });
 }
 
 // The closest-hit record of one ray, CLOSEST's contract below, for the kernels that make their own rays (layers_kernel).

@@ -82,14 +82,15 @@ def test_multihit_matches_oracle(rt, hosts, mesh, bvh):
 
 @pytest.mark.parametrize("bvh", BVHS)
 def test_layered_scene_overflow_and_ties(rt, hosts, bvh):
-    """Lists that overflow and evict (more than 16 layers along a ray) and equal distances ordered by the leaf index."""
+    """Lists that overflow and evict (more than 16 layers along a ray) and equal distances ordered by the leaf index, for
+    every k: each instantiation of the walk (1, 2, 4, 8, 16 slots a lane) with a full list and with k below its slots."""
     host, _, arrays = hosts("layered", bvh)
     o, d, _ = mo.layered_rays(arrays)
     full = oracle_for(("layered", bvh), arrays, o, d, 100000.0)
-    for k in (1, 3, 8, 16):
+    for k in range(1, mo.MAX_K + 1):
         check(host, full, o, d, 100000.0, k)
     check(host, full, o, d, 100000.0, 16, sort=False)
-    assert np.array_equal(host.count_hits(o, d), full["count"])
+    assert np.array_equal(host.count_hits(o, d), full["count"])  # k = 0: the count alone
 
 
 def odd_rays(arrays, n=4000, seed=3):
