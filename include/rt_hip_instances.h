@@ -10,7 +10,8 @@
  * rt_instances_segments_closest and rt_instances_visibility_masks (rt_hip_instance_segments.h).  Closest-point queries have
  * one with rules of its own, in world space: rt_instances_closest_points (rt_hip_instance_nearest.h).  Multi-hit and
  * directional occlusion queries have theirs by the same rules: rt_trace_instances_multihit (rt_hip_instance_multihit.h) and
- * rt_trace_instances_ao_directional (rt_hip_instance_directional.h).
+ * rt_trace_instances_ao_directional (rt_hip_instance_directional.h).  A set can also be made on the device, from transforms
+ * in device memory: rt_build_instances_device (rt_hip_instance_build.h).
  *
  * Transforms.  world_from_object is twelve floats per instance, the rows of W = [A | t]: p_world = A p + t.  Every entry
  * must be finite, the determinant of A (binary64) non-zero and every entry of the inverse finite after its rounding to

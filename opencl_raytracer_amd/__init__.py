@@ -34,6 +34,7 @@ from .api import (  # noqa: F401
     rccl_available,
     rccl_unique_id,
     instance_plan,
+    instance_plan_lbvh,
     resize_cpu,
     unpack_ao_mask,
     unpack_visibility_mask,

@@ -1,5 +1,5 @@
 """ctypes binding of include/rt_hip.h, rt_hip_ring.h, rt_hip_debug.h, rt_hip_query.h, rt_hip_multihit.h, rt_hip_ao.h,
-rt_hip_nearest.h, rt_hip_segment.h, rt_hip_instances.h, rt_hip_instance_segments.h, rt_hip_instance_views.h, rt_hip_instance_multihit.h, rt_hip_instance_directional.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers
+rt_hip_nearest.h, rt_hip_segment.h, rt_hip_instances.h, rt_hip_instance_build.h, rt_hip_instance_segments.h, rt_hip_instance_views.h, rt_hip_instance_multihit.h, rt_hip_instance_directional.h, rt_hip_directional.h, rt_hip_layers.h, rt_hip_views.h, rt_hip_update.h and rt_hip_camera.h (see those headers
 for the contract)."""
 from __future__ import annotations
 
@@ -268,6 +268,13 @@ _SIGNATURES = {
     "rt_trace_instances_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p,
                                                      C.c_void_p]),
     "rt_instance_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    # include/rt_hip_instance_build.h
+    "rt_build_instances_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rt_build_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rt_instances_world_from_object": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_instance_bounds": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rt_last_instance_build_ms": (C.c_float, [C.c_void_p]),
+    "rt_instance_plan_lbvh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     # include/rt_hip_nearest.h
     "rt_closest_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
     "rt_closest_points_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
@@ -570,6 +577,22 @@ def instance_plan(root_lo, root_hi, transforms) -> dict:
     if rc != 0:
         raise RtError(rc, "rt_instance_plan: no transforms, too many, or a refused transform")
     return {"object_from_world": inverse, "nodes": nodes}
+
+
+def instance_plan_lbvh(root_lo, root_hi, transforms) -> dict:
+    """What a device-side instance build makes, restated on the host (rt_instance_plan_lbvh,
+    include/rt_hip_instance_build.h; no device): {"object_from_world": float32 (n, 3, 4), "nodes": INSTANCE_NODE (2n - 1,),
+    the radix tree over the leaf boxes' Morton keys, "bounds": float32 (n, 4), the closest-point walk's} for a scene whose
+    root box is (root_lo, root_hi).  RtError -1 for a refused transform."""
+    w = _transforms12(transforms)
+    lo, hi = np.ascontiguousarray(root_lo, np.float32).reshape(3), np.ascontiguousarray(root_hi, np.float32).reshape(3)
+    n = int(w.shape[0])
+    inverse, nodes, bounds = np.zeros((n, 3, 4), np.float32), np.zeros(max(2 * n - 1, 0), INSTANCE_NODE), np.zeros((n, 4), np.float32)
+    rc = load_library().rt_instance_plan_lbvh(lo.ctypes.data, hi.ctypes.data, w.ctypes.data, n, inverse.ctypes.data, nodes.ctypes.data,
+                                              bounds.ctypes.data)
+    if rc != 0:
+        raise RtError(rc, "rt_instance_plan_lbvh: no transforms, too many, or a refused transform")
+    return {"object_from_world": inverse, "nodes": nodes, "bounds": bounds}
 
 
 def load_library() -> C.CDLL:
@@ -1009,13 +1032,61 @@ class Host:
         w = _transforms12(transforms)
         _check(load_library().rt_set_instances(self._h, w.ctypes.data if len(w) else None, len(w)))
         self._instance_transforms = w.copy()  # (what instances() hands back: the library keeps its own copy)
+        self._instances_built = False
+
+    def build_instances(self, transforms) -> None:
+        """set_instances with the set made ON the device (rt_build_instances, include/rt_hip_instance_build.h): inverses,
+        bounds and the top-level tree -- a radix tree over Morton keys, instance_plan_lbvh restates it -- come from kernels;
+        every instanced query runs on the set as on set_instances's.  `transforms`: a float32 numpy array (n, 3, 4) (one
+        upload), or a contiguous float32 torch tensor (n, 3, 4) on the host's GPU, whose pointer is handed over with no host
+        copy, enqueued on torch.cuda.current_stream(); the tensor may be reused on return.  The call waits once, for 36
+        bytes.  n = 0 clears the set; the set replaces set_instances's and is replaced by it.  RtError -1 for a refused
+        transform, found on the device: the host's set stays what it was."""
+        lib = load_library()
+        if _is_torch(transforms):
+            import torch
+
+            t = transforms
+            if t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape[1:]) != (3, 4):
+                raise ValueError("transforms: expected a float32 tensor of shape (n, 3, 4), the rows of [A | t]")
+            if t.device.type != "cuda" or (t.device.index is not None and t.device.index != self._device):
+                raise ValueError("transforms: the tensor must be on the host's GPU")
+            if not t.is_contiguous():
+                raise ValueError("transforms: the tensor must be contiguous")
+            n = int(t.shape[0])
+            if n and t.data_ptr() % 16:
+                raise ValueError("transforms: the tensor's memory must be 16-byte aligned")
+            _check(lib.rt_build_instances_device(self._h, t.data_ptr() if n else None, n, torch.cuda.current_stream(t.device).cuda_stream))
+        else:
+            if not isinstance(transforms, np.ndarray):
+                raise ValueError("transforms: expected a float32 numpy array or torch tensor of shape (n, 3, 4)")
+            w = _transforms12(transforms)
+            _check(lib.rt_build_instances(self._h, w.ctypes.data if len(w) else None, len(w)))
+        self._instance_transforms = np.zeros((0, 3, 4), np.float32)
+        self._instances_built = True
+
+    def instance_bounds(self) -> np.ndarray:
+        """float32 (n, 4): what the instanced closest-point walk holds a copy's boxes against (rt_instance_bounds), for a
+        set of either kind, as it is on the device (made again first if the scene changed)."""
+        lib = load_library()
+        out = np.zeros((int(lib.rt_instance_count(self._h)), 4), np.float32)
+        _check(lib.rt_instance_bounds(self._h, out.ctypes.data))
+        return out
+
+    def last_instance_build_ms(self) -> float:
+        """HIP-event time of the planning launches of the last device-side plan of the set, a build or a refresh (0: none)."""
+        return float(load_library().rt_last_instance_build_ms(self._h))
 
     def instances(self) -> dict:
         """{"world_from_object": float32 (n, 3, 4) as given, "object_from_world": float32 (n, 3, 4) as the kernel uses it,
-        "nodes": INSTANCE_NODE (2n - 1,), the top-level tree as it is on the device (made again first if the scene changed)}."""
+        "nodes": INSTANCE_NODE (2n - 1,), the top-level tree as it is on the device (made again first if the scene changed)}.
+        A set made by build_instances has all three read from the device."""
         lib = load_library()
         n = int(lib.rt_instance_count(self._h))
         world, inverse = getattr(self, "_instance_transforms", np.zeros((0, 3, 4), np.float32)).copy(), np.zeros((n, 3, 4), np.float32)
+        if getattr(self, "_instances_built", False):
+            world = np.zeros((n, 3, 4), np.float32)
+            _check(lib.rt_instances_world_from_object(self._h, world.ctypes.data))
         nodes = np.zeros(int(lib.rt_instance_node_count(self._h)), INSTANCE_NODE)
         _check(lib.rt_instances_object_from_world(self._h, inverse.ctypes.data))
         _check(lib.rt_instance_nodes(self._h, nodes.ctypes.data))

@@ -11,6 +11,7 @@
 #include "../../include/rt_hip_nearest.h"
 #include "../../include/rt_hip_query.h"
 #include "../../include/rt_hip_segment.h"
+#include "../../include/rt_hip_instance_build.h"
 #include "../../include/rt_hip_instance_directional.h"
 #include "../../include/rt_hip_instance_multihit.h"
 #include "../../include/rt_hip_instance_nearest.h"
@@ -1109,9 +1110,64 @@ int rt_instances_object_from_world(rt_host *h, float *out) {
 	const int rc = owned_precheck(h, "instanced ray");
 	if (rc != RT_OK)
 		return rc;
-	if (out && h->queries)
-		std::copy(h->queries->instanceInverses().begin(), h->queries->instanceInverses().end(), out);
-	return RT_OK;
+	if (!out || !h->queries)
+		return RT_OK;
+	return guarded([&] { h->queries->instanceInverses(out); });
+}
+
+// ---- rt_hip_instance_build.h ----
+int rt_build_instances_device(rt_host *h, const float *world_from_object, uint32_t n, void *hip_stream) {
+	const int rc = owned_precheck(h, "instanced ray");
+	if (rc != RT_OK)
+		return rc;
+	if (n > RT_INSTANCES_MAX)
+		return fail(RT_E_INVALID, "more instances than RT_INSTANCES_MAX");
+	if (n > 0 && !world_from_object)
+		return fail(RT_E_INVALID, "null transform array");
+	if (n > 0 && !aligned({ world_from_object }, 16))
+		return fail(RT_E_INVALID, "the device transform array must be 16-byte aligned");
+	if (n == 0 && !h->queries)
+		return RT_OK;
+	return guarded([&] { queries_of(h).buildInstancesDevice(world_from_object, n, hip_stream); });
+}
+
+int rt_build_instances(rt_host *h, const float *world_from_object, uint32_t n) {
+	const int rc = owned_precheck(h, "instanced ray");
+	if (rc != RT_OK)
+		return rc;
+	if (n > RT_INSTANCES_MAX)
+		return fail(RT_E_INVALID, "more instances than RT_INSTANCES_MAX");
+	if (n > 0 && !world_from_object)
+		return fail(RT_E_INVALID, "null transform array");
+	if (n == 0 && !h->queries)
+		return RT_OK;
+	return guarded([&] { queries_of(h).buildInstancesHost(world_from_object, n); });
+}
+
+int rt_instances_world_from_object(rt_host *h, float *out) {
+	const int rc = owned_precheck(h, "instanced ray");
+	if (rc != RT_OK)
+		return rc;
+	if (!out || !h->queries)
+		return RT_OK;
+	return guarded([&] { h->queries->instanceWorld(out); });
+}
+
+int rt_instance_bounds(rt_host *h, float *out) {
+	const int rc = host_precheck(h, "instanced ray");
+	if (rc != RT_OK)
+		return rc;
+	if (!h->queries || h->queries->instanceCount() == 0)
+		return fail(RT_E_STATE, "instance bounds without an instance set (rt_set_instances, rt_build_instances)");
+	return guarded([&] { h->queries->instanceBounds(out); });
+}
+
+float rt_last_instance_build_ms(rt_host *h) {
+	if (!h || !h->queries)
+		return 0.0f;
+	float ms = 0.0f;
+	guarded([&] { ms = h->queries->lastInstanceBuildMs(); });
+	return ms;
 }
 
 int rt_instance_nodes(rt_host *h, void *out) {

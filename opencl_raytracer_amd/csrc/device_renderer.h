@@ -432,6 +432,9 @@ void launch_node_test_forms(const void *records, uint32_t boxes, const void *ray
 uint32_t build_partials(uint32_t faces);
 void launch_build_keys(const BuildBuffers &b, void *stream);
 void launch_build_tree(const BuildBuffers &b, void *stream);
+// Device-side instance sets (kernels/instance_build.hip.h; InstancePlanBuffers: device_types.h), around the same sort
+void launch_instance_keys(const InstancePlanBuffers &b, void *stream);
+void launch_instance_tree(const InstancePlanBuffers &b, void *stream);
 // build_sort.hip
 size_t build_sort_bytes(uint32_t pairs);
 void launch_build_sort(void *temporary, size_t temporary_bytes, const void *keys_in, void *keys_out, const void *ids_in, void *ids_out,

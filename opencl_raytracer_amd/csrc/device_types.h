@@ -195,6 +195,15 @@ struct BuildBuffers {
 	    *skips, *leaf_node;
 };
 
+// What the launches of a device-side instance build work on (kernels/instance_build.hip.h, InstanceBuildArgs: every array's
+// size is given there).  `reach`, `box`: one double and two float4 for the reductions of a set of many workgroups.
+struct InstancePlanBuffers {
+	const void *world, *scene_root;
+	uint32_t n;
+	void *inverse, *flag, *reach_partials, *reach, *leaves, *bounds, *box_partials, *box, *keys, *ids, *sorted_keys, *sorted_ids, *ranges,
+	    *inner_links, *leaf_links, *counters, *inner_at, *leaf_at, *nodes;
+};
+
 // Outputs of the ray queries (ray_query.h) as their launchers take them: device pointers, null = not written.
 // What a closest-hit query and a multi-hit query both write, by ray index or by ray and slot (slot j of ray i at i * k + j):
 struct RecordOutputs {

@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "instance_plan.h"
+
 namespace ocrt {
 
 // The record the exact walk reads (device_types.h, NodeRec): `skip` the subtree's size, `leaf` the instance or INSTANCE_INNER.
@@ -17,8 +19,8 @@ struct InstanceNode {
 static_assert(sizeof(InstanceNode) == 32, "InstanceNode is NodeRec");
 constexpr uint32_t INSTANCE_INNER = 0xFFFFFFFFu;
 
-// object_from_world of one transform by the header's formula; false where the header refuses the transform (`O` untouched).
-bool instance_inverse(const float W[12], float O[12]);
+// (instance_inverse -- object_from_world of one transform by the header's formula -- and the rest of one instance's
+// arithmetic: instance_plan.h, included above)
 // Every transform of the set, or none: false, and `O` untouched, where one is refused.  O: n * 12 floats.
 bool instance_inverses(const float *W, uint32_t n, std::vector<float> &O);
 // What the instanced closest-point walk holds a copy's object-space boxes against (instance_nearest.h, inp_bounds: scale,
@@ -27,5 +29,10 @@ bool instance_inverses(const float *W, uint32_t n, std::vector<float> &O);
 void instance_bounds(const float root_lo[3], const float root_hi[3], const float *W, const float *O, uint32_t n, std::vector<float> &bounds);
 // The tree over n >= 1 accepted transforms and their inverses: 2n - 1 records in pre-order.
 void instance_tree(const float root_lo[3], const float root_hi[3], const float *W, const float *O, uint32_t n, std::vector<InstanceNode> &nodes);
+// The leaf records of that tree alone, by instance index (skip 1, leaf k): the boxes both trees are made over.
+void instance_leaves(const float root_lo[3], const float root_hi[3], const float *W, const float *O, uint32_t n, std::vector<InstanceNode> &leaves);
+// What a device-side instance build makes (include/rt_hip_instance_build.h; instance_build.cc), restated on the host: the
+// radix tree of lbvh.h over the leaves' keys, 2n - 1 records in pre-order, from leaf records by instance index.
+void instance_lbvh_tree(const std::vector<InstanceNode> &leaves, std::vector<InstanceNode> &nodes);
 
 }  // namespace ocrt

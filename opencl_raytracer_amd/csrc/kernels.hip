@@ -71,7 +71,11 @@
 //   (scenes)        refit_leaves_kernel / refit_inner_kernel make the records and boxes of a scene again from new positions
 //                   (kernels/refit.hip.h, include/rt_hip_update.h); build_boxes_kernel, build_root_kernel, build_keys_kernel,
 //                   build_tree_kernel and build_layout_kernel make a scene's tree from triangles, around a sort that lives in
-//                   build_sort.hip (kernels/build.hip.h, include/rt_hip_build.h).
+//                   build_sort.hip (kernels/build.hip.h, include/rt_hip_build.h); instance_inverse_kernel, instance_reach_kernel,
+//                   instance_leaves_kernel, instance_root_kernel, instance_keys_kernel, instance_tree_kernel,
+//                   instance_layout_kernel and instance_boxes_kernel make an instance set -- inverses, bounds, top-level tree --
+//                   from transforms in device memory, around the same sort (kernels/instance_build.hip.h,
+//                   include/rt_hip_instance_build.h).
 //   (on demand)     entry_kernel: the walk intervals, once per upload; occluded_sum_kernel: the frame's occlusion
 //                   total when the statistics are asked for; resize_kernel: a box filter on its own.
 //   (tests)         node_test_forms_kernel: the any-hit node test against the form it replaced, on the caller's records and
@@ -99,6 +103,7 @@
 #include "device_types.h"
 #include "exact_reciprocal.h"
 #include "lbvh.h"
+#include "instance_plan.h"
 #include "nearest_point.h"
 #include "instance_nearest.h"
 #include "tri_predicate.h"
@@ -117,6 +122,7 @@
 #include "kernels/views.hip.h"
 #include "kernels/refit.hip.h"
 #include "kernels/build.hip.h"
+#include "kernels/instance_build.hip.h"
 #include "kernels/node_test_forms.hip.h"
 #include "kernels/nearest.hip.h"
 #include "kernels/segment.hip.h"
@@ -927,6 +933,73 @@ void launch_build_tree(const BuildBuffers &b, void *stream) {
 	hipLaunchKernelGGL(build_tree_kernel, dim3(build_partials(b.num_faces)), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
 	const uint32_t nodes = 2u * b.num_faces - 1u;
 	hipLaunchKernelGGL(build_layout_kernel, dim3((nodes + BUILD_LANES - 1u) / BUILD_LANES), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
+}
+
+// Device-side instance sets (kernels/instance_build.hip.h, include/rt_hip_instance_build.h): inverses, leaf boxes, bounds and
+// the keys of `b.n` instances with their indices, the pairs the sort takes (build_sort.hip) -- one instance: its leaf record,
+// the whole tree ...
+namespace {
+InstanceBuildArgs instance_build_args(const InstancePlanBuffers &b) {
+	InstanceBuildArgs a{};
+	const uint32_t groups = build_partials(b.n);
+	const bool fused = groups <= INSTANCE_FUSED_PARTIALS;
+	a.world = (const float4 *) b.world;
+	a.inverse = (float4 *) b.inverse;
+	a.n = b.n;
+	a.scene_root = (const float4 *) b.scene_root;
+	a.flag = (uint32_t *) b.flag;
+	a.reach_partials = (double *) b.reach_partials;
+	a.reach = (const double *) (fused ? b.reach_partials : b.reach);
+	a.reach_count = fused ? groups : 1u;
+	a.leaves = (float4 *) b.leaves;
+	a.bounds = (float4 *) b.bounds;
+	a.box_partials = (float4 *) b.box_partials;
+	a.box = (const float4 *) (fused ? b.box_partials : b.box);
+	a.box_count = fused ? groups : 1u;
+	a.keys = (uint32_t *) b.keys;
+	a.ids = (uint32_t *) b.ids;
+	a.sorted_keys = (const uint32_t *) b.sorted_keys;
+	a.sorted_ids = (const uint32_t *) b.sorted_ids;
+	a.ranges = (uint2 *) b.ranges;
+	a.inner_links = (uint32_t *) b.inner_links;
+	a.leaf_links = (uint32_t *) b.leaf_links;
+	a.counters = (uint32_t *) b.counters;
+	a.inner_at = (uint32_t *) b.inner_at;
+	a.leaf_at = (uint32_t *) b.leaf_at;
+	a.nodes = (uint4 *) b.nodes;
+	return a;
+}
+}  // namespace
+
+void launch_instance_keys(const InstancePlanBuffers &b, void *stream) {
+	if (b.n == 0)
+		return;
+	const InstanceBuildArgs a = instance_build_args(b);
+	const uint32_t groups = build_partials(b.n);
+	const bool fused = groups <= INSTANCE_FUSED_PARTIALS;
+	hipLaunchKernelGGL(instance_inverse_kernel, dim3(groups), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
+	if (!fused)
+		hipLaunchKernelGGL(instance_reach_kernel, dim3(1), dim3(BUILD_LANES), 0, (hipStream_t) stream, (const double *) b.reach_partials, groups,
+		                   (double *) b.reach);
+	hipLaunchKernelGGL(instance_leaves_kernel, dim3(groups), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
+	if (b.n == 1u)
+		return;
+	if (!fused)
+		hipLaunchKernelGGL(instance_root_kernel, dim3(1), dim3(BUILD_LANES), 0, (hipStream_t) stream, (const float4 *) b.box_partials, groups,
+		                   (float4 *) b.box);
+	hipLaunchKernelGGL(instance_keys_kernel, dim3(groups), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
+}
+
+// ... and, of the sorted pairs of two instances or more, the tree's shape, its pre-order layout with the leaf records, and the
+// inner boxes.
+void launch_instance_tree(const InstancePlanBuffers &b, void *stream) {
+	if (b.n < 2u)
+		return;
+	const InstanceBuildArgs a = instance_build_args(b);
+	const uint32_t groups = build_partials(b.n), nodes = 2u * b.n - 1u;
+	hipLaunchKernelGGL(instance_tree_kernel, dim3(groups), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
+	hipLaunchKernelGGL(instance_layout_kernel, dim3((nodes + BUILD_LANES - 1u) / BUILD_LANES), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
+	hipLaunchKernelGGL(instance_boxes_kernel, dim3(groups), dim3(BUILD_LANES), 0, (hipStream_t) stream, a);
 }
 
 // Test aid (kernels/node_test_forms.hip.h, include/rt_hip_debug.h): the any-hit node test in both forms, `rays` (a multiple of

@@ -57,9 +57,13 @@ RayQueries::~RayQueries() {
 		return;
 	if (timed)
 		(void) hipEventSynchronize((hipEvent_t) ev_stop);
-	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &ao_rows, &vis_rows, &list, &views, &build, &coords_flag, &nearest_counts, &inst_device })
+	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &ao_rows, &vis_rows, &list, &views, &build, &coords_flag, &nearest_counts, &inst_device,
+		                         &inst_spare, &inst_plan })
 		device_free(scratch->ptr);
 	for (void *ev : ev_build)
+		if (ev)
+			(void) hipEventDestroy((hipEvent_t) ev);
+	for (void *ev : ev_inst)
 		if (ev)
 			(void) hipEventDestroy((hipEvent_t) ev);
 	if (pinned)
@@ -292,8 +296,12 @@ void RayQueries::setInstances(const float *world_from_object, uint32_t n) {
 		throw std::invalid_argument("more instances than RT_INSTANCES_MAX");
 	if (n > 0 && !world_from_object)
 		throw std::invalid_argument("null transform array");
-	if (n > 0 && !instance_inverses(world_from_object, n, inst_inverse))  // (every transform or none: the set stays on a refusal)
+	std::vector<float> inverses;
+	if (n > 0 && !instance_inverses(world_from_object, n, inverses))  // (every transform or none: the set stays on a refusal)
 		throw std::invalid_argument("instance transform refused: an entry that is not finite, a zero determinant, or an inverse that is not finite");
+	inst_inverse.swap(inverses);
+	inst_built = false;  // (a device-built set ends here: include/rt_hip_instance_build.h)
+	inst_built_n = 0;
 	if (n == 0) {
 		inst_inverse.clear();
 		inst_world.clear();
@@ -308,8 +316,17 @@ void RayQueries::setInstances(const float *world_from_object, uint32_t n) {
 
 void RayQueries::requireInstances(const char *what) const {
 	requireScene(what);
-	if (inst_world.empty())
+	if (instanceCount() == 0)
 		throw std::logic_error(std::string(what) + " without an instance set (rt_set_instances)");
+}
+
+void RayQueries::setInstanceBox(const float lo[3], const float hi[3]) {
+	for (int k = 0; k < 3; ++k) {  // (sceneBox's rule, on the top-level root)
+		const float extent = hi[k] - lo[k];
+		const bool usable = std::isfinite(lo[k]) && std::isfinite(extent) && extent > 0.0f && std::isfinite(8.0f / extent);
+		inst_box[k] = usable ? lo[k] : -1.0f;
+		inst_box[3 + k] = usable ? 8.0f / extent : 4.0f;
+	}
 }
 
 // The tree from the root box as it is on the device now, and the set's three arrays into inst_device.  Waits for this
@@ -319,6 +336,11 @@ void RayQueries::refreshInstances() {
 	if (inst_current && inst_scene.lock() == current)
 		return;
 	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	if (inst_built) {  // (on the device, from the transforms that lie there and node 0 as it lies there: nothing to refuse)
+		if (!planInstancesOnDevice((const float *) inst_set.world, inst_built_n, dev.streamHandle()))
+			throw std::logic_error("a device-built instance set was refused when planned again (its transforms were accepted before)");
+		return;
+	}
 	if (timed)
 		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
 	NodeRec root{};
@@ -337,12 +359,7 @@ void RayQueries::refreshInstances() {
 	OCRT_HIP(hipMemcpy(at + 2u * rows, inst_nodes.data(), tree, hipMemcpyHostToDevice));
 	OCRT_HIP(hipMemcpy(at + 2u * rows + tree, bounds.data(), bound_bytes, hipMemcpyHostToDevice));
 	inst_set = InstanceBuffers{ at + 2u * rows, at + rows, (uint32_t) inst_nodes.size(), at, at + 2u * rows + tree };
-	for (int k = 0; k < 3; ++k) {  // (sceneBox's rule, on the top-level root)
-		const float lo = inst_nodes[0].lo[k], extent = inst_nodes[0].hi[k] - lo;
-		const bool usable = std::isfinite(lo) && std::isfinite(extent) && extent > 0.0f && std::isfinite(8.0f / extent);
-		inst_box[k] = usable ? lo : -1.0f;
-		inst_box[3 + k] = usable ? 8.0f / extent : 4.0f;
-	}
+	setInstanceBox(inst_nodes[0].lo, inst_nodes[0].hi);
 	inst_scene = current;
 	inst_current = true;
 }
@@ -354,7 +371,224 @@ void RayQueries::instanceNodes(void *out) {
 	if (timed)
 		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
 	if (out)
-		OCRT_HIP(hipMemcpy(out, inst_set.top, inst_nodes.size() * sizeof(InstanceNode), hipMemcpyDeviceToHost));
+		OCRT_HIP(hipMemcpy(out, inst_set.top, (size_t) inst_set.top_count * sizeof(InstanceNode), hipMemcpyDeviceToHost));
+}
+
+// ---- device-side instance sets (include/rt_hip_instance_build.h) ----
+namespace {
+size_t round256(size_t bytes) { return (bytes + 255u) & ~(size_t) 255u; }
+
+// Where a plan's temporaries lie in inst_plan (kernels/instance_build.hip.h, InstanceBuildArgs, has every array's size).
+struct InstancePlanScratch {
+	size_t reach_partials, reach, leaves, box_partials, box, keys, ids, sorted_keys, sorted_ids, ranges, inner_links, leaf_links, counters, inner_at,
+	    leaf_at, sort, sort_bytes, bytes;
+};
+InstancePlanScratch instance_plan_scratch(uint32_t n) {
+	InstancePlanScratch at{};
+	size_t end = 0;
+	auto take = [&](size_t bytes) {
+		const size_t p = end;
+		end += round256(bytes ? bytes : 1);
+		return p;
+	};
+	const size_t groups = build_partials(n), count = n;
+	at.reach_partials = take(groups * 8);
+	at.reach = take(8);
+	at.leaves = take(count * 32);
+	at.box_partials = take(groups * 32);
+	at.box = take(32);
+	at.keys = take(count * 4);
+	at.ids = take(count * 4);
+	at.sorted_keys = take(count * 4);
+	at.sorted_ids = take(count * 4);
+	at.ranges = take(count * 8);
+	at.inner_links = take(count * 4);
+	at.leaf_links = take(count * 4);
+	at.counters = take(count * 4);
+	at.inner_at = take(count * 4);
+	at.leaf_at = take(count * 4);
+	at.sort_bytes = n >= 2u ? build_sort_bytes(n) : 0;
+	at.sort = take(at.sort_bytes);
+	at.bytes = end;
+	return at;
+}
+}  // namespace
+
+RayQueries::InstanceSetLayout RayQueries::instanceSetLayout(uint32_t n) {
+	InstanceSetLayout at{};
+	const size_t rows = (size_t) n * 12u * sizeof(float), tree = (2u * (size_t) n - 1u) * sizeof(InstanceNode);
+	at.inverse = rows;
+	at.tree = 2u * rows + 16u;  // (16-byte aligned; the flag's word in the four bytes in front: one read brings both)
+	at.flag = at.tree - sizeof(uint32_t);
+	at.bounds = at.tree + tree + sizeof(InstanceNode);  // (a zero record behind the tree, as behind a scene's nodes)
+	at.bytes = at.bounds + (size_t) n * 16u;
+	return at;
+}
+
+void RayQueries::clearInstances() {
+	inst_world.clear();
+	inst_inverse.clear();
+	inst_nodes.clear();
+	inst_built = false;
+	inst_built_n = 0;
+	inst_current = false;
+}
+
+bool RayQueries::planInstancesOnDevice(const float *world_device, uint32_t n, void *stream) {
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
+	// (the queries before it: one of them may still read the allocation the plan before last left as the spare one; an
+	// update on its way to node 0 is waited for too)
+	if (timed)
+		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	const std::shared_ptr<const DeviceScene> scene = dev.sceneReady() ? dev.deviceScene() : nullptr;
+	const bool rooted = scene && scene->nodeCount() > 0;
+	if (rooted && s != (hipStream_t) dev.streamHandle()) {  // (node 0 is read: behind whatever the renderer's stream still does to it)
+		OCRT_HIP(hipEventRecord((hipEvent_t) ev_frames, (hipStream_t) dev.streamHandle()));
+		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_frames, 0));
+	}
+	const InstanceSetLayout set = instanceSetLayout(n);
+	const InstancePlanScratch where = instance_plan_scratch(n);
+	grow(inst_spare, set.bytes);
+	grow(inst_plan, where.bytes);
+	for (void *&ev : ev_inst)
+		if (!ev)
+			OCRT_HIP(hipEventCreate((hipEvent_t *) &ev));
+	char *const made = (char *) inst_spare.ptr, *const base = (char *) inst_plan.ptr;
+	const size_t rows = (size_t) n * 12u * sizeof(float), tree = (2u * (size_t) n - 1u) * sizeof(InstanceNode);
+	OCRT_HIP(hipMemcpyAsync(made, world_device, rows, hipMemcpyDeviceToDevice, s));
+	OCRT_HIP(hipMemsetAsync(made + set.tree - 16u, 0, 16u, s));
+	OCRT_HIP(hipMemsetAsync(made + set.tree + tree, 0, sizeof(InstanceNode), s));
+	InstancePlanBuffers b{};
+	b.world = made;
+	b.scene_root = rooted ? scene->buffers().nodes : nullptr;
+	b.n = n;
+	b.inverse = made + set.inverse;
+	b.flag = made + set.flag;
+	b.reach_partials = base + where.reach_partials;
+	b.reach = base + where.reach;
+	b.leaves = base + where.leaves;
+	b.bounds = made + set.bounds;
+	b.box_partials = base + where.box_partials;
+	b.box = base + where.box;
+	b.keys = base + where.keys;
+	b.ids = base + where.ids;
+	b.sorted_keys = base + where.sorted_keys;
+	b.sorted_ids = base + where.sorted_ids;
+	b.ranges = base + where.ranges;
+	b.inner_links = base + where.inner_links;
+	b.leaf_links = base + where.leaf_links;
+	b.counters = base + where.counters;
+	b.inner_at = base + where.inner_at;
+	b.leaf_at = base + where.leaf_at;
+	b.nodes = made + set.tree;
+	inst_timed = false;
+	OCRT_HIP(hipEventRecord((hipEvent_t) ev_inst[0], s));
+	launch_instance_keys(b, s);
+	if (n >= 2u) {
+		launch_build_sort(base + where.sort, where.sort_bytes, b.keys, b.sorted_keys, b.ids, b.sorted_ids, n, s);
+		launch_instance_tree(b, s);
+	}
+	OCRT_HIP(hipGetLastError());
+	OCRT_HIP(hipEventRecord((hipEvent_t) ev_inst[1], s));
+	inst_timed = true;
+	have_inst_ms = false;
+	// the one wait: the flag and the root record
+	struct {
+		uint32_t flag;
+		InstanceNode root;
+	} head{};
+	static_assert(sizeof head == 36, "the flag's word lies directly in front of the root record");
+	OCRT_HIP(hipMemcpyAsync(&head, made + set.flag, sizeof head, hipMemcpyDeviceToHost, s));
+	OCRT_HIP(hipStreamSynchronize(s));
+	if (head.flag)
+		return false;  // (the launches wrote the spare allocation and the temporaries alone)
+	std::swap(inst_device, inst_spare);
+	inst_set = InstanceBuffers{ made + set.tree, made + set.inverse, 2u * n - 1u, made, made + set.bounds };
+	setInstanceBox(head.root.lo, head.root.hi);
+	inst_world.clear();
+	inst_inverse.clear();
+	inst_nodes.clear();
+	inst_built = true;
+	inst_built_n = n;
+	inst_scene = scene;
+	inst_current = rooted;
+	return true;
+}
+
+void RayQueries::buildInstancesDevice(const float *world_from_object, uint32_t n, void *stream) {
+	if (n > RT_INSTANCES_MAX)
+		throw std::invalid_argument("more instances than RT_INSTANCES_MAX");
+	if (n == 0) {
+		clearInstances();
+		return;
+	}
+	if (!world_from_object)
+		throw std::invalid_argument("null transform array");
+	if (!planInstancesOnDevice(world_from_object, n, stream))
+		throw std::invalid_argument("instance transform refused: an entry that is not finite, a zero determinant, or an inverse that is not finite");
+}
+
+void RayQueries::buildInstancesHost(const float *world_from_object, uint32_t n) {
+	if (n > RT_INSTANCES_MAX)
+		throw std::invalid_argument("more instances than RT_INSTANCES_MAX");
+	if (n > 0 && !world_from_object)
+		throw std::invalid_argument("null transform array");
+	if (n == 0) {
+		clearInstances();
+		return;
+	}
+	Staged p[1] = { input(world_from_object, (size_t) n * 12u * sizeof(float)) };
+	void *s = stageIn(p, 1);
+	buildInstancesDevice((const float *) p[0].device, n, s);  // (waits for its stream: the staging buffer is free again)
+}
+
+void RayQueries::instanceWorld(float *out) {
+	if (!out || instanceCount() == 0)
+		return;
+	if (!inst_built) {
+		std::copy(inst_world.begin(), inst_world.end(), out);
+		return;
+	}
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	if (timed)
+		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
+	OCRT_HIP(hipMemcpy(out, inst_set.world, (size_t) inst_built_n * 12u * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+void RayQueries::instanceInverses(float *out) {
+	if (!out || instanceCount() == 0)
+		return;
+	if (!inst_built) {
+		std::copy(inst_inverse.begin(), inst_inverse.end(), out);
+		return;
+	}
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	if (timed)
+		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
+	OCRT_HIP(hipMemcpy(out, inst_set.inverses, (size_t) inst_built_n * 12u * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+void RayQueries::instanceBounds(float *out) {
+	requireInstances("instance bounds");
+	refreshInstances();
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	if (timed)
+		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
+	if (out)
+		OCRT_HIP(hipMemcpy(out, inst_set.bounds, (size_t) instanceCount() * 4u * sizeof(float), hipMemcpyDeviceToHost));
+}
+
+float RayQueries::lastInstanceBuildMs() {
+	if (!inst_timed)
+		return 0.0f;
+	if (!have_inst_ms) {
+		OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_inst[1]));
+		OCRT_HIP(hipEventElapsedTime(&last_inst_ms, (hipEvent_t) ev_inst[0], (hipEvent_t) ev_inst[1]));
+		have_inst_ms = true;
+	}
+	return last_inst_ms;
 }
 
 void RayQueries::segmentsDevice(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,

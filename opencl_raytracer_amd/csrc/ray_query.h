@@ -88,10 +88,25 @@ class RayQueries {
 		// closest-point walk's bounds), in device memory of this object's own; it outlives updates, builds and uploads, after which the tree is made again before its next use.
 		// std::invalid_argument for a refused transform or too many (the set stays what it was); n == 0 clears the set.
 		void setInstances(const float *world_from_object, uint32_t n);
-		uint32_t instanceCount() const { return (uint32_t) (inst_world.size() / 12u); }
-		const std::vector<float> &instanceInverses() const { return inst_inverse; }
+		uint32_t instanceCount() const { return inst_built ? inst_built_n : (uint32_t) (inst_world.size() / 12u); }
 		// the tree as it is on the device, 2n - 1 records (waits for the queries; std::logic_error before an upload or a set)
 		void instanceNodes(void *out);
+		// Device-side instance sets (include/rt_hip_instance_build.h): the set made on the device from `world_from_object` in
+		// device memory -- copied into memory of this object's own, then checked, inverted, boxed, keyed, sorted and laid out by
+		// kernels/instance_build.hip.h into a SPARE allocation that takes the place of the set's once the flag has come back
+		// clear; the host keeps the count and the root record alone.  Ordered as a build: behind this host's queries by their
+		// event, enqueued on `stream` (null: the renderer's), one wait for the flag and the root record (36 bytes).
+		// std::invalid_argument for a refused transform (the set stays what it was), a null array or too many; n == 0 clears
+		// the set.  Before an upload the transforms are checked and kept; the tree is made at the first use.
+		void buildInstancesDevice(const float *world_from_object, uint32_t n, void *stream);
+		// Host memory: one upload through the staging buffer, then the same.
+		void buildInstancesHost(const float *world_from_object, uint32_t n);
+		// What the set holds, either kind: a built set's arrays are read from the device (waits for the queries).  The bounds
+		// are made again first if the scene changed, as the tree is (std::logic_error before an upload or a set).
+		void instanceWorld(float *out);
+		void instanceInverses(float *out);
+		void instanceBounds(float *out);
+		float lastInstanceBuildMs();  // HIP-event time of the last device-side plan's launches (0: none yet)
 		// Instanced views (include/rt_hip_instance_views.h): viewsDevice's arguments and rules, the rays cast against the
 		// instance set; the records are the instanced ray queries', `instance` [views][N] beside the layers.
 		void instanceViewsDevice(const CameraPose *cameras, uint32_t views, const ViewOutputs &out, uint32_t *instance, void *stream);
@@ -311,6 +326,23 @@ class RayQueries {
 		std::weak_ptr<const DeviceScene> inst_scene;
 		bool inst_current = false;
 		float inst_box[6] = { 0, 0, 0, 0, 0, 0 };  // the sort's origin cells over the top-level root box: lo, scale
+		void setInstanceBox(const float lo[3], const float hi[3]);
+		// A device-built set (include/rt_hip_instance_build.h): inst_built, its size; the vectors above stay empty, inst_device
+		// holds transforms, inverses, flag, tree and bounds (InstanceSetLayout).  inst_spare: the allocation the next plan goes
+		// into; inst_plan: that plan's temporaries.
+		struct InstanceSetLayout {
+			size_t inverse, flag, tree, bounds, bytes;  // (the transforms lie at 0; the flag's word directly in front of the tree)
+		};
+		static InstanceSetLayout instanceSetLayout(uint32_t n);
+		// Plans `n` transforms -- in device memory; may be the current set's own -- into inst_spare and, accepted, swaps it in.
+		bool planInstancesOnDevice(const float *world_device, uint32_t n, void *stream);
+		void clearInstances();
+		bool inst_built = false;
+		uint32_t inst_built_n = 0;
+		Scratch inst_spare, inst_plan;
+		void *ev_inst[2] = { nullptr, nullptr };
+		bool inst_timed = false, have_inst_ms = false;
+		float last_inst_ms = 0.0f;
 };
 
 // kernels.hip

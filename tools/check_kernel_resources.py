@@ -146,6 +146,9 @@ def main():
                "refit_leaves_kernel", "refit_inner_kernel",  # vertex updates (kernels/refit.hip.h): a spill there is memory traffic per record
                # device-side builds (kernels/build.hip.h): a lane per face or node, nothing that should need scratch
                "build_boxes_kernel", "build_root_kernel", "build_keys_kernel", "build_tree_kernel", "build_layout_kernel",
+               # device-side instance sets (kernels/instance_build.hip.h): a lane per instance or node, binary64 in registers
+               "instance_inverse_kernel", "instance_reach_kernel", "instance_leaves_kernel", "instance_root_kernel",
+               "instance_keys_kernel", "instance_tree_kernel", "instance_layout_kernel", "instance_boxes_kernel",
                # closest-point queries (kernels/nearest.hip.h)
                "nearest_key_kernel", "nearest_scatter_kernel", "nearest_coordinates_kernel", "nearest_kernel<false>", "nearest_kernel<true>",
                # segment queries (kernels/segment.hip.h)
