@@ -42,6 +42,15 @@ int rt_set_ao_prefetch(rt_host *h, int on);
  * packets actually use (1.0 = no narrowing: AO_MAX_DISTANCE of the scene's size).  Out pointers may be NULL.
  * RT_E_STATE without a scene. */
 int rt_walk_entries(rt_host *h, uint32_t *tiles_hit, uint32_t *tiles_narrowed, double *mean_share, double *mean_packet_share);
+/* Where those intervals END, read back and held against the node records they index: the any-hit loop compares its place
+ * with the interval's end only where a miss jump or the step off a leaf can land on it, not where it descends to a first
+ * child, which rests on every end being the end of a subtree.  Over the non-empty intervals the packets use (a full tile's:
+ * one per table direction; any other tile's: one): out[0] their number, [1] those that end with the array (a one-shot
+ * host's: all of them), [2] those that end behind a leaf record -- a subtree's end --, [3] those that end behind an inner
+ * node, i.e. on its first child, [4] of [2] the ones no inner node's miss jump inside the interval lands on (left by the
+ * step off the last leaf, or by its miss), [5] of [2] the ones some inner node's miss jump lands on exactly.  A test aid:
+ * it copies the whole table and the records to the host.  RT_E_STATE without a scene. */
+int rt_debug_walk_interval_ends(rt_host *h, uint32_t out[6]);
 
 /* Time stamps of collected frames: ms from the last rt_ring_reset_clock to the frame's begin, the start and the end of
  * its ambient-occlusion kernel, its end.  Begin and end are HIP events on the host's stream; the kernel's times are HIP

@@ -219,6 +219,7 @@ _SIGNATURES = {
     "rt_debug_set_cheap_claims": (C.c_int, [C.c_void_p, C.c_float]),
     "rt_debug_cheap_tiles": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_debug_prune_facts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_debug_walk_interval_ends": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_debug_poison_hit_list": (C.c_int, [C.c_void_p]),
     "rt_debug_node_test_forms": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rt_debug_set_views_chunk": (C.c_int, [C.c_void_p, C.c_uint32]),
@@ -972,6 +973,13 @@ class Host:
         _check(load_library().rt_walk_entries(self._h, C.byref(hit), C.byref(narrowed), C.byref(share), C.byref(packet_share)))
         return {"tiles_hit": hit.value, "tiles_narrowed": narrowed.value, "mean_share": share.value,
                 "mean_packet_share": packet_share.value}
+
+    def walk_interval_ends(self) -> dict:
+        """Where the intervals the any-hit packets use end, by kind (include/rt_hip_debug.h, rt_debug_walk_interval_ends)."""
+        out = np.zeros(6, np.uint32)
+        _check(load_library().rt_debug_walk_interval_ends(self._h, out.ctypes.data))
+        keys = ("intervals", "whole_array", "after_leaf", "after_inner", "last_is_leaf", "last_is_inner")
+        return {k: int(v) for k, v in zip(keys, out)}
 
     def stats(self) -> dict:
         s = _Stats()

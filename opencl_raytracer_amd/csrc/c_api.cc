@@ -621,6 +621,20 @@ int rt_walk_entries(rt_host *h, uint32_t *tiles_hit, uint32_t *tiles_narrowed, d
 	});
 }
 
+int rt_debug_walk_interval_ends(rt_host *h, uint32_t out[6]) {
+	if (!h || !out)
+		return fail(RT_E_INVALID, "null argument");
+	return guarded([&] {
+		const ocrt::DeviceRenderer::IntervalEnds e = h->dev->walkIntervalEnds();
+		out[0] = e.intervals;
+		out[1] = e.whole_array;
+		out[2] = e.after_leaf;
+		out[3] = e.after_inner;
+		out[4] = e.last_is_leaf;
+		out[5] = e.last_is_inner;
+	});
+}
+
 int rt_set_ao_prefetch(rt_host *h, int on) {
 	if (!h)
 		return fail(RT_E_INVALID, "null argument");

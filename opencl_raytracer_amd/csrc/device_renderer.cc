@@ -547,6 +547,64 @@ DeviceRenderer::WalkEntries DeviceRenderer::walkEntries() const {
 	return out;
 }
 
+DeviceRenderer::IntervalEnds DeviceRenderer::walkIntervalEnds() const {
+	if (!scene_ready)
+		throw std::logic_error("walkIntervalEnds: no scene on the device");
+	useDevice();
+	IntervalEnds out{ 0, 0, 0, 0, 0, 0 };
+	const bool has_ao = kp.ao_mode != AO_NONE && kp.ao_dirs > 0;
+	const void *const walk = scene_on_device->buffers().walk;
+	if (tile_count == 0 || !has_ao || kp.node_count == 0 || !walk || kp.walk_ce_bytes == 0)
+		return out;
+	const size_t stride = kp.entry_stride;
+	const uint32_t nodes = kp.node_count;
+	// the records the intervals index (the any-hit rays' copy), the tile words and the table, all of it: a test's frames are small
+	std::vector<NodeRec> records(nodes);
+	std::vector<uint32_t> words(tile_count), ranges(tile_count * stride * 2);
+	OCRT_HIP(hipStreamSynchronize((hipStream_t) stream));
+	OCRT_HIP(hipMemcpyAsync(records.data(), (const char *) walk + kp.walk_ce_bytes, records.size() * sizeof(NodeRec), hipMemcpyDeviceToHost, (hipStream_t) stream));
+	OCRT_HIP(hipMemcpyAsync(words.data(), d_tile_hits, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t) stream));
+	OCRT_HIP(hipMemcpyAsync(ranges.data(), d_tile_entry, ranges.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t) stream));
+	OCRT_HIP(hipStreamSynchronize((hipStream_t) stream));
+	const auto skip_of = [&](uint32_t n) { return records[n].skip / (uint32_t) sizeof(NodeRec); };  // (the walk array keeps byte offsets)
+	// per record index e: the innermost INNER node whose subtree ends at e (subtrees that end together are nested), or none
+	const uint32_t none = 0xFFFFFFFFu;
+	std::vector<uint32_t> innermost(nodes + 1, none);
+	for (uint32_t n = 0; n < nodes; ++n)
+		if (skip_of(n) > 1u && n + skip_of(n) <= nodes)
+			innermost[n + skip_of(n)] = n;  // (pre-order: a later n with the same end lies inside the earlier one)
+	for (size_t t = 0; t < tile_count; ++t) {
+		const uint32_t hits = words[t] & 0xFFu;
+		if (hits == 0u)
+			continue;
+		const bool per_direction = hits == 64u && kp.ao_mode == AO_UNIFORM && stride > 1;
+		// (a tile that is not full has one interval for all its packets: counted once)
+		for (size_t k = 1; k <= (per_direction ? (size_t) kp.ao_dirs : 1); ++k) {
+			const uint32_t *const r = &ranges[2 * (stride * t + (per_direction ? k : 0))];
+			++out.intervals;
+			if (r[1] / sizeof(NodeRec) >= nodes) {
+				++out.whole_array;
+				continue;
+			}
+			const uint32_t begin = r[0] / (uint32_t) sizeof(NodeRec), end = r[1] / (uint32_t) sizeof(NodeRec);
+			if (begin >= end) {  // (nothing in reach: never walked)
+				--out.intervals;
+				continue;
+			}
+			if (skip_of(end - 1u) > 1u) {
+				++out.after_inner;
+				continue;
+			}
+			++out.after_leaf;
+			if (innermost[end] != none && innermost[end] >= begin)
+				++out.last_is_inner;
+			else
+				++out.last_is_leaf;
+		}
+	}
+	return out;
+}
+
 void DeviceRenderer::expectFrames(uint64_t frames) {
 	const bool before = expected_frames >= FRAMES_WORTH_INTERVALS, after = frames >= FRAMES_WORTH_INTERVALS;
 	if (before != after && scene_ready)

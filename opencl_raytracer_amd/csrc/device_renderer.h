@@ -239,6 +239,18 @@ class DeviceRenderer {
 			double mean_packet_share;  // ... by the intervals its packets use (a full tile's: one per table direction)
 		};
 		WalkEntries walkEntries() const;
+		// Where the intervals the packets use END, read back from the device and held against the records they index (the
+		// centre / half-extent copy): the any-hit loop checks `end` only where a miss jump or the step off a leaf can land on
+		// it (kernels/walk.hip.h, OCRT_DESCEND_UNCHECKED), which rests on ends being subtree ends.
+		struct IntervalEnds {
+			uint32_t intervals;      // the intervals looked at: per tile with hits the ones its packets use
+			uint32_t whole_array;    // ... that end at or behind the array's end (a one-shot host's: all)
+			uint32_t after_leaf;     // ... that end behind a leaf record: the end of a subtree
+			uint32_t after_inner;    // ... that end behind an inner node, on its first child (entry_kernel's `end = n`): a descend can land there
+			uint32_t last_is_leaf;   // of after_leaf: the last child taken is a leaf itself (left by the step off it, or its miss)
+			uint32_t last_is_inner;  // of after_leaf: ... an inner node whose miss jump lands exactly on the end
+		};
+		IntervalEnds walkIntervalEnds() const;
 		bool aoPrefetch() const { return ao_prefetch; }
 		// How many frames of the scene the caller is going to render (default 1: the reference's use, one frame per
 		// process, src/render.cc:86-111).  What an upload prepares beyond the scene itself only pays over a stream of frames:

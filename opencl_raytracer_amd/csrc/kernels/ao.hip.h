@@ -444,7 +444,7 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 						shared_walk_any_hit<true>(OCRT_COLD_PTR(const float4 *, nodes_ptr), walk_ptr, tris_ptr, count, ray, sh.frame, h,
 						                          OCRT_COLD_F32(P.ao_max_distance), A.P.ao_below, 0.0f, alive, false, &sh.occluded[h], sh.batch,
 						                          A.P.batch_below, walk_prof);
-					else
+					else  // (the list limit, A.P.batch_below, is fetched here and stays in a register to the packet's end: OCRT_WALK_MIXED_CE)
 						shared_walk_any_hit<false, PREFETCH>(nullptr, walk_ptr, tris_ptr, count, ray, sh.frame, h,
 						                           0.0f, A.P.ao_below, OCRT_COLD_F32(P.walk_scale), alive, tame, &sh.occluded[h], sh.batch,
 						                           A.P.batch_below, walk_prof, entry_begin, entry_end, OCRT_COLD_U32(P.walk_ce_bytes));

@@ -123,7 +123,13 @@ __global__ __launch_bounds__(64 * ENTRY_WAVES) void entry_kernel(const NodeRec *
 					if (meets(c))
 						last = c;
 				if (last == 0u) {
-					end = n;
+					// nothing under n can be reached: the interval may end IN FRONT of n -- where that is the end of a
+					// subtree, i.e. where a leaf stands before n.  A first child stands behind its parent, and an end there
+					// would be one that a descend lands on: the any-hit loop looks for the end only behind a miss jump or a
+					// leaf (kernels/walk.hip.h, OCRT_DESCEND_UNCHECKED), so the interval keeps such an n, one node test
+					// that every lane is likely to fail (tests/test_ao_scalar_side_gpu.py reads the ends back).
+					if (n == 0u || skip_of(n - 1u) == 1u)
+						end = n;
 					break;
 				}
 				end = last + skip_of(last);

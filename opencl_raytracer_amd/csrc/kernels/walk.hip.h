@@ -133,7 +133,12 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 // reads it (SALU reads of VALU-written SGPRs are interlocked); s_mov_b64 exec -> ds_write_b32 / following VALU
 // (EXEC writes by SALU are interlocked for vector and LDS instructions); s_load -> s_waitcnt lgkmcnt(0) before the
 // first use (also drains the ds_write of an append, harmless); no v_readlane / v_div_fmas / VMEM-with-SGPR-address
-// consumers of VALU-written SGPRs in here.  The build fails if the kernels using this loop spill vector registers
+// consumers of VALU-written SGPRs in here.  The any-hit form's own: s_and_saveexec_b64 (OCRT_NARROW_AND) is an SALU write of
+// EXEC like the s_mov_b64 it replaces, same interlock in front of the ds_write; the v_mbcnt / v_add / v_or before it read
+// s44 / s45 / s46, which SALU instructions wrote (no hazard in that direction); s_cmp_eq_u64 (OCRT_ENTRY_ALIVE) reads an
+// operand the compiler made before the block; the second s_load_dwordx16 (OCRT_DESCEND_UNCHECKED) is issued after the last
+// read of s[56:63] -- TEST_B's fmas and the s_cmp on s63 -- and waited for at .Lw_wait like the first.
+// The build fails if the kernels using this loop spill vector registers
 // or leave 8 waves per SIMD (tools/check_kernel_resources.py).
 #define OCRT_TEST_COHERENT(NX, NY, NZ, FX, FY, FZ) \
 	"\tv_fma_f32 v56, " NX ", %[ix], %[oix]\n"     \
@@ -198,12 +203,19 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 	"\tv_max3_f32 v56, v56, v58, v60\n"                                                                               \
 	"\tv_min3_f32 v57, v57, v59, v61\n"                                                                               \
 	"\tv_cmp_lt_f32 vcc, v56, v57\n"
-// (LEAF: the s-register holding the node's leaf field; NEXT: where the walk goes on after an append)
-#define OCRT_WALK_LEAF(LEAF, NOW, NEXT)                 \
+// (LEAF: the s-register holding the node's leaf field; NEXT: where the walk goes on after an append; COUNT: the caller's
+// count of the leaves some lane hit, or nothing; NARROW: EXEC := the hitters for the one ds_write, the old EXEC to s[42:43])
+#define OCRT_COUNT_STOPS "\ts_add_u32 %[stops], %[stops], 1\n"
+#define OCRT_COUNT_NONE ""
+#define OCRT_NARROW_MOV "\ts_mov_b64 s[42:43], exec\n\ts_mov_b64 exec, s[44:45]\n"
+// (one instruction for the two: s[44:45] = vcc & alive holds no lane outside EXEC, so the AND with EXEC changes nothing;
+// it writes SCC, which the s_cmp behind the ds_write sets anew before anybody reads it)
+#define OCRT_NARROW_AND "\ts_and_saveexec_b64 s[42:43], s[44:45]\n"
+#define OCRT_WALK_LEAF(LEAF, NOW, NEXT, COUNT, NARROW)  \
 	"\ts_cmp_eq_u32 " LEAF ", -2\n"                     \
 	"\ts_cbranch_scc1 .Lw_over_%=\n"                    \
 	"\ts_bcnt1_i32_b64 s46, s[44:45]\n"                 \
-	"\ts_add_u32 %[stops], %[stops], 1\n"               \
+	COUNT                                               \
 	"\ts_cmp_ge_u32 s46, %[batch_below]\n"              \
 	"\ts_cbranch_scc1 " NOW "\n"                        \
 	"\tv_mbcnt_lo_u32_b32 v56, s44, 0\n"                \
@@ -211,8 +223,7 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 	"\tv_add_u32 v56, %[waiting], v56\n"                \
 	"\tv_lshl_add_u32 v56, v56, 2, %[list]\n"           \
 	"\tv_or_b32 v57, " LEAF ", %[tag]\n"                \
-	"\ts_mov_b64 s[42:43], exec\n"                      \
-	"\ts_mov_b64 exec, s[44:45]\n"                      \
+	NARROW                                              \
 	"\tds_write_b32 v56, v57\n"                         \
 	"\ts_mov_b64 exec, s[42:43]\n"                      \
 	"\ts_add_u32 %[waiting], %[waiting], s46\n"         \
@@ -247,13 +258,35 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 // once the block ends; the records behind any range are there to be read, END records at the latest).
 #define OCRT_HEAD_NONE ""
 #define OCRT_HEAD_END "\ts_cmp_ge_u32 %[at], %[end]\n\ts_cbranch_scc1 .Lw_over_wait_%=\n"
-#define OCRT_WALK_ASM(HEAD, TEST_A, TEST_B, PF_B)           \
+// ENTRY: what is checked before the first load.  OCRT_ENTRY_ALIVE: nothing to walk for a packet without a live lane (the
+// any-hit walk comes back here after every leaf stop and batch, which may have taken the last ray out) -- with OCRT_HEAD_END
+// on the first load these two scalar instructions ARE the condition of the loop around the block, which the compiler
+// otherwise builds out of eleven (select, and, andn2 ... exec, branch on VCC) in front of every entry.
+#define OCRT_ENTRY_NONE ""
+#define OCRT_ENTRY_ALIVE "\ts_cmp_eq_u64 %[alive], 0\n\ts_cbranch_scc1 .Lw_over_%=\n"
+// DESCEND: the step from an inner node `b` that was hit to its first child.  An interval ends where a subtree does
+// (entry_kernel: end = last + skip_of(last), or the array's end), and the first child of an inner node is never the record
+// behind a subtree: only a miss jump or the step off a leaf can land on `end`.  OCRT_DESCEND_UNCHECKED therefore loads the
+// next pair without OCRT_HEAD_END's compare and branch.  (entry_kernel ends an interval in front of a node nothing can be
+// reached under only where a leaf stands before it, for this loop's sake, and tests/test_ao_scalar_side_gpu.py reads the ends
+// back and holds them against the records.  Were an end a first child all the same, the walk would test that record and
+// whatever of its subtree the lanes hit, and stop at the first miss jump or leaf step, all of which lie at or behind `end`:
+// more candidates, which fail the exact test like every candidate no ray reaches -- the interval only trims the walk, it
+// decides nothing --, and the test of `b` straight out of s[56:63] has always looked one record past a hit `a` unasked.)
+#define OCRT_DESCEND_CHECKED ""
+#define OCRT_DESCEND_UNCHECKED                                \
+	"\ts_add_u32 %[at], %[at], 32\n"                          \
+	"\ts_load_dwordx16 s[48:63], %[base], %[at]\n"            \
+	"\ts_branch .Lw_wait_%=\n"
+#define OCRT_WALK_ASM(ENTRY, HEAD, DESCEND, COUNT, NARROW, TEST_A, TEST_B, PF_B) \
+	ENTRY                                                   \
 	"\ts_branch .Lw_node_%=\n"                              \
 	".Lw_miss_a_%=:\n"                                      \
 	"\ts_add_u32 %[at], %[at], s51\n"                       \
 	".Lw_node_%=:\n"                                        \
 	"\ts_load_dwordx16 s[48:63], %[base], %[at]\n"          \
 	HEAD                                                    \
+	".Lw_wait_%=:\n"                                        \
 	"\ts_waitcnt lgkmcnt(0)\n"                              \
 	TEST_A                                                  \
 	"\ts_and_b64 s[44:45], vcc, %[alive]\n"                 \
@@ -268,6 +301,7 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 	"\ts_cbranch_scc0 .Lw_miss_b_%=\n"                      \
 	"\ts_cmp_lg_u32 s63, -1\n"                              \
 	"\ts_cbranch_scc1 .Lw_leaf_b_%=\n"                      \
+	DESCEND                                                 \
 	".Lw_next_a_%=:\n"                                      \
 	"\ts_add_u32 %[at], %[at], 32\n"                        \
 	"\ts_branch .Lw_node_%=\n"                              \
@@ -275,12 +309,12 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 	"\ts_add_u32 %[at], %[at], s59\n"                       \
 	"\ts_branch .Lw_node_%=\n"                              \
 	".Lw_leaf_a_%=:\n"                                      \
-	OCRT_WALK_LEAF("s55", ".Lw_now_a_%=", ".Lw_next_b_%=")  \
+	OCRT_WALK_LEAF("s55", ".Lw_now_a_%=", ".Lw_next_b_%=", COUNT, NARROW)  \
 	".Lw_now_a_%=:\n"                                       \
 	"\ts_mov_b32 %[leaf], s55\n"                            \
 	"\ts_branch .Lw_now_%=\n"                               \
 	".Lw_leaf_b_%=:\n"                                      \
-	OCRT_WALK_LEAF("s63", ".Lw_now_b_%=", ".Lw_next_a_%=")  \
+	OCRT_WALK_LEAF("s63", ".Lw_now_b_%=", ".Lw_next_a_%=", COUNT, NARROW)  \
 	".Lw_now_b_%=:\n"                                       \
 	"\ts_mov_b32 %[leaf], s63\n"                            \
 	".Lw_now_%=:\n"                                         \
@@ -295,6 +329,20 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 	".Lw_over_%=:\n"                                        \
 	"\ts_mov_b32 %[status], 0\n"                            \
 	".Lw_out_%=:\n"
+// The forms: the closest-hit loops (primary pass) count their leaf stops and check nothing on the way; the any-hit loop
+// checks where it is told to and counts only in the instrumented build (the pass has no use for the number, and the
+// register it would sit in across the walk holds `batch_below` instead: OCRT_WALK_MIXED_CE).
+#define OCRT_WALK_PLAIN(TEST_A, TEST_B, PF) \
+	OCRT_WALK_ASM(OCRT_ENTRY_NONE, OCRT_HEAD_NONE, OCRT_DESCEND_CHECKED, OCRT_COUNT_STOPS, OCRT_NARROW_MOV, TEST_A, TEST_B, PF)
+#ifdef OCRT_STAMPS
+#define OCRT_ANY_HIT_COUNT OCRT_COUNT_STOPS
+#define OCRT_ANY_HIT_STOPS , [stops] "+s"(leaf_stops)
+#else
+#define OCRT_ANY_HIT_COUNT OCRT_COUNT_NONE
+#define OCRT_ANY_HIT_STOPS
+#endif
+#define OCRT_WALK_ANY_HIT(TEST_A, TEST_B, PF) \
+	OCRT_WALK_ASM(OCRT_ENTRY_ALIVE, OCRT_HEAD_END, OCRT_DESCEND_UNCHECKED, OCRT_ANY_HIT_COUNT, OCRT_NARROW_AND, TEST_A, TEST_B, PF)
 #define OCRT_WALK_CLOBBERS                                                                                              \
 	"s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", \
 	    "s59", "s60", "s61", "s62", "s63", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "vcc", "scc", "memory"
@@ -305,7 +353,7 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 #define OCRT_FAR_P(LO, HI) HI
 #define OCRT_FAR_N(LO, HI) LO
 #define OCRT_WALK_COHERENT(TEST, X, Y, Z, PF)                                                                               \
-	asm volatile(OCRT_WALK_ASM(OCRT_HEAD_NONE, TEST(OCRT_NEAR_##X("s48", "s52"), OCRT_NEAR_##Y("s49", "s53"),              \
+	asm volatile(OCRT_WALK_PLAIN(TEST(OCRT_NEAR_##X("s48", "s52"), OCRT_NEAR_##Y("s49", "s53"),              \
 	                                OCRT_NEAR_##Z("s50", "s54"), OCRT_FAR_##X("s48", "s52"),                               \
 	                                OCRT_FAR_##Y("s49", "s53"), OCRT_FAR_##Z("s50", "s54")),                               \
 	                           TEST(OCRT_NEAR_##X("s56", "s60"), OCRT_NEAR_##Y("s57", "s61"),                              \
@@ -319,7 +367,7 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 	             : OCRT_WALK_CLOBBERS)
 
 #define OCRT_WALK_MIXED(TEST, PF)                                                                                         \
-	asm volatile(OCRT_WALK_ASM(OCRT_HEAD_NONE, TEST("s48", "s49", "s50", "s52", "s53", "s54"), TEST("s56", "s57", "s58", "s60", "s61", "s62"), PF) \
+	asm volatile(OCRT_WALK_PLAIN(TEST("s48", "s49", "s50", "s52", "s53", "s54"), TEST("s56", "s57", "s58", "s60", "s61", "s62"), PF) \
 	             : [at] "+s"(at), [waiting] "+s"(waiting), [stops] "+s"(leaf_stops), [hit] "=&s"(hit_mask),               \
 	               [leaf] "=&s"(leaf), [status] "=&s"(status)                                                            \
 	             : [base] "s"(walk_ptr), [alive] "s"(alive_mask), [below] "v"(below), [batch_below] "s"(batch_below),     \
@@ -327,11 +375,14 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 	               [ix] "v"(ray.ix), [iy] "v"(ray.iy), [iz] "v"(ray.iz), [oix] "v"(ray.oix), [oiy] "v"(ray.oiy),          \
 	               [oiz] "v"(ray.oiz)                                                                                    \
 	             : OCRT_WALK_CLOBBERS)
+// (`batch_below` is an in-out operand although the block only reads it: as an input the compiler holds it to be cheap to make
+// again and reloads it from the kernel-argument segment, with a wait, in front of EVERY entry; a value the block may have
+// changed has to stay where it is -- the register the count of leaf stops used to keep across the walk)
 #define OCRT_WALK_MIXED_CE(TEST, PF)                                                                                      \
-	asm volatile(OCRT_WALK_ASM(OCRT_HEAD_END, TEST("s48", "s49", "s50", "s[52:53]", "s[54:55]"), TEST("s56", "s57", "s58", "s[60:61]", "s[62:63]"), PF) \
-	             : [at] "+s"(at), [waiting] "+s"(waiting), [stops] "+s"(leaf_stops), [hit] "=&s"(hit_mask),               \
-	               [leaf] "=&s"(leaf), [status] "=&s"(status)                                                            \
-	             : [base] "s"(walk_ptr), [alive] "s"(alive_mask), [end] "s"(walk_end), [batch_below] "s"(batch_below),    \
+	asm volatile(OCRT_WALK_ANY_HIT(TEST("s48", "s49", "s50", "s[52:53]", "s[54:55]"), TEST("s56", "s57", "s58", "s[60:61]", "s[62:63]"), PF) \
+	             : [at] "+s"(at), [waiting] "+s"(waiting), [batch_below] "+s"(batch_below), [hit] "=&s"(hit_mask),        \
+	               [leaf] "=&s"(leaf), [status] "=&s"(status) OCRT_ANY_HIT_STOPS                                         \
+	             : [base] "s"(walk_ptr), [alive] "s"(alive_mask), [end] "s"(walk_end),                                    \
 	               [list] "s"(list_lds_address), [tag] "v"(lane_tag),                                                      \
 	               [ix] "v"(ray.ix), [iy] "v"(ray.iy), [iz] "v"(ray.iz), [oix] "v"(ray.oix), [oiy] "v"(ray.oiy),          \
 	               [oiz] "v"(ray.oiz), [axy] "v"(abs_xy), [azw] "v"(abs_zw)                                               \
@@ -358,8 +409,9 @@ __device__ __forceinline__ uint32_t walk_collect(uint32_t variant, const float4 
                                                  const SignMasks &sign, float below, unsigned long long alive_mask,
                                                  unsigned long long &hit_mask, uint32_t &leaf, uint32_t &waiting,
                                                  uint32_t &leaf_stops, uint32_t list_lds_address, uint32_t lane_tag,
-                                                 uint32_t batch_below, uint32_t walk_end = 0xFFFFFFFFu) {
+                                                 uint32_t &batch_below, uint32_t walk_end = 0xFFFFFFFFu) {
 	(void) walk_end;  // (the any-hit loop's: byte offset behind the subtree it walks)
+	(void) leaf_stops;  // (the any-hit loop counts them in the instrumented build only)
 	uint32_t status;
 	if (SCALED) {
 		// one loop for every any-hit packet, whatever its rays' signs (the caller starts `at` in the centre / half-extent
@@ -526,14 +578,15 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 #endif
 				wave_lds_sync();
 				const uint32_t bits = batch.occluded_bits[lane >> 5];
-				if (alive && ((bits >> (lane & 31u)) & 1u)) {
+				// (who is alive is kept in the scalar mask alone: a flag per lane carried around the walk's turns is
+				// merged by the compiler with mask arithmetic on every path, the ones that do not touch it included)
+				const bool gone = ((alive_mask >> lane) & 1ull) && ((bits >> (lane & 31u)) & 1u);
+				if (gone)
 					atomicAdd(occluded, 1u);  // once per ray, however many of its pairs were accepted
-					alive = false;
-				}
 				wave_lds_sync();
 				if (lane < 2u)
 					batch.occluded_bits[lane] = 0u;
-				alive_mask = wave_ballot(alive);
+				alive_mask &= ~wave_ballot(gone);
 			}
 #ifdef OCRT_STAMPS
 			prof[1] += __builtin_amdgcn_s_memrealtime() - tb0;
@@ -552,20 +605,23 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 		const uint32_t end = copy + (entry_end < whole ? entry_end : whole);
 		const WalkRay walk_ray = tame ? make_walk_ray(with_origin(), walk_scale, true) : make_walk_ray(with_origin(), walk_scale);  // (wave-uniform)
 		const uint32_t lane_tag = fresh_lane() << 26;
-		while (alive_mask != 0ull && at < end) {
+		// One turn per walk segment.  Whether there is anything left to walk -- a live lane, `at` before `end` -- is asked
+		// INSIDE the block (OCRT_ENTRY_ALIVE, OCRT_HEAD_END on its first load), and the turn has one condition, at its foot:
+		// a loop that is left from its middle, on a status code, is rebuilt by the compiler out of mask registers and
+		// branches on VCC -- some twenty scalar instructions around every segment.
+		uint32_t status;
+		do {
 			uint32_t leaf = 0u;
 			unsigned long long hit_mask = 0ull;
 #ifdef OCRT_STAMPS
 			const unsigned long long tw0 = __builtin_amdgcn_s_memrealtime();
 #endif
-			const uint32_t status = walk_collect<true, PREFETCH>(variant, walk_ptr, at, walk_ray, sign, below, alive_mask, hit_mask, leaf,
-			                                           waiting, leaf_stops, list_lds_address, lane_tag, batch_below, end);
+			status = walk_collect<true, PREFETCH>(variant, walk_ptr, at, walk_ray, sign, below, alive_mask, hit_mask, leaf,
+			                                      waiting, leaf_stops, list_lds_address, lane_tag, batch_below, end);
 #ifdef OCRT_STAMPS
 			prof[0] += __builtin_amdgcn_s_memrealtime() - tw0;
-			prof[2] += 1;
+			prof[2] += 1;  // (entries: one per leaf stop and batch, and one -- the last, possibly empty -- per packet)
 #endif
-			if (status == 0u)
-				break;
 			if (status == 1u) {
 				// enough of the packet is at this leaf: test it here, the triangle and -- only if some lane accepts it, as in
 				// run_batch -- the leaf's own box out of SGPRs
@@ -583,21 +639,20 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 #endif
 				if (any_accepted) {
 					const float4 lo = rec[0], hi = rec[1];
-					if (accepted && exact_leaf_gate(lo, hi, ray, below)) {
+					const bool gone = accepted && exact_leaf_gate(lo, hi, ray, below);  // (a lane of hit_mask, so a live one)
+					if (gone)
 						atomicAdd(occluded, 1u);
-						alive = false;
-					}
-					alive_mask = wave_ballot(alive);
+					alive_mask &= ~wave_ballot(gone);
 				}
-			} else {
+			} else if (status == 2u) {
 				run_batch(64u);
 				waiting -= 64u;
 				const uint32_t me = fresh_lane();
 				if (me < waiting)  // the pairs beyond the batch move to the front
 					batch.entry[me] = batch.entry[64u + me];
 			}
-			at += 32u;
-		}
+			at += 32u;  // (off the leaf the block stopped on; nobody reads it once the walk is over)
+		} while (status != 0u);
 		if (waiting != 0u)
 			run_batch(waiting);
 #ifdef OCRT_STAMPS

@@ -27,7 +27,10 @@ WHERE they land matters: with `--isa` (the device assembly of the same translati
 loop depth and fails the build when one sits inside the hand-scheduled node loop (the asm
 blocks between .Lw_miss_a and .Lw_out), when the loop around it -- one turn per leaf stop or
 batch -- holds more than LANE_OPS_PER_WALK_TURN of them, or when the per-packet code holds more
-than LANE_OPS_PER_PACKET.
+than LANE_OPS_PER_PACKET.  With `--isa` the table also lists, for the ambient-occlusion kernels, the static
+instruction counts by class (VALU, SALU, SMEM, branch, wait, LDS, VMEM) of the node loop's labelled
+stretches, of the code between the loop around it and the block, and by loop depth (scalar_side_by_place):
+what profiles/ao_scalar_side_notes.md multiplies by event counts.  A report; nothing fails on it.
 """
 import re
 import subprocess
@@ -113,6 +116,118 @@ def lane_ops_by_place(isa_text: str):
                     "depths": dict(sorted(by_depth.items())), "walk_depth": walk_depth}
             name = None
     return out
+
+
+CLASSES = ("VALU", "SALU", "SMEM", "branch", "wait", "LDS", "VMEM")
+
+
+def instruction_class(text: str):
+    """The class of one line of device assembly, None for labels, comments and directives.  SALU: scalar instructions other
+    than loads, branches and waits -- the classes of SQ_INSTS_SALU, SQ_INSTS_SMEM and SQ_INSTS_BRANCH."""
+    m = re.match(r"^\s+([a-z_0-9]+)", text)
+    if not m:
+        return None
+    op = m.group(1)
+    if op.startswith(("s_load_", "s_buffer_load_", "s_memrealtime", "s_memtime")):
+        return "SMEM"
+    if op.startswith(("s_branch", "s_cbranch", "s_setpc", "s_swappc", "s_endpgm", "s_call")):
+        return "branch"
+    if op.startswith(("s_waitcnt", "s_nop", "s_sleep", "s_barrier")):
+        return "wait"
+    if op.startswith("s_"):
+        return "SALU"
+    if op.startswith("ds_"):
+        return "LDS"
+    if op.startswith(("global_", "buffer_", "flat_", "scratch_")):
+        return "VMEM"
+    if op.startswith("v_"):
+        return "VALU"
+    return None
+
+
+def count_classes(lines):
+    out = dict.fromkeys(CLASSES, 0)
+    for text in lines:
+        c = instruction_class(text)
+        if c:
+            out[c] += 1
+    return out
+
+
+def class_row(name, counts):
+    return f"  {name:40s} " + " ".join(f"{counts[c]:6d}" for c in CLASSES)
+
+
+def scalar_side_by_place(isa_text: str):
+    """For the kernels that hold the ANY-HIT form of the node loop (ao_kernel<..>, one block each): static instruction counts
+    by class
+      - per labelled stretch of the hand-scheduled block (.Lw_miss_a = the pair's load, its checks and the test of `a`;
+        .Lw_next_b = the test of `b` and, behind it, the descend; .Lw_next_a / .Lw_miss_b = the steps to the next pair;
+        .Lw_leaf_a / .Lw_leaf_b = a leaf some lane hit, up to the append's end; .Lw_now / .Lw_full / .Lw_over = the exits),
+      - from the header of the loop around the block to ;;#ASMSTART, and from ;;#ASMEND on while the instructions stay
+        scalar (the dispatch on the block's status, along the text: the fall-through path),
+      - by loop depth outside the block: the block's own depth is the turn around it (dispatch, the leaf tested on the spot,
+        a full batch), one above it the packet (its set-up, the flush of a partial batch), two above it the job.
+    Multiplied by the event counts of an instrumented run (tools/analysis/stamps_run.py) these give the per-launch table of
+    profiles/ao_scalar_side_notes.md.  Returns the report's lines."""
+    lines = isa_text.split("\n")
+    report, name, start = [], None, 0
+    for i, line in enumerate(lines):
+        m = re.match(r"^(_Z\w+):", line)
+        if m and name is None:
+            name, start = m.group(1), i
+        if not (line.startswith(".Lfunc_end") and name is not None):
+            continue
+        body, kernel, name = lines[start:i], name, None
+        over = [j for j, text in enumerate(body) if re.match(r"^\.Lw_over_wait_\d+:", text)]
+        if not over or not demangle(kernel).replace("ocrt::", "").replace("void ", "").startswith("ao_kernel<"):
+            continue
+        a = max(j for j in range(over[0]) if "ASMSTART" in body[j])
+        b = min(j for j in range(over[0], len(body)) if "ASMEND" in body[j])
+        report.append(demangle(kernel).replace("ocrt::", "").replace("void ", "") + "   " + " ".join(f"{c:>6s}" for c in CLASSES))
+        report.append(class_row("whole kernel", count_classes(body)))
+        # the block by labelled stretch
+        label, stretch = "entry checks", []
+        for text in body[a + 1:b]:
+            m = re.match(r"^(\.Lw_[a-z_]+?)_\d+:", text)
+            if m:
+                if any(instruction_class(t) for t in stretch):
+                    report.append(class_row("block: " + label, count_classes(stretch)))
+                label, stretch = m.group(1), []
+            else:
+                stretch.append(text)
+        report.append(class_row("block: " + label, count_classes(stretch)))
+        # loop depths, as lane_ops_by_place reads them
+        depth, depths = 0, []
+        for j, text in enumerate(body):
+            m = re.match(r"^(\.LBB\d+_\d+:|; %bb\.\d+:)(.*)", text)
+            if m:
+                note, k = m.group(2), j + 1
+                while k < len(body) and re.match(r"^\s+;", body[k]):
+                    note += body[k]
+                    k += 1
+                own = re.search(r"This (?:Inner )?Loop Header: Depth=(\d+)", note)
+                inside = re.search(r"in Loop: Header=\S+ Depth=(\d+)", note)
+                depth = int(own.group(1)) if own else int(inside.group(1)) if inside else 0
+            depths.append(depth)
+        walk_depth = depths[a]
+        # header of the loop around the block -> ASMSTART
+        header = max((j for j in range(a) if re.match(r"^\.LBB\d+_\d+:", body[j]) and depths[j] == walk_depth
+                      and re.search(r"Loop Header: Depth=%d" % walk_depth, "".join(body[j:j + 8]))), default=None)
+        if header is not None:
+            report.append(class_row("loop header -> ASMSTART", count_classes(body[header:a])))
+        tail = []
+        for text in body[b + 1:]:
+            c = instruction_class(text)
+            if c in ("VALU", "LDS", "VMEM"):
+                break
+            tail.append(text)
+        report.append(class_row("ASMEND -> first vector instruction", count_classes(tail)))
+        outside = [j for j in range(len(body)) if not a <= j <= b]
+        for d, what in ((walk_depth, "the turn around the block"), (walk_depth - 1, "per packet"), (walk_depth - 2, "per job")):
+            report.append(class_row(f"depth {d}: {what}", count_classes(body[j] for j in outside if depths[j] == d)))
+        report.append("")
+    return report
 
 
 def main():
@@ -207,6 +322,9 @@ def main():
         for want in HOT_PRIMARY:
             if not any(k.replace("ocrt::", "").replace("void ", "").startswith(want) for k in places):
                 errors.append(f"{want}: no hand-scheduled node loop found in the device assembly")
+        lines.append("")
+        lines.append("Instructions by class and place, the kernels with the any-hit node loop (static counts; scalar_side_by_place says what the rows are)")
+        lines.extend(scalar_side_by_place(open(sys.argv[sys.argv.index("--isa") + 1]).read()))
     table = "\n".join(lines) + "\n"
     if "--table" in sys.argv:
         with open(sys.argv[sys.argv.index("--table") + 1], "w") as f:
