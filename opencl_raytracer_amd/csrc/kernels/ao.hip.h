@@ -426,6 +426,10 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 						shared_dir = OCRT_COLD_PTR(const float4 *, ao_table)[dir0 + (base >> 6)];
 					// the interval of the walk array this packet has to walk (entry_kernel): the one of its table direction,
 					// or the tile's.  Two words, made scalar by hand like every load through a re-read pointer.
+					// (One s_load_dwordx2 from a scalar address in their place -- every input is wave-uniform -- was built and measured:
+					// three vector instructions and the vector load fewer per packet, and the frame no faster, the stream of frames 1 %
+					// slower: the scalar load's wait stops the wave where the vector load travels under the ray's set-up.
+					// profiles/any_hit_issue_cuts_notes.md)
 					uint32_t entry_begin, entry_end;
 					{
 						const uint32_t stride = OCRT_COLD_U32(P.entry_stride);  // (1: this frame keeps the tiles' own intervals only)
@@ -445,7 +449,7 @@ __device__ __forceinline__ void ao_pass(const FrameArgs &A, TileShared *shared_t
 						                          OCRT_COLD_F32(P.ao_max_distance), A.P.ao_below, 0.0f, alive, false, &sh.occluded[h], sh.batch,
 						                          A.P.batch_below, walk_prof);
 					else  // (the list limit, A.P.batch_below, is fetched here and stays in a register to the packet's end: OCRT_WALK_MIXED_CE)
-						shared_walk_any_hit<false, PREFETCH>(nullptr, walk_ptr, tris_ptr, count, ray, sh.frame, h,
+						shared_walk_any_hit<false, PREFETCH, MODE != AO_UNIFORM>(nullptr, walk_ptr, tris_ptr, count, ray, sh.frame, h,
 						                           0.0f, A.P.ao_below, OCRT_COLD_F32(P.walk_scale), alive, tame, &sh.occluded[h], sh.batch,
 						                           A.P.batch_below, walk_prof, entry_begin, entry_end, OCRT_COLD_U32(P.walk_ce_bytes));
 				}

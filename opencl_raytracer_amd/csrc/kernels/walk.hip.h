@@ -123,7 +123,8 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 // s_and (sets SCC), branch, add = 5 on a miss.
 // At a leaf hit by fewer than `batch_below` lanes it does not stop but appends the (lane, leaf) pairs to the
 // wave's list in LDS (entry = leaf | lane << 26 at index waiting + rank of the lane among the hitters) and walks
-// on; `leaf_stops` counts the leaves some lane hit.
+// on; `leaf_stops` counts the leaves some lane hit.  (The any-hit loop keeps the list by its next free byte address
+// instead of the count: OCRT_APPEND_CURSOR.)
 // Returns 0: walk over; 1: `leaf` is hit by many lanes (`hit`), test it now, `at` is on it; 2: 64 or more pairs
 // are waiting, run a batch, `at` is on the leaf appended last.
 // Scratch: s[42:63], v56-v62; only scalar outputs, so that the compiler knows the results to be wave-uniform.
@@ -134,8 +135,10 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 // (EXEC writes by SALU are interlocked for vector and LDS instructions); s_load -> s_waitcnt lgkmcnt(0) before the
 // first use (also drains the ds_write of an append, harmless); no v_readlane / v_div_fmas / VMEM-with-SGPR-address
 // consumers of VALU-written SGPRs in here.  The any-hit form's own: s_and_saveexec_b64 (OCRT_NARROW_AND) is an SALU write of
-// EXEC like the s_mov_b64 it replaces, same interlock in front of the ds_write; the v_mbcnt / v_add / v_or before it read
-// s44 / s45 / s46, which SALU instructions wrote (no hazard in that direction); s_cmp_eq_u64 (OCRT_ENTRY_ALIVE) reads an
+// EXEC like the s_mov_b64 it replaces, same interlock in front of the ds_write; the v_mbcnt / v_lshl_add / v_or before it read
+// s44 / s45 and the cursor, which SALU instructions wrote (no hazard in that direction; s_lshl2_add_u32, which advances the
+// cursor, is an SALU write like the s_add_u32 of the count, read by the next append's VALU or by the compiler's code behind the
+// block); s_cmp_eq_u64 (OCRT_ENTRY_ALIVE) reads an
 // operand the compiler made before the block; the second s_load_dwordx16 (OCRT_DESCEND_UNCHECKED) is issued after the last
 // read of s[56:63] -- TEST_B's fmas and the s_cmp on s63 -- and waited for at .Lw_wait like the first.
 // The build fails if the kernels using this loop spill vector registers
@@ -193,6 +196,11 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 // twelve-instruction form, a v_fma_f32 per value (tests/test_node_test_forms_gpu.py holds the two against each other on the
 // device, kernels/node_test_forms.hip.h).  Against that form the any-hit pass issues 13.8 % fewer vector instructions and
 // the headline frame is 2 ... 6 % shorter (profiles/node_test_packed_notes.md).
+// Nine is NOT taken to eight: t_c of x and y from one more packed fma -- (c.x, c.y) is an aligned SGPR pair, (ix, iy) and
+// (oix, oiy) would be register pairs, the consumers pick a half each with op_sel -- is the floor of this formulation by count,
+// and the probe runs it at 33.4 ... 33.9 cycles per SIMD in each of three schedules against 30.4 ... 30.6 for the nine, seven
+// repeats each in one process (tools/microbench/valu_rate_probe.hip `tests`, profiles/any_hit_issue_cuts_probe.txt): eight
+// instructions of 4.2 cycles, where the three plain fmas with a scalar operand issue at about 2.9 among the packed ones.
 #define OCRT_TEST_CE_SCALED(CX, CY, CZ, E_XY, E_ZW)                                                                   \
 	"\tv_fma_f32 v56, " CX ", %[ix], %[oix]\n"                                                                        \
 	"\tv_fma_f32 v58, " CY ", %[iy], %[oiy]\n"                                                                        \
@@ -211,7 +219,18 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 // (one instruction for the two: s[44:45] = vcc & alive holds no lane outside EXEC, so the AND with EXEC changes nothing;
 // it writes SCC, which the s_cmp behind the ds_write sets anew before anybody reads it)
 #define OCRT_NARROW_AND "\ts_and_saveexec_b64 s[42:43], s[44:45]\n"
-#define OCRT_WALK_LEAF(LEAF, NOW, NEXT, COUNT, NARROW)  \
+// APPEND: how the list is kept.  OCRT_APPEND_COUNT (the closest-hit loops): %[waiting] counts the pairs, a lane's slot is
+// waiting + rank, its address list + 4 * slot -- five vector instructions per append, four of the slow class.
+// OCRT_APPEND_CURSOR (the any-hit loop, 5.3 M appends per headline launch): the block carries the list's next free BYTE
+// ADDRESS in %[cursor] (list + 4 * waiting, as wave-uniform as the count was), so the rank goes straight into
+// v_lshl_add_u32 and the v_add_u32 that added one scalar to every lane is gone: four.  s_lshl2_add_u32 advances the cursor
+// by four bytes per hitter (it writes SCC, which the s_cmp behind it sets anew), and "64 or more waiting" is a compare with
+// %[full] = list + 256, the operand that takes %[list]'s place: as many scalar instructions and operands as before.
+#define OCRT_APPEND_COUNT_ADDRESS "\tv_add_u32 v56, %[waiting], v56\n\tv_lshl_add_u32 v56, v56, 2, %[list]\n"
+#define OCRT_APPEND_COUNT_ADVANCE "\ts_add_u32 %[waiting], %[waiting], s46\n\ts_cmp_ge_u32 %[waiting], 64\n"
+#define OCRT_APPEND_CURSOR_ADDRESS "\tv_lshl_add_u32 v56, v56, 2, %[cursor]\n"
+#define OCRT_APPEND_CURSOR_ADVANCE "\ts_lshl2_add_u32 %[cursor], s46, %[cursor]\n\ts_cmp_ge_u32 %[cursor], %[full]\n"
+#define OCRT_WALK_LEAF(LEAF, NOW, NEXT, COUNT, NARROW, ADDRESS, ADVANCE)  \
 	"\ts_cmp_eq_u32 " LEAF ", -2\n"                     \
 	"\ts_cbranch_scc1 .Lw_over_%=\n"                    \
 	"\ts_bcnt1_i32_b64 s46, s[44:45]\n"                 \
@@ -220,14 +239,12 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 	"\ts_cbranch_scc1 " NOW "\n"                        \
 	"\tv_mbcnt_lo_u32_b32 v56, s44, 0\n"                \
 	"\tv_mbcnt_hi_u32_b32 v56, s45, v56\n"              \
-	"\tv_add_u32 v56, %[waiting], v56\n"                \
-	"\tv_lshl_add_u32 v56, v56, 2, %[list]\n"           \
+	ADDRESS                                             \
 	"\tv_or_b32 v57, " LEAF ", %[tag]\n"                \
 	NARROW                                              \
 	"\tds_write_b32 v56, v57\n"                         \
 	"\ts_mov_b64 exec, s[42:43]\n"                      \
-	"\ts_add_u32 %[waiting], %[waiting], s46\n"         \
-	"\ts_cmp_ge_u32 %[waiting], 64\n"                   \
+	ADVANCE                                             \
 	"\ts_cbranch_scc1 .Lw_full_%=\n"                    \
 	"\ts_branch " NEXT "\n"
 // PF_B: what the loop does between the tests of a pair, once `a` is known to be hit.  OCRT_PF_SUCCESSORS touches -- with
@@ -278,7 +295,7 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 	"\ts_add_u32 %[at], %[at], 32\n"                          \
 	"\ts_load_dwordx16 s[48:63], %[base], %[at]\n"            \
 	"\ts_branch .Lw_wait_%=\n"
-#define OCRT_WALK_ASM(ENTRY, HEAD, DESCEND, COUNT, NARROW, TEST_A, TEST_B, PF_B) \
+#define OCRT_WALK_ASM(ENTRY, HEAD, DESCEND, COUNT, NARROW, ADDRESS, ADVANCE, TEST_A, TEST_B, PF_B) \
 	ENTRY                                                   \
 	"\ts_branch .Lw_node_%=\n"                              \
 	".Lw_miss_a_%=:\n"                                      \
@@ -309,12 +326,12 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 	"\ts_add_u32 %[at], %[at], s59\n"                       \
 	"\ts_branch .Lw_node_%=\n"                              \
 	".Lw_leaf_a_%=:\n"                                      \
-	OCRT_WALK_LEAF("s55", ".Lw_now_a_%=", ".Lw_next_b_%=", COUNT, NARROW)  \
+	OCRT_WALK_LEAF("s55", ".Lw_now_a_%=", ".Lw_next_b_%=", COUNT, NARROW, ADDRESS, ADVANCE)  \
 	".Lw_now_a_%=:\n"                                       \
 	"\ts_mov_b32 %[leaf], s55\n"                            \
 	"\ts_branch .Lw_now_%=\n"                               \
 	".Lw_leaf_b_%=:\n"                                      \
-	OCRT_WALK_LEAF("s63", ".Lw_now_b_%=", ".Lw_next_a_%=", COUNT, NARROW)  \
+	OCRT_WALK_LEAF("s63", ".Lw_now_b_%=", ".Lw_next_a_%=", COUNT, NARROW, ADDRESS, ADVANCE)  \
 	".Lw_now_b_%=:\n"                                       \
 	"\ts_mov_b32 %[leaf], s63\n"                            \
 	".Lw_now_%=:\n"                                         \
@@ -333,7 +350,8 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 // checks where it is told to and counts only in the instrumented build (the pass has no use for the number, and the
 // register it would sit in across the walk holds `batch_below` instead: OCRT_WALK_MIXED_CE).
 #define OCRT_WALK_PLAIN(TEST_A, TEST_B, PF) \
-	OCRT_WALK_ASM(OCRT_ENTRY_NONE, OCRT_HEAD_NONE, OCRT_DESCEND_CHECKED, OCRT_COUNT_STOPS, OCRT_NARROW_MOV, TEST_A, TEST_B, PF)
+	OCRT_WALK_ASM(OCRT_ENTRY_NONE, OCRT_HEAD_NONE, OCRT_DESCEND_CHECKED, OCRT_COUNT_STOPS, OCRT_NARROW_MOV, OCRT_APPEND_COUNT_ADDRESS, \
+	              OCRT_APPEND_COUNT_ADVANCE, TEST_A, TEST_B, PF)
 #ifdef OCRT_STAMPS
 #define OCRT_ANY_HIT_COUNT OCRT_COUNT_STOPS
 #define OCRT_ANY_HIT_STOPS , [stops] "+s"(leaf_stops)
@@ -342,7 +360,8 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 #define OCRT_ANY_HIT_STOPS
 #endif
 #define OCRT_WALK_ANY_HIT(TEST_A, TEST_B, PF) \
-	OCRT_WALK_ASM(OCRT_ENTRY_ALIVE, OCRT_HEAD_END, OCRT_DESCEND_UNCHECKED, OCRT_ANY_HIT_COUNT, OCRT_NARROW_AND, TEST_A, TEST_B, PF)
+	OCRT_WALK_ASM(OCRT_ENTRY_ALIVE, OCRT_HEAD_END, OCRT_DESCEND_UNCHECKED, OCRT_ANY_HIT_COUNT, OCRT_NARROW_AND, OCRT_APPEND_CURSOR_ADDRESS, \
+	              OCRT_APPEND_CURSOR_ADVANCE, TEST_A, TEST_B, PF)
 #define OCRT_WALK_CLOBBERS                                                                                              \
 	"s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", \
 	    "s59", "s60", "s61", "s62", "s63", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "vcc", "scc", "memory"
@@ -380,10 +399,10 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 // changed has to stay where it is -- the register the count of leaf stops used to keep across the walk)
 #define OCRT_WALK_MIXED_CE(TEST, PF)                                                                                      \
 	asm volatile(OCRT_WALK_ANY_HIT(TEST("s48", "s49", "s50", "s[52:53]", "s[54:55]"), TEST("s56", "s57", "s58", "s[60:61]", "s[62:63]"), PF) \
-	             : [at] "+s"(at), [waiting] "+s"(waiting), [batch_below] "+s"(batch_below), [hit] "=&s"(hit_mask),        \
+	             : [at] "+s"(at), [cursor] "+s"(waiting), [batch_below] "+s"(batch_below), [hit] "=&s"(hit_mask),         \
 	               [leaf] "=&s"(leaf), [status] "=&s"(status) OCRT_ANY_HIT_STOPS                                         \
 	             : [base] "s"(walk_ptr), [alive] "s"(alive_mask), [end] "s"(walk_end),                                    \
-	               [list] "s"(list_lds_address), [tag] "v"(lane_tag),                                                      \
+	               [full] "s"(list_lds_address), [tag] "v"(lane_tag),                                                      \
 	               [ix] "v"(ray.ix), [iy] "v"(ray.iy), [iz] "v"(ray.iz), [oix] "v"(ray.oix), [oiy] "v"(ray.oiy),          \
 	               [oiz] "v"(ray.oiz), [axy] "v"(abs_xy), [azw] "v"(abs_zw)                                               \
 	             : OCRT_WALK_CLOBBERS)
@@ -401,7 +420,9 @@ __device__ __forceinline__ void exact_walk(const float4 *nodes_ptr, uint32_t cou
 	}
 
 // `variant`: 0..7 = sign octant of a coherent packet (bit 0: x reciprocals >= 0, bit 1: y, bit 2: z), 8 = mixed.
-// SCALED: `ray` was made with the frame's walk_scale and `below` is not looked at (the limit is 1.0).
+// SCALED: `ray` was made with the frame's walk_scale and `below` is not looked at (the limit is 1.0); `waiting` is the
+// list's next free byte address in LDS and `list_lds_address` the address 64 entries behind the list's head, at or
+// behind which a batch is due (OCRT_APPEND_CURSOR).
 constexpr uint32_t WALK_MIXED = 8u;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <bool SCALED, bool PREFETCH = false>
@@ -461,6 +482,21 @@ __device__ __forceinline__ bool exact_leaf_gate(const float4 lo, const float4 hi
 	return t_near <= t_far;
 }
 
+// The lane number out of the tag an any-hit packet's list entries carry (lane << 26), which is live across the walk anyway:
+// one shift where fresh_lane() issues two v_mbcnt, 2.4 M times per headline launch.  AGAIN: by an asm volatile like
+// fresh_lane's.  A plain shift is loop-invariant to the compiler, which then holds the lane number across the walk beside
+// the tag: the UNIFORM kernels have that register to spare and are the better for it (30 scalar registers spilled and 6 lane
+// operations per packet, as before; 35 and 7 with the shift made anew each time), the RANDOM kernel has not and spilled four
+// vector registers to scratch memory over it -- so the caller says which (build/kernel_resources.txt shows both).
+template <bool AGAIN>
+__device__ __forceinline__ uint32_t lane_of_tag(uint32_t lane_tag) {
+	if (!AGAIN)
+		return lane_tag >> 26;
+	uint32_t lane;
+	asm volatile("v_lshrrev_b32 %0, 26, %1" : "=v"(lane) : "v"(lane_tag));
+	return lane;
+}
+
 // Triangle tests of an any-hit packet waiting to be run 64 at a time (LDS, one per wave).
 struct LeafBatch {
 	unsigned int entry[128];       // leaf | owning lane << 26; up to 63 waiting + 64 appended at one leaf
@@ -496,7 +532,8 @@ constexpr uint32_t INF_BITS = 0x7F800000u;
 // candidates, while 70 % of the batches and 82 % of the leaves tested on the spot hold no accepted triangle at all on the
 // headline frame, and those skip the box's loads, the gate's 27 vector instructions and the bookkeeping behind a batch
 // (counted and measured: profiles/ao_leaf_batches_notes.md).
-template <bool EXACT, bool PREFETCH = false>
+// LANE_AGAIN (the fast form only): how the lane number is had behind the block, lane_of_tag.
+template <bool EXACT, bool PREFETCH = false, bool LANE_AGAIN = false>
 __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ nodes_ptr, const float4 *__restrict__ walk_ptr,
                                                     const float4 *__restrict__ tris_ptr,
                                                     uint32_t count, const Ray &ray_in, const float (&frame)[12][64], uint32_t h,
@@ -523,7 +560,14 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 		// tests nor who computes them matters, and every test is the same arithmetic on the same
 		// operands as before.  A ray found occluded leaves the walk after the batch instead of at
 		// the leaf, which only lets it ride along a little longer.
-		uint32_t waiting = 0u;  // pairs in batch.entry (wave-uniform)
+		// The pairs waiting in batch.entry are kept as the list's next free byte address (wave-uniform), which is what an
+		// append needs; their number is (cursor - list) / 4 where a batch is run.  The lane number is live across the walk
+		// as the tag of an entry, lane << 26: behind the block one shift gives it back where two v_mbcnt did.
+		// (Everything is reckoned from ONE held scalar, `list_full` = the address 64 entries behind the list's head, the
+		// block's operand: the list's head held beside it would be one register more across the walk.)
+		const uint32_t list_full = (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) (uintptr_t) &batch.entry[64]);  // (low half of the flat address; scalar)
+		uint32_t cursor = list_full - 256u;
+		uint32_t lane_tag;  // (made below, behind the walk ray: its register is not live while that one is made)
 		uint32_t leaf_stops = 0u;  // (not used by this pass)
 #ifdef OCRT_STAMPS
 		// the leaf-test events by kind, counted in the wave's LDS slice: seven more accumulators in registers made the
@@ -538,7 +582,7 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 			const unsigned long long tb0 = __builtin_amdgcn_s_memrealtime();
 #endif
 			wave_lds_sync();
-			const uint32_t lane = fresh_lane();
+			const uint32_t lane = lane_of_tag<LANE_AGAIN>(lane_tag);
 			const uint32_t pair = batch.entry[lane < n ? lane : 0u];
 			const int owner = (int) (pair >> 26);
 			const Ray ray = with_origin();
@@ -593,7 +637,6 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 			prof[3] += 1;
 #endif
 		};
-		const uint32_t list_lds_address = (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) (uintptr_t) &batch.entry[0]);  // (low half of the flat address; scalar)
 		const SignMasks sign{ 0ull, 0ull, 0ull };  // (not looked at by the any-hit loop)
 		const uint32_t variant = WALK_MIXED;
 		// byte offset of the node: the walk reads the centre / half-extent copy of the records, which lies behind the plane
@@ -604,7 +647,7 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 		const uint32_t whole = count * 32u;
 		const uint32_t end = copy + (entry_end < whole ? entry_end : whole);
 		const WalkRay walk_ray = tame ? make_walk_ray(with_origin(), walk_scale, true) : make_walk_ray(with_origin(), walk_scale);  // (wave-uniform)
-		const uint32_t lane_tag = fresh_lane() << 26;
+		lane_tag = fresh_lane() << 26;
 		// One turn per walk segment.  Whether there is anything left to walk -- a live lane, `at` before `end` -- is asked
 		// INSIDE the block (OCRT_ENTRY_ALIVE, OCRT_HEAD_END on its first load), and the turn has one condition, at its foot:
 		// a loop that is left from its middle, on a status code, is rebuilt by the compiler out of mask registers and
@@ -617,7 +660,7 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 			const unsigned long long tw0 = __builtin_amdgcn_s_memrealtime();
 #endif
 			status = walk_collect<true, PREFETCH>(variant, walk_ptr, at, walk_ray, sign, below, alive_mask, hit_mask, leaf,
-			                                      waiting, leaf_stops, list_lds_address, lane_tag, batch_below, end);
+			                                      cursor, leaf_stops, list_full, lane_tag, batch_below, end);
 #ifdef OCRT_STAMPS
 			prof[0] += __builtin_amdgcn_s_memrealtime() - tw0;
 			prof[2] += 1;  // (entries: one per leaf stop and batch, and one -- the last, possibly empty -- per packet)
@@ -630,7 +673,7 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 				const float inv_d = rec[1].w;
 				const Ray ray = with_origin();
 				bool accepted = false;
-				if ((hit_mask >> fresh_lane()) & 1ull)
+				if ((hit_mask >> lane_of_tag<LANE_AGAIN>(lane_tag)) & 1ull)
 					accepted = tri_any_hit(q0, q1, q2, q3, inv_d, ray);
 				const bool any_accepted = wave_ballot(accepted) != 0ull;
 #ifdef OCRT_STAMPS
@@ -646,15 +689,15 @@ __device__ __forceinline__ void shared_walk_any_hit(const float4 *__restrict__ n
 				}
 			} else if (status == 2u) {
 				run_batch(64u);
-				waiting -= 64u;
-				const uint32_t me = fresh_lane();
-				if (me < waiting)  // the pairs beyond the batch move to the front
+				const uint32_t me = lane_of_tag<LANE_AGAIN>(lane_tag);
+				if (me < (cursor - list_full) >> 2)  // the pairs beyond the batch move to the front
 					batch.entry[me] = batch.entry[64u + me];
+				cursor -= 256u;
 			}
 			at += 32u;  // (off the leaf the block stopped on; nobody reads it once the walk is over)
 		} while (status != 0u);
-		if (waiting != 0u)
-			run_batch(waiting);
+		if (cursor != list_full - 256u)
+			run_batch((cursor - list_full + 256u) >> 2);
 #ifdef OCRT_STAMPS
 		prof[4] += leaf_stops;
 #endif

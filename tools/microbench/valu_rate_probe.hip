@@ -4,6 +4,8 @@
 // with the packed node test: profiles/node_test_packed_probe.txt)
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 typedef float f2v __attribute__((ext_vector_type(2)));
 
 #define R4(S) S S S S
@@ -90,6 +92,21 @@ KERNEL(node_test_12pk, "v_fma_f32 v40, s20, v52, v53\n v_fma_f32 v42, s21, v52, 
        "v_pk_fma_f32 v[42:43], s[20:21], v[48:49], v[42:43] op_sel:[1,1,0] op_sel_hi:[1,1,0] neg_lo:[1,0,0]",
        "v_pk_fma_f32 v[44:45], s[22:23], v[50:51], v[44:45] op_sel:[0,0,0] op_sel_hi:[0,0,0] neg_lo:[1,0,0] clamp", "v_max3_f32 v40, v40, v42, v44",
        "v_min3_f32 v41, v41, v43, v45", "v_cmp_lt_f32 vcc, v40, v41", "s_and_b64 s[24:25], vcc, exec")
+// ... and the eight-instruction form: t_c of x and y from ONE packed fma too -- (c.x, c.y) is an aligned SGPR pair, (ix, iy)
+// and (oix, oiy) aligned register pairs --, whose two consumers pick a half each (the y one over its own input).  Operand kinds
+// as in node_test_12pk: s[20:21] the centre pair, s[22:23] the half-extents, v[48:49] = (|ix|, |iy|), v[50:51] stands for
+// (oix, oiy) and for (|iz|, -), v[52:53] for (ix, iy) and for iz, oiz.  Three schedules: the packed t_c first with its two
+// consumers directly behind it (a), v_fma_f32 of t_c.z between producer and consumers (b), and t_c.z in front of all (c).
+#define T8_TC "v_pk_fma_f32 v[40:41], s[20:21], v[52:53], v[50:51]"
+#define T8_Z "v_fma_f32 v44, s22, v52, v53"
+#define T8_X "v_pk_fma_f32 v[42:43], s[22:23], v[48:49], v[40:41] op_sel:[0,0,0] op_sel_hi:[0,0,0] neg_lo:[1,0,0]"
+#define T8_Y "v_pk_fma_f32 v[40:41], s[22:23], v[48:49], v[40:41] op_sel:[1,1,1] op_sel_hi:[1,1,1] neg_lo:[1,0,0]"
+#define T8_ZZ "v_pk_fma_f32 v[44:45], s[20:21], v[50:51], v[44:45] op_sel:[0,0,0] op_sel_hi:[0,0,0] neg_lo:[1,0,0] clamp"
+#define T8_TAIL "v_max3_f32 v42, v42, v40, v44", "v_min3_f32 v43, v43, v41, v45", "v_cmp_lt_f32 vcc, v42, v43\n s_and_b64 s[24:25], vcc, exec"
+#define KERNEL_EXPANDED(...) KERNEL(__VA_ARGS__)  // (T8_TAIL is three arguments)
+KERNEL_EXPANDED(node_test_8pk_a, T8_TC, T8_X, T8_Y, T8_Z, T8_ZZ, T8_TAIL)
+KERNEL_EXPANDED(node_test_8pk_b, T8_TC, T8_Z, T8_X, T8_Y, T8_ZZ, T8_TAIL)
+KERNEL_EXPANDED(node_test_8pk_c, T8_Z, T8_TC, T8_X, T8_Y, T8_ZZ, T8_TAIL)
 #define PKNEG(D, S) "v_pk_fma_f32 v[" D "], s[" S "], v[50:51], v[52:53] op_sel:[1,1,1] op_sel_hi:[1,1,1] neg_lo:[1,0,0]"
 KERNEL(pk_fma_svv_neg, PKNEG("40:41", "20:21"), PKNEG("42:43", "22:23"), PKNEG("44:45", "20:21"), PKNEG("46:47", "22:23"), PKNEG("40:41", "20:21"),
        PKNEG("42:43", "22:23"), PKNEG("44:45", "20:21"), PKNEG("46:47", "22:23"))
@@ -97,8 +114,37 @@ KERNEL1(fma_svv_clamp, "v_fma_f32", "s20, v49, v50 clamp")
 KERNEL(fma_svv_4regs, "v_fma_f32 v40, s20, v48, v49", "v_fma_f32 v41, s21, v48, v49", "v_fma_f32 v42, s22, v48, v49", "v_fma_f32 v43, s23, v48, v49",
        "v_fma_f32 v44, s20, v48, v49", "v_fma_f32 v45, s21, v48, v49", "v_fma_f32 v46, s22, v48, v49", "v_fma_f32 v47, s23, v48, v49")
 struct Kind { const char *name; void (*k)(unsigned long long *, int, float, float); double vector_per_turn; };
-int main() {
+// `valu_rate_probe tests [repeats]`: only the any-hit node test, nine instructions against eight in its schedules, every
+// repeat of every form printed (interleaved, one process) -- the spread between the repeats of one form is what a difference
+// between two forms has to exceed (profiles/any_hit_issue_cuts_probe.txt).
+static int node_tests(int repeats) {
+	unsigned long long *d, h[3]; hipMalloc(&d, 64);
+	hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+	const Kind forms[] = {{"node_test_12pk (9 instructions)", node_test_12pk, 36.0}, {"node_test_8pk_a (8: t_c.xy, x, y, t_c.z, z)", node_test_8pk_a, 32.0},
+	                      {"node_test_8pk_b (8: t_c.xy, t_c.z, x, y, z)", node_test_8pk_b, 32.0}, {"node_test_8pk_c (8: t_c.z, t_c.xy, x, y, z)", node_test_8pk_c, 32.0}};
+	const int iters = 10000;
+	for (const Kind &form : forms) {  // (warm-up: clocks up, code in the instruction caches)
+		form.k<<<256 * 8, 256>>>(d, iters, 1.0001f, 0.5f);
+		hipDeviceSynchronize();
+	}
+	for (int rep = 0; rep < repeats; ++rep)
+		for (const Kind &form : forms) {
+			hipMemset(d, 0, 24);
+			hipEventRecord(e0);
+			form.k<<<256 * 8, 256>>>(d, iters, 1.0001f, 0.5f);
+			hipEventRecord(e1); hipEventSynchronize(e1);
+			float ms; hipEventElapsedTime(&ms, e0, e1);
+			hipMemcpy(h, d, 24, hipMemcpyDeviceToHost);
+			const double ghz = (double)h[1] / (h[2] * 10.0);
+			printf("repeat %d  %-46s %.3f ms  clock %.2f GHz  %.2f cycles per SIMD per TEST (%.2f per vector instruction)\n", rep, form.name, ms, ghz,
+			       ms * 1e6 * ghz / (4.0 * iters * 8), ms * 1e6 * ghz / (form.vector_per_turn * iters * 8));
+		}
+	return 0;
+}
+int main(int argc, char **argv) {
 	setvbuf(stdout, nullptr, _IONBF, 0);
+	if (argc > 1 && !strcmp(argv[1], "tests"))
+		return node_tests(argc > 2 ? atoi(argv[2]) : 7);
 	unsigned long long *d, h[3]; hipMalloc(&d, 64);
 	hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
 #define K(N) {#N, N, 32.0}
@@ -106,7 +152,8 @@ int main() {
 	                      K(max3_vvv), K(min3_svv), K(med3_vvv), K(mov_v), K(mov_s), K(cndmask_vcc), K(cndmask_s), K(and_vv), K(add_u32), K(lshl_add), K(cmp_vcc), K(cmp_sgpr),
 	                      K(pk_fma_vvv), K(pk_fma_svv), K(pk_fma_svv_sel), K(pk_mul_vv), {"node_test_11 (4 tests per turn)", node_test_11, 44.0}, {"node_test_8 (4 tests per turn)", node_test_8, 32.0},
 	                      {"node_test_9 (4 tests per turn)", node_test_9, 36.0}, {"node_test_12 (4 tests per turn)", node_test_12, 48.0}, {"node_test_12pk (4 tests per turn)", node_test_12pk, 36.0},
-	                      K(pk_fma_svv_neg), K(fma_svv_clamp),
+	                      {"node_test_8pk_a (4 tests per turn)", node_test_8pk_a, 32.0}, {"node_test_8pk_b (4 tests per turn)", node_test_8pk_b, 32.0},
+	                      {"node_test_8pk_c (4 tests per turn)", node_test_8pk_c, 32.0}, K(pk_fma_svv_neg), K(fma_svv_clamp),
 	                      K(fma_svv_4regs)};
 	const int iters = 10000;
 	for (const Kind &kind : kinds) {
@@ -123,7 +170,7 @@ int main() {
 		const double per_simd = kind.vector_per_turn * iters * 8;
 		printf("%-32s %.3f ms  %.3f instr/ns/SIMD  clock %.2f GHz  -> %.2f cycles per vector instruction per SIMD", kind.name, best, per_simd / (best * 1e6), ghz,
 		       best * 1e6 * ghz / per_simd);
-		if (kind.vector_per_turn != 32.0 || kind.k == node_test_8)
+		if (kind.vector_per_turn != 32.0 || !strncmp(kind.name, "node_test_8", 11))
 			printf("  = %.2f cycles per TEST", best * 1e6 * ghz / (4.0 * iters * 8));
 		printf("\n");
 	}
