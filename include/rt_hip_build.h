@@ -7,7 +7,9 @@
  * normals), plus the options' direction table.  The CPU never sees the tree.  Results do not depend on the tree: the
  * queries of a built scene answer what they answer after an upload of the same triangles, bit for bit, except that `leaf`
  * counts in the build's leaf order (rt_built_faces) and that, of several triangles hit at exactly the same distance, the
- * one with the lowest leaf index is reported, which is another face where the orders differ.
+ * one with the lowest leaf index is reported, which is another face where the orders differ; and that the signed distance
+ * queries' sign table (rt_hip_signed.h) sums a vertex's and an edge's pseudonormal in leaf order, so that its last bits may
+ * differ from an upload's -- which can change a sign only for points within the distance tolerance of the surface.
  *
  * What a build is.  It REPLACES the host's scene on the device; it may follow an upload or come first.  The new scene has
  * no padded walk array.  rt_update_vertices works on it unchanged -- the scene keeps its leaf-ordered faces, its leaf ->

@@ -15,6 +15,9 @@ from .api import (  # noqa: F401
     INSTANCE_VIEW_OUTPUTS,
     LAYER_OUTPUTS,
     NEAREST_OUTPUTS,
+    SIGNED_OUTPUTS,
+    FEATURES,
+    SIGN_RECORD,
     SEGMENT_INTERVAL,
     SEGMENT_OUTPUTS,
     VIEW_OUTPUTS,

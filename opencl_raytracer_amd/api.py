@@ -279,6 +279,14 @@ _SIGNATURES = {
     # include/rt_hip_nearest.h
     "rt_closest_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
     "rt_closest_points_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_signed_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
+    "rt_signed_distance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_signed_distance_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "rt_signed_distance_grid_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
+    "rt_prepare_signed_distance": (C.c_int, [C.c_void_p]),
+    "rt_last_sign_build_ms": (C.c_float, [C.c_void_p]),
+    "rt_debug_sign_table": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_instances_closest_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
     "rt_instances_closest_points_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_debug_set_nearest_walk": (C.c_int, [C.c_void_p, C.c_uint32]),
@@ -368,6 +376,11 @@ class _InstanceHitArrays(C.Structure):
     _fields_ = [("record", _HitArrays), ("instance", C.c_void_p)]
 
 
+class _SignedArrays(C.Structure):
+    """rt_signed_arrays (include/rt_hip_signed.h)."""
+    _fields_ = [("hit", _HitArrays), ("feature", C.c_void_p), ("pseudonormal4", C.c_void_p)]
+
+
 class _InstanceMultiHitArrays(C.Structure):
     """rt_instance_multihit_arrays (include/rt_hip_instance_multihit.h)."""
     _fields_ = [("slots", _MultiHitArrays), ("instance", C.c_void_p)]
@@ -405,6 +418,10 @@ RT_MULTIHIT_MAX_K = 16
 MULTIHIT_OUTPUTS = ("count", "distance", "leaf", "barycentric", "position", "normal")
 QUERY_OUTPUTS = ("hit", "distance", "leaf", "barycentric", "position", "normal")
 NEAREST_OUTPUTS = QUERY_OUTPUTS  # closest-point queries: "hit" is `found`
+# signed distance queries: the record with `distance` signed, the feature code (FEATURES) and the pseudonormal with g behind it
+SIGNED_OUTPUTS = QUERY_OUTPUTS + ("feature", "pseudonormal")
+FEATURES = ("face", "vertex A", "vertex B", "vertex C", "edge AB", "edge AC", "edge BC")
+SIGN_RECORD = np.dtype([("edge", np.float32, (3, 4)), ("vertex", np.float32, (3, 4))])  # a leaf of Host.sign_table()
 INSTANCE_MULTIHIT_OUTPUTS = MULTIHIT_OUTPUTS + ("instance",)  # instanced multi-hit queries: the copy of every slot beside it
 INSTANCE_OUTPUTS = QUERY_OUTPUTS + ("instance",)  # instanced ray queries: the record and the instance it lies in
 RT_INSTANCES_MAX = 1 << 20
@@ -423,7 +440,7 @@ INSTANCE_VIEW_OUTPUTS = VIEW_OUTPUTS + ("instance",)  # instanced views: the cop
 _OUTPUT_LAYOUT = {"hit": (np.uint8, 1), "count": (np.uint32, 1), "ao": (np.float32, 1), "occluded": (np.uint32, 1),
                   "distance": (np.float32, 1), "leaf": (np.uint32, 1), "barycentric": (np.float32, 3), "position": (np.float32, 3),
                   "normal": (np.float32, 3), "direction": (np.float32, 3), "shade": (np.float32, 1), "value": (np.float32, 1),
-                  "bent": (np.float32, 3), "instance": (np.uint32, 1)}
+                  "bent": (np.float32, 3), "instance": (np.uint32, 1), "feature": (np.uint8, 1), "pseudonormal": (np.float32, 4)}
 _RECORD_FIELDS = ("distance", "leaf", "barycentric", "position", "normal")
 
 
@@ -1289,6 +1306,72 @@ class Host:
         out = io.outputs(outputs)
         io.call(self._h, "rt_closest_points", io.n, float(max_distance), 0 if sort else RT_QUERY_NO_SORT,
                 C.byref(_HitArrays(*io.pointers(out, NEAREST_OUTPUTS))))
+        return out
+
+    # ---- signed distance queries (include/rt_hip_signed.h) ----
+    def signed_distance(self, points, max_distance: float = float("inf"), outputs=SIGNED_OUTPUTS, sort: bool = True) -> dict:
+        """closest_points with a sign: the same record, "distance" negative where the point lies inside a closed, outward
+        oriented mesh -- by the angle-weighted pseudonormal of the vertex, edge or face the nearest point lies on --, and
+        "feature": uint8 (N,), an index into FEATURES (0xFF: nothing within max_distance); "pseudonormal": float32 (N, 4), that
+        feature's pseudonormal and its dot product with point - position.  Inputs and the numpy / torch forms as for
+        closest_points.  The first call after an upload or a build makes the sign table (prepare_signed_distance)."""
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in SIGNED_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}; choose from {SIGNED_OUTPUTS}")
+        io = _QueryArrays(points, None, ("points",), "points")
+        out = io.outputs(outputs)
+        at = io.pointers(out, SIGNED_OUTPUTS)
+        io.call(self._h, "rt_signed_distance", io.n, float(max_distance), 0 if sort else RT_QUERY_NO_SORT,
+                C.byref(_SignedArrays(_HitArrays(*at[:6]), at[6], at[7])))
+        return out
+
+    def signed_distance_grid(self, origin, spacing, shape, max_distance: float = float("inf"), as_torch: bool = False, leaf: bool = False):
+        """The signed distance field of the scene on a regular grid: float32 (nz, ny, nx) for shape = (nx, ny, nz), voxel
+        [k, j, i] at origin + (i, j, k) * spacing (float32, each coordinate origin + float32(i) * spacing), +inf where
+        nothing lies within max_distance; every voxel is, bit for bit, signed_distance's answer for that point.  leaf=True:
+        (distances, uint32 leaves of the same shape).  A numpy array (blocking), or with as_torch=True a torch tensor on the
+        host's GPU, enqueued on torch.cuda.current_stream() without waiting."""
+        o = np.ascontiguousarray(origin, np.float32).reshape(3)
+        sp = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float32), (3,)))
+        dims = np.ascontiguousarray([int(x) for x in shape], np.int64).reshape(3)
+        if (dims < 0).any() or (dims >= 1 << 32).any():
+            raise ValueError("shape: expected three counts (nx, ny, nz)")
+        if int(dims[0]) * int(dims[1]) * int(dims[2]) > 1 << 31:  # (before anything of that size is allocated)
+            raise RtError(RT_E_INVALID, "signed_distance_grid: more than 2^31 voxels in one grid")
+        dims = dims.astype(np.uint32)
+        lib, nzyx = load_library(), (int(dims[2]), int(dims[1]), int(dims[0]))
+        if as_torch:
+            import torch
+
+            device = torch.device("cuda", self._device)
+            d = torch.empty(nzyx, dtype=torch.float32, device=device)
+            l = torch.empty(nzyx, dtype=torch.uint32, device=device) if leaf else None
+            _check(lib.rt_signed_distance_grid_device(self._h, o.ctypes.data, sp.ctypes.data, dims.ctypes.data, float(max_distance),
+                                                      d.data_ptr() or 4, None if l is None else l.data_ptr() or 4,
+                                                      torch.cuda.current_stream(device).cuda_stream))
+        else:
+            d = np.empty(nzyx, np.float32)
+            l = np.empty(nzyx, np.uint32) if leaf else None
+            _check(lib.rt_signed_distance_grid(self._h, o.ctypes.data, sp.ctypes.data, dims.ctypes.data, float(max_distance),
+                                               d.ctypes.data, None if l is None else l.ctypes.data))
+        return (d, l) if leaf else d
+
+    def prepare_signed_distance(self) -> None:
+        """Makes the signed queries' sign table now (rt_prepare_signed_distance), so that the first query does not."""
+        _check(load_library().rt_prepare_signed_distance(self._h))
+
+    def last_sign_build_ms(self) -> float:
+        """HIP-event time of the last build or refresh of the sign table, ms (0.0 before the first)."""
+        return float(load_library().rt_last_sign_build_ms(self._h))
+
+    def sign_table(self) -> np.ndarray:
+        """(rt_debug_sign_table, for tests) The sign table as the device holds it: SIGN_RECORD (leaves,) -- per leaf the
+        pseudonormals of the edges AB, AC, BC (.w: the face's unit normal) and of the vertices A, B, C (.w: the corner angles)."""
+        lib, leaves = load_library(), C.c_uint32()
+        _check(lib.rt_debug_record_counts(self._h, None, C.byref(leaves)))
+        out = np.zeros(leaves.value, SIGN_RECORD)
+        _check(lib.rt_debug_sign_table(self._h, out.ctypes.data or 4))
         return out
 
     # ---- instanced closest-point queries (include/rt_hip_instance_nearest.h) ----

@@ -9,6 +9,7 @@
 #include "../../include/rt_hip_debug.h"
 #include "../../include/rt_hip_multihit.h"
 #include "../../include/rt_hip_nearest.h"
+#include "../../include/rt_hip_signed.h"
 #include "../../include/rt_hip_query.h"
 #include "../../include/rt_hip_segment.h"
 #include "../../include/rt_hip_instance_build.h"
@@ -122,6 +123,7 @@ constexpr Family SEGMENTS = { "segment", "segments", "null point arrays", "devic
 constexpr Family INSTANCED_SEGMENTS = { "instanced segment", "segments", "null point arrays", "device point arrays must be 16-byte aligned",
 	                                    true };
 constexpr Family POINTS = { "closest-point", "points", "null point array", "the device point array must be 16-byte aligned", false };
+constexpr Family SIGNED_POINTS = { "signed distance", "points", "null point array", "the device point array must be 16-byte aligned", false };
 constexpr Family INSTANCED_POINTS = { "instanced closest-point", "points", "null point array",
 	                                  "the device point array must be 16-byte aligned", true };
 
@@ -1315,6 +1317,95 @@ int rt_closest_points_device(rt_host *h, const float *points4, uint32_t n, float
 	if (!records_aligned(q))
 		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
 	return guarded([&] { queries_of(h).nearestDevice(points4, n, max_distance, flags, q, hip_stream); });
+}
+
+// ---- rt_hip_signed.h ----
+int rt_signed_distance(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags, const rt_signed_arrays *out) {
+	const int rc = query_precheck(h, SIGNED_POINTS, points4, points4, n, false);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	return guarded([&] {
+		queries_of(h).signedHost(points4, n, max_distance, flags, hit_outputs(out ? &out->hit : nullptr), out ? out->feature : nullptr,
+		                         out ? out->pseudonormal4 : nullptr);
+	});
+}
+
+int rt_signed_distance_device(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags, const rt_signed_arrays *out,
+                              void *hip_stream) {
+	const int rc = query_precheck(h, SIGNED_POINTS, points4, points4, n, true);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	const ocrt::QueryOutputs q = hit_outputs(out ? &out->hit : nullptr);
+	if (!records_aligned(q))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	if (out && !aligned({ out->pseudonormal4 }, 16))
+		return fail(RT_E_INVALID, "the device pseudonormal array must be 16-byte aligned");
+	return guarded([&] {
+		queries_of(h).signedDevice(points4, n, max_distance, flags, q, out ? out->feature : nullptr, out ? out->pseudonormal4 : nullptr, hip_stream);
+	});
+}
+
+namespace {
+// What both grid forms check before they touch the device (include/rt_hip_signed.h, "Errors").
+int grid_precheck(const rt_host *h, const float *origin, const float *spacing, const uint32_t *dims) {
+	const int rc = host_precheck(h, "signed distance");
+	if (rc != RT_OK)
+		return rc;
+	if (!origin || !spacing || !dims)
+		return fail(RT_E_INVALID, "null origin, spacing or dims");
+	for (int k = 0; k < 3; ++k) {
+		if (!(spacing[k] > 0.0f) || !std::isfinite(spacing[k]))
+			return fail(RT_E_INVALID, "the grid's spacing must be positive and finite");
+		if (dims[k] == 0)
+			return fail(RT_E_INVALID, "a grid dimension of 0");
+	}
+	// (each factor below 2^32: the first product cannot wrap, the second is checked before it is made)
+	const uint64_t slice = (uint64_t) dims[0] * dims[1], limit = (uint64_t) 1 << 31;
+	if (slice > limit || slice * dims[2] > limit)
+		return fail(RT_E_INVALID, "more than 2^31 voxels in one grid");
+	return RT_OK;
+}
+}  // namespace
+
+int rt_signed_distance_grid(rt_host *h, const float *origin, const float *spacing, const uint32_t *dims, float max_distance, float *distance,
+                            uint32_t *leaf) {
+	if (const int rc = grid_precheck(h, origin, spacing, dims); rc != RT_OK)
+		return rc;
+	return guarded([&] { queries_of(h).signedGridHost(origin, spacing, dims, max_distance, distance, leaf); });
+}
+
+int rt_signed_distance_grid_device(rt_host *h, const float *origin, const float *spacing, const uint32_t *dims, float max_distance,
+                                   float *distance, uint32_t *leaf, void *hip_stream) {
+	if (const int rc = grid_precheck(h, origin, spacing, dims); rc != RT_OK)
+		return rc;
+	if (!aligned({ distance, leaf }, 4))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).signedGridDevice(origin, spacing, dims, max_distance, distance, leaf, hip_stream); });
+}
+
+int rt_prepare_signed_distance(rt_host *h) {
+	if (const int rc = host_precheck(h, "signed distance"); rc != RT_OK)
+		return rc;
+	return guarded([&] { queries_of(h).prepareSigned(nullptr); });
+}
+
+float rt_last_sign_build_ms(rt_host *h) {
+	if (!h || !h->queries)
+		return 0.0f;
+	try {
+		return h->queries->lastSignBuildMs();
+	} catch (...) {
+		fail_from_exception();
+		return 0.0f;
+	}
+}
+
+int rt_debug_sign_table(rt_host *h, float *table) {
+	if (const int rc = host_precheck(h, "signed distance"); rc != RT_OK)
+		return rc;
+	if (!table)
+		return fail(RT_E_INVALID, "null table");
+	return guarded([&] { queries_of(h).downloadSignTable(table); });
 }
 
 // ---- rt_hip_instance_nearest.h ----

@@ -95,6 +95,11 @@ class DeviceScene {
 		static std::shared_ptr<DeviceScene> build(int device, const RayTracer::Options &options, const float *vertices4, const float *vnormals4,
 		                                          uint32_t num_vertices, const uint32_t *faces, uint32_t num_faces, uint32_t group_nodes,
 		                                          void *scratch, void *stream, void *const events[4], float *host_ms);
+		// The leaf-ordered faces (three vertex ids per leaf), for what is made of the topology beside the records (the signed
+		// distance queries' sign table, ray_query.cc): on the device where a build or a first update has put them, else
+		// null; on the host where an upload kept them, else null.
+		const void *deviceFaces() const { return d_faces; }
+		const std::vector<uint32_t> *hostFaces() const { return leaf_faces.get(); }
 		// the file-order face of every leaf of a built scene (empty: the scene was uploaded)
 		const std::vector<uint32_t> &builtFaces() const { return built_faces; }
 

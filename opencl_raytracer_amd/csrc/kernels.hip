@@ -40,7 +40,11 @@
 //                   nearest_key_kernel / nearest_scatter_kernel order caller-supplied POINTS by position, nearest_kernel finds
 //                   the nearest point of the surface for each (kernels/nearest.hip.h, include/rt_hip_nearest.h);
 //                   instance_nearest_kernel finds it among the posed copies of an instance set, measured in world space
-//                   (kernels/instance_nearest.hip.h, include/rt_hip_instance_nearest.h).
+//                   (kernels/instance_nearest.hip.h, include/rt_hip_instance_nearest.h);
+//                   signed_kernel and signed_grid_kernel are nearest_kernel's walk with a signed tail -- for points, and for
+//                   the voxels of a grid made in registers, a 4 x 4 x 4 brick per wave --, over the sign table that
+//                   sign_keys_kernel, sign_heads_kernel, sign_sum_kernel and sign_leaf_kernel make around sign_sort.hip's
+//                   sorts (kernels/signed.hip.h, include/rt_hip_signed.h).
 //                   segment_kernel<CLOSEST> answers whether the line between two caller-supplied points is free, or where it is
 //                   blocked first (segment_key_kernel / segment_scatter_kernel order the segments), visibility_mask_kernel
 //                   does so for P points against T targets, a bit per pair, visibility_count_kernel counts a point's bits
@@ -105,6 +109,7 @@
 #include "lbvh.h"
 #include "instance_plan.h"
 #include "nearest_point.h"
+#include "signed_point.h"
 #include "instance_nearest.h"
 #include "tri_predicate.h"
 
@@ -125,6 +130,7 @@
 #include "kernels/instance_build.hip.h"
 #include "kernels/node_test_forms.hip.h"
 #include "kernels/nearest.hip.h"
+#include "kernels/signed.hip.h"
 #include "kernels/segment.hip.h"
 #include "kernels/instances.hip.h"
 #include "kernels/instance_views.hip.h"
@@ -514,6 +520,80 @@ void launch_nearest(const SceneBuffers &scene, uint32_t node_count, uint32_t tri
 	} else {
 		hipLaunchKernelGGL(nearest_kernel<false>, dim3(blocks), dim3(64 * NEAREST_WAVES), 0, (hipStream_t) stream, a);
 	}
+}
+
+// Signed distance queries (kernels/signed.hip.h).  The table's pieces, in the order ray_query.cc runs them: the sorts' inputs
+// of the 3 tri_count corners; (sign_sort.hip's sorts;) the kept incidence words out of a sort's result; the sums and the
+// per-leaf words, which are all an update redoes.
+void launch_sign_keys(const void *faces, uint32_t tri_count, void *vertex_keys, void *edge_keys, void *values, void *stream) {
+	const uint32_t corners = 3u * tri_count;
+	if (corners == 0)
+		return;
+	hipLaunchKernelGGL(sign_keys_kernel, dim3((corners + 255u) / 256u), dim3(256), 0, (hipStream_t) stream, (const uint32_t *) faces, corners,
+	                   (uint32_t *) vertex_keys, (unsigned long long *) edge_keys, (uint32_t *) values);
+}
+
+void launch_sign_heads(bool wide, const void *sorted_keys, const void *sorted_values, uint32_t tri_count, void *kept, void *stream) {
+	const uint32_t corners = 3u * tri_count;
+	if (corners == 0)
+		return;
+	if (wide)
+		hipLaunchKernelGGL(sign_heads_kernel<unsigned long long>, dim3((corners + 255u) / 256u), dim3(256), 0, (hipStream_t) stream,
+		                   (const unsigned long long *) sorted_keys, (const uint32_t *) sorted_values, corners, (uint32_t *) kept);
+	else
+		hipLaunchKernelGGL(sign_heads_kernel<uint32_t>, dim3((corners + 255u) / 256u), dim3(256), 0, (hipStream_t) stream,
+		                   (const uint32_t *) sorted_keys, (const uint32_t *) sorted_values, corners, (uint32_t *) kept);
+}
+
+void launch_sign_sums(const void *kept_vertices, const void *kept_edges, const SceneBuffers &scene, uint32_t tri_count, void *table, void *stream) {
+	const uint32_t corners = 3u * tri_count;
+	if (corners == 0)
+		return;
+	hipStream_t s = (hipStream_t) stream;
+	hipLaunchKernelGGL(sign_leaf_kernel, dim3((tri_count + 255u) / 256u), dim3(256), 0, s, (const float4 *) scene.tris, tri_count, (float4 *) table);
+	hipLaunchKernelGGL(sign_sum_kernel<false>, dim3((corners + 255u) / 256u), dim3(256), 0, s, (const uint32_t *) kept_vertices, corners,
+	                   (const float4 *) scene.tris, tri_count, (float4 *) table);
+	hipLaunchKernelGGL(sign_sum_kernel<true>, dim3((corners + 255u) / 256u), dim3(256), 0, s, (const uint32_t *) kept_edges, corners,
+	                   (const float4 *) scene.tris, tri_count, (float4 *) table);
+}
+
+// The point form: launch_nearest's arguments, the table, and the two outputs of its own.
+void launch_signed(const SceneBuffers &scene, uint32_t node_count, uint32_t tri_count, const void *points, const void *order, uint32_t n,
+                   float max_distance, uint32_t walk, const QueryOutputs &out, uint8_t *feature, float *pseudonormal4, const void *table,
+                   const void *coords_flag, void *stream) {
+	if (n == 0)
+		return;
+	SignedArgs a{};
+	fill(a.nearest, scene, node_count, tri_count, points, order, n, max_distance, walk, out, coords_flag, nullptr);
+	a.table = (const float4 *) table;
+	a.feature = feature;
+	a.pseudonormal = (float4 *) pseudonormal4;
+	const uint32_t blocks = (n + 64u * NEAREST_WAVES - 1u) / (64u * NEAREST_WAVES);
+	hipLaunchKernelGGL(signed_kernel, dim3(blocks), dim3(64 * NEAREST_WAVES), 0, (hipStream_t) stream, a);
+}
+
+// The grid form over the slab of `nz` slices from `z_first` on: `distance`, `leaf` hold [nz][ny][nx] (either may be null).
+void launch_signed_grid(const SceneBuffers &scene, uint32_t node_count, uint32_t tri_count, const float origin[3], const float spacing[3],
+                        uint32_t nx, uint32_t ny, uint32_t nz, uint32_t z_first, float max_distance, uint32_t walk, float *distance,
+                        uint32_t *leaf, const void *table, const void *coords_flag, void *stream) {
+	if (nx == 0 || ny == 0 || nz == 0)
+		return;
+	SignedGridArgs a{};
+	fill(a.nearest, scene, node_count, tri_count, nullptr, nullptr, 0u, max_distance, walk, QueryOutputs{}, coords_flag, nullptr);
+	a.table = (const float4 *) table;
+	for (int k = 0; k < 3; ++k) {
+		a.origin[k] = origin[k];
+		a.spacing[k] = spacing[k];
+	}
+	a.nx = nx; a.ny = ny; a.nz = nz; a.z_first = z_first;
+	a.bricks_x = (nx + 3u) / 4u;
+	a.bricks_y = (ny + 3u) / 4u;
+	const uint64_t bricks = (uint64_t) a.bricks_x * a.bricks_y * ((nz + 3u) / 4u);  // (at most 2^31 voxels: fewer bricks than 2^31)
+	a.bricks = (uint32_t) bricks;
+	a.distance = distance;
+	a.leaf = leaf;
+	const uint32_t blocks = (a.bricks + NEAREST_WAVES - 1u) / NEAREST_WAVES;
+	hipLaunchKernelGGL(signed_grid_kernel, dim3(blocks), dim3(64 * NEAREST_WAVES), 0, (hipStream_t) stream, a);
 }
 
 // Segment queries (kernels/segment.hip.h); their sort is launch_query_sort's with `segments`.  `set`, `instance`: as for

@@ -118,10 +118,12 @@ __global__ __launch_bounds__(256) void nearest_coordinates_kernel(const float4 *
 }
 
 // A lane's record: the minimum of (d2, leaf) so far, and the point it belongs to.
+// (`region`: np_point's, the feature the point lies on; only the signed tails read it -- kernels/signed.hip.h)
 struct Nearest {
 	float d2;
 	uint32_t leaf;
 	float s, t, px, py, pz;
+	int region;
 };
 
 __device__ __forceinline__ np_tri nearest_tri(const float4 q0, const float4 q1, const float4 q2, const float4 q3) {
@@ -142,6 +144,7 @@ __device__ __forceinline__ bool nearest_take(Nearest &best, const np_tri &tri, u
 	best.leaf = leaf;
 	best.s = r.s; best.t = r.t;
 	best.px = r.px; best.py = r.py; best.pz = r.pz;
+	best.region = r.region;
 	return true;
 }
 
@@ -189,24 +192,16 @@ __device__ __forceinline__ void nearest_descend(const SceneViews &scene, uint32_
 
 constexpr uint32_t NEAREST_WAVES = 4u;
 
-// COUNT: the counted form for tools/distance_bench.py (rt_debug_set_nearest_walk); the product's host code never launches it.
+// Both parts for one packet: the record of the lane's point q (`alive`: the lane has one that looks at anything).  Every
+// kernel of the family -- nearest_kernel, and the signed forms of kernels/signed.hip.h -- is this walk and a tail.
 template <bool COUNT>
-__global__ __launch_bounds__(64 * NEAREST_WAVES) void nearest_kernel(NearestArgs a) {
-	const uint32_t k = blockIdx.x * (64u * NEAREST_WAVES) + threadIdx.x;
-	const bool live = k < a.n;
-	uint32_t idx = k;
-	if (live && a.order)
-		idx = a.order[k];
-	float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-	if (live)
-		q = a.points[idx];
-	const bool alive = live && np_point_ok(q.x, q.y, q.z) && np_radius_ok(a.max_distance);
+__device__ __forceinline__ Nearest nearest_walk(const NearestArgs &a, const float4 q, bool alive, uint32_t &node_tests, uint32_t &tri_tests) {
 	Nearest best;
 	best.d2 = __builtin_inff();
 	best.leaf = NONE;
 	best.s = best.t = 0.0f;
 	best.px = best.py = best.pz = 0.0f;
-	uint32_t node_tests = 0u, tri_tests = 0u;
+	best.region = NP_FACE;
 	// the limit a box's distance is held against: +inf where nothing may be passed by
 	const uint32_t walk = (a.coords_flag && *a.coords_flag != 0u) ? 0u : a.walk;  // (wave-uniform)
 	const bool prune = (walk & NEAREST_PRUNE) != 0u;
@@ -246,6 +241,23 @@ __global__ __launch_bounds__(64 * NEAREST_WAVES) void nearest_kernel(NearestArgs
 		const uint32_t step = any ? 1u : (size ? size : 1u);
 		at = (uint32_t) __builtin_amdgcn_readfirstlane((int) (at + step));
 	}
+	return best;
+}
+
+// COUNT: the counted form for tools/distance_bench.py (rt_debug_set_nearest_walk); the product's host code never launches it.
+template <bool COUNT>
+__global__ __launch_bounds__(64 * NEAREST_WAVES) void nearest_kernel(NearestArgs a) {
+	const uint32_t k = blockIdx.x * (64u * NEAREST_WAVES) + threadIdx.x;
+	const bool live = k < a.n;
+	uint32_t idx = k;
+	if (live && a.order)
+		idx = a.order[k];
+	float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+	if (live)
+		q = a.points[idx];
+	const bool alive = live && np_point_ok(q.x, q.y, q.z) && np_radius_ok(a.max_distance);
+	uint32_t node_tests = 0u, tri_tests = 0u;
+	const Nearest best = nearest_walk<COUNT>(a, q, alive, node_tests, tri_tests);
 	if (COUNT) {
 		// (one atomic pair per wave: the lanes' counts summed across the wave first)
 		unsigned long long nodes = node_tests, tris = tri_tests;

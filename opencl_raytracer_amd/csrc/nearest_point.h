@@ -48,8 +48,13 @@ typedef struct np_tri {
 	float tax, tay, taz, ux, uy, uz, vx, vy, vz, uu, uv, vv, D;
 } np_tri;
 
+/* `region`: the feature of the triangle the point lies on, as the test that was taken names it -- never derived from
+ * (s, t): in the BC region 1 - s - t is not exactly 0.  The signed queries read it (signed_point.h); no distance does. */
+enum { NP_FACE = 0, NP_VERTEX_A = 1, NP_VERTEX_B = 2, NP_VERTEX_C = 3, NP_EDGE_AB = 4, NP_EDGE_AC = 5, NP_EDGE_BC = 6 };
+
 typedef struct np_point {
 	float s, t, px, py, pz, d2;
+	int region;
 } np_point;
 
 OCRT_NP_FN float np_dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
@@ -59,6 +64,7 @@ OCRT_NP_FN np_point np_at(const np_tri tri, float qx, float qy, float qz, float 
 	np_point r;
 	r.s = s;
 	r.t = t;
+	r.region = NP_FACE;
 	r.px = tri.tax + (tri.ux * s + tri.vx * t);
 	r.py = tri.tay + (tri.uy * s + tri.vy * t);
 	r.pz = tri.taz + (tri.uz * s + tri.vz * t);
@@ -83,7 +89,7 @@ OCRT_NP_FN float np_clamped(float num, float den) {
 /* Parameters, and whether they are a region's. */
 typedef struct np_params {
 	float s, t;
-	int found;
+	int found, region;
 } np_params;
 
 /* The parameters of the vertex or edge region whose test holds first; found = 0 where none did (np_face then). */
@@ -96,19 +102,20 @@ OCRT_NP_FN np_params np_region(const np_tri tri, float d1, float d2) {
 	r.s = 0.0f;
 	r.t = 0.0f;
 	r.found = 1;
+	r.region = NP_FACE;
 	if (d1 <= 0.0f && d2 <= 0.0f) {
-		r.s = 0.0f, r.t = 0.0f;
+		r.s = 0.0f, r.t = 0.0f, r.region = NP_VERTEX_A;
 	} else if (d3 >= 0.0f && d4 <= d3) {
-		r.s = 1.0f, r.t = 0.0f;
+		r.s = 1.0f, r.t = 0.0f, r.region = NP_VERTEX_B;
 	} else if (uu > 0.0f && vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
-		r.s = d1 / uu, r.t = 0.0f;
+		r.s = d1 / uu, r.t = 0.0f, r.region = NP_EDGE_AB;
 	} else if (d6 >= 0.0f && d5 <= d6) {
-		r.s = 0.0f, r.t = 1.0f;
+		r.s = 0.0f, r.t = 1.0f, r.region = NP_VERTEX_C;
 	} else if (vv > 0.0f && vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
-		r.s = 0.0f, r.t = d2 / vv;
+		r.s = 0.0f, r.t = d2 / vv, r.region = NP_EDGE_AC;
 	} else if (gh > 0.0f && va <= 0.0f && g >= 0.0f && h >= 0.0f) {
 		const float k = g / gh;
-		r.s = 1.0f - k, r.t = k;
+		r.s = 1.0f - k, r.t = k, r.region = NP_EDGE_BC;
 	} else {
 		r.found = 0;
 	}
@@ -121,6 +128,7 @@ OCRT_NP_FN np_params np_region(const np_tri tri, float d1, float d2) {
 OCRT_NP_FN np_params np_solve(const np_tri tri, float m, float r1, float r2) {
 	np_params r;
 	r.found = 0;
+	r.region = NP_FACE;
 	if (tri.uu >= tri.vv) {
 		const float t = (tri.uu * r2 - tri.uv * r1) / m;
 		r.t = t;
@@ -144,18 +152,26 @@ OCRT_NP_FN np_params np_face(const np_tri tri, float qx, float qy, float qz, flo
 	np_params r;
 	r.s = first.s + step.s;
 	r.t = first.t + step.t;
+	r.region = NP_FACE;
 	r.found = m > 0.0f && r.s >= 0.0f && r.t >= 0.0f && r.s + r.t <= 1.0f;
 	return r;
 }
+
+/* The feature a clamped parameter k of an edge stands for: the edge, or its end vertex where the clamp hit 0 or 1 (an edge
+ * of no length has k = 0: its first vertex). */
+OCRT_NP_FN int np_edge_region(float k, int edge, int first, int second) { return k == 0.0f ? first : k == 1.0f ? second : edge; }
 
 /* The nearest of the three edges as segments, in the order AB, AC, BC; the first of equals stays, a NaN never replaces. */
 OCRT_NP_FN np_point np_edges(const np_tri tri, float qx, float qy, float qz, float d1, float d2) {
 	const float d3 = d1 - tri.uu, d4 = d2 - tri.uv, d5 = d1 - tri.uv, d6 = d2 - tri.vv;
 	const float g = d4 - d3, h = d5 - d6;
-	const float k = np_clamped(g, g + h);
-	np_point best = np_at(tri, qx, qy, qz, np_clamped(d1, tri.uu), 0.0f);
-	const np_point ac = np_at(tri, qx, qy, qz, 0.0f, np_clamped(d2, tri.vv));
-	const np_point bc = np_at(tri, qx, qy, qz, 1.0f - k, k);
+	const float k = np_clamped(g, g + h), kab = np_clamped(d1, tri.uu), kac = np_clamped(d2, tri.vv);
+	np_point best = np_at(tri, qx, qy, qz, kab, 0.0f);
+	np_point ac = np_at(tri, qx, qy, qz, 0.0f, kac);
+	np_point bc = np_at(tri, qx, qy, qz, 1.0f - k, k);
+	best.region = np_edge_region(kab, NP_EDGE_AB, NP_VERTEX_A, NP_VERTEX_B);
+	ac.region = np_edge_region(kac, NP_EDGE_AC, NP_VERTEX_A, NP_VERTEX_C);
+	bc.region = np_edge_region(k, NP_EDGE_BC, NP_VERTEX_B, NP_VERTEX_C);
 	if (ac.d2 < best.d2)
 		best = ac;
 	if (bc.d2 < best.d2)
@@ -170,8 +186,11 @@ OCRT_NP_FN np_point np_nearest(const np_tri tri, float qx, float qy, float qz) {
 	np_params r = np_region(tri, d1, d2);
 	if (!r.found)
 		r = np_face(tri, qx, qy, qz, d1, d2);
-	if (r.found)
-		return np_at(tri, qx, qy, qz, r.s, r.t);
+	if (r.found) {
+		np_point p = np_at(tri, qx, qy, qz, r.s, r.t);
+		p.region = r.region;
+		return p;
+	}
 	return np_edges(tri, qx, qy, qz, d1, d2);
 }
 

@@ -50,6 +50,8 @@ RayQueries::RayQueries(DeviceRenderer &renderer) : dev(renderer) {
 	OCRT_HIP(hipEventCreateWithFlags((hipEvent_t *) &ev_frames, hipEventDisableTiming));
 	for (void *&ev : ev_build)
 		OCRT_HIP(hipEventCreate((hipEvent_t *) &ev));
+	for (void *&ev : ev_sign)
+		OCRT_HIP(hipEventCreate((hipEvent_t *) &ev));
 }
 
 RayQueries::~RayQueries() {
@@ -58,8 +60,11 @@ RayQueries::~RayQueries() {
 	if (timed)
 		(void) hipEventSynchronize((hipEvent_t) ev_stop);
 	for (Scratch *scratch : { &count, &order, &stage, &ao_hits, &ao_rows, &vis_rows, &list, &views, &build, &coords_flag, &nearest_counts, &inst_device,
-		                         &inst_spare, &inst_plan })
+		                         &inst_spare, &inst_plan, &sign_table, &sign_vertices, &sign_edges })
 		device_free(scratch->ptr);
+	for (void *ev : ev_sign)
+		if (ev)
+			(void) hipEventDestroy((hipEvent_t) ev);
 	for (void *ev : ev_build)
 		if (ev)
 			(void) hipEventDestroy((hipEvent_t) ev);
@@ -684,6 +689,189 @@ void RayQueries::nearestHost(const float *points4, uint32_t n, float max_distanc
 	});
 }
 
+// ---- signed distance queries (include/rt_hip_signed.h) ----
+namespace {
+constexpr size_t SIGN_REC_BYTES = 96u;                    // signed_point.h: SP_REC_FLOATS floats
+constexpr uint64_t SIGNED_GRID_CHUNK = (uint64_t) 1 << 24;  // voxels per slab of the host form, as far as whole slices allow
+}  // namespace
+
+uint32_t RayQueries::nearestWalk(const DeviceScene &scene) const {
+	uint32_t walk = scene.boxesEnclose() ? 3u : 0u;  // NEAREST_START | NEAREST_PRUNE (nearestDevice)
+	if (nearest_debug & 1u)
+		walk &= ~1u;
+	if (nearest_debug & 2u)
+		walk = 0u;
+	return walk;
+}
+
+// The table of the current scene on `stream`, which has waited for the host's last query already: made in full where the
+// topology is new -- the two sorts of the corners, the kept incidence, the sums; blocking: the sorts' scratch is let go
+// before the call returns --, its sums redone where only the positions are.
+const void *RayQueries::ensureSignTable(void *stream) {
+	hipStream_t s = (hipStream_t) stream;
+	const std::shared_ptr<const DeviceScene> scene = dev.deviceScene();
+	const uint32_t leaves = scene->triCount();
+	const size_t corners = (size_t) leaves * 3u;
+	const bool topology = signed_scene.lock() != scene;
+	if (!topology && sign_fresh)
+		return sign_table.ptr;
+	if (!topology) {
+		OCRT_HIP(hipEventRecord((hipEvent_t) ev_sign[0], s));
+		launch_sign_sums(sign_vertices.ptr, sign_edges.ptr, scene->buffers(), leaves, sign_table.ptr, s);
+		OCRT_HIP(hipEventRecord((hipEvent_t) ev_sign[1], s));
+		OCRT_HIP(hipGetLastError());
+		sign_fresh = sign_timed = true;
+		return sign_table.ptr;
+	}
+	const std::vector<uint32_t> *host_faces = scene->hostFaces();
+	if (!scene->deviceFaces() && (!host_faces || host_faces->size() != corners))
+		throw std::logic_error("signed distance query: the scene was uploaded without its faces");
+	signed_scene.reset();
+	grow(sign_table, (size_t) leaves * SIGN_REC_BYTES);
+	grow(sign_vertices, corners * sizeof(uint32_t));
+	grow(sign_edges, corners * sizeof(uint32_t));
+	// the sorts' scratch: the faces (where only the host has them), keys and values in and out, rocPRIM's own
+	const size_t words = round256(corners * 4u), wide = round256(corners * 8u), sort_bytes = sign_sort_bytes((uint32_t) corners);
+	void *scratch = device_alloc(5u * words + 2u * wide + round256(sort_bytes));
+	try {
+		char *at = (char *) scratch;
+		auto take = [&](size_t bytes) {
+			void *p = at;
+			at += bytes;
+			return p;
+		};
+		void *faces = take(words), *vertex_keys = take(words), *vertex_sorted = take(words), *values = take(words), *values_sorted = take(words);
+		void *edge_keys = take(wide), *edge_sorted = take(wide), *temporary = take(round256(sort_bytes));
+		OCRT_HIP(hipEventRecord((hipEvent_t) ev_sign[0], s));
+		const void *leaf_faces = scene->deviceFaces();
+		if (!leaf_faces) {
+			OCRT_HIP(hipMemcpyAsync(faces, host_faces->data(), corners * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+			leaf_faces = faces;
+		}
+		launch_sign_keys(leaf_faces, leaves, vertex_keys, edge_keys, values, s);
+		launch_sign_sort(false, temporary, sort_bytes, vertex_keys, vertex_sorted, values, values_sorted, (uint32_t) corners, s);
+		launch_sign_heads(false, vertex_sorted, values_sorted, leaves, sign_vertices.ptr, s);
+		launch_sign_sort(true, temporary, sort_bytes, edge_keys, edge_sorted, values, values_sorted, (uint32_t) corners, s);
+		launch_sign_heads(true, edge_sorted, values_sorted, leaves, sign_edges.ptr, s);
+		launch_sign_sums(sign_vertices.ptr, sign_edges.ptr, scene->buffers(), leaves, sign_table.ptr, s);
+		OCRT_HIP(hipEventRecord((hipEvent_t) ev_sign[1], s));
+		OCRT_HIP(hipGetLastError());
+		OCRT_HIP(hipStreamSynchronize(s));
+	} catch (...) {
+		device_free(scratch);
+		throw;
+	}
+	device_free(scratch);
+	signed_scene = scene;
+	sign_fresh = sign_timed = true;
+	return sign_table.ptr;
+}
+
+void RayQueries::prepareSigned(void *stream) {
+	requireScene("signed distance query");
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
+	if (timed)
+		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	(void) ensureSignTable(s);
+	OCRT_HIP(hipStreamSynchronize(s));
+}
+
+float RayQueries::lastSignBuildMs() {
+	if (!sign_timed)
+		return 0.0f;
+	float ms = 0.0f;
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_sign[1]));
+	OCRT_HIP(hipEventElapsedTime(&ms, (hipEvent_t) ev_sign[0], (hipEvent_t) ev_sign[1]));
+	return ms;
+}
+
+void RayQueries::downloadSignTable(void *out) {
+	prepareSigned(nullptr);
+	if (timed)
+		OCRT_HIP(hipEventSynchronize((hipEvent_t) ev_stop));
+	const size_t bytes = (size_t) dev.deviceScene()->triCount() * SIGN_REC_BYTES;
+	if (out && bytes)
+		OCRT_HIP(hipMemcpy(out, sign_table.ptr, bytes, hipMemcpyDeviceToHost));
+}
+
+void RayQueries::signedDevice(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, uint8_t *feature,
+                              float *pseudonormal4, void *stream) {
+	requireScene("signed distance query");
+	if (n == 0)
+		return;
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
+	if (timed)
+		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	const void *table = ensureSignTable(s);  // (ahead of ev_start where prepareSigned has been called; else part of this query's time)
+	const std::shared_ptr<const DeviceScene> scene = dev.deviceScene();
+	const Enqueue q = begin(s, points4, nullptr, n, n, flags, {}, false, nullptr);
+	launch_signed(scene->buffers(), scene->nodeCount(), scene->triCount(), points4, q.order, n, max_distance, nearestWalk(*scene), out, feature,
+	              pseudonormal4, table, flagged.lock() == scene ? coords_flag.ptr : nullptr, q.stream);
+	end(q);
+}
+
+void RayQueries::signedHost(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &host, uint8_t *feature,
+                            float *pseudonormal4) {
+	requireScene("signed distance query");
+	if (n == 0)
+		return;
+	enum { POINTS, HIT, RECORDS, FEATURE = RECORDS + 5, PSEUDONORMAL, PIECES };
+	Staged p[PIECES];
+	p[POINTS] = input(points4, (size_t) n * 16u);
+	p[HIT] = output(host.hit, n);
+	recordPieces(p + RECORDS, host, n);
+	p[FEATURE] = output(feature, n);
+	p[PSEUDONORMAL] = output(pseudonormal4, (size_t) n * 16u);
+	void *s = stageIn(p, PIECES);
+	QueryOutputs out;
+	out.hit = (unsigned char *) p[HIT].device;
+	recordDevice(p + RECORDS, out);
+	signedDevice((const float *) p[POINTS].device, n, max_distance, flags, out, (uint8_t *) p[FEATURE].device, (float *) p[PSEUDONORMAL].device, s);
+	stageOut(p, PIECES, s);
+}
+
+void RayQueries::signedGridDevice(const float origin[3], const float spacing[3], const uint32_t dims[3], float max_distance, float *distance,
+                                  uint32_t *leaf, void *stream, uint32_t z_first) {
+	requireScene("signed distance query");
+	if ((uint64_t) dims[0] * dims[1] * dims[2] == 0u)
+		return;
+	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
+	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
+	if (timed)
+		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	const void *table = ensureSignTable(s);
+	const std::shared_ptr<const DeviceScene> scene = dev.deviceScene();
+	const Enqueue q = begin(s, nullptr, nullptr, 0u, 0u, QUERY_NO_SORT, {}, false, nullptr);  // (no points, no order, no sort)
+	launch_signed_grid(scene->buffers(), scene->nodeCount(), scene->triCount(), origin, spacing, dims[0], dims[1], dims[2], z_first, max_distance,
+	                   nearestWalk(*scene), distance, leaf, table, flagged.lock() == scene ? coords_flag.ptr : nullptr, q.stream);
+	end(q);
+}
+
+void RayQueries::signedGridHost(const float origin[3], const float spacing[3], const uint32_t dims[3], float max_distance, float *distance,
+                                uint32_t *leaf) {
+	requireScene("signed distance query");
+	const uint64_t slice = (uint64_t) dims[0] * dims[1];
+	if (slice * dims[2] == 0u)
+		return;
+	// slab by slab through the staging buffer, so that it holds one slab's voxels, not the grid's
+	const uint32_t per_slab = (uint32_t) std::min<uint64_t>(dims[2], std::max<uint64_t>(1u, SIGNED_GRID_CHUNK / slice));
+	float ms = 0.0f;
+	for (uint32_t first = 0; first < dims[2]; first += per_slab) {
+		const uint32_t slab[3] = { dims[0], dims[1], std::min(per_slab, dims[2] - first) };
+		const size_t voxels = (size_t) (slice * slab[2]), offset = (size_t) (slice * first);
+		Staged p[2] = { output(distance ? distance + offset : nullptr, voxels * 4u), output(leaf ? leaf + offset : nullptr, voxels * 4u) };
+		void *s = stageIn(p, 2);
+		signedGridDevice(origin, spacing, slab, max_distance, (float *) p[0].device, (uint32_t *) p[1].device, s, first);
+		stageOut(p, 2, s);
+		ms += lastMs();
+	}
+	last_ms = ms;  // (every slab's events have been read: the call's time is their sum)
+	have_ms = true;
+}
+
 void RayQueries::setNearestWalk(uint32_t debug_flags) {
 #ifndef OCRT_DEBUG_KNOBS
 	if (debug_flags != 0u)
@@ -1138,6 +1326,7 @@ void RayQueries::updateDevice(const float *vertices4, const float *vnormals4, ui
 	dev.markSceneUpdated();
 	boxed.reset();
 	inst_current = false;
+	sign_fresh = false;  // (the sign table's sums are the old positions': redone by the next signed query, from the kept incidence)
 	grow(coords_flag, sizeof(uint32_t));
 	OCRT_HIP(hipEventRecord((hipEvent_t) ev_start, s));
 	OCRT_HIP(hipEventRecord((hipEvent_t) ev_update_start, s));

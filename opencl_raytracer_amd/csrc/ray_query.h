@@ -57,6 +57,23 @@ class RayQueries {
 		// Host memory, blocking.
 		void nearestHost(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, bool instanced = false,
 		                 uint32_t *instance = nullptr);
+		// Signed distance queries (include/rt_hip_signed.h): nearestDevice's walk and rules, the distance signed by the
+		// pseudonormal of the feature the nearest point lies on, out of the sign table -- made by the first of these calls
+		// after an upload or a build (prepareSigned: ahead of time), its sums redone after an update.  `feature` (n bytes),
+		// `pseudonormal4` (float4[n]): outputs beside the record's, either may be null.
+		void signedDevice(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, uint8_t *feature,
+		                  float *pseudonormal4, void *stream);
+		void signedHost(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, uint8_t *feature,
+		                float *pseudonormal4);
+		// The grid form: voxel (i, j, k) is origin + (i, j, k) * spacing; `distance`, `leaf`: [dims[2]][dims[1]][dims[0]], either
+		// may be null.  The host form goes through the staging buffer in slabs of z-slices.
+		void signedGridDevice(const float origin[3], const float spacing[3], const uint32_t dims[3], float max_distance, float *distance,
+		                      uint32_t *leaf, void *stream, uint32_t z_first = 0);
+		void signedGridHost(const float origin[3], const float spacing[3], const uint32_t dims[3], float max_distance, float *distance,
+		                    uint32_t *leaf);
+		void prepareSigned(void *stream);  // blocking
+		float lastSignBuildMs();           // HIP-event time of the last build or refresh of the table (0: none yet)
+		void downloadSignTable(void *out);  // triCount() records of 96 bytes (made first, if need be), once everything enqueued has finished
 		// (include/rt_hip_debug.h) how the later closest-point queries walk (RT_DEBUG_NEAREST_*; the A/B build's: std::logic_error
 		// for a flag in the product library), and the counts of the last counted one (waits for it)
 		void setNearestWalk(uint32_t debug_flags);
@@ -309,6 +326,15 @@ class RayQueries {
 		// walks pass no box by.  nearest_counts: the counted form's two words.
 		void checkCoordinates(const std::shared_ptr<const DeviceScene> &scene, const float *vertices4, uint32_t num_vertices, void *stream);
 		Scratch coords_flag, nearest_counts;
+		// Signed distance queries.  sign_table: a SignRec of 96 bytes per leaf; sign_vertices, sign_edges: the kept incidence, a
+		// word per corner each (kernels/signed.hip.h).  signed_scene: the scene whose topology they were made for (an upload
+		// or a build brings another); sign_fresh: the sums are the current positions' (an update ends that).
+		Scratch sign_table, sign_vertices, sign_edges;
+		std::weak_ptr<const DeviceScene> signed_scene;
+		bool sign_fresh = false, sign_timed = false;
+		void *ev_sign[2] = { nullptr, nullptr };
+		const void *ensureSignTable(void *stream);
+		uint32_t nearestWalk(const DeviceScene &scene) const;
 		std::weak_ptr<const DeviceScene> flagged;  // the scene coords_flag speaks of
 		uint32_t nearest_debug = 0;
 		bool nearest_counted = false;
@@ -357,6 +383,19 @@ void launch_nearest(const SceneBuffers &scene, uint32_t node_count, uint32_t tri
                     const void *order, uint32_t n, float max_distance, uint32_t walk, const QueryOutputs &out, uint32_t *instance,
                     const void *coords_flag, void *counts, void *stream);
 void launch_nearest_coordinates(const void *vertices4, uint32_t num_vertices, void *flag, void *stream);
+// signed distance queries (kernels/signed.hip.h, sign_sort.hip)
+size_t sign_sort_bytes(uint32_t pairs);
+void launch_sign_sort(bool wide, void *temporary, size_t temporary_bytes, const void *keys_in, void *keys_out, const void *values_in,
+                      void *values_out, uint32_t pairs, void *stream);
+void launch_sign_keys(const void *faces, uint32_t tri_count, void *vertex_keys, void *edge_keys, void *values, void *stream);
+void launch_sign_heads(bool wide, const void *sorted_keys, const void *sorted_values, uint32_t tri_count, void *kept, void *stream);
+void launch_sign_sums(const void *kept_vertices, const void *kept_edges, const SceneBuffers &scene, uint32_t tri_count, void *table, void *stream);
+void launch_signed(const SceneBuffers &scene, uint32_t node_count, uint32_t tri_count, const void *points, const void *order, uint32_t n,
+                   float max_distance, uint32_t walk, const QueryOutputs &out, uint8_t *feature, float *pseudonormal4, const void *table,
+                   const void *coords_flag, void *stream);
+void launch_signed_grid(const SceneBuffers &scene, uint32_t node_count, uint32_t tri_count, const float origin[3], const float spacing[3],
+                        uint32_t nx, uint32_t ny, uint32_t nz, uint32_t z_first, float max_distance, uint32_t walk, float *distance,
+                        uint32_t *leaf, const void *table, const void *coords_flag, void *stream);
 void launch_segments(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, bool closest, const void *from, const void *to,
                      const void *order, uint32_t n, float t_lo, float t_hi, const QueryOutputs &out, uint32_t *instance, void *stream);
 void launch_visibility(const SceneBuffers &scene, uint32_t node_count, const InstanceBuffers *set, const void *points, uint32_t np,

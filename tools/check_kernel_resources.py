@@ -280,10 +280,14 @@ def main():
                "instance_multihit_walk_kernel<4", "instance_multihit_walk_kernel<8", "instance_multihit_walk_kernel<16",
                "instance_multihit_resolve_kernel",
                # instanced directional occlusion (kernels/instance_directional.hip.h): the nested walks, ao_mask_kernel's tail
-               "instance_ao_mask_kernel<1", "instance_ao_mask_kernel<2")
+               "instance_ao_mask_kernel<1", "instance_ao_mask_kernel<2",
+               # signed distance queries (kernels/signed.hip.h): nearest_kernel's walk with a signed tail, and the sign table
+               "signed_kernel", "signed_grid_kernel", "sign_keys_kernel", "sign_heads_kernel<", "sign_sum_kernel<", "sign_leaf_kernel")
     # the directional occlusion queries' walk is ao_query_kernel's with another tail (kernels/directional.hip.h): it must keep
     # that kernel's occupancy, 8 waves per SIMD -- a tail that needs more live state than the old one shows here
     full_occupancy = ("ao_mask_kernel<1", "ao_mask_kernel<2")
+    # the signed distance queries keep nearest_kernel's register budget: 8 waves per SIMD are what hides its scalar load
+    nearest_occupancy = ("nearest_kernel<false>", "signed_kernel", "signed_grid_kernel")
     names = [k["name"].replace("ocrt::", "").replace("void ", "") for k in kernels]
     for p in HOT_PRIMARY:
         if not any(n.startswith(p) for n in names):
@@ -300,6 +304,8 @@ def main():
                 errors.append(f"{q}: SGPR spill {k.get('SGPRs Spill')} in a directional-occlusion kernel")
             if q in full_occupancy and k.get("Occupancy [waves/SIMD]") != "8":
                 errors.append(f"{q}: occupancy {k.get('Occupancy [waves/SIMD]')} waves/SIMD, ao_query_kernel's walk runs at 8")
+            if q in nearest_occupancy and k.get("Occupancy [waves/SIMD]") != "8":
+                errors.append(f"{q}: occupancy {k.get('Occupancy [waves/SIMD]')} waves/SIMD, the closest-point walk runs at 8")
     if "--isa" in sys.argv:
         places = lane_ops_by_place(open(sys.argv[sys.argv.index("--isa") + 1]).read())
         lines.append("")
