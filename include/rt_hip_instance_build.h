@@ -46,6 +46,14 @@
  * too for a null pointer, a device pointer that is not 16-byte aligned and n > RT_INSTANCES_MAX; RT_E_STATE on the hosts
  * of a frame ring.
  *
+ * Sizes at which the device path changes (tests/test_thresholds_gpu.py crosses each; DESIGN.md "Size thresholds").  More
+ * than 65 536 instances -- more than 256 workgroups -- reduce the set's reach and the tree's root box in launches of their
+ * own; below that every workgroup of the next kernel reduces the partials for itself.  The sort of the (key, index)
+ * pairs is rocPRIM's: one block up to 1 024 pairs, block sort and merge up to 2^20.  RT_INSTANCES_MAX IS 2^20: the check
+ * above refuses the first size at which that sort would run its third path (onesweep), so an instance set never takes
+ * it -- a scene build does (rt_hip_build.h has no such limit).  Raising RT_INSTANCES_MAX puts that path under the stable
+ * order above; a test has to cross it then.
+ *
  * Ordering.  As a build (rt_hip_build.h): the call is serialised with this host's queries by their event, enqueued on
  * `hip_stream` (NULL: the host's stream), and blocks for the one small read.  The caller's array may be reused on return:
  * the library keeps a copy of the transforms in memory of its own.
