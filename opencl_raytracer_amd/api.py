@@ -444,6 +444,24 @@ _OUTPUT_LAYOUT = {"hit": (np.uint8, 1), "count": (np.uint32, 1), "ao": (np.float
 _RECORD_FIELDS = ("distance", "leaf", "barycentric", "position", "normal")
 
 
+def _known(outputs, legal: tuple) -> tuple:
+    """`outputs` as a tuple, every name of it one of `legal`."""
+    outputs = tuple(outputs)
+    unknown = [o for o in outputs if o not in legal]
+    if unknown:
+        raise ValueError(f"unknown outputs {unknown}; choose from {legal}")
+    return outputs
+
+
+# How an instanced family's output structure is made of its pointers: the plain family's, and "instance" behind them.
+def _instance_hits(*at):
+    return _InstanceHitArrays(_HitArrays(*at[:-1]), at[-1])
+
+
+def _instance_multihits(*at):
+    return _InstanceMultiHitArrays(_MultiHitArrays(*at[:-1]), at[-1])
+
+
 def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
 
@@ -1030,23 +1048,24 @@ class Host:
     def trace_closest(self, origins, directions, max_distance: float = 100000.0, outputs=QUERY_OUTPUTS, sort: bool = True) -> dict:
         """Closest hit of every ray: {output name: array}.  numpy (N, 3) / (N, 4) float32 in, numpy out (blocking); torch
         tensors on the host's GPU in, torch tensors out, enqueued on torch.cuda.current_stream() without waiting."""
-        return self._trace(True, origins, directions, max_distance, tuple(outputs), sort)
+        return Host._trace(self, "rt_trace", QUERY_OUTPUTS, _HitArrays, True, origins, directions, max_distance, outputs, sort)
 
     def trace_occluded(self, origins, directions, max_distance: float = 100000.0, sort: bool = True):
         """Occlusion of every ray (the `hit` of trace_closest for the same rays and max_distance): uint8 (N,)."""
-        return self._trace(False, origins, directions, max_distance, ("hit",), sort)["hit"]
+        return Host._trace(self, "rt_trace", QUERY_OUTPUTS, _HitArrays, False, origins, directions, max_distance, ("hit",), sort)["hit"]
 
-    def _trace(self, closest: bool, origins, directions, max_distance: float, outputs: tuple, sort: bool) -> dict:
-        unknown = [o for o in outputs if o not in QUERY_OUTPUTS]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {QUERY_OUTPUTS}")
+    def _trace(self, family: str, legal: tuple, wrap, closest: bool, origins, directions, max_distance: float, outputs, sort: bool) -> dict:
+        """The ray queries, plain and instanced: <family>_closest with wrap(the pointers of `legal`), or <family>_occluded.
+        (The public methods reach these shared bodies through the class: nothing is looked up on `self` before the inputs
+        have been checked.)"""
+        outputs = _known(outputs, legal)
         io = _QueryArrays(origins, directions, ("origins", "directions"), "rays")
         out = io.outputs(outputs)
         args = (io.n, float(max_distance), 0 if sort else RT_QUERY_NO_SORT)
         if closest:
-            io.call(self._h, "rt_trace_closest", *args, C.byref(_HitArrays(*io.pointers(out, QUERY_OUTPUTS))))
+            io.call(self._h, family + "_closest", *args, C.byref(wrap(*io.pointers(out, legal))))
         else:
-            io.call(self._h, "rt_trace_occluded", *args, *io.pointers(out, ("hit",)))
+            io.call(self._h, family + "_occluded", *args, *io.pointers(out, ("hit",)))
         return out
 
     # ---- instanced ray queries (include/rt_hip_instances.h) ----
@@ -1122,25 +1141,12 @@ class Host:
         """Closest hit of every WORLD-space ray among the posed copies of the scene: the record of trace_closest -- position,
         distance and normal in world space, leaf and barycentrics of the copy's triangle -- and "instance", the copy
         (0xFFFFFFFF without a hit).  Inputs and forms as for trace_closest."""
-        return self._trace_instances(True, origins, directions, max_distance, tuple(outputs), sort)
+        return Host._trace(self, "rt_trace_instances", INSTANCE_OUTPUTS, _instance_hits, True, origins, directions, max_distance, outputs, sort)
 
     def trace_instances_occluded(self, origins, directions, max_distance: float = 100000.0, sort: bool = True):
         """Occlusion of every world-space ray by any copy (the `hit` of trace_instances_closest): uint8 (N,)."""
-        return self._trace_instances(False, origins, directions, max_distance, ("hit",), sort)["hit"]
-
-    def _trace_instances(self, closest: bool, origins, directions, max_distance: float, outputs: tuple, sort: bool) -> dict:
-        unknown = [o for o in outputs if o not in INSTANCE_OUTPUTS]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {INSTANCE_OUTPUTS}")
-        io = _QueryArrays(origins, directions, ("origins", "directions"), "rays")
-        out = io.outputs(outputs)
-        args = (io.n, float(max_distance), 0 if sort else RT_QUERY_NO_SORT)
-        if closest:
-            at = io.pointers(out, INSTANCE_OUTPUTS)
-            io.call(self._h, "rt_trace_instances_closest", *args, C.byref(_InstanceHitArrays(_HitArrays(*at[:-1]), at[-1])))
-        else:
-            io.call(self._h, "rt_trace_instances_occluded", *args, *io.pointers(out, ("hit",)))
-        return out
+        return Host._trace(self, "rt_trace_instances", INSTANCE_OUTPUTS, _instance_hits, False, origins, directions, max_distance, ("hit",),
+                           sort)["hit"]
 
     # ---- instanced ambient occlusion (include/rt_hip_instance_views.h) ----
     def instances_ambient_occlusion(self, points, normals, seeds=None, outputs=AO_OUTPUTS, sort: bool = True) -> dict:
@@ -1148,17 +1154,7 @@ class Host:
         ambient_occlusion makes for a point -- ao_rays writes them out --, each cast as trace_instances_occluded casts it with
         max_distance = ao_max_distance: {"ao": float32 (N,), "occluded": uint32 (N,)} (those named in `outputs`).  Inputs,
         seeds, sorting and the numpy / torch forms are ambient_occlusion's."""
-        outputs = tuple(outputs)
-        unknown = [o for o in outputs if o not in AO_OUTPUTS]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {AO_OUTPUTS}")
-        io = _QueryArrays(points, normals, ("points", "normals", "seeds"), "points", also=seeds)
-        if seeds is not None:
-            seeds = io.seeds(seeds)
-        out = io.outputs(outputs)
-        io.call(self._h, "rt_trace_instances_ao", io.ptr(seeds) if seeds is not None and io.n else None, io.n,
-                0 if sort else RT_QUERY_NO_SORT, *io.pointers(out, AO_OUTPUTS))
-        return out
+        return Host._ao(self, "rt_trace_instances_ao", points, normals, seeds, outputs, sort)
 
     # ---- instanced multi-hit queries (include/rt_hip_instance_multihit.h) ----
     def trace_instances_multihit(self, origins, directions, max_distance: float = 100000.0, k: int = 4,
@@ -1168,19 +1164,8 @@ class Host:
         (distance, instance, leaf index), records as trace_instances_closest makes them -- and "instance": uint32 (N, k),
         the copy of every slot (0xFFFFFFFF in unused slots) (those named in `outputs`).  k, inputs and the numpy / torch
         forms are trace_multihit's."""
-        outputs = tuple(outputs)
-        unknown = [o for o in outputs if o not in INSTANCE_MULTIHIT_OUTPUTS]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {INSTANCE_MULTIHIT_OUTPUTS}")
-        k = int(k)
-        if k < 0:
-            raise ValueError("k must not be negative")
-        io = _QueryArrays(origins, directions, ("origins", "directions"), "rays")
-        out = io.outputs(outputs, k, shapes={"instance": (np.uint32, (k,))})
-        at = io.pointers(out, INSTANCE_MULTIHIT_OUTPUTS, name_empty=True)
-        io.call(self._h, "rt_trace_instances_multihit", io.n, float(max_distance), k, 0 if sort else RT_QUERY_NO_SORT,
-                C.byref(_InstanceMultiHitArrays(_MultiHitArrays(*at[:-1]), at[-1])))
-        return out
+        return Host._multihit(self, "rt_trace_instances_multihit", INSTANCE_MULTIHIT_OUTPUTS, _instance_multihits, origins, directions,
+                              max_distance, k, outputs, sort)
 
     def count_instances_hits(self, origins, directions, max_distance: float = 100000.0, sort: bool = True):
         """The number of (copy, triangle) pairs the walks accept for every world-space ray (trace_instances_multihit's
@@ -1193,18 +1178,7 @@ class Host:
         point are ao_rays's, each cast as trace_instances_occluded casts it with max_distance = ao_max_distance; "mask",
         "occluded", "ao" and "bent" are made of those flags as directional_occlusion makes them ("occluded" and "ao" are
         instances_ambient_occlusion's).  Inputs, seeds, sorting and the numpy / torch forms are ambient_occlusion's."""
-        outputs = tuple(outputs)
-        unknown = [o for o in outputs if o not in DIRECTIONAL_OUTPUTS]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {DIRECTIONAL_OUTPUTS}")
-        io = _QueryArrays(points, normals, ("points", "normals", "seeds"), "points", also=seeds)
-        if seeds is not None:
-            seeds = io.seeds(seeds)
-        out = io.outputs(outputs, shapes={"mask": (np.uint32, (self.ao_mask_words,))} if "mask" in outputs else None)
-        arrays = _DirectionalArrays(*io.pointers(out, DIRECTIONAL_OUTPUTS))
-        io.call(self._h, "rt_trace_instances_ao_directional", io.ptr(seeds) if seeds is not None and io.n else None, io.n,
-                0 if sort else RT_QUERY_NO_SORT, C.byref(arrays))
-        return out
+        return Host._directional(self, "rt_trace_instances_ao_directional", points, normals, seeds, outputs, sort)
 
     # ---- segment queries (include/rt_hip_segment.h) ----
     def segments_occluded(self, a, b, interval=SEGMENT_INTERVAL, sort: bool = True):
@@ -1219,21 +1193,16 @@ class Host:
         without a blocker: +inf, 0xFFFFFFFF, zeros.  Inputs and forms as for segments_occluded."""
         return self._segments(True, a, b, interval, tuple(outputs), sort)
 
-    def _segments(self, closest: bool, a, b, interval, outputs: tuple, sort: bool, instanced: bool = False) -> dict:
-        known = INSTANCE_OUTPUTS if instanced else SEGMENT_OUTPUTS
-        unknown = [o for o in outputs if o not in known]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {known}")
+    def _segments(self, closest: bool, a, b, interval, outputs, sort: bool, instanced: bool = False) -> dict:
+        family, legal, wrap = (("rt_instances_segments", INSTANCE_OUTPUTS, _instance_hits) if instanced
+                               else ("rt_segments", SEGMENT_OUTPUTS, _HitArrays))
+        outputs = _known(outputs, legal)
         t_lo, t_hi = interval
         io = _QueryArrays(a, b, ("a", "b"), "points")
         out = io.outputs(outputs)
         args = (io.n, float(t_lo), float(t_hi), 0 if sort else RT_QUERY_NO_SORT)
-        family = "rt_instances_segments" if instanced else "rt_segments"
-        if closest and instanced:
-            at = io.pointers(out, INSTANCE_OUTPUTS)
-            io.call(self._h, family + "_closest", *args, C.byref(_InstanceHitArrays(_HitArrays(*at[:-1]), at[-1])))
-        elif closest:
-            io.call(self._h, family + "_closest", *args, C.byref(_HitArrays(*io.pointers(out, SEGMENT_OUTPUTS))))
+        if closest:
+            io.call(self._h, family + "_closest", *args, C.byref(wrap(*io.pointers(out, legal))))
         else:
             io.call(self._h, family + "_occluded", *args, *io.pointers(out, ("hit",)))
         return out
@@ -1247,10 +1216,7 @@ class Host:
         return self._visibility("rt_visibility_masks", points, targets, interval, outputs, sort)
 
     def _visibility(self, function: str, points, targets, interval, outputs, sort: bool) -> dict:
-        outputs = tuple(outputs)
-        unknown = [o for o in outputs if o not in VISIBILITY_OUTPUTS]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {VISIBILITY_OUTPUTS}")
+        outputs = _known(outputs, VISIBILITY_OUTPUTS)
         t_lo, t_hi = interval
         both = _is_torch(points), _is_torch(targets)
         if both[0] != both[1]:
@@ -1298,14 +1264,14 @@ class Host:
         `outputs`); without one: +inf, 0xFFFFFFFF, zeros.  points: (N, 3) / (N, 4) float32.  numpy in, numpy out (blocking);
         a torch tensor on the host's GPU in, torch tensors out, enqueued on torch.cuda.current_stream() without waiting (as
         for trace_closest)."""
-        outputs = tuple(outputs)
-        unknown = [o for o in outputs if o not in NEAREST_OUTPUTS]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {NEAREST_OUTPUTS}")
+        return Host._points(self, "rt_closest_points", NEAREST_OUTPUTS, _HitArrays, points, max_distance, outputs, sort)
+
+    def _points(self, function: str, legal: tuple, wrap, points, max_distance: float, outputs, sort: bool) -> dict:
+        """The closest-point queries, plain, signed and instanced: `function` with wrap(the pointers of `legal`)."""
+        outputs = _known(outputs, legal)
         io = _QueryArrays(points, None, ("points",), "points")
         out = io.outputs(outputs)
-        io.call(self._h, "rt_closest_points", io.n, float(max_distance), 0 if sort else RT_QUERY_NO_SORT,
-                C.byref(_HitArrays(*io.pointers(out, NEAREST_OUTPUTS))))
+        io.call(self._h, function, io.n, float(max_distance), 0 if sort else RT_QUERY_NO_SORT, C.byref(wrap(*io.pointers(out, legal))))
         return out
 
     # ---- signed distance queries (include/rt_hip_signed.h) ----
@@ -1315,16 +1281,8 @@ class Host:
         "feature": uint8 (N,), an index into FEATURES (0xFF: nothing within max_distance); "pseudonormal": float32 (N, 4), that
         feature's pseudonormal and its dot product with point - position.  Inputs and the numpy / torch forms as for
         closest_points.  The first call after an upload or a build makes the sign table (prepare_signed_distance)."""
-        outputs = tuple(outputs)
-        unknown = [o for o in outputs if o not in SIGNED_OUTPUTS]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {SIGNED_OUTPUTS}")
-        io = _QueryArrays(points, None, ("points",), "points")
-        out = io.outputs(outputs)
-        at = io.pointers(out, SIGNED_OUTPUTS)
-        io.call(self._h, "rt_signed_distance", io.n, float(max_distance), 0 if sort else RT_QUERY_NO_SORT,
-                C.byref(_SignedArrays(_HitArrays(*at[:6]), at[6], at[7])))
-        return out
+        return Host._points(self, "rt_signed_distance", SIGNED_OUTPUTS, lambda *at: _SignedArrays(_HitArrays(*at[:6]), at[6], at[7]), points,
+                            max_distance, outputs, sort)
 
     def signed_distance_grid(self, origin, spacing, shape, max_distance: float = float("inf"), as_torch: bool = False, leaf: bool = False):
         """The signed distance field of the scene on a regular grid: float32 (nz, ny, nx) for shape = (nx, ny, nz), voxel
@@ -1380,16 +1338,7 @@ class Host:
         the record of closest_points in world space -- distance, position, normal; leaf and barycentrics of the copy's
         triangle -- and "instance", the copy (those named in `outputs`); without one: +inf, 0xFFFFFFFF, zeros.  Inputs and
         the numpy / torch forms as for closest_points."""
-        outputs = tuple(outputs)
-        unknown = [o for o in outputs if o not in INSTANCE_OUTPUTS]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {INSTANCE_OUTPUTS}")
-        io = _QueryArrays(points, None, ("points",), "points")
-        out = io.outputs(outputs)
-        at = io.pointers(out, INSTANCE_OUTPUTS)
-        io.call(self._h, "rt_instances_closest_points", io.n, float(max_distance), 0 if sort else RT_QUERY_NO_SORT,
-                C.byref(_InstanceHitArrays(_HitArrays(*at[:-1]), at[-1])))
-        return out
+        return Host._points(self, "rt_instances_closest_points", INSTANCE_OUTPUTS, _instance_hits, points, max_distance, outputs, sort)
 
     def set_nearest_walk(self, no_start: bool = False, no_prune: bool = False, count: bool = False) -> None:
         """(rt_debug_set_nearest_walk) How later closest_points and instances_closest_points calls walk; anything but the
@@ -1411,17 +1360,18 @@ class Host:
         0 <= k <= RT_MULTIHIT_MAX_K; with k = 0 only "count" can be asked for.  numpy (N, 3) / (N, 4) float32 in, numpy
         out (blocking); torch tensors on the host's GPU in, torch tensors out, enqueued on torch.cuda.current_stream()
         without waiting (as for trace_closest)."""
-        outputs = tuple(outputs)
-        unknown = [o for o in outputs if o not in MULTIHIT_OUTPUTS]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {MULTIHIT_OUTPUTS}")
+        return Host._multihit(self, "rt_trace_multihit", MULTIHIT_OUTPUTS, _MultiHitArrays, origins, directions, max_distance, k, outputs, sort)
+
+    def _multihit(self, function: str, legal: tuple, wrap, origins, directions, max_distance: float, k: int, outputs, sort: bool) -> dict:
+        """The multi-hit queries, plain and instanced: `function` with wrap(the pointers of `legal`)."""
+        outputs = _known(outputs, legal)
         k = int(k)
         if k < 0:
             raise ValueError("k must not be negative")
         io = _QueryArrays(origins, directions, ("origins", "directions"), "rays")
-        out = io.outputs(outputs, k)
-        arrays = _MultiHitArrays(*io.pointers(out, MULTIHIT_OUTPUTS, name_empty=True))
-        io.call(self._h, "rt_trace_multihit", io.n, float(max_distance), k, 0 if sort else RT_QUERY_NO_SORT, C.byref(arrays))
+        out = io.outputs(outputs, k, shapes={"instance": (np.uint32, (k,))})
+        arrays = wrap(*io.pointers(out, legal, name_empty=True))
+        io.call(self._h, function, io.n, float(max_distance), k, 0 if sort else RT_QUERY_NO_SORT, C.byref(arrays))
         return out
 
     def count_hits(self, origins, directions, max_distance: float = 100000.0, sort: bool = True):
@@ -1450,16 +1400,17 @@ class Host:
         numpy in, numpy out (blocking); torch tensors on the host's GPU in, torch tensors out, enqueued on
         torch.cuda.current_stream() without waiting (as for the ray queries, the default stream's handle is NULL, which
         the library reads as the host's own stream: work under a stream of your own, or synchronise around the call)."""
-        outputs = tuple(outputs)
-        unknown = [o for o in outputs if o not in AO_OUTPUTS]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {AO_OUTPUTS}")
+        return Host._ao(self, "rt_trace_ao", points, normals, seeds, outputs, sort)
+
+    def _ao(self, function: str, points, normals, seeds, outputs, sort: bool) -> dict:
+        """The ambient-occlusion queries, plain and instanced."""
+        outputs = _known(outputs, AO_OUTPUTS)
         io = _QueryArrays(points, normals, ("points", "normals", "seeds"), "points", also=seeds)
         if seeds is not None:
             seeds = io.seeds(seeds)
         out = io.outputs(outputs)
-        io.call(self._h, "rt_trace_ao", io.ptr(seeds) if seeds is not None and io.n else None, io.n,
-                0 if sort else RT_QUERY_NO_SORT, *io.pointers(out, AO_OUTPUTS))
+        io.call(self._h, function, io.ptr(seeds) if seeds is not None and io.n else None, io.n, 0 if sort else RT_QUERY_NO_SORT,
+                *io.pointers(out, AO_OUTPUTS))
         return out
 
     # ---- directional occlusion queries (include/rt_hip_directional.h) ----
@@ -1477,17 +1428,18 @@ class Host:
         "bent": float32 (N, 3), the sum of the directions of the point's open rays, added in ray order and not normalised}
         (those named in `outputs`).  Ray k is the k-th ray the reference's ambient_occlusion() casts; ao_rays returns
         the rays themselves.  Inputs, seeds, sorting and the numpy / torch forms are ambient_occlusion's."""
-        outputs = tuple(outputs)
-        unknown = [o for o in outputs if o not in DIRECTIONAL_OUTPUTS]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {DIRECTIONAL_OUTPUTS}")
+        return Host._directional(self, "rt_trace_ao_directional", points, normals, seeds, outputs, sort)
+
+    def _directional(self, function: str, points, normals, seeds, outputs, sort: bool) -> dict:
+        """The directional occlusion queries, plain and instanced."""
+        outputs = _known(outputs, DIRECTIONAL_OUTPUTS)
         io = _QueryArrays(points, normals, ("points", "normals", "seeds"), "points", also=seeds)
         if seeds is not None:
             seeds = io.seeds(seeds)
         out = io.outputs(outputs, shapes={"mask": (np.uint32, (self.ao_mask_words,))} if "mask" in outputs else None)
         arrays = _DirectionalArrays(*io.pointers(out, DIRECTIONAL_OUTPUTS))
-        io.call(self._h, "rt_trace_ao_directional", io.ptr(seeds) if seeds is not None and io.n else None, io.n,
-                0 if sort else RT_QUERY_NO_SORT, C.byref(arrays))
+        io.call(self._h, function, io.ptr(seeds) if seeds is not None and io.n else None, io.n, 0 if sort else RT_QUERY_NO_SORT,
+                C.byref(arrays))
         return out
 
     def ao_rays(self, points, normals, seeds=None) -> dict:
@@ -1518,10 +1470,7 @@ class Host:
         numpy out (blocking), or with as_torch=True torch tensors on the host's GPU, enqueued on
         torch.cuda.current_stream() without waiting (as for the ray queries, the default stream's handle is NULL, which the
         library reads as the host's own stream: work under a stream of your own, or synchronise around the call)."""
-        outputs = tuple(outputs)
-        unknown = [o for o in outputs if o not in LAYER_OUTPUTS]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {LAYER_OUTPUTS}")
+        outputs = _known(outputs, LAYER_OUTPUTS)
         h, w = self.options.total_height, self.options.total_width
         shapes = {name: (h, w) + ((_OUTPUT_LAYOUT[name][1],) if _OUTPUT_LAYOUT[name][1] > 1 else ()) for name in outputs}
         lib = load_library()
@@ -1563,9 +1512,7 @@ class Host:
         return self._render_views(cameras, tuple(outputs), as_torch, INSTANCE_VIEW_OUTPUTS)
 
     def _render_views(self, cameras, outputs: tuple, as_torch: bool, legal: tuple) -> dict:
-        unknown = [o for o in outputs if o not in legal]
-        if unknown:
-            raise ValueError(f"unknown outputs {unknown}; choose from {legal}")
+        outputs = _known(outputs, legal)
         instanced = legal is INSTANCE_VIEW_OUTPUTS
         if isinstance(cameras, np.ndarray):
             if cameras.dtype != np.float32 or cameras.ndim != 3 or cameras.shape[1:] != (4, 3):

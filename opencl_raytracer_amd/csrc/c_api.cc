@@ -199,6 +199,18 @@ ocrt::MultiHitOutputs multihit_outputs(const rt_multihit_arrays *from) {
 	return q;
 }
 bool records_aligned(const ocrt::RecordOutputs &q) { return aligned({ q.distance, q.leaf, q.barycentric, q.position, q.normal }, 4); }
+// ... and the instanced families' arrays apart: the record or the slots, and the instance indices beside them.
+ocrt::QueryOutputs hit_outputs(const rt_instance_hit_arrays *from) { return hit_outputs(from ? &from->record : nullptr); }
+ocrt::MultiHitOutputs multihit_outputs(const rt_instance_multihit_arrays *from) { return multihit_outputs(from ? &from->slots : nullptr); }
+template <class Arrays> uint32_t *instance_of(const Arrays *from) { return from ? from->instance : nullptr; }
+
+// Where a call's arrays live (ray_query.h): host memory for the blocking entry points, device memory and the caller's
+// stream for the *_device ones.  Every family below is written once, as <family>_call(h, ..., where): its checks in the
+// header's order -- the alignment of device arrays among them --, then the one RayQueries method; the exported functions
+// forward to it.
+using Where = ocrt::RayQueries::Where;
+const Where HOST = Where::hostMemory();
+Where on(void *hip_stream) { return Where::deviceMemory(hip_stream); }
 
 // Maps the exception in flight to an RT_E_* code.
 int fail_from_exception() {
@@ -994,39 +1006,39 @@ int rt_ring_rccl_self_test(rt_ring *r) {
 
 void rt_print_info(void) { HipHost::printInfo(); }
 // ---- rt_hip_query.h ----
-int rt_trace_closest(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
-                     const rt_hit_arrays *out) {
-	const int rc = query_precheck(h, RAYS, origins4, directions4, n, false);
+namespace {
+
+// (`f`: RAYS or INSTANCED_RAYS; `instance`: the instanced closest form's indices, or null)
+int rays_call(rt_host *h, const Family &f, bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
+              uint32_t flags, const ocrt::QueryOutputs &q, uint32_t *instance, Where where) {
+	const int rc = query_precheck(h, f, origins4, directions4, n, !where.host);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	return guarded([&] { queries_of(h).traceHost(true, origins4, directions4, n, max_distance, flags, hit_outputs(out)); });
+	if (!where.host && !(records_aligned(q) && aligned({ instance }, 4)))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).trace(closest, origins4, directions4, n, max_distance, flags, q, where, f.instanced, instance); });
+}
+
+}  // namespace
+
+int rt_trace_closest(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
+                     const rt_hit_arrays *out) {
+	return rays_call(h, RAYS, true, origins4, directions4, n, max_distance, flags, hit_outputs(out), nullptr, HOST);
 }
 
 int rt_trace_occluded(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
                       uint8_t *occluded) {
-	const int rc = query_precheck(h, RAYS, origins4, directions4, n, false);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] { queries_of(h).traceHost(false, origins4, directions4, n, max_distance, flags, occlusion_outputs(occluded)); });
+	return rays_call(h, RAYS, false, origins4, directions4, n, max_distance, flags, occlusion_outputs(occluded), nullptr, HOST);
 }
 
 int rt_trace_closest_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
                             uint32_t flags, const rt_hit_arrays *out, void *hip_stream) {
-	const int rc = query_precheck(h, RAYS, origins4, directions4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	const ocrt::QueryOutputs q = hit_outputs(out);
-	if (!records_aligned(q))
-		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).traceDevice(true, origins4, directions4, n, max_distance, flags, q, hip_stream); });
+	return rays_call(h, RAYS, true, origins4, directions4, n, max_distance, flags, hit_outputs(out), nullptr, on(hip_stream));
 }
 
 int rt_trace_occluded_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
                              uint32_t flags, uint8_t *occluded, void *hip_stream) {
-	const int rc = query_precheck(h, RAYS, origins4, directions4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] { queries_of(h).traceDevice(false, origins4, directions4, n, max_distance, flags, occlusion_outputs(occluded), hip_stream); });
+	return rays_call(h, RAYS, false, origins4, directions4, n, max_distance, flags, occlusion_outputs(occluded), nullptr, on(hip_stream));
 }
 
 // ---- rt_hip_segment.h ----
@@ -1041,63 +1053,59 @@ ocrt::RayQueries::VisibilityOutputs visibility_outputs(const rt_visibility_array
 	return q;
 }
 
+// (`f`: SEGMENTS or INSTANCED_SEGMENTS)
+int segments_call(rt_host *h, const Family &f, bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi,
+                  uint32_t flags, const ocrt::QueryOutputs &q, uint32_t *instance, Where where) {
+	const int rc = query_precheck(h, f, from4, to4, n, !where.host);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	if (!where.host && !(records_aligned(q) && aligned({ instance }, 4)))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).segments(closest, from4, to4, n, t_lo, t_hi, flags, q, where, f.instanced, instance); });
+}
+
+int visibility_call(rt_host *h, const Family &f, const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
+                    uint32_t flags, const rt_visibility_arrays *out, Where where) {
+	const uint64_t pairs = (uint64_t) np * nt;
+	const int rc = query_precheck(h, f, points4, targets4, pairs, !where.host);
+	if (rc != RT_OK || pairs == 0)
+		return rc;
+	const ocrt::RayQueries::VisibilityOutputs q = visibility_outputs(out);
+	if (!where.host && !aligned({ q.mask, q.count }, 4))
+		return fail(RT_E_INVALID, "device uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).visibility(points4, np, targets4, nt, t_lo, t_hi, flags, q, where, f.instanced); });
+}
+
 }  // namespace
 
 int rt_segments_closest(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
                         const rt_hit_arrays *out) {
-	const int rc = query_precheck(h, SEGMENTS, from4, to4, n, false);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] { queries_of(h).segmentsHost(true, from4, to4, n, t_lo, t_hi, flags, hit_outputs(out)); });
+	return segments_call(h, SEGMENTS, true, from4, to4, n, t_lo, t_hi, flags, hit_outputs(out), nullptr, HOST);
 }
 
 int rt_segments_occluded(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
                          uint8_t *occluded) {
-	const int rc = query_precheck(h, SEGMENTS, from4, to4, n, false);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] { queries_of(h).segmentsHost(false, from4, to4, n, t_lo, t_hi, flags, occlusion_outputs(occluded)); });
+	return segments_call(h, SEGMENTS, false, from4, to4, n, t_lo, t_hi, flags, occlusion_outputs(occluded), nullptr, HOST);
 }
 
 int rt_segments_closest_device(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
                                const rt_hit_arrays *out, void *hip_stream) {
-	const int rc = query_precheck(h, SEGMENTS, from4, to4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	const ocrt::QueryOutputs q = hit_outputs(out);
-	if (!records_aligned(q))
-		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).segmentsDevice(true, from4, to4, n, t_lo, t_hi, flags, q, hip_stream); });
+	return segments_call(h, SEGMENTS, true, from4, to4, n, t_lo, t_hi, flags, hit_outputs(out), nullptr, on(hip_stream));
 }
 
 int rt_segments_occluded_device(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
                                 uint8_t *occluded, void *hip_stream) {
-	const int rc = query_precheck(h, SEGMENTS, from4, to4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] { queries_of(h).segmentsDevice(false, from4, to4, n, t_lo, t_hi, flags, occlusion_outputs(occluded), hip_stream); });
+	return segments_call(h, SEGMENTS, false, from4, to4, n, t_lo, t_hi, flags, occlusion_outputs(occluded), nullptr, on(hip_stream));
 }
 
 int rt_visibility_masks(rt_host *h, const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
                         uint32_t flags, const rt_visibility_arrays *out) {
-	const uint64_t pairs = (uint64_t) np * nt;
-	const int rc = query_precheck(h, SEGMENTS, points4, targets4, pairs, false);
-	if (rc != RT_OK || pairs == 0)
-		return rc;
-	const ocrt::RayQueries::VisibilityOutputs q = visibility_outputs(out);
-	return guarded([&] { queries_of(h).visibilityHost(points4, np, targets4, nt, t_lo, t_hi, flags, q); });
+	return visibility_call(h, SEGMENTS, points4, np, targets4, nt, t_lo, t_hi, flags, out, HOST);
 }
 
 int rt_visibility_masks_device(rt_host *h, const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo,
                                float t_hi, uint32_t flags, const rt_visibility_arrays *out, void *hip_stream) {
-	const uint64_t pairs = (uint64_t) np * nt;
-	const int rc = query_precheck(h, SEGMENTS, points4, targets4, pairs, true);
-	if (rc != RT_OK || pairs == 0)
-		return rc;
-	const ocrt::RayQueries::VisibilityOutputs q = visibility_outputs(out);
-	if (!aligned({ q.mask, q.count }, 4))
-		return fail(RT_E_INVALID, "device uint32 outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).visibilityDevice(points4, np, targets4, nt, t_lo, t_hi, flags, q, hip_stream); });
+	return visibility_call(h, SEGMENTS, points4, np, targets4, nt, t_lo, t_hi, flags, out, on(hip_stream));
 }
 
 // ---- rt_hip_instances.h ----
@@ -1197,152 +1205,103 @@ int rt_instance_nodes(rt_host *h, void *out) {
 
 int rt_trace_instances_closest(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
                                const rt_instance_hit_arrays *out) {
-	const int rc = query_precheck(h, INSTANCED_RAYS, origins4, directions4, n, false);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] {
-		queries_of(h).traceHost(true, origins4, directions4, n, max_distance, flags, hit_outputs(out ? &out->record : nullptr), true,
-		                        out ? out->instance : nullptr);
-	});
+	return rays_call(h, INSTANCED_RAYS, true, origins4, directions4, n, max_distance, flags, hit_outputs(out), instance_of(out), HOST);
 }
 
 int rt_trace_instances_occluded(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
                                 uint8_t *occluded) {
-	const int rc = query_precheck(h, INSTANCED_RAYS, origins4, directions4, n, false);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] { queries_of(h).traceHost(false, origins4, directions4, n, max_distance, flags, occlusion_outputs(occluded), true, nullptr); });
+	return rays_call(h, INSTANCED_RAYS, false, origins4, directions4, n, max_distance, flags, occlusion_outputs(occluded), nullptr, HOST);
 }
 
 int rt_trace_instances_closest_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
                                       uint32_t flags, const rt_instance_hit_arrays *out, void *hip_stream) {
-	const int rc = query_precheck(h, INSTANCED_RAYS, origins4, directions4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	const ocrt::QueryOutputs q = hit_outputs(out ? &out->record : nullptr);
-	uint32_t *const instance = out ? out->instance : nullptr;
-	if (!records_aligned(q) || !aligned({ instance }, 4))
-		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).traceDevice(true, origins4, directions4, n, max_distance, flags, q, hip_stream, true, instance); });
+	return rays_call(h, INSTANCED_RAYS, true, origins4, directions4, n, max_distance, flags, hit_outputs(out), instance_of(out), on(hip_stream));
 }
 
 int rt_trace_instances_occluded_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
                                        uint32_t flags, uint8_t *occluded, void *hip_stream) {
-	const int rc = query_precheck(h, INSTANCED_RAYS, origins4, directions4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] {
-		queries_of(h).traceDevice(false, origins4, directions4, n, max_distance, flags, occlusion_outputs(occluded), hip_stream, true, nullptr);
-	});
+	return rays_call(h, INSTANCED_RAYS, false, origins4, directions4, n, max_distance, flags, occlusion_outputs(occluded), nullptr,
+	                 on(hip_stream));
 }
 
 // ---- rt_hip_instance_segments.h ----
 int rt_instances_segments_closest(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
                                   const rt_instance_hit_arrays *out) {
-	const int rc = query_precheck(h, INSTANCED_SEGMENTS, from4, to4, n, false);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] {
-		queries_of(h).segmentsHost(true, from4, to4, n, t_lo, t_hi, flags, hit_outputs(out ? &out->record : nullptr), true,
-		                           out ? out->instance : nullptr);
-	});
+	return segments_call(h, INSTANCED_SEGMENTS, true, from4, to4, n, t_lo, t_hi, flags, hit_outputs(out), instance_of(out), HOST);
 }
 
 int rt_instances_segments_occluded(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
                                    uint8_t *occluded) {
-	const int rc = query_precheck(h, INSTANCED_SEGMENTS, from4, to4, n, false);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] { queries_of(h).segmentsHost(false, from4, to4, n, t_lo, t_hi, flags, occlusion_outputs(occluded), true, nullptr); });
+	return segments_call(h, INSTANCED_SEGMENTS, false, from4, to4, n, t_lo, t_hi, flags, occlusion_outputs(occluded), nullptr, HOST);
 }
 
 int rt_instances_segments_closest_device(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi,
                                          uint32_t flags, const rt_instance_hit_arrays *out, void *hip_stream) {
-	const int rc = query_precheck(h, INSTANCED_SEGMENTS, from4, to4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	const ocrt::QueryOutputs q = hit_outputs(out ? &out->record : nullptr);
-	uint32_t *const instance = out ? out->instance : nullptr;
-	if (!records_aligned(q) || !aligned({ instance }, 4))
-		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).segmentsDevice(true, from4, to4, n, t_lo, t_hi, flags, q, hip_stream, true, instance); });
+	return segments_call(h, INSTANCED_SEGMENTS, true, from4, to4, n, t_lo, t_hi, flags, hit_outputs(out), instance_of(out), on(hip_stream));
 }
 
 int rt_instances_segments_occluded_device(rt_host *h, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi,
                                           uint32_t flags, uint8_t *occluded, void *hip_stream) {
-	const int rc = query_precheck(h, INSTANCED_SEGMENTS, from4, to4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] {
-		queries_of(h).segmentsDevice(false, from4, to4, n, t_lo, t_hi, flags, occlusion_outputs(occluded), hip_stream, true, nullptr);
-	});
+	return segments_call(h, INSTANCED_SEGMENTS, false, from4, to4, n, t_lo, t_hi, flags, occlusion_outputs(occluded), nullptr, on(hip_stream));
 }
 
 int rt_instances_visibility_masks(rt_host *h, const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
                                   uint32_t flags, const rt_visibility_arrays *out) {
-	const uint64_t pairs = (uint64_t) np * nt;
-	const int rc = query_precheck(h, INSTANCED_SEGMENTS, points4, targets4, pairs, false);
-	if (rc != RT_OK || pairs == 0)
-		return rc;
-	const ocrt::RayQueries::VisibilityOutputs q = visibility_outputs(out);
-	return guarded([&] { queries_of(h).visibilityHost(points4, np, targets4, nt, t_lo, t_hi, flags, q, true); });
+	return visibility_call(h, INSTANCED_SEGMENTS, points4, np, targets4, nt, t_lo, t_hi, flags, out, HOST);
 }
 
 int rt_instances_visibility_masks_device(rt_host *h, const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo,
                                          float t_hi, uint32_t flags, const rt_visibility_arrays *out, void *hip_stream) {
-	const uint64_t pairs = (uint64_t) np * nt;
-	const int rc = query_precheck(h, INSTANCED_SEGMENTS, points4, targets4, pairs, true);
-	if (rc != RT_OK || pairs == 0)
-		return rc;
-	const ocrt::RayQueries::VisibilityOutputs q = visibility_outputs(out);
-	if (!aligned({ q.mask, q.count }, 4))
-		return fail(RT_E_INVALID, "device uint32 outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).visibilityDevice(points4, np, targets4, nt, t_lo, t_hi, flags, q, hip_stream, true); });
+	return visibility_call(h, INSTANCED_SEGMENTS, points4, np, targets4, nt, t_lo, t_hi, flags, out, on(hip_stream));
 }
 
 // ---- rt_hip_nearest.h ----
-int rt_closest_points(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags, const rt_hit_arrays *out) {
-	const int rc = query_precheck(h, POINTS, points4, points4, n, false);
+namespace {
+
+// (`f`: POINTS or INSTANCED_POINTS)
+int points_call(rt_host *h, const Family &f, const float *points4, uint32_t n, float max_distance, uint32_t flags, const ocrt::QueryOutputs &q,
+                uint32_t *instance, Where where) {
+	const int rc = query_precheck(h, f, points4, points4, n, !where.host);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	return guarded([&] { queries_of(h).nearestHost(points4, n, max_distance, flags, hit_outputs(out)); });
+	if (!where.host && !(records_aligned(q) && aligned({ instance }, 4)))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).nearest(points4, n, max_distance, flags, q, where, f.instanced, instance); });
+}
+
+int signed_call(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags, const rt_signed_arrays *out, Where where) {
+	const int rc = query_precheck(h, SIGNED_POINTS, points4, points4, n, !where.host);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	const ocrt::QueryOutputs q = hit_outputs(out ? &out->hit : nullptr);
+	if (!where.host && !records_aligned(q))
+		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
+	if (!where.host && out && !aligned({ out->pseudonormal4 }, 16))
+		return fail(RT_E_INVALID, "the device pseudonormal array must be 16-byte aligned");
+	return guarded([&] {
+		queries_of(h).signedDistance(points4, n, max_distance, flags, q, out ? out->feature : nullptr, out ? out->pseudonormal4 : nullptr, where);
+	});
+}
+
+}  // namespace
+
+int rt_closest_points(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags, const rt_hit_arrays *out) {
+	return points_call(h, POINTS, points4, n, max_distance, flags, hit_outputs(out), nullptr, HOST);
 }
 
 int rt_closest_points_device(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags, const rt_hit_arrays *out,
                              void *hip_stream) {
-	const int rc = query_precheck(h, POINTS, points4, points4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	const ocrt::QueryOutputs q = hit_outputs(out);
-	if (!records_aligned(q))
-		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).nearestDevice(points4, n, max_distance, flags, q, hip_stream); });
+	return points_call(h, POINTS, points4, n, max_distance, flags, hit_outputs(out), nullptr, on(hip_stream));
 }
 
 // ---- rt_hip_signed.h ----
 int rt_signed_distance(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags, const rt_signed_arrays *out) {
-	const int rc = query_precheck(h, SIGNED_POINTS, points4, points4, n, false);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] {
-		queries_of(h).signedHost(points4, n, max_distance, flags, hit_outputs(out ? &out->hit : nullptr), out ? out->feature : nullptr,
-		                         out ? out->pseudonormal4 : nullptr);
-	});
+	return signed_call(h, points4, n, max_distance, flags, out, HOST);
 }
 
 int rt_signed_distance_device(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags, const rt_signed_arrays *out,
                               void *hip_stream) {
-	const int rc = query_precheck(h, SIGNED_POINTS, points4, points4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	const ocrt::QueryOutputs q = hit_outputs(out ? &out->hit : nullptr);
-	if (!records_aligned(q))
-		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
-	if (out && !aligned({ out->pseudonormal4 }, 16))
-		return fail(RT_E_INVALID, "the device pseudonormal array must be 16-byte aligned");
-	return guarded([&] {
-		queries_of(h).signedDevice(points4, n, max_distance, flags, q, out ? out->feature : nullptr, out ? out->pseudonormal4 : nullptr, hip_stream);
-	});
+	return signed_call(h, points4, n, max_distance, flags, out, on(hip_stream));
 }
 
 namespace {
@@ -1411,24 +1370,12 @@ int rt_debug_sign_table(rt_host *h, float *table) {
 // ---- rt_hip_instance_nearest.h ----
 int rt_instances_closest_points(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags,
                                 const rt_instance_hit_arrays *out) {
-	const int rc = query_precheck(h, INSTANCED_POINTS, points4, points4, n, false);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] {
-		queries_of(h).nearestHost(points4, n, max_distance, flags, hit_outputs(out ? &out->record : nullptr), true, out ? out->instance : nullptr);
-	});
+	return points_call(h, INSTANCED_POINTS, points4, n, max_distance, flags, hit_outputs(out), instance_of(out), HOST);
 }
 
 int rt_instances_closest_points_device(rt_host *h, const float *points4, uint32_t n, float max_distance, uint32_t flags,
                                        const rt_instance_hit_arrays *out, void *hip_stream) {
-	const int rc = query_precheck(h, INSTANCED_POINTS, points4, points4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	const ocrt::QueryOutputs q = hit_outputs(out ? &out->record : nullptr);
-	uint32_t *const instance = out ? out->instance : nullptr;
-	if (!records_aligned(q) || !aligned({ instance }, 4))
-		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).nearestDevice(points4, n, max_distance, flags, q, hip_stream, true, instance); });
+	return points_call(h, INSTANCED_POINTS, points4, n, max_distance, flags, hit_outputs(out), instance_of(out), on(hip_stream));
 }
 
 int rt_debug_set_nearest_walk(rt_host *h, uint32_t flags) {
@@ -1454,9 +1401,9 @@ namespace {
 
 // The checks of include/rt_hip_multihit.h ("Errors") beyond query_precheck's; `q`: the outputs asked for.
 // (`f`: RAYS, or INSTANCED_RAYS with the slots' `instance` array beside them -- include/rt_hip_instance_multihit.h)
-int multihit_precheck(rt_host *h, const float *origins4, const float *directions4, uint32_t n, uint32_t k, const ocrt::MultiHitOutputs &q,
-                      bool device, const Family &f = RAYS, const uint32_t *instance = nullptr) {
-	const int rc = query_precheck(h, f, origins4, directions4, n, device);
+int multihit_call(rt_host *h, const Family &f, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
+                  uint32_t flags, const ocrt::MultiHitOutputs &q, uint32_t *instance, Where where) {
+	const int rc = query_precheck(h, f, origins4, directions4, n, !where.host);
 	if (rc != RT_OK)
 		return rc;
 	if (k > RT_MULTIHIT_MAX_K)
@@ -1465,50 +1412,35 @@ int multihit_precheck(rt_host *h, const float *origins4, const float *directions
 		return fail(RT_E_INVALID, "k == 0 asks for the count alone: the slot arrays must be null");
 	if ((uint64_t) n * (k ? k : 1u) > RT_QUERY_MAX_RAYS)
 		return fail(RT_E_INVALID, "more than RT_QUERY_MAX_RAYS slots (n * k) in one call");
-	if (device && !(aligned({ q.count, instance }, 4) && records_aligned(q)))
+	if (!where.host && !(aligned({ q.count, instance }, 4) && records_aligned(q)))
 		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
-	return RT_OK;
+	if (n == 0)
+		return RT_OK;
+	return guarded([&] { queries_of(h).multihit(origins4, directions4, n, max_distance, k, flags, q, where, f.instanced, instance); });
 }
 
 }  // namespace
 
 int rt_trace_multihit(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
                       uint32_t flags, const rt_multihit_arrays *out) {
-	const ocrt::MultiHitOutputs q = multihit_outputs(out);
-	const int rc = multihit_precheck(h, origins4, directions4, n, k, q, false);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] { queries_of(h).multihitHost(origins4, directions4, n, max_distance, k, flags, q); });
+	return multihit_call(h, RAYS, origins4, directions4, n, max_distance, k, flags, multihit_outputs(out), nullptr, HOST);
 }
 
 int rt_trace_multihit_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
                              uint32_t flags, const rt_multihit_arrays *out, void *hip_stream) {
-	const ocrt::MultiHitOutputs q = multihit_outputs(out);
-	const int rc = multihit_precheck(h, origins4, directions4, n, k, q, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] { queries_of(h).multihitDevice(origins4, directions4, n, max_distance, k, flags, q, hip_stream); });
+	return multihit_call(h, RAYS, origins4, directions4, n, max_distance, k, flags, multihit_outputs(out), nullptr, on(hip_stream));
 }
 
 // ---- rt_hip_instance_multihit.h ----
 int rt_trace_instances_multihit(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
                                 uint32_t flags, const rt_instance_multihit_arrays *out) {
-	const ocrt::MultiHitOutputs q = multihit_outputs(out ? &out->slots : nullptr);
-	uint32_t *const instance = out ? out->instance : nullptr;
-	const int rc = multihit_precheck(h, origins4, directions4, n, k, q, false, INSTANCED_RAYS, instance);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] { queries_of(h).multihitHost(origins4, directions4, n, max_distance, k, flags, q, true, instance); });
+	return multihit_call(h, INSTANCED_RAYS, origins4, directions4, n, max_distance, k, flags, multihit_outputs(out), instance_of(out), HOST);
 }
 
 int rt_trace_instances_multihit_device(rt_host *h, const float *origins4, const float *directions4, uint32_t n, float max_distance,
                                        uint32_t k, uint32_t flags, const rt_instance_multihit_arrays *out, void *hip_stream) {
-	const ocrt::MultiHitOutputs q = multihit_outputs(out ? &out->slots : nullptr);
-	uint32_t *const instance = out ? out->instance : nullptr;
-	const int rc = multihit_precheck(h, origins4, directions4, n, k, q, true, INSTANCED_RAYS, instance);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] { queries_of(h).multihitDevice(origins4, directions4, n, max_distance, k, flags, q, hip_stream, true, instance); });
+	return multihit_call(h, INSTANCED_RAYS, origins4, directions4, n, max_distance, k, flags, multihit_outputs(out), instance_of(out),
+	                     on(hip_stream));
 }
 
 // ---- rt_hip_ao.h ----
@@ -1524,22 +1456,36 @@ int rt_ao_rays_per_point(const rt_host *h, uint32_t *rays, uint32_t *divisor) {
 	return RT_OK;
 }
 
-int rt_trace_ao(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
-                uint32_t *occluded) {
-	const int rc = ao_precheck(h, points4, normals4, n, false, nullptr);
+namespace {
+
+// ao_precheck; `instanced` (include/rt_hip_instance_views.h, "Errors"): behind the instanced families' own two checks.
+int ao_query_precheck(const rt_host *h, bool instanced, const float *points4, const float *normals4, uint32_t n, Where where) {
+	int rc = instanced ? host_precheck(h, "instanced ambient-occlusion") : RT_OK;
+	if (rc == RT_OK && instanced)
+		rc = instance_set_required(h, "instanced ambient-occlusion query");
+	return rc != RT_OK ? rc : ao_precheck(h, points4, normals4, n, !where.host, nullptr);
+}
+
+int ao_call(rt_host *h, bool instanced, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
+            float *ao, uint32_t *occluded, Where where) {
+	const int rc = ao_query_precheck(h, instanced, points4, normals4, n, where);
 	if (rc != RT_OK || n == 0)
 		return rc;
-	return guarded([&] { queries_of(h).aoHost(points4, normals4, seeds, n, flags, ao, occluded); });
+	if (!where.host && !aligned({ seeds, ao, occluded }, 4))
+		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).ao(points4, normals4, seeds, n, flags, ao, occluded, where, instanced); });
+}
+
+}  // namespace
+
+int rt_trace_ao(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
+                uint32_t *occluded) {
+	return ao_call(h, false, points4, normals4, seeds, n, flags, ao, occluded, HOST);
 }
 
 int rt_trace_ao_device(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
                        float *ao, uint32_t *occluded, void *hip_stream) {
-	const int rc = ao_precheck(h, points4, normals4, n, true, nullptr);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	if (!aligned({ seeds, ao, occluded }, 4))
-		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).aoDevice(points4, normals4, seeds, n, flags, ao, occluded, hip_stream); });
+	return ao_call(h, false, points4, normals4, seeds, n, flags, ao, occluded, on(hip_stream));
 }
 
 // ---- rt_hip_directional.h ----
@@ -1568,44 +1514,51 @@ int rt_ao_mask_words(const rt_host *h, uint32_t *words) {
 	return RT_OK;
 }
 
-int rt_trace_ao_directional(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
-                            const rt_ao_directional_arrays *out) {
-	const int rc = ao_precheck(h, points4, normals4, n, false, nullptr);
+namespace {
+
+int directional_call(rt_host *h, bool instanced, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n,
+                     uint32_t flags, const rt_ao_directional_arrays *out, Where where) {
+	const int rc = ao_query_precheck(h, instanced, points4, normals4, n, where);
 	if (rc != RT_OK || n == 0)
 		return rc;
 	const ocrt::RayQueries::DirectionalOutputs q = directional_outputs(out);
-	return guarded([&] { queries_of(h).directionalHost(points4, normals4, seeds, n, flags, q); });
+	if (!where.host && !aligned({ seeds, q.ao, q.occluded, q.mask, q.bent }, 4))
+		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
+	return guarded([&] { queries_of(h).directional(points4, normals4, seeds, n, flags, q, where, instanced); });
+}
+
+int ao_rays_call(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4,
+                 float *directions4, Where where) {
+	const int rc = ao_query_precheck(h, false, points4, normals4, n, where);
+	if (rc != RT_OK || n == 0)
+		return rc;
+	if (!where.host && !aligned({ origins4, directions4 }, 16))
+		return fail(RT_E_INVALID, "device origin and direction arrays must be 16-byte aligned");
+	if (!where.host && !aligned({ seeds }, 4))
+		return fail(RT_E_INVALID, "device seeds must be 4-byte aligned");
+	return guarded([&] { queries_of(h).aoRays(points4, normals4, seeds, n, origins4, directions4, where); });
+}
+
+}  // namespace
+
+int rt_trace_ao_directional(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
+                            const rt_ao_directional_arrays *out) {
+	return directional_call(h, false, points4, normals4, seeds, n, flags, out, HOST);
 }
 
 int rt_trace_ao_directional_device(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n,
                                    uint32_t flags, const rt_ao_directional_arrays *out, void *hip_stream) {
-	const int rc = ao_precheck(h, points4, normals4, n, true, nullptr);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	const ocrt::RayQueries::DirectionalOutputs q = directional_outputs(out);
-	if (!aligned({ seeds, q.ao, q.occluded, q.mask, q.bent }, 4))
-		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).directionalDevice(points4, normals4, seeds, n, flags, q, hip_stream); });
+	return directional_call(h, false, points4, normals4, seeds, n, flags, out, on(hip_stream));
 }
 
 int rt_ao_rays(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4,
                float *directions4) {
-	const int rc = ao_precheck(h, points4, normals4, n, false, nullptr);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] { queries_of(h).aoRaysHost(points4, normals4, seeds, n, origins4, directions4); });
+	return ao_rays_call(h, points4, normals4, seeds, n, origins4, directions4, HOST);
 }
 
 int rt_ao_rays_device(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4,
                       float *directions4, void *hip_stream) {
-	const int rc = ao_precheck(h, points4, normals4, n, true, nullptr);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	if (!aligned({ origins4, directions4 }, 16))
-		return fail(RT_E_INVALID, "device origin and direction arrays must be 16-byte aligned");
-	if (!aligned({ seeds }, 4))
-		return fail(RT_E_INVALID, "device seeds must be 4-byte aligned");
-	return guarded([&] { queries_of(h).aoRaysDevice(points4, normals4, seeds, n, origins4, directions4, hip_stream); });
+	return ao_rays_call(h, points4, normals4, seeds, n, origins4, directions4, on(hip_stream));
 }
 
 // ---- rt_hip_layers.h ----
@@ -1633,24 +1586,21 @@ int layers_precheck(const rt_host *h, const rt_layer_arrays *out) {
 	return RT_OK;
 }
 
-}  // namespace
-
-int rt_render_layers(rt_host *h, const rt_layer_arrays *out) {
-	const int rc = layers_precheck(h, out);
-	if (rc != RT_OK)
-		return rc;
-	return guarded([&] { queries_of(h).layersHost(layer_outputs(*out)); });
-}
-
-int rt_render_layers_device(rt_host *h, const rt_layer_arrays *out, void *hip_stream) {
+int layers_call(rt_host *h, const rt_layer_arrays *out, Where where) {
 	const int rc = layers_precheck(h, out);
 	if (rc != RT_OK)
 		return rc;
 	const ocrt::LayerOutputs q = layer_outputs(*out);
-	if (!(records_aligned(q) && aligned({ q.direction, q.shade, q.ao, q.value }, 4)))
+	if (!where.host && !(records_aligned(q) && aligned({ q.direction, q.shade, q.ao, q.value }, 4)))
 		return fail(RT_E_INVALID, "device float / uint32 outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).layersDevice(q, hip_stream); });
+	return guarded([&] { queries_of(h).layers(q, where); });
 }
+
+}  // namespace
+
+int rt_render_layers(rt_host *h, const rt_layer_arrays *out) { return layers_call(h, out, HOST); }
+
+int rt_render_layers_device(rt_host *h, const rt_layer_arrays *out, void *hip_stream) { return layers_call(h, out, on(hip_stream)); }
 
 // ---- rt_hip_views.h ----
 namespace {
@@ -1697,14 +1647,6 @@ int rt_render_views_device(rt_host *h, const rt_camera *cameras, uint32_t views,
 // ---- rt_hip_instance_views.h ----
 namespace {
 
-// The union of ao_precheck's and instance_precheck's checks (include/rt_hip_instance_views.h, "Errors").
-int instance_ao_precheck(const rt_host *h, const float *points4, const float *normals4, uint32_t n, bool device) {
-	int rc = host_precheck(h, "instanced ambient-occlusion");
-	if (rc == RT_OK)
-		rc = instance_set_required(h, "instanced ambient-occlusion query");
-	return rc != RT_OK ? rc : ao_precheck(h, points4, normals4, n, device, nullptr);
-}
-
 int instance_views_precheck(const rt_host *h, const rt_camera *cameras, uint32_t views, const rt_instance_view_arrays *out) {
 	int rc = host_precheck(h, "instanced multi-view");
 	if (rc == RT_OK)
@@ -1716,41 +1658,23 @@ int instance_views_precheck(const rt_host *h, const rt_camera *cameras, uint32_t
 
 int rt_trace_instances_ao(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
                           float *ao, uint32_t *occluded) {
-	const int rc = instance_ao_precheck(h, points4, normals4, n, false);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	return guarded([&] { queries_of(h).aoHost(points4, normals4, seeds, n, flags, ao, occluded, true); });
+	return ao_call(h, true, points4, normals4, seeds, n, flags, ao, occluded, HOST);
 }
 
 int rt_trace_instances_ao_device(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n,
                                  uint32_t flags, float *ao, uint32_t *occluded, void *hip_stream) {
-	const int rc = instance_ao_precheck(h, points4, normals4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	if (!aligned({ seeds, ao, occluded }, 4))
-		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).aoDevice(points4, normals4, seeds, n, flags, ao, occluded, hip_stream, true); });
+	return ao_call(h, true, points4, normals4, seeds, n, flags, ao, occluded, on(hip_stream));
 }
 
 // ---- rt_hip_instance_directional.h ----
 int rt_trace_instances_ao_directional(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n,
                                       uint32_t flags, const rt_ao_directional_arrays *out) {
-	const int rc = instance_ao_precheck(h, points4, normals4, n, false);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	const ocrt::RayQueries::DirectionalOutputs q = directional_outputs(out);
-	return guarded([&] { queries_of(h).directionalHost(points4, normals4, seeds, n, flags, q, true); });
+	return directional_call(h, true, points4, normals4, seeds, n, flags, out, HOST);
 }
 
 int rt_trace_instances_ao_directional_device(rt_host *h, const float *points4, const float *normals4, const uint32_t *seeds,
                                              uint32_t n, uint32_t flags, const rt_ao_directional_arrays *out, void *hip_stream) {
-	const int rc = instance_ao_precheck(h, points4, normals4, n, true);
-	if (rc != RT_OK || n == 0)
-		return rc;
-	const ocrt::RayQueries::DirectionalOutputs q = directional_outputs(out);
-	if (!aligned({ seeds, q.ao, q.occluded, q.mask, q.bent }, 4))
-		return fail(RT_E_INVALID, "device seeds and outputs must be 4-byte aligned");
-	return guarded([&] { queries_of(h).directionalDevice(points4, normals4, seeds, n, flags, q, hip_stream, true); });
+	return directional_call(h, true, points4, normals4, seeds, n, flags, out, on(hip_stream));
 }
 
 // ---- rt_hip_instance_views.h: the views ----

@@ -18,24 +18,6 @@ constexpr size_t QUERY_COUNT_BYTES = (size_t) 1 << 18;  // kernels/query.hip.h: 
 constexpr uint32_t QUERY_NO_SORT = 1u, QUERY_SORT_MIN = 16384u;  // include/rt_hip_query.h
 constexpr uint32_t MULTIHIT_MAX_SLOTS = 16u;                     // include/rt_hip_multihit.h, kernels/multihit.hip.h
 size_t round16(size_t bytes) { return (bytes + 15u) & ~(size_t) 15u; }
-// The staged pieces of the host-memory forms.  Rays: the two inputs, the family's first output (hit flags or counts),
-// then the five record arrays.  Ambient occlusion: the counts come third, so that they are placed as they always were.
-enum { RAY_ORIGINS, RAY_DIRECTIONS, RAY_FIRST, RAY_RECORDS, RAY_PIECES = RAY_RECORDS + 5 };
-enum { AO_POINTS, AO_NORMALS, AO_COUNTS, AO_SEEDS, AO_VALUES, AO_PIECES };
-// Directional occlusion: the inputs, the rows (staged whether they are copied back or not), then the outputs made of them;
-// the rays of the points: the inputs and the two ray arrays.
-enum { DIR_POINTS, DIR_NORMALS, DIR_SEEDS, DIR_ROWS, DIR_COUNTS, DIR_VALUES, DIR_BENT, DIR_PIECES };
-enum { AORAY_POINTS, AORAY_NORMALS, AORAY_SEEDS, AORAY_ORIGINS, AORAY_DIRECTIONS, AORAY_PIECES };
-// Instanced ray and segment queries: the rays' pieces, then the instance indices (absent for a plain call).
-enum { INST_INDEX = RAY_PIECES, INST_PIECES };
-// Visibility masks: the two inputs, the rows (staged whether they are copied back or not), the counts.
-enum { VIS_POINTS, VIS_TARGETS, VIS_ROWS, VIS_COUNTS, VIS_PIECES };
-// Frame layers: the hit flags, the five record arrays, then the four layers of their own.
-enum { LAYER_HIT, LAYER_RECORDS, LAYER_DIRECTION = LAYER_RECORDS + 5, LAYER_SHADE, LAYER_AO, LAYER_VALUE, LAYER_PIECES };
-// Multi-view rendering: the layers' pieces, then the 8-bit images.
-enum { VIEW_IMAGE = LAYER_PIECES, VIEW_PIECES };
-// Instanced views: the views' pieces, then the instance indices.
-enum { VIEW_INSTANCE = VIEW_PIECES, INSTANCE_VIEW_PIECES };
 constexpr uint32_t QUERY_MAX_RAYS = 1u << 27;  // include/rt_hip_query.h
 constexpr uint32_t VIEWS_MAX_CHUNK = 65535u;   // layers_kernel, views_resize_kernel: a grid's second and third dimension
 constexpr size_t PINNED_HEAD = 16u;            // viewsDevice: the read-back word in front of the poses
@@ -134,17 +116,22 @@ void RayQueries::sceneBox(const DeviceScene &scene, float lo[3], float scale[3])
 	}
 }
 
-// The way into every device-memory form, up to its own launches: the stream (null: the renderer's), the wait for the
-// query before -- one set of scratch per host, so a query on another stream waits before any scratch is touched --, the
-// scratch (the sort's, and what the family needs of its own, `needs`: every grow comes before ev_start, because hipFree
-// synchronises), ev_start, and the sort of the n items keyed by (keys_a4, keys_b4) where the call allows it and makes
-// RT_QUERY_SORT_MIN `rays` or more.
-RayQueries::Enqueue RayQueries::begin(void *stream, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags,
-                                      std::initializer_list<Need> needs, bool segments, const float *box) {
+// The way into everything enqueued here, up to its own launches.  enter(): the stream (null: the renderer's) and the wait
+// for the query before -- one set of scratch per host, so a query on another stream waits before any scratch is touched.
+// begin(), on the stream entered: the scratch (the sort's, and what the family needs of its own, `needs`: every grow comes
+// before ev_start, because hipFree synchronises), ev_start, and the sort of the n items keyed by (keys_a4, keys_b4) where
+// the call allows it and makes RT_QUERY_SORT_MIN `rays` or more.
+void *RayQueries::enter(void *stream) {
 	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
 	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
 	if (timed)
 		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	return s;
+}
+
+RayQueries::Enqueue RayQueries::begin(void *entered, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags,
+                                      std::initializer_list<Need> needs, bool segments, const float *box) {
+	hipStream_t s = (hipStream_t) entered;
 	const bool sort = !(flags & QUERY_NO_SORT) && rays >= QUERY_SORT_MIN;
 	if (sort) {
 		grow(count, QUERY_COUNT_BYTES);
@@ -176,68 +163,67 @@ void RayQueries::end(const Enqueue &q) {
 	have_ms = false;
 }
 
-// The host-memory forms run on the renderer's own stream through one staging buffer: stageIn places the wanted pieces
-// one behind the other, each rounded up to 16 bytes, and uploads the inputs; stageOut copies the outputs back and waits.
-void *RayQueries::stageIn(Staged *pieces, size_t n) {
+// ---- arrays in host memory: one staging buffer, one path (ray_query.h: Arrays, staged) ----
+// (the pointer variables are of many types: their values are read and written as bytes, never through a void **)
+RayQueries::Arrays &RayQueries::Arrays::add(void *variable, size_t bytes, bool wanted, bool input) {
+	if (!wanted)
+		return *this;
+	if (count == sizeof piece / sizeof piece[0])
+		throw std::logic_error("more arrays in one call than RayQueries::Arrays holds");
+	Piece &p = piece[count++];
+	p.variable = variable;
+	p.bytes = bytes;
+	p.input = input;
+	std::memcpy(&p.host, variable, sizeof p.host);
+	return *this;
+}
+
+RayQueries::Arrays &RayQueries::Arrays::records(RecordOutputs &r, size_t records) {
+	return out(r.distance, records * 4u).out(r.leaf, records * 4u).out(r.barycentric, records * 12u).out(r.position, records * 12u).out(
+	    r.normal, records * 12u);
+}
+
+RayQueries::Arrays &RayQueries::Arrays::layers(LayerOutputs &l, size_t records) {
+	out(l.hit, records).records(l, records);
+	return out(l.direction, records * 12u).out(l.shade, records * 4u).out(l.ao, records * 4u).out(l.value, records * 4u);
+}
+
+void *RayQueries::stageIn(Arrays &arrays) {
 	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
 	hipStream_t s = (hipStream_t) dev.streamHandle();
 	size_t total = 0;
-	for (size_t i = 0; i < n; ++i)
-		if (pieces[i].wanted)
-			total += round16(pieces[i].bytes);
+	for (size_t i = 0; i < arrays.count; ++i)
+		total += round16(arrays.piece[i].bytes);
 	grow(stage, total);
 	char *at = (char *) stage.ptr;
-	for (size_t i = 0; i < n; ++i) {
-		Staged &piece = pieces[i];
-		if (!piece.wanted)
-			continue;
-		piece.device = at;
-		at += round16(piece.bytes);
-		if (piece.from)
-			OCRT_HIP(hipMemcpyAsync(piece.device, piece.from, piece.bytes, hipMemcpyHostToDevice, s));
+	for (size_t i = 0; i < arrays.count; ++i) {
+		Arrays::Piece &p = arrays.piece[i];
+		p.device = at;
+		at += round16(p.bytes);
+		std::memcpy(p.variable, &p.device, sizeof p.device);
+		if (p.input)
+			OCRT_HIP(hipMemcpyAsync(p.device, p.host, p.bytes, hipMemcpyHostToDevice, s));
 	}
 	return s;
 }
 
-void RayQueries::stageOut(const Staged *pieces, size_t n, void *stream) {
-	for (size_t i = 0; i < n; ++i)
-		if (pieces[i].to && pieces[i].device && pieces[i].bytes)
-			OCRT_HIP(hipMemcpyAsync(pieces[i].to, pieces[i].device, pieces[i].bytes, hipMemcpyDeviceToHost, (hipStream_t) stream));
+void RayQueries::stageOut(const Arrays &arrays, void *stream) {
+	for (size_t i = 0; i < arrays.count; ++i) {
+		const Arrays::Piece &p = arrays.piece[i];
+		if (!p.input && p.host && p.bytes)
+			OCRT_HIP(hipMemcpyAsync(p.host, p.device, p.bytes, hipMemcpyDeviceToHost, (hipStream_t) stream));
+	}
 	OCRT_HIP(hipStreamSynchronize((hipStream_t) stream));
 }
 
-void RayQueries::recordPieces(Staged *p, const RecordOutputs &host, size_t records) {
-	p[0] = output(host.distance, records * 4u);
-	p[1] = output(host.leaf, records * 4u);
-	p[2] = output(host.barycentric, records * 12u);
-	p[3] = output(host.position, records * 12u);
-	p[4] = output(host.normal, records * 12u);
-}
-
-void RayQueries::recordDevice(const Staged *p, RecordOutputs &out) {
-	out.distance = (float *) p[0].device;
-	out.leaf = (uint32_t *) p[1].device;
-	out.barycentric = (float *) p[2].device;
-	out.position = (float *) p[3].device;
-	out.normal = (float *) p[4].device;
-}
-
-void RayQueries::layerPieces(Staged *p, const LayerOutputs &host, size_t records) {
-	p[LAYER_HIT] = output(host.hit, records);
-	recordPieces(p + LAYER_RECORDS, host, records);
-	p[LAYER_DIRECTION] = output(host.direction, records * 12u);
-	p[LAYER_SHADE] = output(host.shade, records * 4u);
-	p[LAYER_AO] = output(host.ao, records * 4u);
-	p[LAYER_VALUE] = output(host.value, records * 4u);
-}
-
-void RayQueries::layerDevice(const Staged *p, LayerOutputs &out) {
-	out.hit = (unsigned char *) p[LAYER_HIT].device;
-	recordDevice(p + LAYER_RECORDS, out);
-	out.direction = (float *) p[LAYER_DIRECTION].device;
-	out.shade = (float *) p[LAYER_SHADE].device;
-	out.ao = (float *) p[LAYER_AO].device;
-	out.value = (float *) p[LAYER_VALUE].device;
+template <class Body> void RayQueries::staged(Where where, Arrays &arrays, Body &&body) {
+	if (!where.host) {
+		body(where.stream);
+		return;
+	}
+	void *s = stageIn(arrays);
+	body(s);
+	stageOut(arrays, s);
 }
 
 void RayQueries::requireQuery(bool instanced, const char *query) const {
@@ -254,45 +240,24 @@ RayQueries::Target RayQueries::target(bool instanced) {
 	return Target{ &inst_set, inst_box };
 }
 
-template <class Run>
-void RayQueries::stagedRecords(const float *a4, const float *b4, uint32_t n, bool records, const QueryOutputs &host, uint32_t *instance,
-                               Run &&run) {
-	QueryOutputs want;  // (occlusion: the flags alone)
-	if (records)
-		want = host;
-	want.hit = host.hit;
-	Staged p[INST_PIECES] = { input(a4, (size_t) n * 16u), input(b4, b4 ? (size_t) n * 16u : 0u), output(want.hit, n) };
-	recordPieces(p + RAY_RECORDS, want, n);
-	p[INST_INDEX] = output(records ? instance : nullptr, (size_t) n * 4u);
-	void *s = stageIn(p, INST_PIECES);
-	QueryOutputs out;
-	out.hit = (unsigned char *) p[RAY_FIRST].device;
-	recordDevice(p + RAY_RECORDS, out);
-	run((const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, out, (uint32_t *) p[INST_INDEX].device, s);
-	stageOut(p, INST_PIECES, s);
-}
-
-void RayQueries::traceDevice(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
-                             uint32_t flags, const QueryOutputs &out, void *stream, bool instanced, uint32_t *instance) {
+void RayQueries::trace(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
+                       QueryOutputs out, Where where, bool instanced, uint32_t *instance) {
 	requireQuery(instanced, "ray query");
 	if (n == 0)
 		return;
-	const Target to = target(instanced);
-	const Enqueue q = begin(stream, origins4, directions4, n, n, flags, {}, false, to.box);
-	launch_query(dev.deviceScene()->buffers(), dev.params().node_count, to.set, closest, origins4, directions4, q.order, n, max_distance, out,
-	             closest ? instance : nullptr, q.stream);
-	end(q);
-}
-
-void RayQueries::traceHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
-                           uint32_t flags, const QueryOutputs &host, bool instanced, uint32_t *instance) {
-	requireQuery(instanced, "ray query");
-	if (n == 0)
-		return;
-	stagedRecords(origins4, directions4, n, closest, host, instance,
-	              [&](const float *o4, const float *d4, const QueryOutputs &out, uint32_t *inst, void *s) {
-		              traceDevice(closest, o4, d4, n, max_distance, flags, out, s, instanced, inst);
-	              });
+	if (!closest) {  // (occlusion: the flags alone)
+		static_cast<RecordOutputs &>(out) = RecordOutputs();
+		instance = nullptr;
+	}
+	Arrays arrays;
+	arrays.in(origins4, (size_t) n * 16u).in(directions4, (size_t) n * 16u).out(out.hit, n).records(out, n).out(instance, (size_t) n * 4u);
+	staged(where, arrays, [&](void *stream) {
+		const Target to = target(instanced);
+		const Enqueue q = begin(enter(stream), origins4, directions4, n, n, flags, {}, false, to.box);
+		launch_query(dev.deviceScene()->buffers(), dev.params().node_count, to.set, closest, origins4, directions4, q.order, n, max_distance, out,
+		             instance, q.stream);
+		end(q);
+	});
 }
 
 // ---- the instance set (include/rt_hip_instances.h) ----
@@ -440,12 +405,9 @@ void RayQueries::clearInstances() {
 }
 
 bool RayQueries::planInstancesOnDevice(const float *world_device, uint32_t n, void *stream) {
-	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
-	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
-	// (the queries before it: one of them may still read the allocation the plan before last left as the spare one; an
+	// (behind the queries before it: one of them may still read the allocation the plan before last left as the spare one; an
 	// update on its way to node 0 is waited for too)
-	if (timed)
-		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	hipStream_t s = (hipStream_t) enter(stream);
 	const std::shared_ptr<const DeviceScene> scene = dev.sceneReady() ? dev.deviceScene() : nullptr;
 	const bool rooted = scene && scene->nodeCount() > 0;
 	if (rooted && s != (hipStream_t) dev.streamHandle()) {  // (node 0 is read: behind whatever the renderer's stream still does to it)
@@ -543,9 +505,9 @@ void RayQueries::buildInstancesHost(const float *world_from_object, uint32_t n) 
 		clearInstances();
 		return;
 	}
-	Staged p[1] = { input(world_from_object, (size_t) n * 12u * sizeof(float)) };
-	void *s = stageIn(p, 1);
-	buildInstancesDevice((const float *) p[0].device, n, s);  // (waits for its stream: the staging buffer is free again)
+	Arrays arrays;
+	arrays.in(world_from_object, (size_t) n * 12u * sizeof(float));
+	staged(Where::hostMemory(), arrays, [&](void *s) { buildInstancesDevice(world_from_object, n, s); });
 }
 
 void RayQueries::instanceWorld(float *out) {
@@ -596,59 +558,44 @@ float RayQueries::lastInstanceBuildMs() {
 	return last_inst_ms;
 }
 
-void RayQueries::segmentsDevice(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
-                                const QueryOutputs &out, void *stream, bool instanced, uint32_t *instance) {
+void RayQueries::segments(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+                          QueryOutputs out, Where where, bool instanced, uint32_t *instance) {
 	requireQuery(instanced, "segment query");
 	if (n == 0)
 		return;
-	const Target to = target(instanced);
-	const Enqueue q = begin(stream, from4, to4, n, n, flags, {}, true, to.box);
-	launch_segments(dev.deviceScene()->buffers(), dev.params().node_count, to.set, closest, from4, to4, q.order, n, t_lo, t_hi, out,
-	                closest ? instance : nullptr, q.stream);
-	end(q);
+	if (!closest) {  // (occlusion: the flags alone)
+		static_cast<RecordOutputs &>(out) = RecordOutputs();
+		instance = nullptr;
+	}
+	Arrays arrays;
+	arrays.in(from4, (size_t) n * 16u).in(to4, (size_t) n * 16u).out(out.hit, n).records(out, n).out(instance, (size_t) n * 4u);
+	staged(where, arrays, [&](void *stream) {
+		const Target to = target(instanced);
+		const Enqueue q = begin(enter(stream), from4, to4, n, n, flags, {}, true, to.box);
+		launch_segments(dev.deviceScene()->buffers(), dev.params().node_count, to.set, closest, from4, to4, q.order, n, t_lo, t_hi, out, instance,
+		                q.stream);
+		end(q);
+	});
 }
 
-void RayQueries::segmentsHost(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
-                              const QueryOutputs &host, bool instanced, uint32_t *instance) {
-	requireQuery(instanced, "segment query");
-	if (n == 0)
-		return;
-	stagedRecords(from4, to4, n, closest, host, instance,
-	              [&](const float *a4, const float *b4, const QueryOutputs &out, uint32_t *inst, void *s) {
-		              segmentsDevice(closest, a4, b4, n, t_lo, t_hi, flags, out, s, instanced, inst);
-	              });
-}
-
-void RayQueries::visibilityDevice(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi,
-                                  uint32_t flags, const VisibilityOutputs &out, void *stream, bool instanced) {
+void RayQueries::visibility(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
+                            VisibilityOutputs out, Where where, bool instanced) {
 	requireQuery(instanced, "visibility query");
 	if (np == 0 || nt == 0 || !out.any())
 		return;
-	const Target to = target(instanced);
 	const size_t row_bytes = (size_t) visibilityWords(nt) * sizeof(uint32_t);
-	// the POINTS are ordered, by position alone, from RT_QUERY_SORT_MIN of them on; the rows are the caller's, or scratch where
-	// only the counts are wanted
-	const Enqueue q = begin(stream, points4, nullptr, np, np, flags, { Need{ out.mask ? nullptr : &vis_rows, (size_t) np * row_bytes } }, false,
-	                        to.box);
-	launch_visibility(dev.deviceScene()->buffers(), dev.params().node_count, to.set, points4, np, targets4, nt, q.order, t_lo, t_hi,
-	                  out.mask ? out.mask : (uint32_t *) vis_rows.ptr, out.count, q.stream);
-	end(q);
-}
-
-void RayQueries::visibilityHost(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
-                                const VisibilityOutputs &host, bool instanced) {
-	requireQuery(instanced, "visibility query");
-	if (np == 0 || nt == 0 || !host.any())
-		return;
-	const size_t row_bytes = (size_t) visibilityWords(nt) * sizeof(uint32_t);
-	Staged p[VIS_PIECES] = { input(points4, (size_t) np * 16u), input(targets4, (size_t) nt * 16u), scratch(host.mask, (size_t) np * row_bytes),
-		                     output(host.count, (size_t) np * 4u) };
-	void *s = stageIn(p, VIS_PIECES);
-	VisibilityOutputs out;
-	out.mask = (uint32_t *) p[VIS_ROWS].device;
-	out.count = (uint32_t *) p[VIS_COUNTS].device;
-	visibilityDevice((const float *) p[VIS_POINTS].device, np, (const float *) p[VIS_TARGETS].device, nt, t_lo, t_hi, flags, out, s, instanced);
-	stageOut(p, VIS_PIECES, s);
+	Arrays arrays;  // (host memory: the rows are staged whether they are copied back or not)
+	arrays.in(points4, (size_t) np * 16u).in(targets4, (size_t) nt * 16u).scratch(out.mask, (size_t) np * row_bytes).out(out.count, (size_t) np * 4u);
+	staged(where, arrays, [&](void *stream) {
+		const Target to = target(instanced);
+		// the POINTS are ordered, by position alone, from RT_QUERY_SORT_MIN of them on; the rows are the caller's, or scratch where
+		// only the counts are wanted
+		const Enqueue q = begin(enter(stream), points4, nullptr, np, np, flags, { Need{ out.mask ? nullptr : &vis_rows, (size_t) np * row_bytes } },
+		                        false, to.box);
+		launch_visibility(dev.deviceScene()->buffers(), dev.params().node_count, to.set, points4, np, targets4, nt, q.order, t_lo, t_hi,
+		                  out.mask ? out.mask : (uint32_t *) vis_rows.ptr, out.count, q.stream);
+		end(q);
+	});
 }
 
 // What the closest-point walk may do follows from the scene: where every box holds the triangles beneath it -- an upload the
@@ -657,35 +604,23 @@ void RayQueries::visibilityHost(const float *points4, uint32_t np, const float *
 // coordinates only the device has seen, the word they left (checkCoordinates) decides it once more, in the kernel.
 // `instanced` (include/rt_hip_instance_nearest.h): the same rules decide what the nested walk may do in both of its trees --
 // the top-level boxes are made from the scene's root box and promise what it promises (kernels/instance_nearest.hip.h).
-void RayQueries::nearestDevice(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, void *stream,
-                               bool instanced, uint32_t *instance) {
+void RayQueries::nearest(const float *points4, uint32_t n, float max_distance, uint32_t flags, QueryOutputs out, Where where, bool instanced,
+                         uint32_t *instance) {
 	requireQuery(instanced, "closest-point query");
 	if (n == 0)
 		return;
-	const Target to = target(instanced);
-	const std::shared_ptr<const DeviceScene> scene = dev.deviceScene();
-	uint32_t walk = scene->boxesEnclose() ? 3u : 0u;  // NEAREST_START | NEAREST_PRUNE
-	if (nearest_debug & 1u)
-		walk &= ~1u;
-	if (nearest_debug & 2u)
-		walk = 0u;
-	const bool counting = (nearest_debug & 4u) != 0u;
-	const Enqueue q = begin(stream, points4, nullptr, n, n, flags, { Need{ counting ? &nearest_counts : nullptr, 2u * sizeof(uint64_t) } }, false,
-	                        to.box);
-	launch_nearest(scene->buffers(), scene->nodeCount(), scene->triCount(), to.set, points4, q.order, n, max_distance, walk, out, instance,
-	               flagged.lock() == scene ? coords_flag.ptr : nullptr, counting ? nearest_counts.ptr : nullptr, q.stream);
-	nearest_counted = counting;
-	end(q);
-}
-
-void RayQueries::nearestHost(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &host, bool instanced,
-                             uint32_t *instance) {
-	requireQuery(instanced, "closest-point query");
-	if (n == 0)
-		return;
-	// (the second piece stays empty: the points have no directions)
-	stagedRecords(points4, nullptr, n, true, host, instance, [&](const float *p4, const float *, const QueryOutputs &out, uint32_t *inst, void *s) {
-		nearestDevice(p4, n, max_distance, flags, out, s, instanced, inst);
+	Arrays arrays;
+	arrays.in(points4, (size_t) n * 16u).out(out.hit, n).records(out, n).out(instance, (size_t) n * 4u);
+	staged(where, arrays, [&](void *stream) {
+		const Target to = target(instanced);
+		const std::shared_ptr<const DeviceScene> scene = dev.deviceScene();
+		const bool counting = (nearest_debug & 4u) != 0u;
+		const Enqueue q = begin(enter(stream), points4, nullptr, n, n, flags,
+		                        { Need{ counting ? &nearest_counts : nullptr, 2u * sizeof(uint64_t) } }, false, to.box);
+		launch_nearest(scene->buffers(), scene->nodeCount(), scene->triCount(), to.set, points4, q.order, n, max_distance, nearestWalk(*scene), out,
+		               instance, flagged.lock() == scene ? coords_flag.ptr : nullptr, counting ? nearest_counts.ptr : nullptr, q.stream);
+		nearest_counted = counting;
+		end(q);
 	});
 }
 
@@ -696,7 +631,7 @@ constexpr uint64_t SIGNED_GRID_CHUNK = (uint64_t) 1 << 24;  // voxels per slab o
 }  // namespace
 
 uint32_t RayQueries::nearestWalk(const DeviceScene &scene) const {
-	uint32_t walk = scene.boxesEnclose() ? 3u : 0u;  // NEAREST_START | NEAREST_PRUNE (nearestDevice)
+	uint32_t walk = scene.boxesEnclose() ? 3u : 0u;  // NEAREST_START | NEAREST_PRUNE
 	if (nearest_debug & 1u)
 		walk &= ~1u;
 	if (nearest_debug & 2u)
@@ -769,10 +704,7 @@ const void *RayQueries::ensureSignTable(void *stream) {
 
 void RayQueries::prepareSigned(void *stream) {
 	requireScene("signed distance query");
-	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
-	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
-	if (timed)
-		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	hipStream_t s = (hipStream_t) enter(stream);
 	(void) ensureSignTable(s);
 	OCRT_HIP(hipStreamSynchronize(s));
 }
@@ -796,41 +728,22 @@ void RayQueries::downloadSignTable(void *out) {
 		OCRT_HIP(hipMemcpy(out, sign_table.ptr, bytes, hipMemcpyDeviceToHost));
 }
 
-void RayQueries::signedDevice(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, uint8_t *feature,
-                              float *pseudonormal4, void *stream) {
+void RayQueries::signedDistance(const float *points4, uint32_t n, float max_distance, uint32_t flags, QueryOutputs out, uint8_t *feature,
+                                float *pseudonormal4, Where where) {
 	requireScene("signed distance query");
 	if (n == 0)
 		return;
-	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
-	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
-	if (timed)
-		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
-	const void *table = ensureSignTable(s);  // (ahead of ev_start where prepareSigned has been called; else part of this query's time)
-	const std::shared_ptr<const DeviceScene> scene = dev.deviceScene();
-	const Enqueue q = begin(s, points4, nullptr, n, n, flags, {}, false, nullptr);
-	launch_signed(scene->buffers(), scene->nodeCount(), scene->triCount(), points4, q.order, n, max_distance, nearestWalk(*scene), out, feature,
-	              pseudonormal4, table, flagged.lock() == scene ? coords_flag.ptr : nullptr, q.stream);
-	end(q);
-}
-
-void RayQueries::signedHost(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &host, uint8_t *feature,
-                            float *pseudonormal4) {
-	requireScene("signed distance query");
-	if (n == 0)
-		return;
-	enum { POINTS, HIT, RECORDS, FEATURE = RECORDS + 5, PSEUDONORMAL, PIECES };
-	Staged p[PIECES];
-	p[POINTS] = input(points4, (size_t) n * 16u);
-	p[HIT] = output(host.hit, n);
-	recordPieces(p + RECORDS, host, n);
-	p[FEATURE] = output(feature, n);
-	p[PSEUDONORMAL] = output(pseudonormal4, (size_t) n * 16u);
-	void *s = stageIn(p, PIECES);
-	QueryOutputs out;
-	out.hit = (unsigned char *) p[HIT].device;
-	recordDevice(p + RECORDS, out);
-	signedDevice((const float *) p[POINTS].device, n, max_distance, flags, out, (uint8_t *) p[FEATURE].device, (float *) p[PSEUDONORMAL].device, s);
-	stageOut(p, PIECES, s);
+	Arrays arrays;
+	arrays.in(points4, (size_t) n * 16u).out(out.hit, n).records(out, n).out(feature, n).out(pseudonormal4, (size_t) n * 16u);
+	staged(where, arrays, [&](void *stream) {
+		void *s = enter(stream);
+		const void *table = ensureSignTable(s);  // (made here unless prepareSigned has been called: ahead of begin() either way)
+		const std::shared_ptr<const DeviceScene> scene = dev.deviceScene();
+		const Enqueue q = begin(s, points4, nullptr, n, n, flags, {}, false, nullptr);
+		launch_signed(scene->buffers(), scene->nodeCount(), scene->triCount(), points4, q.order, n, max_distance, nearestWalk(*scene), out, feature,
+		              pseudonormal4, table, flagged.lock() == scene ? coords_flag.ptr : nullptr, q.stream);
+		end(q);
+	});
 }
 
 void RayQueries::signedGridDevice(const float origin[3], const float spacing[3], const uint32_t dims[3], float max_distance, float *distance,
@@ -838,10 +751,7 @@ void RayQueries::signedGridDevice(const float origin[3], const float spacing[3],
 	requireScene("signed distance query");
 	if ((uint64_t) dims[0] * dims[1] * dims[2] == 0u)
 		return;
-	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
-	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
-	if (timed)
-		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	void *s = enter(stream);
 	const void *table = ensureSignTable(s);
 	const std::shared_ptr<const DeviceScene> scene = dev.deviceScene();
 	const Enqueue q = begin(s, nullptr, nullptr, 0u, 0u, QUERY_NO_SORT, {}, false, nullptr);  // (no points, no order, no sort)
@@ -862,10 +772,12 @@ void RayQueries::signedGridHost(const float origin[3], const float spacing[3], c
 	for (uint32_t first = 0; first < dims[2]; first += per_slab) {
 		const uint32_t slab[3] = { dims[0], dims[1], std::min(per_slab, dims[2] - first) };
 		const size_t voxels = (size_t) (slice * slab[2]), offset = (size_t) (slice * first);
-		Staged p[2] = { output(distance ? distance + offset : nullptr, voxels * 4u), output(leaf ? leaf + offset : nullptr, voxels * 4u) };
-		void *s = stageIn(p, 2);
-		signedGridDevice(origin, spacing, slab, max_distance, (float *) p[0].device, (uint32_t *) p[1].device, s, first);
-		stageOut(p, 2, s);
+		float *slab_distance = distance ? distance + offset : nullptr;
+		uint32_t *slab_leaf = leaf ? leaf + offset : nullptr;
+		Arrays arrays;
+		arrays.out(slab_distance, voxels * 4u).out(slab_leaf, voxels * 4u);
+		staged(Where::hostMemory(), arrays,
+		       [&](void *s) { signedGridDevice(origin, spacing, slab, max_distance, slab_distance, slab_leaf, s, first); });
 		ms += lastMs();
 	}
 	last_ms = ms;  // (every slab's events have been read: the call's time is their sum)
@@ -896,43 +808,28 @@ void RayQueries::checkCoordinates(const std::shared_ptr<const DeviceScene> &scen
 	flagged = scene;
 }
 
-void RayQueries::multihitDevice(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k,
-                                uint32_t flags, const MultiHitOutputs &out, void *stream, bool instanced, uint32_t *instance) {
-	if (instanced)
-		requireInstances("instanced multi-hit query");
-	requireSlots(k);
-	// without a slot array the lists are not wanted: the count-only walk
-	const uint32_t slots = out.anySlot() || (instanced && instance) ? k : 0u;
-	if (n == 0 || (slots == 0 && !out.count))
-		return;
-	const Target to = target(instanced);
-	const Enqueue q = begin(stream, origins4, directions4, n, n, flags,
-	                        { Need{ slots ? &list : nullptr, (size_t) n * slots * (instanced ? 12u : 8u) } }, false, to.box);
-	launch_multihit(dev.deviceScene()->buffers(), dev.params().node_count, to.set, origins4, directions4, q.order, n, max_distance, slots,
-	                list.ptr, out, instanced ? instance : nullptr, q.stream);
-	end(q);
-}
-
-void RayQueries::multihitHost(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
-                              const MultiHitOutputs &host, bool instanced, uint32_t *instance) {
+void RayQueries::multihit(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
+                          MultiHitOutputs out, Where where, bool instanced, uint32_t *instance) {
 	if (instanced)
 		requireInstances("instanced multi-hit query");
 	requireSlots(k);
 	if (!instanced)
 		instance = nullptr;
-	if (n == 0 || (!host.count && !host.anySlot() && !instance))
+	// without a slot array the lists are not wanted: the count-only walk
+	const uint32_t slots = out.anySlot() || instance ? k : 0u;
+	if (n == 0 || (slots == 0 && !out.count))
 		return;
-	Staged p[INST_PIECES] = { input(origins4, (size_t) n * 16u), input(directions4, (size_t) n * 16u),
-		                       output(host.count, (size_t) n * 4u) };
-	recordPieces(p + RAY_RECORDS, host, (size_t) n * k);
-	p[INST_INDEX] = output(instance, (size_t) n * k * 4u);
-	void *s = stageIn(p, INST_PIECES);
-	MultiHitOutputs out;
-	out.count = (uint32_t *) p[RAY_FIRST].device;
-	recordDevice(p + RAY_RECORDS, out);
-	multihitDevice((const float *) p[RAY_ORIGINS].device, (const float *) p[RAY_DIRECTIONS].device, n, max_distance, k, flags, out, s, instanced,
-	               (uint32_t *) p[INST_INDEX].device);
-	stageOut(p, INST_PIECES, s);
+	Arrays arrays;
+	arrays.in(origins4, (size_t) n * 16u).in(directions4, (size_t) n * 16u).out(out.count, (size_t) n * 4u).records(out, (size_t) n * k);
+	arrays.out(instance, (size_t) n * k * 4u);
+	staged(where, arrays, [&](void *stream) {
+		const Target to = target(instanced);
+		const Enqueue q = begin(enter(stream), origins4, directions4, n, n, flags,
+		                        { Need{ slots ? &list : nullptr, (size_t) n * slots * (instanced ? 12u : 8u) } }, false, to.box);
+		launch_multihit(dev.deviceScene()->buffers(), dev.params().node_count, to.set, origins4, directions4, q.order, n, max_distance, slots,
+		                list.ptr, out, instance, q.stream);
+		end(q);
+	});
 }
 
 uint32_t RayQueries::aoRaysPerPoint(const DeviceRenderer &renderer) {
@@ -943,20 +840,24 @@ uint32_t RayQueries::aoRaysPerPoint(const DeviceRenderer &renderer) {
 }
 uint32_t RayQueries::aoDivisor(const DeviceRenderer &renderer) { return aoRaysPerPoint(renderer) ? renderer.params().ao_divisor : 0u; }
 
-void RayQueries::aoDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
-                          uint32_t *occluded, void *stream, bool instanced) {
+void RayQueries::ao(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
+                    uint32_t *occluded, Where where, bool instanced) {
 	if (instanced)
 		requireInstances("instanced ambient-occlusion query");
 	requireAo();
 	if (n == 0 || (!ao && !occluded))
 		return;
-	const Target to = target(instanced);
-	const KernelParams &kp = dev.params();
-	// the POINTS are ordered (key: point and normal) from as many on as make RT_QUERY_SORT_MIN rays
-	const Enqueue q = begin(stream, points4, normals4, n, (uint64_t) n * kp.ao_dirs, flags,
-	                        { Need{ occluded ? nullptr : &ao_hits, (size_t) n * sizeof(uint32_t) } }, false, to.box);
-	aoEnqueue(q, points4, normals4, seeds, q.order, n, occluded ? occluded : (uint32_t *) ao_hits.ptr, ao, instanced);
-	end(q);
+	Arrays arrays;  // (host memory: the counts are staged whether they are copied back or not: the kernel counts into them)
+	arrays.in(points4, (size_t) n * 16u).in(normals4, (size_t) n * 16u).scratch(occluded, (size_t) n * 4u).in(seeds, (size_t) n * 4u);
+	arrays.out(ao, (size_t) n * 4u);
+	staged(where, arrays, [&](void *stream) {
+		const Target to = target(instanced);
+		// the POINTS are ordered (key: point and normal) from as many on as make RT_QUERY_SORT_MIN rays
+		const Enqueue q = begin(enter(stream), points4, normals4, n, (uint64_t) n * dev.params().ao_dirs, flags,
+		                        { Need{ occluded ? nullptr : &ao_hits, (size_t) n * sizeof(uint32_t) } }, false, to.box);
+		aoEnqueue(q, points4, normals4, seeds, q.order, n, occluded ? occluded : (uint32_t *) ao_hits.ptr, ao, instanced);
+		end(q);
+	});
 }
 
 void RayQueries::aoEnqueue(const Enqueue &q, const float *points4, const float *normals4, const uint32_t *seeds, const void *order,
@@ -966,85 +867,44 @@ void RayQueries::aoEnqueue(const Enqueue &q, const float *points4, const float *
 	                kp.ao_max_distance, points4, normals4, seeds, order, n, count, ao, q.stream);
 }
 
-void RayQueries::aoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
-                        uint32_t *occluded, bool instanced) {
-	if (instanced)
-		requireInstances("instanced ambient-occlusion query");
-	requireAo();
-	if (n == 0 || (!ao && !occluded))
-		return;
-	// (the counts are staged whether they are copied back or not: the kernel counts into them)
-	Staged p[AO_PIECES] = { input(points4, (size_t) n * 16u), input(normals4, (size_t) n * 16u), scratch(occluded, (size_t) n * 4u),
-		                    input(seeds, (size_t) n * 4u), output(ao, (size_t) n * 4u) };
-	void *s = stageIn(p, AO_PIECES);
-	aoDevice((const float *) p[AO_POINTS].device, (const float *) p[AO_NORMALS].device, (const uint32_t *) p[AO_SEEDS].device, n, flags,
-	         (float *) p[AO_VALUES].device, (uint32_t *) p[AO_COUNTS].device, s, instanced);
-	stageOut(p, AO_PIECES, s);
-}
-
-void RayQueries::directionalDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
-                                   const DirectionalOutputs &out, void *stream, bool instanced) {
+void RayQueries::directional(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
+                             DirectionalOutputs out, Where where, bool instanced) {
 	if (instanced)
 		requireInstances("instanced directional occlusion query");
 	requireAo();
 	if (n == 0 || !out.any())
 		return;
-	const Target to = target(instanced);
-	const KernelParams &kp = dev.params();
 	const size_t row_bytes = (size_t) aoMaskWords(dev) * sizeof(uint32_t);
-	// the POINTS are ordered as for aoDevice; the rows are the caller's, or scratch where only what is made of them is wanted
-	const Enqueue q = begin(stream, points4, normals4, n, (uint64_t) n * kp.ao_dirs, flags,
-	                        { Need{ out.mask ? nullptr : &ao_rows, (size_t) n * row_bytes } }, false, to.box);
-	launch_ao_directional(dev.deviceScene()->buffers(), kp.node_count, to.set, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4,
-	                      normals4, seeds, q.order, n, out.mask ? out.mask : (uint32_t *) ao_rows.ptr, out.occluded, out.ao, out.bent,
-	                      q.stream);
-	end(q);
+	Arrays arrays;  // (host memory: the rows are staged whether they are copied back or not)
+	arrays.in(points4, (size_t) n * 16u).in(normals4, (size_t) n * 16u).in(seeds, (size_t) n * 4u).scratch(out.mask, (size_t) n * row_bytes);
+	arrays.out(out.occluded, (size_t) n * 4u).out(out.ao, (size_t) n * 4u).out(out.bent, (size_t) n * 12u);
+	staged(where, arrays, [&](void *stream) {
+		const Target to = target(instanced);
+		const KernelParams &kp = dev.params();
+		// the POINTS are ordered as for ao; the rows are the caller's, or scratch where only what is made of them is wanted
+		const Enqueue q = begin(enter(stream), points4, normals4, n, (uint64_t) n * kp.ao_dirs, flags,
+		                        { Need{ out.mask ? nullptr : &ao_rows, (size_t) n * row_bytes } }, false, to.box);
+		launch_ao_directional(dev.deviceScene()->buffers(), kp.node_count, to.set, kp.ao_mode, kp.ao_dirs, kp.ao_divisor, kp.ao_max_distance, points4,
+		                      normals4, seeds, q.order, n, out.mask ? out.mask : (uint32_t *) ao_rows.ptr, out.occluded, out.ao, out.bent,
+		                      q.stream);
+		end(q);
+	});
 }
 
-void RayQueries::directionalHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
-                                 const DirectionalOutputs &host, bool instanced) {
-	if (instanced)
-		requireInstances("instanced directional occlusion query");
-	requireAo();
-	if (n == 0 || !host.any())
-		return;
-	const size_t row_bytes = (size_t) aoMaskWords(dev) * sizeof(uint32_t);
-	Staged p[DIR_PIECES] = { input(points4, (size_t) n * 16u), input(normals4, (size_t) n * 16u), input(seeds, (size_t) n * 4u),
-		                     scratch(host.mask, (size_t) n * row_bytes), output(host.occluded, (size_t) n * 4u),
-		                     output(host.ao, (size_t) n * 4u), output(host.bent, (size_t) n * 12u) };
-	void *s = stageIn(p, DIR_PIECES);
-	DirectionalOutputs out;
-	out.mask = (uint32_t *) p[DIR_ROWS].device;
-	out.occluded = (uint32_t *) p[DIR_COUNTS].device;
-	out.ao = (float *) p[DIR_VALUES].device;
-	out.bent = (float *) p[DIR_BENT].device;
-	directionalDevice((const float *) p[DIR_POINTS].device, (const float *) p[DIR_NORMALS].device, (const uint32_t *) p[DIR_SEEDS].device, n,
-	                  flags, out, s, instanced);
-	stageOut(p, DIR_PIECES, s);
-}
-
-void RayQueries::aoRaysDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4,
-                              float *directions4, void *stream) {
+void RayQueries::aoRays(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4, float *directions4,
+                        Where where) {
 	requireAo();
 	if (n == 0 || (!origins4 && !directions4))
 		return;
 	const KernelParams &kp = dev.params();
-	const Enqueue q = begin(stream, nullptr, nullptr, n, (uint64_t) n * kp.ao_dirs, QUERY_NO_SORT);  // (nothing is walked: no order)
-	launch_ao_rays(dev.deviceScene()->buffers(), kp.ao_mode, kp.ao_dirs, points4, normals4, seeds, n, origins4, directions4, q.stream);
-	end(q);
-}
-
-void RayQueries::aoRaysHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4,
-                            float *directions4) {
-	requireAo();
-	if (n == 0 || (!origins4 && !directions4))
-		return;
-	Staged p[AORAY_PIECES] = { input(points4, (size_t) n * 16u), input(normals4, (size_t) n * 16u), input(seeds, (size_t) n * 4u),
-		                       output(origins4, (size_t) n * 16u), output(directions4, (size_t) n * aoRaysPerPoint(dev) * 16u) };
-	void *s = stageIn(p, AORAY_PIECES);
-	aoRaysDevice((const float *) p[AORAY_POINTS].device, (const float *) p[AORAY_NORMALS].device, (const uint32_t *) p[AORAY_SEEDS].device, n,
-	             (float *) p[AORAY_ORIGINS].device, (float *) p[AORAY_DIRECTIONS].device, s);
-	stageOut(p, AORAY_PIECES, s);
+	Arrays arrays;
+	arrays.in(points4, (size_t) n * 16u).in(normals4, (size_t) n * 16u).in(seeds, (size_t) n * 4u).out(origins4, (size_t) n * 16u);
+	arrays.out(directions4, (size_t) n * kp.ao_dirs * 16u);
+	staged(where, arrays, [&](void *stream) {
+		const Enqueue q = begin(enter(stream), nullptr, nullptr, n, (uint64_t) n * kp.ao_dirs, QUERY_NO_SORT);  // (nothing is walked: no order)
+		launch_ao_rays(dev.deviceScene()->buffers(), kp.ao_mode, kp.ao_dirs, points4, normals4, seeds, n, origins4, directions4, q.stream);
+		end(q);
+	});
 }
 
 // What a layers call may ask of this host; returns whether it needs the ambient-occlusion step (`ao`, or `value` on a host
@@ -1131,34 +991,24 @@ uint32_t RayQueries::castChunk(const Enqueue &q, const ChunkScratch &at, bool li
 	return entries;
 }
 
-void RayQueries::layersDevice(const LayerOutputs &out, void *stream) {
+void RayQueries::layers(LayerOutputs out, Where where) {
 	const bool with_ao = requireLayers(out);
 	const KernelParams &kp = dev.params();
 	const uint32_t n = kp.width * kp.height;
 	if (n == 0 || !out.any())
 		return;
-	// one view, the host's own pose: with the ambient-occlusion step every sub-pixel is an entry of it -- nothing is
-	// listed, nothing read back, the call only enqueues
-	const ChunkScratch at = chunkScratch(0u, with_ao ? n : 0u, false, 0u);
-	const Enqueue q = begin(stream, nullptr, nullptr, n, n, QUERY_NO_SORT,
-	                        { Need{ with_ao ? &views : nullptr, at.bytes }, Need{ with_ao ? &ao_hits : nullptr, (size_t) n * sizeof(uint32_t) } });
-	(void) castChunk(q, at, false, nullptr, 1u, out, out.value, with_ao);
-	end(q);
-}
-
-void RayQueries::layersHost(const LayerOutputs &host) {
-	requireLayers(host);
-	const KernelParams &kp = dev.params();
-	const size_t n = (size_t) kp.width * kp.height;
-	if (n == 0 || !host.any())
-		return;
-	Staged p[LAYER_PIECES];
-	layerPieces(p, host, n);
-	void *s = stageIn(p, LAYER_PIECES);
-	LayerOutputs out;
-	layerDevice(p, out);
-	layersDevice(out, s);
-	stageOut(p, LAYER_PIECES, s);
+	Arrays arrays;
+	arrays.layers(out, n);
+	staged(where, arrays, [&](void *stream) {
+		// one view, the host's own pose: with the ambient-occlusion step every sub-pixel is an entry of it -- nothing is
+		// listed, nothing read back, the call only enqueues
+		const ChunkScratch at = chunkScratch(0u, with_ao ? n : 0u, false, 0u);
+		const Enqueue q =
+		    begin(enter(stream), nullptr, nullptr, n, n, QUERY_NO_SORT,
+		          { Need{ with_ao ? &views : nullptr, at.bytes }, Need{ with_ao ? &ao_hits : nullptr, (size_t) n * sizeof(uint32_t) } });
+		(void) castChunk(q, at, false, nullptr, 1u, out, out.value, with_ao);
+		end(q);
+	});
 }
 
 // What a views call may ask of this host: what a layers call may, with the image counted among the layers made of `value`.
@@ -1244,7 +1094,7 @@ void RayQueries::viewsCall(bool instanced, const CameraPose *cameras, uint32_t v
 	// float images where the caller has no `value` array for them
 	const bool own_product = out.image && !out.value;
 	const ChunkScratch at = chunkScratch(per_chunk, with_ao ? most : 0u, true, own_product ? most : 0u);
-	const Enqueue q = begin(stream, nullptr, nullptr, n, n, QUERY_NO_SORT,
+	const Enqueue q = begin(enter(stream), nullptr, nullptr, n, n, QUERY_NO_SORT,
 	                        { Need{ &this->views, at.bytes }, Need{ with_ao ? &ao_hits : nullptr, most * sizeof(uint32_t) } });
 	char *const base = (char *) this->views.ptr;
 	hipStream_t s = (hipStream_t) q.stream;
@@ -1280,17 +1130,11 @@ void RayQueries::viewsStaged(bool instanced, const CameraPose *cameras, uint32_t
 	float ms = 0.0f;
 	for (uint32_t first = 0; first < views; first += per_chunk) {
 		const size_t chunk = std::min(per_chunk, views - first), m = chunk * n;
-		const ViewOutputs to = viewsFrom(host, first, kp, image_bytes);
-		Staged p[INSTANCE_VIEW_PIECES];  // (the last piece: the instanced form's alone)
-		layerPieces(p, to, m);
-		p[VIEW_IMAGE] = output(to.image, chunk * image_bytes);
-		p[VIEW_INSTANCE] = output(instance ? instance + (size_t) first * n : nullptr, m * 4u);
-		void *s = stageIn(p, INSTANCE_VIEW_PIECES);
-		ViewOutputs out;
-		layerDevice(p, out);
-		out.image = (unsigned char *) p[VIEW_IMAGE].device;
-		viewsCall(instanced, cameras + first, (uint32_t) chunk, out, (uint32_t *) p[VIEW_INSTANCE].device, s);
-		stageOut(p, INSTANCE_VIEW_PIECES, s);
+		ViewOutputs to = viewsFrom(host, first, kp, image_bytes);
+		uint32_t *to_instance = instance ? instance + (size_t) first * n : nullptr;  // (the instanced form's alone)
+		Arrays arrays;
+		arrays.layers(to, m).out(to.image, chunk * image_bytes).out(to_instance, m * 4u);
+		staged(Where::hostMemory(), arrays, [&](void *s) { viewsCall(instanced, cameras + first, (uint32_t) chunk, to, to_instance, s); });
 		ms += lastMs();
 		done.views += last_views.views;
 		done.chunks += last_views.chunks;
@@ -1313,10 +1157,7 @@ void RayQueries::updateDevice(const float *vertices4, const float *vnormals4, ui
 		throw std::invalid_argument("vertex update: the number of vertices differs from the upload's (the topology stays: every position is replaced)");
 	if (!vertices4)
 		throw std::invalid_argument("vertex update: null vertex array");
-	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
-	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
-	if (timed)
-		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	hipStream_t s = (hipStream_t) enter(stream);
 	if (s != (hipStream_t) dev.streamHandle()) {
 		OCRT_HIP(hipEventRecord((hipEvent_t) ev_frames, (hipStream_t) dev.streamHandle()));
 		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_frames, 0));
@@ -1353,10 +1194,9 @@ void RayQueries::updateHost(const float *vertices4, const float *vnormals4, uint
 				throw std::invalid_argument("vertex update: a coordinate is not finite or exceeds 1e37 (nothing was written)");
 	if (num_vertices == 0)
 		return;
-	Staged p[2] = { input(vertices4, (size_t) num_vertices * 16u), input(vnormals4, (size_t) num_vertices * 16u) };
-	void *s = stageIn(p, 2);
-	updateDevice((const float *) p[0].device, (const float *) p[1].device, num_vertices, s);
-	stageOut(p, 2, s);
+	Arrays arrays;
+	arrays.in(vertices4, (size_t) num_vertices * 16u).in(vnormals4, (size_t) num_vertices * 16u);
+	staged(Where::hostMemory(), arrays, [&](void *s) { updateDevice(vertices4, vnormals4, num_vertices, s); });
 }
 
 float RayQueries::lastUpdateMs() {
@@ -1384,10 +1224,7 @@ void RayQueries::buildDevice(const float *vertices4, const float *vnormals4, uin
 		throw std::invalid_argument("build: no faces, or no vertices");
 	if (num_faces >= (1u << 25))
 		throw std::invalid_argument("build: scene too large for 32-bit device offsets");
-	OCRT_HIP(hipSetDevice(dev.deviceIndex()));
-	hipStream_t s = (hipStream_t) (stream ? stream : dev.streamHandle());
-	if (timed)
-		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_stop, 0));
+	hipStream_t s = (hipStream_t) enter(stream);
 	if (s != (hipStream_t) dev.streamHandle()) {
 		OCRT_HIP(hipEventRecord((hipEvent_t) ev_frames, (hipStream_t) dev.streamHandle()));
 		OCRT_HIP(hipStreamWaitEvent(s, (hipEvent_t) ev_frames, 0));
@@ -1423,11 +1260,9 @@ void RayQueries::buildHost(const float *vertices4, const float *vnormals4, uint3
 		for (unsigned k = 0; k < 3; ++k)
 			if (!(std::fabs(vertices4[4 * i + k]) <= 1.0e37f))  // (false for a NaN too)
 				throw std::invalid_argument("build: a coordinate is not finite or exceeds 1e37 (nothing was written)");
-	Staged p[3] = { input(vertices4, (size_t) num_vertices * 16u), input(vnormals4, (size_t) num_vertices * 16u),
-		            input(faces, (size_t) num_faces * 12u) };
-	void *s = stageIn(p, 3);
-	buildDevice((const float *) p[0].device, (const float *) p[1].device, num_vertices, (const uint32_t *) p[2].device, num_faces, s);
-	stageOut(p, 3, s);
+	Arrays arrays;
+	arrays.in(vertices4, (size_t) num_vertices * 16u).in(vnormals4, (size_t) num_vertices * 16u).in(faces, (size_t) num_faces * 12u);
+	staged(Where::hostMemory(), arrays, [&](void *s) { buildDevice(vertices4, vnormals4, num_vertices, faces, num_faces, s); });
 }
 
 void RayQueries::lastBuildTimes(float ms[3]) {

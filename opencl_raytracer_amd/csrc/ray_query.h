@@ -1,11 +1,8 @@
-// ray_query.h -- ray queries, multi-hit queries, ambient-occlusion queries, frame layers and multi-view rendering on a render
-// host's uploaded scene (include/rt_hip_query.h, include/rt_hip_multihit.h, include/rt_hip_ao.h, include/rt_hip_directional.h,
-// include/rt_hip_layers.h, include/rt_hip_views.h, include/rt_hip_segment.h; kernels/query.hip.h, kernels/segment.hip.h, kernels/multihit.hip.h, kernels/ao_query.hip.h,
-// kernels/directional.hip.h, kernels/layers.hip.h, kernels/views.hip.h); instanced ray queries (include/rt_hip_instances.h,
-// kernels/instances.hip.h, instances.h); instanced ambient occlusion and views (include/rt_hip_instance_views.h,
-// kernels/instance_views.hip.h); instanced segment queries (include/rt_hip_instance_segments.h,
-// kernels/instance_segments.hip.h); instanced multi-hit and directional occlusion queries (include/rt_hip_instance_multihit.h,
-// include/rt_hip_instance_directional.h, kernels/instance_multihit.hip.h, kernels/instance_directional.hip.h).
+// ray_query.h -- RayQueries: everything a render host answers about its uploaded scene beyond its own frames.  One
+// method per query family (rays, segments, visibility masks, closest and signed points, multi-hit, ambient and
+// directional occlusion, the rays of a point, frame layers), each for arrays in device memory or in host memory
+// (Where); multi-view rendering; the instance set the `instanced` forms are cast against; vertex updates and
+// device-side builds of the renderer's scene.  The C contracts are include/rt_hip_*.h, the kernels kernels/*.hip.h.
 #pragma once
 #include <cstdint>
 #include <initializer_list>
@@ -29,42 +26,38 @@ class RayQueries {
 		RayQueries(const RayQueries &) = delete;
 		RayQueries &operator=(const RayQueries &) = delete;
 
-		// Rays, segments, visibility masks and ambient-occlusion points are cast against the uploaded scene or -- `instanced`
-		// -- in world space against the host's instance set (setInstances below; include/rt_hip_instances.h,
+		// Where a call's arrays live: device memory, the call enqueued on `stream` (null: the renderer's) -- or host memory,
+		// the call blocking: the arrays go through the staging buffer on the renderer's own stream (staged(), below).
+		struct Where {
+			bool host;
+			void *stream;
+			static Where deviceMemory(void *stream) { return Where{ false, stream }; }
+			static Where hostMemory() { return Where{ true, nullptr }; }
+		};
+		// Rays, segments, visibility masks, points and ambient-occlusion points are cast against the uploaded scene or --
+		// `instanced` -- in world space against the host's instance set (setInstances below; include/rt_hip_instances.h,
 		// rt_hip_instance_segments.h, rt_hip_instance_views.h): the family's own arguments and rules, the sort keyed over the
 		// top-level root box, `instance` (or null) beside a closest form's record.  std::logic_error without a set; its tree
 		// is made again first if the scene changed.
-		// Device memory, enqueued on `stream` (null: the renderer's); `closest` false: occlusion into out.hit alone.
-		void traceDevice(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance,
-		                 uint32_t flags, const QueryOutputs &out, void *stream, bool instanced = false, uint32_t *instance = nullptr);
-		// Host memory, blocking: the rays go through the staging buffers on the renderer's stream.
-		void traceHost(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
-		               const QueryOutputs &out, bool instanced = false, uint32_t *instance = nullptr);
-		// Multi-hit queries (include/rt_hip_multihit.h): the count of accepted triangles per ray and the first k of them.
-		// Device memory, enqueued on `stream` (null: the renderer's); k <= RT_MULTIHIT_MAX_K, 0 = the count alone.
-		// `instanced` (include/rt_hip_instance_multihit.h): the (instance, triangle) pairs among the posed copies, `instance`
-		// [n * k] (or null) beside the slot arrays.
-		void multihitDevice(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
-		                    const MultiHitOutputs &out, void *stream, bool instanced = false, uint32_t *instance = nullptr);
-		// Host memory, blocking.
-		void multihitHost(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
-		                  const MultiHitOutputs &out, bool instanced = false, uint32_t *instance = nullptr);
+		// Ray queries (include/rt_hip_query.h); `closest` false: occlusion into out.hit alone.
+		void trace(bool closest, const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t flags,
+		           QueryOutputs out, Where where, bool instanced = false, uint32_t *instance = nullptr);
+		// Multi-hit queries (include/rt_hip_multihit.h): the count of accepted triangles per ray and the first k of them;
+		// k <= RT_MULTIHIT_MAX_K, 0 = the count alone.  `instanced` (include/rt_hip_instance_multihit.h): the (instance,
+		// triangle) pairs among the posed copies, `instance` [n * k] (or null) beside the slot arrays; ignored on a plain call.
+		void multihit(const float *origins4, const float *directions4, uint32_t n, float max_distance, uint32_t k, uint32_t flags,
+		              MultiHitOutputs out, Where where, bool instanced = false, uint32_t *instance = nullptr);
 		// Closest-point queries (include/rt_hip_nearest.h): the nearest point of the surface for each of n points, the record
-		// of a closest hit (out.hit: `found`).  Device memory, enqueued on `stream` (null: the renderer's).
-		// `instanced` (include/rt_hip_instance_nearest.h): the nearest point among the posed copies, in world space.
-		void nearestDevice(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, void *stream,
-		                   bool instanced = false, uint32_t *instance = nullptr);
-		// Host memory, blocking.
-		void nearestHost(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, bool instanced = false,
-		                 uint32_t *instance = nullptr);
-		// Signed distance queries (include/rt_hip_signed.h): nearestDevice's walk and rules, the distance signed by the
+		// of a closest hit (out.hit: `found`).  `instanced` (include/rt_hip_instance_nearest.h): the nearest point among the
+		// posed copies, in world space.
+		void nearest(const float *points4, uint32_t n, float max_distance, uint32_t flags, QueryOutputs out, Where where,
+		             bool instanced = false, uint32_t *instance = nullptr);
+		// Signed distance queries (include/rt_hip_signed.h): nearest's walk and rules, the distance signed by the
 		// pseudonormal of the feature the nearest point lies on, out of the sign table -- made by the first of these calls
 		// after an upload or a build (prepareSigned: ahead of time), its sums redone after an update.  `feature` (n bytes),
 		// `pseudonormal4` (float4[n]): outputs beside the record's, either may be null.
-		void signedDevice(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, uint8_t *feature,
-		                  float *pseudonormal4, void *stream);
-		void signedHost(const float *points4, uint32_t n, float max_distance, uint32_t flags, const QueryOutputs &out, uint8_t *feature,
-		                float *pseudonormal4);
+		void signedDistance(const float *points4, uint32_t n, float max_distance, uint32_t flags, QueryOutputs out, uint8_t *feature,
+		                    float *pseudonormal4, Where where);
 		// The grid form: voxel (i, j, k) is origin + (i, j, k) * spacing; `distance`, `leaf`: [dims[2]][dims[1]][dims[0]], either
 		// may be null.  The host form goes through the staging buffer in slabs of z-slices.
 		void signedGridDevice(const float origin[3], const float spacing[3], const uint32_t dims[3], float max_distance, float *distance,
@@ -81,12 +74,8 @@ class RayQueries {
 		// Segment queries (include/rt_hip_segment.h): segment i runs from from4[i] to to4[i]; its blockers are the triangles
 		// the reference accepts for the ray (from, to - from) with a plane parameter inside (t_lo, t_hi), behind boxes that
 		// pass the slab test with max_distance = t_hi.  `closest` false: occlusion into out.hit alone.
-		// Device memory, enqueued on `stream` (null: the renderer's).
-		void segmentsDevice(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
-		                    const QueryOutputs &out, void *stream, bool instanced = false, uint32_t *instance = nullptr);
-		// Host memory, blocking.
-		void segmentsHost(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
-		                  const QueryOutputs &out, bool instanced = false, uint32_t *instance = nullptr);
+		void segments(bool closest, const float *from4, const float *to4, uint32_t n, float t_lo, float t_hi, uint32_t flags,
+		              QueryOutputs out, Where where, bool instanced = false, uint32_t *instance = nullptr);
 		// The many-to-many form: np points against nt targets, bit j of point i's row (visibilityWords(nt) words) set where
 		// segment (i, j) is occluded, and the row's popcount.  Either output may be null.  No np x nt array is made.
 		struct VisibilityOutputs {
@@ -94,12 +83,8 @@ class RayQueries {
 			bool any() const { return mask || count; }
 		};
 		static uint32_t visibilityWords(uint32_t nt) { return (nt + 31u) / 32u; }
-		// Device memory, enqueued on `stream` (null: the renderer's).
-		void visibilityDevice(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
-		                      const VisibilityOutputs &out, void *stream, bool instanced = false);
-		// Host memory, blocking.
-		void visibilityHost(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
-		                    const VisibilityOutputs &out, bool instanced = false);
+		void visibility(const float *points4, uint32_t np, const float *targets4, uint32_t nt, float t_lo, float t_hi, uint32_t flags,
+		                VisibilityOutputs out, Where where, bool instanced = false);
 		// The instance set (include/rt_hip_instances.h).  The set -- transforms, inverses and the top-level tree over the
 		// scene's root box (instances.h) -- is kept here and, as float4[3n] + float4[3n] + NodeRec[2n - 1] + float4[n] (the
 		// closest-point walk's bounds), in device memory of this object's own; it outlives updates, builds and uploads, after which the tree is made again before its next use.
@@ -134,15 +119,13 @@ class RayQueries {
 		// (static: what a renderer's uploaded scene answers, before any query has made scratch for it)
 		static uint32_t aoRaysPerPoint(const DeviceRenderer &renderer);  // 0: not available
 		static uint32_t aoDivisor(const DeviceRenderer &renderer);
-		// Device memory, enqueued on `stream` (null: the renderer's); `seeds`, `ao`, `occluded` may be null.
-		void aoDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
-		              uint32_t *occluded, void *stream, bool instanced = false);
-		// Host memory, blocking.
-		void aoHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao,
-		            uint32_t *occluded, bool instanced = false);
+		// `seeds`, `ao`, `occluded` may be null.
+		void ao(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags, float *ao, uint32_t *occluded,
+		        Where where, bool instanced = false);
 		// Directional occlusion queries (include/rt_hip_directional.h): the same rays, their hit flags a bit each in `mask`
 		// (aoMaskWords() words per point), the count and value made of a point's row, and the ordered sum of its open rays'
-		// directions.  Any output may be null; errors as for aoDevice.
+		// directions.  Any output may be null; errors as for ao.  `instanced` (include/rt_hip_instance_directional.h):
+		// world-space points, the rays cast against the instance set.
 		struct DirectionalOutputs {
 			float *ao = nullptr;
 			uint32_t *occluded = nullptr, *mask = nullptr;
@@ -150,25 +133,16 @@ class RayQueries {
 			bool any() const { return ao || occluded || mask || bent; }
 		};
 		static uint32_t aoMaskWords(const DeviceRenderer &renderer) { return (aoRaysPerPoint(renderer) + 31u) / 32u; }
-		// Device memory, enqueued on `stream` (null: the renderer's).  `instanced` (include/rt_hip_instance_directional.h):
-		// world-space points, the rays cast against the instance set.
-		void directionalDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
-		                       const DirectionalOutputs &out, void *stream, bool instanced = false);
-		// Host memory, blocking.
-		void directionalHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
-		                     const DirectionalOutputs &out, bool instanced = false);
+		void directional(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, uint32_t flags,
+		                 DirectionalOutputs out, Where where, bool instanced = false);
 		// The rays themselves: origins4 float4[n], directions4 float4[n * rays per point]; either may be null; no walk is run.
-		void aoRaysDevice(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4, float *directions4,
-		                  void *stream);
-		void aoRaysHost(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4, float *directions4);
+		void aoRays(const float *points4, const float *normals4, const uint32_t *seeds, uint32_t n, float *origins4, float *directions4,
+		            Where where);
 		// Frame layers (include/rt_hip_layers.h): the closest-hit record of every sub-pixel's own ray -- the host's pose,
 		// DeviceRenderer::camera() / cameraIsSet() --, its direction, head-light term, ambient-occlusion factor and their
 		// product.  std::logic_error on a band-partitioned host and for out.ao where the options have ambient occlusion
 		// off; std::invalid_argument where the ambient-occlusion step would exceed a query's rays.
-		// Device memory, enqueued on `stream` (null: the renderer's).
-		void layersDevice(const LayerOutputs &out, void *stream);
-		// Host memory, blocking.
-		void layersHost(const LayerOutputs &out);
+		void layers(LayerOutputs out, Where where);
 		// Multi-view rendering (include/rt_hip_views.h): the layers and the 8-bit image of `views` poses -- `cameras`, host
 		// memory, copied before the call returns -- against the uploaded scene, whatever pose the host itself has; view v's
 		// block of every array lies behind view v - 1's.  Worked through in chunks of viewsPerChunk() views, scratch for one
@@ -218,24 +192,34 @@ class RayQueries {
 			void *ptr = nullptr;
 			size_t bytes = 0;
 		};
-		// A piece of the staging buffer of the host-memory forms: `from` is copied in before the query, `to` is copied
-		// back to after it (either may be null); not `wanted`: no piece, `device` stays null.
-		struct Staged {
-			const void *from;
-			void *to;
-			size_t bytes;
-			bool wanted;
-			void *device = nullptr;
+		// The arrays of a call, named once: the address of each pointer variable, its bytes, and whether the array is read
+		// (`in`), written (`out`) or written whether the caller wants it or not (`scratch`: staged even where the pointer is
+		// null, never copied back then).  A null `in` or `out` is no array at all.
+		class Arrays {
+			public:
+				template <class T> Arrays &in(const T *&p, size_t bytes) { return add(&p, bytes, p != nullptr, true); }
+				template <class T> Arrays &out(T *&p, size_t bytes) { return add(&p, bytes, p != nullptr, false); }
+				template <class T> Arrays &scratch(T *&p, size_t bytes) { return add(&p, bytes, true, false); }
+				Arrays &records(RecordOutputs &r, size_t records);  // the five arrays of a record, `records` records each
+				Arrays &layers(LayerOutputs &l, size_t records);    // the hit flags, the record and the four layers of a frame's rays
+
+			private:
+				friend class RayQueries;
+				struct Piece {
+					void *variable;  // where the pointer is kept: read as the host's address, then given the staging buffer's
+					size_t bytes;
+					bool input;
+					void *host = nullptr, *device = nullptr;
+				};
+				Arrays &add(void *variable, size_t bytes, bool wanted, bool input);
+				Piece piece[16];
+				size_t count = 0;
 		};
-		static Staged input(const void *from, size_t bytes) { return Staged{ from, nullptr, bytes, from != nullptr }; }
-		static Staged output(void *to, size_t bytes) { return Staged{ nullptr, to, bytes, to != nullptr }; }
-		static Staged scratch(void *to, size_t bytes) { return Staged{ nullptr, to, bytes, true }; }  // staged even if `to` is null
-		// The five record arrays of `host`, `records` records each, as pieces p[0..4]; and those pieces' device pointers.
-		static void recordPieces(Staged *p, const RecordOutputs &host, size_t records);
-		static void recordDevice(const Staged *p, RecordOutputs &out);
-		// The same for the layers of `host`, `records` sub-pixels each: pieces p[LAYER_HIT .. LAYER_VALUE].
-		static void layerPieces(Staged *p, const LayerOutputs &host, size_t records);
-		static void layerDevice(const Staged *p, LayerOutputs &out);
+		// What every call does with its arrays once it knows that it has work.  Device memory: body(where.stream).  Host
+		// memory: the wanted arrays one behind the other in the staging buffer, each rounded up to 16 bytes, the inputs
+		// uploaded, the pointer variables set to the device addresses, body(the renderer's own stream), the outputs copied back,
+		// one wait.
+		template <class Body> void staged(Where where, Arrays &arrays, Body &&body);
 		struct Need {  // scratch of a family's own that begin() grows with the sort's
 			Scratch *scratch;  // (null: none)
 			size_t bytes;
@@ -254,11 +238,6 @@ class RayQueries {
 			const float *box;            // the sort's origin cells where they are not the scene's root box's, or null
 		};
 		Target target(bool instanced);
-		// The host-memory form of a family with two float4 inputs of n items (`b4` may be null), the hit flags and the five
-		// record arrays -- `records` false: the flags alone --, and `instance`: staged, run(a4, b4, out, instance, stream) on
-		// the device pointers, copied back.
-		template <class Run>
-		void stagedRecords(const float *a4, const float *b4, uint32_t n, bool records, const QueryOutputs &host, uint32_t *instance, Run &&run);
 		void requireSlots(uint32_t k) const;
 		void requireAo() const;
 		bool requireLayers(const LayerOutputs &out) const;  // true: the call needs the ambient-occlusion step
@@ -284,26 +263,29 @@ class RayQueries {
 		static ViewOutputs viewsFrom(const ViewOutputs &out, size_t view, const KernelParams &kp, size_t image_bytes);
 		void grow(Scratch &scratch, size_t bytes);
 		void sceneBox(const DeviceScene &scene, float lo[3], float scale[3]);
+		// The way into a call's launches, in two steps: enter() -- this device, the stream (null: the renderer's), behind the
+		// query before -- and begin() on the stream entered.
 		// (`segments`: keys_a4, keys_b4 are the two ends of segments, keyed as the rays (a, b - a); `box`: lo[3] and scale[3] of
 		// the origin cells where they are not the scene's root box's)
-		Enqueue begin(void *stream, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags,
+		void *enter(void *stream);
+		Enqueue begin(void *entered, const float *keys_a4, const float *keys_b4, uint32_t n, uint64_t rays, uint32_t flags,
 		              std::initializer_list<Need> needs = {}, bool segments = false, const float *box = nullptr);
 		void end(const Enqueue &q);
 		// The ambient-occlusion step between begin() and end(): n entries -- point order[j], or j where `order` is null --,
 		// counted into `count` by point index (the caller's `occluded` or ao_hits).  `instanced`: against the instance set.
 		void aoEnqueue(const Enqueue &q, const float *points4, const float *normals4, const uint32_t *seeds, const void *order, uint32_t n,
 		               uint32_t *count, float *ao, bool instanced = false);
-		void *stageIn(Staged *pieces, size_t n);  // returns the stream
-		void stageOut(const Staged *pieces, size_t n, void *stream);
+		void *stageIn(Arrays &arrays);  // returns the stream
+		void stageOut(const Arrays &arrays, void *stream);
 
 		DeviceRenderer &dev;
 		Scratch count, order;  // the sort's histogram and the order it makes
 		Scratch stage;         // the host-memory forms' inputs and outputs
-		Scratch ao_hits;       // aoDevice without an `occluded` array: the points' counts
-		Scratch ao_rows;       // directionalDevice without a `mask` array: the points' rows
-		Scratch vis_rows;      // visibilityDevice without a `mask` array: the points' rows
-	Scratch list;          // multihitDevice: the rays' key lists, n * k * 8 bytes (instanced: 12)
-		Scratch views;         // layersDevice, viewsDevice (ChunkScratch): a chunk's poses, the points and normals of its
+		Scratch ao_hits;       // ao without an `occluded` array: the points' counts
+		Scratch ao_rows;       // directional without a `mask` array: the points' rows
+		Scratch vis_rows;      // visibility without a `mask` array: the points' rows
+		Scratch list;          // multihit: the rays' key lists, n * k * 8 bytes (instanced: 12)
+		Scratch views;         // layers, viewsDevice (ChunkScratch): a chunk's poses, the points and normals of its
 		                       // ambient-occlusion step, the list of the hit ones (ViewList), its float images where the caller
 		                       // gave no `value` array
 		void *pinned = nullptr;  // viewsDevice, host memory: the list's size as read back, then the call's poses
